@@ -10,8 +10,10 @@ T=1024, bf16 compute (autocast numerics), fp32 master weights, fused AdamW (lr 1
 betas 0.9/0.95), dropout 0.1 as the reference's default config (model.py:47-51), grad_accum 1.
 Data: synthetic uniform token batches already resident in HBM (no network).
 
-Also reported:
-  mfu          tok/s * 854,438,400 FLOP/token / (N * 2.5166e15)   (bf16 dense peak)
+A plain run sets up, warms up, times the K steps and prints the line (with ``mfu``: tok/s * 854,438,400 FLOP/token /
+(N * 2.5166e15); bf16 dense peak). ``--dump-outputs DIR`` also writes what the last timed step returned to
+its caller (see dump_outputs). Everything else is measured under ``--full`` only, where ``roofline``, ``kernels`` and
+``cpu_baseline`` are filled in (null / empty in a plain run):
   roofline     for the dominant kernel (the tied lm_head GEMMs are the largest launches): algorithmic
                FLOP per launch / average launch time measured live with HIP events on the launch stream
   kernels      the same for every probed launch family
@@ -74,6 +76,35 @@ def cpu_baseline(batch=4, seq_len=1024, steps=3):
                       f"({dt:.1f} s) after 1 warm-up"}
 
 
+DUMP_LOGIT_ROWS = 128     # x V floats (26 MB at V = 50257)
+DUMP_PARAMS = 4_000_000   # floats (16 MB); with the logits rows under the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, kept, arena):
+    """What a caller of the timed step holds after the last timed one, as float32 out_dir/<name>.npy:
+      loss.npy    the loss the step returned (of its last micro-batch, divided by grad_accum as the loop forms it)
+      logits.npy  DUMP_LOGIT_ROWS of the [B*T, V] logits it returned (every row if there are fewer)
+      params.npy  DUMP_PARAMS elements of the flat fp32 master weights after its optimizer step (all if fewer)
+    The rows and elements are drawn once from a fixed seed, so two runs with the same arguments write the same ones."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(20240607)
+    out = {}
+    if "loss" in kept:
+        out["loss"] = kept["loss"].detach().float().reshape(1)
+    if "logits" in kept:
+        logits = kept["logits"].detach()  # [B, T, V], a view of the padded-vocab buffer: indexed, never reshaped
+        B, T, _ = logits.shape
+        rows = torch.sort(torch.randperm(B * T, generator=g)[:DUMP_LOGIT_ROWS]).values.to(logits.device)
+        out["logits"] = logits[rows // T, rows % T].float()
+    flat = arena.detach().reshape(-1)
+    if flat.numel() > DUMP_PARAMS:
+        flat = flat[torch.randint(0, flat.numel(), (DUMP_PARAMS,), generator=g).to(flat.device)]
+    out["params"] = flat.float()
+    for name, t in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -94,7 +125,12 @@ def main():
                          "memory behaviour as in the reference)")
     ap.add_argument("--reshard", action="store_true", help="--parallel fsdp: the default (kept for older scripts)")
     ap.add_argument("--probe-every", type=int, default=5,
-                    help="time the probed kernel launches (HIP events) in every N-th timed step")
+                    help="--full: time the probed kernel launches (HIP events) in every N-th timed step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-kernel probes and roofline "
+                         "inside the timed steps, and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -134,8 +170,9 @@ def main():
         batches.append((t[:, :-1].contiguous().to(dev), t[:, 1:].contiguous().to(dev)))
 
     GA = args.grad_accum
+    kept = {}  # --dump-outputs: what the last timed step returned to its caller
 
-    def step(i):
+    def step(i, keep=False):
         # the reference loop (:400-425) runs every micro-step's backward synced; the resident wrappers skip the
         # collective on all but the last one (no_sync: the same sums), the resharded FSDP reduce-scatters every one
         # as the reference does (its gradients do not outlive their unit's backward)
@@ -146,11 +183,13 @@ def main():
                 else contextlib.nullcontext()
             with ctx:
                 with torch.autocast("cuda", dtype=torch.bfloat16):  # the reference trainer's step (:404)
-                    _, loss = fwd(x, labels=y)
+                    logits, loss = fwd(x, labels=y)
                     loss = loss / GA
                 loss.backward()
         opt.step()
         opt.zero_grad()
+        if keep:  # references only: nothing is copied or launched inside the timed region
+            kept.update(logits=logits, loss=loss)
         return loss
 
     for i in range(args.warmup):
@@ -159,7 +198,7 @@ def main():
     if wrapped:
         dist.barrier()
     probes = ["lm_head_fwd", "lm_head_dgrad", "lm_head_wgrad", "fc1_fwd", "attn_fwd", "wgrad"]
-    armed = {p: [] for p in probes}
+    armed = {p: [] for p in probes} if args.full else {}
     every = max(1, args.probe_every)
     torch.cuda.synchronize()
     if wrapped:
@@ -167,7 +206,7 @@ def main():
     t0 = time.perf_counter()
     for i in range(args.steps):
         eng.probes = armed if i % every == 0 else {}  # the sampled steps record events around every probed launch
-        loss = step(i)
+        loss = step(i, keep=args.dump_outputs is not None and i == args.steps - 1)
     torch.cuda.synchronize()
     if wrapped:
         dist.barrier()
@@ -188,7 +227,7 @@ def main():
         # launch with its split-K reduction; 1 + L launches a step since round 6, a block's four grouped in one, 1 + 4L
         # before): the average algorithmic FLOPs of a launch = the step's weight-gradient FLOPs / its launches
         "wgrad": (2.0 * M * V * C + cfg.n_layer * 2.0 * M * 12 * C * C)
-        / max(1.0, len(armed["wgrad"]) / len(range(0, args.steps, every))),
+        / max(1.0, len(armed.get("wgrad", ())) / max(1, len(range(0, args.steps, every)))),
     }
     kernels = {}
     for name, evs in armed.items():
@@ -255,7 +294,12 @@ def main():
         "kernels": kernels,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs is not None:
+        # FSDP keeps 1/world of the master weights per rank: the full arena is gathered (a collective, every rank)
+        arena = ddp.full_arena() if wrapped and args.parallel == "fsdp" else model.arena
+        if rank == 0:
+            dump_outputs(args.dump_outputs, kept, arena)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline(seq_len=T)
         except Exception as e:  # reported, never fatal to the GPU measurement

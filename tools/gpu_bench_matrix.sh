@@ -16,7 +16,7 @@ run() {  # name, timeout, command...
   return $rc
 }
 TR="python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr=127.0.0.1 --master-port=29571"
-run bench 300 python bench.py --no-cpu-baseline || exit $?
+run bench 300 python bench.py --full --no-cpu-baseline || exit $?  # --full: the per-kernel / roofline figures too
 run ddp1 300 env GPT2MI_FORCE_COLLECTIVES=1 $TR bench.py --gpus 1 --parallel ddp --no-cpu-baseline || exit $?
 run fsdp1 300 env GPT2MI_FORCE_COLLECTIVES=1 $TR bench.py --gpus 1 --parallel fsdp --no-cpu-baseline || exit $?
 run m350 300 python bench.py --model 350M --batch 32 --steps 10 --warmup 3 --no-cpu-baseline || exit $?
