@@ -17,4 +17,6 @@ Modules
 model_ref   functional fp32 / bf16-autocast restatement of ``model.py`` (init, forward, per-op)
 loader_ref  pure-python restatement of ``dataloader.py``'s shard/offset/batch order
 train_ref   restatement of the ``train_gpt2_distributed.py:374-425`` step loop + AdamW math
+dropout_ref numpy restatement of the HIP step's counter-based dropout masks
+attn_stress stress inputs, a bf16 rounding model and a per-block error metric for the attention kernels
 """
