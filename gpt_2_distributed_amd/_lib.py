@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -72,8 +72,17 @@ _SIGS = {
     # sched, stream
     "gpt2mi_gemm_wgrad_grouped": [_c_int, _p, _p, _c_int, _p, _p, _p, _p, _p, _c_int, _c_float, _p, _p, _c_size,
                                   _c_int, _c_int, _p],
+    # v14 decode: epilogue, M, N, K, A, lda, W, ldw, C, ldc, bias, resid, workspace, workspace_floats, stream
+    "gpt2mi_gemm_skinny": [_c_int, _c_int, _c_int, _c_int, _p, _c_int, _p, _c_int, _p, _c_int, _p, _p, _p, _c_size, _p],
+    "gpt2mi_gemm_skinny_workspace": [_c_int, _c_int, _c_int],
+    "gpt2mi_kv_store": [_p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p],
+    "gpt2mi_attn_decode": [_p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _c_int, _p],
+    "gpt2mi_attn_decode_workspace": [_c_int, _c_int, _c_int],
+    "gpt2mi_embed_decode": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p],
+    "gpt2mi_decode_step": [_p, _p, _c_int, _p],
 }
-_RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p}
+_RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
+             "gpt2mi_attn_decode_workspace": _c_size}
 
 EXPORTED = tuple(_SIGS)
 
@@ -344,3 +353,56 @@ def zero_ranges(t: torch.Tensor, ranges: torch.Tensor):
     """Zero the element ranges of fp32 t given as a cuda int64 [n, 2] tensor of (offset, count)."""
     assert t.dtype == torch.float32 and ranges.dtype == torch.int64 and ranges.is_cuda
     _call("gpt2mi_zero_ranges", _ptr(t), _ptr(ranges), ranges.shape[0], _stream())
+
+
+# ---- v14: autoregressive decode (csrc/decode.hip) -------------------------------------------------
+class DecodeLayer(ctypes.Structure):
+    """gpt2mi_decode_layer (include/gpt2mi.h)."""
+    _fields_ = [(n, _p) for n in ("ln1_w", "ln1_b", "ln2_w", "ln2_b", "qkv_w", "proj_w", "fc1_w", "fc2_w",
+                                  "qkv_b", "proj_b", "fc1_b", "fc2_b", "kcache", "vcache")]
+
+
+class DecodePlan(ctypes.Structure):
+    """gpt2mi_decode_plan (include/gpt2mi.h). `layers` points at a host array the owner keeps alive."""
+    _fields_ = ([(n, _c_int) for n in ("B", "C", "H", "L", "Vp", "Tcap")] + [("eps", _c_float)] +
+                [(n, _p) for n in ("wte", "wpe", "lnf_w", "lnf_b", "wte_bf16")] +
+                [("layers", ctypes.POINTER(DecodeLayer))] +
+                [(n, _p) for n in ("x", "xmid", "ln", "qkv", "ao", "h", "mean", "rstd")] +
+                [("attn_ws", _p), ("attn_ws_floats", _c_size), ("gemm_ws", _p), ("gemm_ws_floats", _c_size),
+                 ("logits", _p)])
+
+
+def gemm_skinny_workspace(M, N, K) -> int:
+    """fp32 elements of workspace gemm_skinny needs at this shape (0: the strips alone cover the chip)."""
+    return load().gpt2mi_gemm_skinny_workspace(M, N, K)
+
+
+def gemm_skinny(epilogue, M, N, K, A, lda, W, ldw, C, ldc, bias=None, resid=None, workspace=None):
+    """C[m][n] = epi(sum_k A[m][k] W[n][k] + bias[n]) for 1 <= M <= 64 rows (EPI_BF16 / EPI_F32 / EPI_RESID / EPI_GELU)."""
+    ws_n = workspace.numel() if workspace is not None else 0
+    _call("gpt2mi_gemm_skinny", epilogue, M, N, K, _ptr(A), lda, _ptr(W), ldw, _ptr(C), ldc, _ptr(bias), _ptr(resid),
+          _ptr(workspace), ws_n, _stream())
+
+
+def kv_store(qkv, kcache, vcache, B, T_src, n, t0, H, D, Tcap):
+    """Copy the K / V columns of the first n rows of each sequence of qkv [B*T_src, 3C] to cache positions t0.."""
+    _call("gpt2mi_kv_store", _ptr(qkv), _ptr(kcache), _ptr(vcache), B, T_src, n, t0, H, D, Tcap, _stream())
+
+
+def attn_decode_workspace(B, H, Tcap) -> int:
+    return load().gpt2mi_attn_decode_workspace(B, H, Tcap)
+
+
+def attn_decode(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos):
+    """The new token's attention over cache positions 0..pos (its own k / v are written at pos first)."""
+    _call("gpt2mi_attn_decode", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(workspace), workspace.numel(),
+          B, H, D, Tcap, pos, _stream())
+
+
+def embed_decode(tok, wte, wpe, x, B, C, pos):
+    _call("gpt2mi_embed_decode", _ptr(tok), _ptr(wte), _ptr(wpe), _ptr(x), B, C, pos, _stream())
+
+
+def decode_step(plan: DecodePlan, tok, pos):
+    """One token step of the whole network (gpt2mi_decode_step) into plan.logits."""
+    _call("gpt2mi_decode_step", ctypes.byref(plan), _ptr(tok), pos, _stream())

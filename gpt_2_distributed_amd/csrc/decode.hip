@@ -1,0 +1,439 @@
+// Autoregressive decode: one new token per sequence and step, against a per-layer key/value cache. gfx950, wave64.
+//
+// The training kernels cannot serve this step: gpt2mi_gemm tiles 256x256 and needs M % 64 == 0 (3 workgroups at
+// M = batch, N = 768), gpt2mi_attn_fwd recomputes every query row of a 64-multiple T. At M <= 64 rows the cost of a
+// Linear is streaming its weight once, and of the attention streaming the cached K and V once: both kernels here load
+// the streamed operand straight to VGPRs in full 128-byte lines (no LDS round trip: nothing is shared between waves),
+// and split the reduction (K, or the keys) over enough waves to cover the chip. No atomics: partial results are
+// combined in a fixed order, so every output is bitwise reproducible.
+#include <algorithm>
+
+#include "common.h"
+#include "gpt2mi.h"
+
+namespace {
+
+enum { SK_BF16 = 0, SK_F32 = 1, SK_RESID = 2, SK_GELU = 3 };
+
+// ---------------------------------------------------------------------------------------------------------------
+// Skinny GEMM. One wave owns a strip of 16 weight rows (output columns) over a range of 64-wide K chunks; the MFMA is
+// v_mfma_f32_16x16x32_bf16 with the weight strip as its 16-row operand and up to 4 tiles of 16 activation rows as its
+// 16-column operand. Within a chunk lane (r = lane % 16, g = lane / 16) holds k = 16 g .. 16 g + 15 of row r as two
+// 16-byte loads (the four lanes of a row read one 128-byte line); the first halves feed one MFMA and the second
+// halves the next. Both operands use the same k assignment, so the product is the plain dot product.
+// A block's waves take consecutive chunk ranges of the block's K slice and are summed in wave order through LDS; the
+// blocks of one strip (gridDim.y K slices) write fp32 partials that skinny_reduce_kernel sums in slice order.
+// acc[mt][j] = C[m = 16 mt + lane % 16][n = n0 + 4 (lane / 16) + j].
+constexpr int SK_MAX_WAVES = 4;
+
+__device__ __forceinline__ float gelu_tanh1(float u) {
+  // NewGELU in the sigmoid form of gemm_common.h gelu4: u / (1 + 2^(u (A + B u^2)))
+  const float k0 = 0.7978845608028654f, k1 = 0.044715f, m2log2e = -2.0f * 1.4426950408889634f;
+  const float arg = u * __builtin_fmaf(u * u, k0 * k1 * m2log2e, k0 * m2log2e);
+  return u * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(arg) + 1.f);
+}
+
+template <int EPI>
+__device__ __forceinline__ void skinny_epilogue(f32x4 v, void* __restrict__ C, size_t off,
+                                                const float* __restrict__ bias, const float* __restrict__ resid,
+                                                int n) {
+  if (bias) v += *reinterpret_cast<const f32x4*>(bias + n);
+  if constexpr (EPI == SK_BF16) {
+    *reinterpret_cast<bf16x4*>((bf16*)C + off) = bf16x4{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+  } else if constexpr (EPI == SK_F32) {
+    *reinterpret_cast<f32x4*>((float*)C + off) = v;
+  } else if constexpr (EPI == SK_RESID) {
+    *reinterpret_cast<f32x4*>((float*)C + off) = *reinterpret_cast<const f32x4*>(resid + off) + v;
+  } else {
+    *reinterpret_cast<bf16x4*>((bf16*)C + off) =
+        bf16x4{f2bf(gelu_tanh1(v[0])), f2bf(gelu_tanh1(v[1])), f2bf(gelu_tanh1(v[2])), f2bf(gelu_tanh1(v[3]))};
+  }
+}
+
+template <int MT, int EPI>
+__global__ __launch_bounds__(64 * SK_MAX_WAVES) void skinny_gemm_kernel(
+    const bf16* __restrict__ A, int lda, const bf16* __restrict__ W, int ldw, void* __restrict__ C, int ldc,
+    const float* __restrict__ bias, const float* __restrict__ resid, float* __restrict__ partial, int M, int N,
+    int chunks, int cpu) {
+  __shared__ f32x4 red[SK_MAX_WAVES - 1][MT][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const int r = lane & 15, g = lane >> 4;
+  const int n0 = blockIdx.x * 16;
+  const int unit = blockIdx.y * nw + wave;
+  const int c0 = unit * cpu;
+  const int c1 = min(c0 + cpu, chunks);
+
+  const bf16* wp = W + (size_t)(n0 + r) * ldw + 16 * g;
+  const bf16* ap[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) ap[mt] = A + (size_t)min(16 * mt + r, M - 1) * lda + 16 * g;  // rows >= M: not stored
+
+  f32x4 acc[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int c = c0; c < c1; ++c) {
+    const bf16x8 w0 = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp + 64 * c));
+    const bf16x8 w1 = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(wp + 64 * c + 8));
+    bf16x8 a0[MT], a1[MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      a0[mt] = *reinterpret_cast<const bf16x8*>(ap[mt] + 64 * c);
+      a1[mt] = *reinterpret_cast<const bf16x8*>(ap[mt] + 64 * c + 8);
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w0, a0[mt], acc[mt], 0, 0, 0);
+      acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1, a1[mt], acc[mt], 0, 0, 0);
+    }
+  }
+
+  // waves 1.. hand their sums to wave 0, which adds them in wave order
+  if (nw > 1) {
+    if (wave > 0) {
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) red[wave - 1][mt][lane] = acc[mt];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+    for (int w = 0; w < nw - 1; ++w)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) acc[mt] += red[w][mt][lane];
+  }
+
+  const int n = n0 + 4 * g;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int m = 16 * mt + r;
+    if (m >= M) continue;
+    if (partial)  // one of gridDim.y K slices: [slice][M][N] fp32
+      *reinterpret_cast<f32x4*>(partial + ((size_t)blockIdx.y * M + m) * N + n) = acc[mt];
+    else
+      skinny_epilogue<EPI>(acc[mt], C, (size_t)m * ldc + n, bias, resid, n);
+  }
+}
+
+template <int EPI>
+__global__ __launch_bounds__(256) void skinny_reduce_kernel(const float* __restrict__ partial, int slices,
+                                                            void* __restrict__ C, int ldc,
+                                                            const float* __restrict__ bias,
+                                                            const float* __restrict__ resid, int M, int N) {
+  const int i = blockIdx.x * 256 + threadIdx.x;  // one thread per 4 columns
+  const int n4 = N / 4;
+  if (i >= M * n4) return;
+  const int m = i / n4, n = 4 * (i % n4);
+  f32x4 v = *reinterpret_cast<const f32x4*>(partial + (size_t)m * N + n);
+  for (int s = 1; s < slices; ++s) v += *reinterpret_cast<const f32x4*>(partial + ((size_t)s * M + m) * N + n);
+  skinny_epilogue<EPI>(v, C, (size_t)m * ldc + n, bias, resid, n);
+}
+
+// The K split of a shape, from (N, K) only (an output row's bits must not depend on M): `slices` blocks per strip until
+// the grid reaches the CU count, `nw` waves per block, `cpu` chunks per wave. From 128 strips on (N >= 2048: qkv, fc1,
+// the lm_head) the strips' own blocks of 4 waves are kept: a second K slice would add the reduction launch, which
+// costs more than the idle CUs of a launch that streams a few megabytes.
+struct SkinnySplit {
+  int chunks, slices, nw, cpu;
+};
+SkinnySplit skinny_split(int N, int K) {
+  SkinnySplit s;
+  const int strips = N / 16;
+  s.chunks = K / 64;
+  s.slices = strips >= 128 ? 1 : std::max(1, std::min(s.chunks, (256 + strips - 1) / strips));
+  s.nw = std::max(1, std::min(SK_MAX_WAVES, s.chunks / s.slices));
+  const int units = s.slices * s.nw;
+  s.cpu = (s.chunks + units - 1) / units;
+  return s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Cache fill of the prefill: one thread per 16 bytes of the K and V columns of the n valid rows of each sequence.
+__global__ __launch_bounds__(256) void kv_store_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
+                                                       bf16* __restrict__ vc, int B, int T_src, int n, int t0, int H,
+                                                       int Tcap) {
+  const int C = H * 64, per_row = 2 * C / 8;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)B * n * per_row) return;
+  const int j = (int)(i % per_row);
+  const size_t row = i / per_row;
+  const int t = (int)(row % n), b = (int)(row / n);
+  const int col = 8 * j;  // in [0, 2C): K then V
+  const int which = col / C, c = col % C, h = c / 64, d = c % 64;
+  const bf16x8 v = *reinterpret_cast<const bf16x8*>(qkv + ((size_t)b * T_src + t) * 3 * C + C + col);
+  bf16* dst = (which ? vc : kc) + (((size_t)b * H + h) * Tcap + t0 + t) * 64 + d;
+  *reinterpret_cast<bf16x8*>(dst) = v;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Single-query attention. One wave per (range of 32 keys, b, h): lane (kk = lane / 8, dg = lane % 8) holds dims
+// 8 dg .. 8 dg + 7 of keys k0 + kk + 8 i, i < 4 (the 8 lanes of a key read its 128-byte row), so a K or V load of the
+// wave is 8 whole rows. The key at pos is the new token's: its lanes take k and v from qkv and write them to the
+// cache (no lane reads what another wrote). Scores in fp32, one softmax over the range, partial (max, sum, acc[64])
+// to the workspace; attn_combine_kernel merges the ranges in order.
+constexpr int AD_KEYS = 32;
+
+__device__ __forceinline__ void unpack8(bf16x8 v, float* f) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] = bf2f(v[j]);
+}
+
+__global__ __launch_bounds__(64) void attn_decode_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
+                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
+                                                         float* __restrict__ ws_acc, int H, int Tcap, int pos,
+                                                         int nr_max) {
+  const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
+  const int range = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H;
+  const int C = H * 64;
+  const bf16* tok = qkv + (size_t)b * 3 * C + h * 64 + 8 * dg;  // q; k at + C, v at + 2C
+  float q[8];
+  unpack8(*reinterpret_cast<const bf16x8*>(tok), q);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) q[j] *= 0.125f;  // 1/sqrt(64), exact
+
+  const size_t base = (size_t)bh * Tcap * 64 + 8 * dg;
+  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  bf16x8 kv[4], vv[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int key = range * AD_KEYS + kk + 8 * i;
+    kv[i] = zero;
+    vv[i] = zero;
+    if (key < pos) {
+      kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
+      vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
+    } else if (key == pos) {
+      kv[i] = *reinterpret_cast<const bf16x8*>(tok + C);
+      vv[i] = *reinterpret_cast<const bf16x8*>(tok + 2 * C);
+      *reinterpret_cast<bf16x8*>(kc + base + (size_t)key * 64) = kv[i];
+      *reinterpret_cast<bf16x8*>(vc + base + (size_t)key * 64) = vv[i];
+    }
+  }
+
+  float s[4], mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float kf[8], d = 0.f;
+    unpack8(kv[i], kf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], kf[j], d);
+    d += __shfl_xor(d, 1, 64);
+    d += __shfl_xor(d, 2, 64);
+    d += __shfl_xor(d, 4, 64);
+    s[i] = (range * AD_KEYS + kk + 8 * i <= pos) ? d : -INFINITY;
+    mx = fmaxf(mx, s[i]);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 8, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // finite: the range's first key is <= pos
+
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float p = __expf(s[i] - mx);  // 0 for a masked key
+    float vf[8];
+    unpack8(vv[i], vf);
+    l += p;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(p, vf[j], acc[j]);
+  }
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) {
+    l += __shfl_xor(l, o, 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], o, 64);
+  }
+  const size_t slot = (size_t)bh * nr_max + range;
+  if (kk == 0) {
+    float* a = ws_acc + slot * 64 + 8 * dg;
+    *reinterpret_cast<f32x4*>(a) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+    *reinterpret_cast<f32x4*>(a + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    if (dg == 0) {
+      ws_ml[2 * slot] = mx;
+      ws_ml[2 * slot + 1] = l;
+    }
+  }
+}
+
+// out[b, h*64 + d] = sum_r e^(m_r - m) acc_r[d] / sum_r e^(m_r - m) l_r, r in range order; lane d.
+__global__ __launch_bounds__(64) void attn_combine_kernel(const float* __restrict__ ws_ml,
+                                                          const float* __restrict__ ws_acc, bf16* __restrict__ out,
+                                                          int H, int nr, int nr_max) {
+  const int d = threadIdx.x, bh = blockIdx.x;
+  const size_t slot0 = (size_t)bh * nr_max;
+  float m = -INFINITY;
+  for (int r = 0; r < nr; ++r) m = fmaxf(m, ws_ml[2 * (slot0 + r)]);
+  float l = 0.f, o = 0.f;
+  for (int r = 0; r < nr; ++r) {
+    const float w = __expf(ws_ml[2 * (slot0 + r)] - m);
+    l = __builtin_fmaf(w, ws_ml[2 * (slot0 + r) + 1], l);
+    o = __builtin_fmaf(w, ws_acc[(slot0 + r) * 64 + d], o);
+  }
+  out[(size_t)(bh / H) * H * 64 + (bh % H) * 64 + d] = f2bf(o / l);
+}
+
+__global__ __launch_bounds__(256) void embed_decode_kernel(const int64_t* __restrict__ tok,
+                                                           const float* __restrict__ wte,
+                                                           const float* __restrict__ wpe, float* __restrict__ x, int B,
+                                                           int C, int pos) {
+  const int i = blockIdx.x * 256 + threadIdx.x;  // one thread per 4 floats
+  const int c4 = C / 4;
+  if (i >= B * c4) return;
+  const int b = i / c4, c = 4 * (i % c4);
+  const f32x4 e = *reinterpret_cast<const f32x4*>(wte + (size_t)tok[b] * C + c);
+  const f32x4 p = *reinterpret_cast<const f32x4*>(wpe + (size_t)pos * C + c);
+  *reinterpret_cast<f32x4*>(x + (size_t)b * C + c) = e + p;
+}
+
+int attn_ranges(int Tcap) { return (Tcap + AD_KEYS - 1) / AD_KEYS; }
+
+template <int MT>
+int skinny_launch(int epi, const SkinnySplit& sp, const bf16* A, int lda, const bf16* W, int ldw, void* C, int ldc,
+                  const float* bias, const float* resid, float* partial, int M, int N, hipStream_t s) {
+  const dim3 grid(N / 16, sp.slices);
+  const int threads = 64 * sp.nw;
+#define X(E)                                                                                                     \
+  if (epi == E)                                                                                                  \
+    skinny_gemm_kernel<MT, E><<<grid, threads, 0, s>>>(A, lda, W, ldw, C, ldc, bias, resid, partial, M, N, sp.chunks, \
+                                                       sp.cpu);
+  X(SK_BF16) X(SK_F32) X(SK_RESID) X(SK_GELU)
+#undef X
+  return gpt2mi::check_launch("gemm_skinny");
+}
+
+}  // namespace
+
+GPT2MI_EXPORT size_t gpt2mi_gemm_skinny_workspace(int M, int N, int K) {
+  if (M < 1 || N < 64 || K < 64 || N % 64 || K % 64) return 0;
+  const SkinnySplit sp = skinny_split(N, K);
+  return sp.slices > 1 ? (size_t)sp.slices * M * N : 0;
+}
+
+GPT2MI_EXPORT int gpt2mi_gemm_skinny(int epilogue, int M, int N, int K, const uint16_t* A, int lda, const uint16_t* W,
+                                     int ldw, void* C, int ldc, const float* bias, const float* resid,
+                                     float* workspace, size_t workspace_floats, void* stream) {
+  GPT2MI_REQUIRE(epilogue >= SK_BF16 && epilogue <= SK_GELU, "gemm_skinny: epilogue %d not in [0, 3]", epilogue);
+  GPT2MI_REQUIRE(M >= 1 && M <= 64, "gemm_skinny: M=%d not in [1, 64] (larger M: gpt2mi_gemm)", M);
+  GPT2MI_REQUIRE(N >= 64 && K >= 64 && N % 64 == 0 && K % 64 == 0,
+                 "gemm_skinny: N=%d and K=%d must be positive multiples of 64", N, K);
+  GPT2MI_REQUIRE(lda >= K && ldw >= K && ldc >= N && lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0,
+                 "gemm_skinny: lda=%d, ldw=%d (>= K, multiples of 8) or ldc=%d (>= N, multiple of 4) invalid", lda, ldw,
+                 ldc);
+  const SkinnySplit sp = skinny_split(N, K);
+  const size_t need = sp.slices > 1 ? (size_t)sp.slices * M * N : 0;
+  GPT2MI_REQUIRE(workspace_floats >= need,
+                 "gemm_skinny: workspace too small (%zu floats given, %zu needed for %d K slices)", workspace_floats, need,
+                 sp.slices);
+  GPT2MI_REQUIRE(A && W && C && (need == 0 || workspace), "gemm_skinny: A, W, C or a needed workspace is NULL");
+  GPT2MI_REQUIRE(epilogue != SK_RESID || resid, "gemm_skinny: the RESID epilogue needs resid");
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = need ? workspace : nullptr;
+  const bf16 *a = (const bf16*)A, *w = (const bf16*)W;
+  int rc;
+  switch ((M + 15) / 16) {
+    case 1: rc = skinny_launch<1>(epilogue, sp, a, lda, w, ldw, C, ldc, bias, resid, partial, M, N, s); break;
+    case 2: rc = skinny_launch<2>(epilogue, sp, a, lda, w, ldw, C, ldc, bias, resid, partial, M, N, s); break;
+    case 3: rc = skinny_launch<3>(epilogue, sp, a, lda, w, ldw, C, ldc, bias, resid, partial, M, N, s); break;
+    default: rc = skinny_launch<4>(epilogue, sp, a, lda, w, ldw, C, ldc, bias, resid, partial, M, N, s); break;
+  }
+  if (rc || !partial) return rc;
+  const int g = (M * (N / 4) + 255) / 256;
+#define X(E) \
+  if (epilogue == E) skinny_reduce_kernel<E><<<g, 256, 0, s>>>(partial, sp.slices, C, ldc, bias, resid, M, N);
+  X(SK_BF16) X(SK_F32) X(SK_RESID) X(SK_GELU)
+#undef X
+  return gpt2mi::check_launch("gemm_skinny reduce");
+}
+
+GPT2MI_EXPORT int gpt2mi_kv_store(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, int B, int T_src, int n,
+                                  int t0, int H, int head_dim, int Tcap, void* stream) {
+  GPT2MI_REQUIRE(head_dim == 64, "kv_store: head_dim=%d (the decode kernels implement 64)", head_dim);
+  GPT2MI_REQUIRE(B >= 1 && H >= 1 && Tcap >= 1, "kv_store: B=%d, H=%d, Tcap=%d must be positive", B, H, Tcap);
+  GPT2MI_REQUIRE(n >= 1 && n <= T_src, "kv_store: n=%d not in [1, T_src=%d]", n, T_src);
+  GPT2MI_REQUIRE(t0 >= 0 && (long long)t0 + n <= Tcap, "kv_store: t0=%d + n=%d exceeds the cache length Tcap=%d", t0, n,
+                 Tcap);
+  GPT2MI_REQUIRE(qkv && kcache && vcache, "kv_store: qkv and the caches must not be NULL");
+  const size_t total = (size_t)B * n * (2 * H * 64 / 8);
+  kv_store_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
+      (const bf16*)qkv, (bf16*)kcache, (bf16*)vcache, B, T_src, n, t0, H, Tcap);
+  return gpt2mi::check_launch("kv_store");
+}
+
+GPT2MI_EXPORT size_t gpt2mi_attn_decode_workspace(int B, int H, int Tcap) {
+  if (B < 1 || H < 1 || Tcap < 1) return 0;
+  return (size_t)B * H * attn_ranges(Tcap) * 66;  // (max, sum) + acc[64] per range
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_decode(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
+                                     float* workspace, size_t workspace_floats, int B, int H, int head_dim, int Tcap,
+                                     int pos, void* stream) {
+  GPT2MI_REQUIRE(head_dim == 64, "attn_decode: head_dim=%d (the decode kernels implement 64)", head_dim);
+  GPT2MI_REQUIRE(B >= 1 && H >= 1 && Tcap >= 1 && (long long)B * H <= 65535,
+                 "attn_decode: B=%d, H=%d, Tcap=%d must be positive and B*H <= 65535", B, H, Tcap);
+  GPT2MI_REQUIRE(pos >= 0 && pos < Tcap, "attn_decode: pos=%d not in [0, Tcap=%d)", pos, Tcap);
+  const size_t need = gpt2mi_attn_decode_workspace(B, H, Tcap);
+  GPT2MI_REQUIRE(workspace_floats >= need,
+                 "attn_decode: workspace too small (%zu floats given, %zu needed)", workspace_floats, need);
+  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
+                 "attn_decode: qkv, the caches, out and workspace must not be NULL");
+  hipStream_t s = (hipStream_t)stream;
+  const int nr_max = attn_ranges(Tcap), nr = pos / AD_KEYS + 1;
+  float* ws_ml = workspace;
+  float* ws_acc = workspace + (size_t)B * H * nr_max * 2;
+  attn_decode_kernel<<<dim3(nr, B * H), 64, 0, s>>>((const bf16*)qkv, (bf16*)kcache, (bf16*)vcache, ws_ml, ws_acc, H,
+                                                    Tcap, pos, nr_max);
+  int rc = gpt2mi::check_launch("attn_decode");
+  if (rc) return rc;
+  attn_combine_kernel<<<B * H, 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, nr, nr_max);
+  return gpt2mi::check_launch("attn_decode combine");
+}
+
+GPT2MI_EXPORT int gpt2mi_embed_decode(const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C,
+                                      int pos, void* stream) {
+  GPT2MI_REQUIRE(B >= 1 && C >= 4 && C % 4 == 0, "embed_decode: B=%d must be positive and C=%d a multiple of 4", B, C);
+  GPT2MI_REQUIRE(pos >= 0, "embed_decode: pos=%d is negative", pos);
+  GPT2MI_REQUIRE(tok && wte && wpe && x, "embed_decode: tok, wte, wpe and x must not be NULL");
+  embed_decode_kernel<<<(B * (C / 4) + 255) / 256, 256, 0, (hipStream_t)stream>>>(tok, wte, wpe, x, B, C, pos);
+  return gpt2mi::check_launch("embed_decode");
+}
+
+GPT2MI_EXPORT int gpt2mi_decode_step(const gpt2mi_decode_plan* P, const int64_t* tok, int pos, void* stream) {
+  GPT2MI_REQUIRE(P != nullptr, "decode_step: plan is NULL");
+  const int B = P->B, C = P->C, H = P->H;
+  GPT2MI_REQUIRE(B >= 1 && B <= 64, "decode_step: B=%d not in [1, 64]", B);
+  GPT2MI_REQUIRE(H >= 1 && C == 64 * H, "decode_step: head_dim = C/H must be 64 (C=%d, H=%d)", C, H);
+  GPT2MI_REQUIRE(P->L >= 1 && P->Vp >= 64 && P->Vp % 64 == 0, "decode_step: L=%d, Vp=%d (a multiple of 64) invalid", P->L,
+                 P->Vp);
+  GPT2MI_REQUIRE(pos >= 0 && pos < P->Tcap, "decode_step: pos=%d not in [0, Tcap=%d)", pos, P->Tcap);
+  GPT2MI_REQUIRE(P->attn_ws_floats >= gpt2mi_attn_decode_workspace(B, H, P->Tcap),
+                 "decode_step: attention workspace too small (%zu floats)", P->attn_ws_floats);
+  size_t need = 0;
+  const int shapes[5][2] = {{3 * C, C}, {C, C}, {4 * C, C}, {C, 4 * C}, {P->Vp, C}};
+  for (const auto& sh : shapes) need = std::max(need, gpt2mi_gemm_skinny_workspace(B, sh[0], sh[1]));
+  GPT2MI_REQUIRE(P->gemm_ws_floats >= need, "decode_step: GEMM workspace too small (%zu floats given, %zu needed)",
+                 P->gemm_ws_floats, need);
+  GPT2MI_REQUIRE(P->layers && tok, "decode_step: layers and tok must not be NULL");
+#define STEP(call)       \
+  do {                   \
+    const int rc = call; \
+    if (rc) return rc;   \
+  } while (0)
+  float *x = P->x, *xmid = P->xmid;
+  float* gws = P->gemm_ws;
+  const size_t gwn = P->gemm_ws_floats;
+  STEP(gpt2mi_embed_decode(tok, P->wte, P->wpe, x, B, C, pos, stream));
+  for (int l = 0; l < P->L; ++l) {
+    const gpt2mi_decode_layer& Y = P->layers[l];
+    STEP(gpt2mi_layernorm_fwd(x, Y.ln1_w, Y.ln1_b, P->ln, nullptr, P->mean, P->rstd, B, C, P->eps, stream));
+    STEP(gpt2mi_gemm_skinny(SK_BF16, B, 3 * C, C, P->ln, C, Y.qkv_w, C, P->qkv, 3 * C, Y.qkv_b, nullptr, gws, gwn, stream));
+    STEP(gpt2mi_attn_decode(P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap, pos,
+                            stream));
+    STEP(gpt2mi_gemm_skinny(SK_RESID, B, C, C, P->ao, C, Y.proj_w, C, xmid, C, Y.proj_b, x, gws, gwn, stream));
+    STEP(gpt2mi_layernorm_fwd(xmid, Y.ln2_w, Y.ln2_b, P->ln, nullptr, P->mean, P->rstd, B, C, P->eps, stream));
+    STEP(gpt2mi_gemm_skinny(SK_GELU, B, 4 * C, C, P->ln, C, Y.fc1_w, C, P->h, 4 * C, Y.fc1_b, nullptr, gws, gwn, stream));
+    STEP(gpt2mi_gemm_skinny(SK_RESID, B, C, 4 * C, P->h, 4 * C, Y.fc2_w, 4 * C, x, C, Y.fc2_b, xmid, gws, gwn, stream));
+  }
+  STEP(gpt2mi_layernorm_fwd(x, P->lnf_w, P->lnf_b, P->ln, nullptr, P->mean, P->rstd, B, C, P->eps, stream));
+  STEP(gpt2mi_gemm_skinny(SK_F32, B, P->Vp, C, P->ln, C, P->wte_bf16, C, P->logits, P->Vp, nullptr, nullptr, gws, gwn,
+                          stream));
+#undef STEP
+  return 0;
+}

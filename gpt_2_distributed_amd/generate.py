@@ -1,0 +1,70 @@
+"""Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
+--prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --seed S --batch B]``.
+
+Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
+``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
+included). No tokenizer is shipped: prompts and outputs are GPT-2 BPE ids (50256 = <|endoftext|>)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+from .model import GPT2, GPT2Config, MODEL_SIZES
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p.add_argument("--checkpoint", required=True, help="a step_XXXXXXX directory written by save_checkpoint")
+    p.add_argument("--model", default="124M", choices=sorted(MODEL_SIZES) + ["auto"],
+                   help="model size; auto: widths and depth from the checkpoint (n_head = n_embd / 64)")
+    p.add_argument("--prompt_ids", default="50256", help="comma-separated token ids")
+    p.add_argument("--max_new_tokens", type=int, default=64)
+    p.add_argument("--temperature", type=float, default=1.0)
+    p.add_argument("--top_k", type=int, default=None)
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--batch", type=int, default=1)
+    p.add_argument("--eos_token_id", type=int, default=None)
+    return p.parse_args(argv)
+
+
+def load_model(ckpt_dir: str, size: str) -> GPT2:
+    """A GPT2 on cuda:0 with the weights of ``ckpt_dir``/model.pt (as load_checkpoint restores them); the vocabulary
+    and context length are read from the checkpoint's embedding tables."""
+    sd = torch.load(os.path.join(ckpt_dir, "model.pt"), map_location="cpu", weights_only=True)
+    V, C = sd["transformer.wte.weight"].shape
+    L = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("transformer.h."))
+    dims = dict(n_layer=L, n_head=C // 64, n_embd=C) if size == "auto" else dict(MODEL_SIZES[size])
+    if (dims["n_embd"], dims["n_layer"]) != (C, L):
+        raise ValueError(f"--model {size} is {dims['n_layer']} layers of width {dims['n_embd']}, the checkpoint {L} "
+                         f"of width {C}")
+    cfg = GPT2Config(vocab_size=V, n_positions=sd["transformer.wpe.weight"].shape[0], **dims)
+    model = GPT2(cfg).to("cuda:0")
+    with torch.no_grad():
+        for n, p in model.named_parameters():
+            p.copy_(sd[n])
+    model.engine().refresh_shadow()
+    return model
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
+    prompt = [int(t) for t in a.prompt_ids.split(",") if t.strip()]
+    if not prompt:
+        raise SystemExit("--prompt_ids is empty")
+    model = load_model(a.checkpoint, a.model)
+    idx = torch.tensor([prompt] * a.batch, dtype=torch.int64, device="cuda:0")
+    gen = torch.Generator(device="cuda:0").manual_seed(a.seed)
+    out = model.generate(idx, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, generator=gen,
+                         eos_token_id=a.eos_token_id)
+    for row in out.tolist():
+        print(json.dumps(row))
+    return 0
+
+
+if __name__ == "__main__":
+    os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")  # kernel arguments from device memory (see __init__.py)
+    sys.exit(main())

@@ -1,0 +1,222 @@
+"""Autoregressive generation: a per-layer key/value cache, one-token decode steps and nanoGPT's ``generate``.
+
+The reference (model.py, train_gpt2_distributed.py) trains and evaluates only; continuing a prompt with it means
+calling ``model(idx)`` on the whole growing sequence for every new token. Here a prompt is run once through the
+engine's trunk forward (``DecodeSession.prefill``), its keys and values are copied into the cache, and every further
+token is one call of ``gpt2mi_decode_step`` (csrc/decode.hip): weight-streaming skinny GEMMs and single-query attention
+over the cache, about 10 launches per layer issued from C.
+
+Numerics are the autocast path's whatever the autocast state: bf16 GEMM operands from the engine's weight shadow, fp32
+accumulation, fp32 residual stream / LayerNorm / softmax, dropout off (p = 0 whatever ``model.training`` is, and
+``.training`` is not touched). Logits are fp32. ``model.precision == "fp32"`` has no decode kernels and raises.
+
+Generation leaves training untouched: it does not advance the engine's dropout stream (``_step_seed``) or its forward
+token, and does not replace the activations record a pending backward reads. It does run the prompt through the
+engine's workspace, so (a) it may evict the training workspace of another (B, T) shape, which the next training
+forward re-allocates, and (b) it must not be called between a forward and its backward.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import torch
+
+from . import _lib as K
+
+BF16 = torch.bfloat16
+F32 = torch.float32
+MAX_BATCH = 64  # rows of the skinny GEMM (gpt2mi_gemm_skinny)
+
+
+def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None,
+                generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """Next token ids [B] from logits [B, V] (nanoGPT's rule; pure torch, any device).
+
+    ``temperature == 0`` is greedy argmax. Otherwise ``logits / temperature``, optionally everything below the
+    ``top_k``-th largest logit of a row set to -inf, softmax, and one ``torch.multinomial`` draw per row from
+    ``generator``."""
+    if logits.dim() != 2:
+        raise ValueError(f"sample_next takes logits [B, V] (got {tuple(logits.shape)})")
+    if temperature < 0:
+        raise ValueError(f"temperature must be >= 0 (got {temperature})")
+    if top_k is not None and top_k < 1:
+        raise ValueError(f"top_k must be >= 1 (got {top_k})")
+    logits = logits.float()
+    if temperature == 0:
+        return logits.argmax(dim=-1)
+    logits = logits / temperature
+    if top_k is not None and top_k < logits.size(-1):
+        kth = torch.topk(logits, top_k, dim=-1).values[:, -1:]
+        logits = logits.masked_fill(logits < kth, float("-inf"))
+    probs = torch.softmax(logits, dim=-1)
+    return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
+
+
+def _check_model(model):
+    """The engine of a model generation can run on (see the module docstring), or the reason it cannot."""
+    if getattr(model, "precision", "auto") == "fp32":
+        raise NotImplementedError('generation computes in bf16 with fp32 accumulation; model.precision == "fp32" has '
+                                  "no decode kernels")
+    if not model.arena.is_cuda:
+        raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the model to a cuda device "
+                           "(there is no CPU fallback)")
+    eng = model.engine()
+    if eng.param_provider is not None or eng.store is not None:
+        raise NotImplementedError("generation needs the whole model's parameters on this rank: a "
+                                  "FullyShardedDataParallel-wrapped model keeps only its shard (gather a state_dict into "
+                                  "an unwrapped GPT2 and generate with that)")
+    cfg = model.config
+    if cfg.n_embd != 64 * cfg.n_head:
+        raise NotImplementedError(f"the decode kernels implement head_dim 64 (n_embd {cfg.n_embd} / n_head {cfg.n_head})")
+    return eng
+
+
+class DecodeSession:
+    """The key/value cache of ``batch_size`` sequences of up to ``max_len`` tokens, and the step that extends them.
+
+    Cache: per layer ``kcache`` and ``vcache``, bf16 ``[B][H][Tcap][64]`` (a (b, h) stream is contiguous 128-byte rows).
+    ``prefill(idx)`` starts the sequences from a prompt, ``step(tokens)`` appends one token to each; both return the fp32
+    logits ``[B, V]`` of the newest position. ``pos`` is the number of cached tokens."""
+
+    def __init__(self, model, batch_size: int, max_len: Optional[int] = None):
+        eng = _check_model(model)
+        cfg = model.config
+        Tcap = cfg.n_positions if max_len is None else int(max_len)
+        if not 1 <= batch_size <= MAX_BATCH:
+            raise ValueError(f"batch_size {batch_size} not in [1, {MAX_BATCH}] (the decode GEMM's row limit)")
+        if not 1 <= Tcap <= cfg.n_positions:
+            raise ValueError(f"max_len {Tcap} not in [1, n_positions={cfg.n_positions}]")
+        self.model, self.engine, self.cfg = model, eng, cfg
+        self.B, self.Tcap, self.pos = int(batch_size), Tcap, 0
+        B, C, H, L, Vp = self.B, cfg.n_embd, cfg.n_head, cfg.n_layer, model.vpad
+        dev = eng.device
+        e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
+        self.kcache = e(L, B, H, Tcap, 64)
+        self.vcache = e(L, B, H, Tcap, 64)
+        self.x, self.xmid = e(B, C, dt=F32), e(B, C, dt=F32)
+        self.ln, self.qkv, self.ao, self.h = e(B, C), e(B, 3 * C), e(B, C), e(B, 4 * C)
+        self.mean, self.rstd = e(B, dt=F32), e(B, dt=F32)
+        self.attn_ws = e(max(K.attn_decode_workspace(B, H, Tcap), 1), dt=F32)
+        shapes = [(3 * C, C), (C, C), (4 * C, C), (C, 4 * C), (Vp, C)]
+        self.gemm_ws = e(max(max(K.gemm_skinny_workspace(B, n, k) for n, k in shapes), 1), dt=F32)
+        self.logits = e(B, Vp, dt=F32)
+        self._plan = self._build_plan()
+
+    def _build_plan(self) -> K.DecodePlan:
+        eng, cfg = self.engine, self.cfg
+        p = lambda n: eng.p(n).data_ptr()  # noqa: E731  fp32 master view
+        w = lambda n: eng.w16(n).data_ptr()  # noqa: E731  bf16 shadow
+        self._layers = (K.DecodeLayer * cfg.n_layer)()  # host array the plan points at: kept alive with the session
+        for l, Y in enumerate(self._layers):
+            pre = f"transformer.h.{l}."
+            Y.ln1_w, Y.ln1_b, Y.ln2_w, Y.ln2_b = (p(pre + s) for s in ("ln1.weight", "ln1.bias", "ln2.weight",
+                                                                         "ln2.bias"))
+            Y.qkv_w, Y.proj_w, Y.fc1_w, Y.fc2_w = (w(pre + s) for s in ("attn.qkv.weight", "attn.proj.weight",
+                                                                         "mlp.fc1.weight", "mlp.fc2.weight"))
+            Y.qkv_b, Y.proj_b, Y.fc1_b, Y.fc2_b = (p(pre + s) for s in ("attn.qkv.bias", "attn.proj.bias",
+                                                                         "mlp.fc1.bias", "mlp.fc2.bias"))
+            Y.kcache, Y.vcache = self.kcache[l].data_ptr(), self.vcache[l].data_ptr()
+        P = K.DecodePlan()
+        P.B, P.C, P.H, P.L, P.Vp, P.Tcap = self.B, cfg.n_embd, cfg.n_head, cfg.n_layer, self.model.vpad, self.Tcap
+        P.eps = cfg.layer_norm_eps
+        P.wte, P.wpe = p("transformer.wte.weight"), p("transformer.wpe.weight")
+        P.lnf_w, P.lnf_b = p("transformer.ln_f.weight"), p("transformer.ln_f.bias")
+        P.wte_bf16 = w("transformer.wte.weight")  # the zero-padded [Vp, C] slot: the tied lm_head
+        P.layers = ctypes.cast(self._layers, ctypes.POINTER(K.DecodeLayer))
+        for n in ("x", "xmid", "ln", "qkv", "ao", "h", "mean", "rstd", "attn_ws", "gemm_ws", "logits"):
+            setattr(P, n, getattr(self, n).data_ptr())
+        P.attn_ws_floats, P.gemm_ws_floats = self.attn_ws.numel(), self.gemm_ws.numel()
+        return P
+
+    def _ready(self, sync: bool):
+        if self.model._engine is not self.engine:
+            raise RuntimeError("the model was moved or copied after this DecodeSession was created: call "
+                               "model.decoder() again")
+        if sync:  # a foreign in-place update of the weights since the last forward: re-cast the bf16 shadow
+            self.engine._sync_shadows(BF16, False)
+
+    def reset(self) -> None:
+        """Rewind to an empty cache (the next call is ``prefill``)."""
+        self.pos = 0
+
+    @torch.no_grad()
+    def prefill(self, idx: torch.Tensor) -> torch.Tensor:
+        """Run the prompt ``idx`` [B, P] and cache its keys and values; fp32 logits [B, V] of its last position.
+
+        The prompt goes through the engine's trunk forward (the training kernels at bf16, p = 0, padded to the attention
+        tile), the K / V columns of each layer's qkv activations are copied into the cache, and the lm_head runs on the
+        last valid row of each sequence only."""
+        eng, cfg = self.engine, self.cfg
+        if idx.dim() != 2 or idx.size(0) != self.B:
+            raise ValueError(f"prefill takes idx [B={self.B}, P] (got {tuple(idx.shape)})")
+        P = idx.size(1)
+        if not 1 <= P <= self.Tcap:
+            raise ValueError(f"prompt length {P} not in [1, max_len={self.Tcap}]")
+        if not idx.is_cuda:
+            raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
+        self._ready(True)
+        eng.gemm_sched = eng.base_sched
+        idx_p, _, _ = eng._pad(idx, None)
+        B, Tp = idx_p.shape
+        C, H, Vp = cfg.n_embd, cfg.n_head, self.model.vpad
+        ws = eng.workspace(B, Tp, BF16)
+        # p = 0: no dropout site reads its seed, so the step's dropout stream is not advanced
+        eng._trunk_fwd(ws, idx_p, B, Tp, P, BF16, 0.0, 0.0, eng._seeds(0))
+        for l in range(cfg.n_layer):
+            K.kv_store(ws.blocks[l].qkv, self.kcache[l], self.vcache[l], B, Tp, P, 0, H, 64, self.Tcap)
+        last = ws.lnf.view(B, Tp, C)[:, P - 1]  # rows b*Tp + P-1: row stride Tp*C
+        K.gemm_skinny(K.EPI_F32, B, Vp, C, last, Tp * C, eng.w16("transformer.wte.weight"), C, self.logits, Vp,
+                      workspace=self.gemm_ws)
+        self.pos = P
+        return self.logits[:, :cfg.vocab_size].clone()
+
+    @torch.no_grad()
+    def step(self, tokens: torch.Tensor) -> torch.Tensor:
+        """Append ``tokens`` [B] (one per sequence) at position ``pos``; fp32 logits [B, V] for the position after."""
+        if self.pos == 0:
+            raise RuntimeError("step before prefill: the cache is empty")
+        if self.pos >= self.Tcap:
+            raise ValueError(f"the cache is full ({self.Tcap} positions): reset() or a larger max_len")
+        if tokens.shape != (self.B,):
+            raise ValueError(f"step takes tokens [B={self.B}] (got {tuple(tokens.shape)})")
+        if not tokens.is_cuda:
+            raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
+        self._ready(False)  # (the weights are those of the prefill: the shadow is synced there)
+        tok = tokens.contiguous() if tokens.dtype == torch.int64 else tokens.long()
+        K.decode_step(self._plan, tok, self.pos)
+        self.pos += 1
+        return self.logits[:, :self.cfg.vocab_size].clone()
+
+
+@torch.no_grad()
+def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
+             generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None) -> torch.Tensor:
+    """``GPT2.generate``: see there."""
+    if idx.dim() != 2:
+        raise ValueError(f"generate takes idx [B, P] (got {tuple(idx.shape)})")
+    B, P = idx.shape
+    n = int(max_new_tokens)
+    if n < 0:
+        raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
+    if P + n > model.config.n_positions:
+        raise ValueError(f"prompt length {P} + max_new_tokens {n} > n_positions {model.config.n_positions}")
+    _check_model(model)
+    idx = idx.long()
+    if n == 0:
+        return idx.clone()
+    sess = DecodeSession(model, B, P + n)
+    out = [idx]
+    done = torch.zeros(B, dtype=torch.bool, device=idx.device)
+    logits = sess.prefill(idx)
+    for i in range(n):
+        nxt = sample_next(logits, temperature, top_k, generator)
+        if eos_token_id is not None:
+            nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)  # a finished row keeps emitting eos
+            done = done | (nxt == eos_token_id)
+        out.append(nxt[:, None])
+        if eos_token_id is not None and bool(done.all()):
+            break
+        if i + 1 < n:
+            logits = sess.step(nxt)
+    return torch.cat(out, dim=1)

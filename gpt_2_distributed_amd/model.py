@@ -271,6 +271,31 @@ class GPT2(nn.Module):
                                "inputs to a cuda device (there is no CPU fallback)")
         return self.engine().forward(idx, labels)
 
+    # ---- generation (nanoGPT's surface; the reference has none) ----------------------------------------
+    def decoder(self, batch_size: int, max_len: Optional[int] = None):
+        """A ``generation.DecodeSession``: the per-layer key/value cache (L x 2 x bf16 ``[B][H][Tcap][64]``,
+        ``Tcap = max_len or n_positions``) of ``batch_size`` sequences with ``prefill(idx)`` / ``step(tokens)``."""
+        from .generation import DecodeSession
+        return DecodeSession(self, batch_size, max_len)
+
+    def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
+                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None) -> torch.Tensor:
+        """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
+        sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
+        filter, softmax and ``torch.multinomial`` with ``generator`` (``generation.sample_next``). With
+        ``eos_token_id`` a finished row keeps emitting it and generation stops once every row has finished (n is then
+        smaller). ``P + max_new_tokens > n_positions`` raises ``ValueError``.
+
+        Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
+        the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
+        ``NotImplementedError``. It does not advance the dropout stream or touch what a later backward needs, so a
+        training run with a ``generate`` between two steps is bit-identical to one without, but it may evict the
+        engine's training workspace (re-allocated by the next forward) and must not run between a forward and its
+        backward. Through ``DistributedDataParallel`` call ``.module.generate``; a ``FullyShardedDataParallel``-wrapped
+        model holds only a shard of the parameters and raises ``NotImplementedError``."""
+        from .generation import generate
+        return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id)
+
     # ---- optimizer (nanoGPT-style name the north star uses) -----------------------------------------
     def configure_optimizers(self, weight_decay: float = 0.1, learning_rate: float = 1e-4,
                              betas=(0.9, 0.95), device_type: Optional[str] = None, eps: float = 1e-8):

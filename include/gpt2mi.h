@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 13
+#define GPT2MI_ABI_VERSION 14
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -222,6 +222,66 @@ int gpt2mi_memset_zero(void* ptr, size_t bytes, void* stream);
  * the full-arena zero of optimizer.zero_grad() (torch/optim/optimizer.py zero_grad via
  * train_gpt2_distributed.py:409-425) when the backward's weight-gradient GEMMs write their slots outright. */
 int gpt2mi_zero_ranges(float* base, const int64_t* ranges, int n, void* stream);
+
+/* ---- v14: autoregressive decode (csrc/decode.hip). The reference has no generation loop; these are the nanoGPT /
+ * llm.c style `generate` of the model.py forward (model.py:335-351) with a per-layer key/value cache, one token per
+ * sequence and step. bf16 operands, fp32 accumulation, head_dim 64, no dropout, no atomics: every reduction runs in
+ * a fixed order, so outputs are bitwise reproducible. ---- */
+/* Skinny forward GEMM (nn.Linear at M = batch rows): C[m][n] = epi(sum_k A[m][k] W[n][k] + bias[n]), A bf16 [M][K]
+ * (row stride lda), W bf16 [N][K] (row stride ldw: the forward layout of the weight shadow), 1 <= M <= 64, N and K
+ * multiples of 64 (N need not be a multiple of 256). epilogue: 0 BF16 (+bias), 1 F32 (+bias), 2 RESID: C fp32 =
+ * resid + acc + bias (resid row stride ldc, not aliasing C), 3 GELU: C = bf16(gelu_tanh(acc + bias)) (no aux). bias may
+ * be NULL. W streams from HBM once, in 16-column strips; K is split across the waves of a block and, while the
+ * strips alone leave CUs idle, across blocks whose fp32 partial sums go through `workspace`
+ * (>= gpt2mi_gemm_skinny_workspace(M, N, K) floats; may be NULL when that is 0) and are summed in split order. The
+ * split depends on (N, K) only and every output row is formed from its own A row: row m has the same bits at any M. */
+int gpt2mi_gemm_skinny(int epilogue, int M, int N, int K, const uint16_t* A, int lda, const uint16_t* W, int ldw,
+                       void* C, int ldc, const float* bias, const float* resid, float* workspace,
+                       size_t workspace_floats, void* stream);
+size_t gpt2mi_gemm_skinny_workspace(int M, int N, int K);
+/* Prefill's cache fill: for b < B, t < n copy the K and V columns of row b*T_src + t of qkv [B*T_src, 3C] (C = H*64)
+ * to position t0 + t of kcache / vcache, each bf16 [B][H][Tcap][64] (one layer). Rows t >= n of a sequence (tile
+ * padding) are not copied; nothing else of the cache is written. */
+int gpt2mi_kv_store(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, int B, int T_src, int n, int t0, int H,
+                    int head_dim, int Tcap, void* stream);
+/* Single-query attention over the cache (model.py:124-155 for the newest position): qkv bf16 [B, 3C] of the new
+ * token; its k and v are written to position pos of the caches, and out[b, h*64..] = softmax(q.K[0..pos]^T / 8)
+ * V[0..pos] (bf16 [B, C]). Keys are split in ranges of 32 across workgroups; the partial (max, sum, acc) go through
+ * `workspace` (>= gpt2mi_attn_decode_workspace(B, H, Tcap) floats) and are combined in range order. Cache positions
+ * > pos are neither read nor written. */
+int gpt2mi_attn_decode(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out, float* workspace,
+                       size_t workspace_floats, int B, int H, int head_dim, int Tcap, int pos, void* stream);
+size_t gpt2mi_attn_decode_workspace(int B, int H, int Tcap);
+/* K1 for one new token per sequence: x[b,:] = wte[tok[b],:] + wpe[pos,:] (fp32, no dropout). */
+int gpt2mi_embed_decode(const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C, int pos,
+                        void* stream);
+
+/* One decode step as one call (about 10 launches per layer without a Python round trip each). All pointers device
+ * memory except `layers` (a host array of L entries). */
+typedef struct gpt2mi_decode_layer {
+  const float *ln1_w, *ln1_b, *ln2_w, *ln2_b;             /* fp32 [C] */
+  const uint16_t *qkv_w, *proj_w, *fc1_w, *fc2_w;         /* bf16 [3C][C], [C][C], [4C][C], [C][4C] */
+  const float *qkv_b, *proj_b, *fc1_b, *fc2_b;            /* fp32 */
+  uint16_t *kcache, *vcache;                              /* bf16 [B][H][Tcap][64] */
+} gpt2mi_decode_layer;
+typedef struct gpt2mi_decode_plan {
+  int B, C, H, L, Vp, Tcap;                               /* batch, n_embd, heads, layers, padded vocab, cache length */
+  float eps;                                              /* LayerNorm eps */
+  const float *wte, *wpe, *lnf_w, *lnf_b;                 /* fp32 tables and the final LayerNorm */
+  const uint16_t* wte_bf16;                               /* bf16 [Vp][C]: the tied lm_head */
+  const gpt2mi_decode_layer* layers;                      /* host array [L] */
+  float *x, *xmid;                                        /* fp32 [B][C] residual stream */
+  uint16_t *ln, *qkv, *ao, *h;                            /* bf16 [B][C], [B][3C], [B][C], [B][4C] */
+  float *mean, *rstd;                                     /* fp32 [B] */
+  float* attn_ws;                                         /* gpt2mi_attn_decode_workspace(B, H, Tcap) floats */
+  size_t attn_ws_floats;
+  float* gemm_ws;                                         /* the largest gpt2mi_gemm_skinny_workspace of the step */
+  size_t gemm_ws_floats;
+  float* logits;                                          /* fp32 [B][Vp] */
+} gpt2mi_decode_plan;
+/* embed -> per layer (LN1, qkv, attention at pos, proj + resid, LN2, fc1 + GELU, fc2 + resid) -> ln_f -> lm_head into
+ * plan->logits, for the B tokens `tok` (device int64 [B]) at position pos (model.py:295-351 at one position). */
+int gpt2mi_decode_step(const gpt2mi_decode_plan* plan, const int64_t* tok, int pos, void* stream);
 
 #ifdef __cplusplus
 }
