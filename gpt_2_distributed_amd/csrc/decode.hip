@@ -27,7 +27,7 @@ enum { SK_BF16 = 0, SK_F32 = 1, SK_RESID = 2, SK_GELU = 3 };
 constexpr int SK_MAX_WAVES = 4;
 
 __device__ __forceinline__ float gelu_tanh1(float u) {
-  // NewGELU in the sigmoid form of gemm_common.h gelu4: u / (1 + 2^(u (A + B u^2)))
+  // NewGELU in the sigmoid form of gemm_epilogue.h gelu4: u / (1 + 2^(u (A + B u^2)))
   const float k0 = 0.7978845608028654f, k1 = 0.044715f, m2log2e = -2.0f * 1.4426950408889634f;
   const float arg = u * __builtin_fmaf(u * u, k0 * k1 * m2log2e, k0 * m2log2e);
   return u * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(arg) + 1.f);

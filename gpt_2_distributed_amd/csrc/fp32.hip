@@ -15,7 +15,7 @@
 //    Dropout masks are the bf16 kernel's (seed, head, query-pair, key) hash, so both precisions
 //    drop the same probabilities.
 #include "common.h"
-#include "gemm_common.h"
+#include "gemm_epilogue.h"
 #include "gpt2mi.h"
 
 namespace {

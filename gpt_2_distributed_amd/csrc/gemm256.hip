@@ -1,4 +1,4 @@
-// bf16 MFMA GEMM, 256x256 block tile — the forward / dgrad workhorse (see gemm.hip for the API).
+// bf16 MFMA GEMM, 256x256 block tile — the 2-stage kernel (see gemm_api.hip for the API).
 //
 // 512 threads = 8 waves as 2 (M) x 4 (N), 128x64 outputs per wave (8x4 v_mfma_f32_16x16x32_bf16
 // accumulators, 128 registers), BK = 64, one workgroup per CU, 2 LDS stages (2 x 64 KiB).
@@ -18,7 +18,7 @@
 // CONSECUTIVE output columns of one row -> 8-B (bf16) / 16-B (fp32) stores and 16-B bias /
 // residual / pre-activation loads, no LDS round trip.
 #include "common.h"
-#include "gemm_common.h"
+#include "gemm_epilogue.h"
 
 namespace {
 
@@ -63,10 +63,6 @@ __device__ __forceinline__ void dma_tile(const bf16* __restrict__ src, int ld, i
 #define WG_BUFDMA 1
 #endif
 GPT2MI_PRODUCT_KNOB(WG_BUFDMA, 1);
-#ifndef WG_ABL
-#define WG_ABL 0
-#endif
-GPT2MI_PRODUCT_KNOB(WG_ABL, 0);
 __device__ __forceinline__ uint32_t mc_lane_off(int ld, int wid, int par, int lane) {
   const int k = 8 * (wid & 1) + 2 * par + (lane >> 5);  // k-row mod 16 of instruction t = par (mod 2)
   return (uint32_t)(((lane >> 5) * ld + 8 * ((lane & 31) ^ mc_swz(k))) * (int)sizeof(bf16));
@@ -80,12 +76,6 @@ __device__ __forceinline__ void dma_tile_mc_buf(const bf16* __restrict__ src, in
     const int soff = ((2 * ins) * ld + row0) * (int)sizeof(bf16);
     lds_dma16_buf(rs, loff[t & 1], soff, tile + ins * 1024);
   }
-}
-
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ s16x8 s16x8v(int v) {
-  const short x = (short)v;
-  return s16x8{x, x, x, x, x, x, x, x};
 }
 
 __device__ __forceinline__ bf16x8 frag_kc(const char* base, int row, int chunk) {
@@ -134,9 +124,6 @@ __global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmParams P) {
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   constexpr bool kBufDma = WG_BUFDMA && A_T && B_T;  // the weight-gradient instantiation
-  // WG_ABL (tools/wgrad_ablation.sh; never set in the product build): the wgrad main loop with parts removed
-  // (1: MFMAs, 2: fragment reads, 4: next-tile DMAs) to time what bounds it. Results are garbage.
-  constexpr int kAbl = WG_ABL;
   [[maybe_unused]] uint32_t loff_a[2] = {0, 0}, loff_b[2] = {0, 0};
   if constexpr (kBufDma) {
     loff_a[0] = mc_lane_off(P.lda, wid, 0, lane);
@@ -159,7 +146,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmParams P) {
   for (int kt = 0; kt < nk; ++kt) {
     const char* As = smem + (kt & 1) * kStageBytes;
     const char* Bs = As + kOpBytes;
-    if (!(kAbl & 4) && kt + 1 < nk) stage(kbeg + (kt + 1) * BK, smem + ((kt + 1) & 1) * kStageBytes);
+    if (kt + 1 < nk) stage(kbeg + (kt + 1) * BK, smem + ((kt + 1) & 1) * kStageBytes);
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       bf16x8 bf[4];
@@ -172,47 +159,19 @@ __global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmParams P) {
         bf16x8 af[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) af[i] = frag_mc(As, 32 * kk, wm * 128 + 16 * i, lane);
-        if constexpr (kAbl & 2) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) af[i] = __builtin_bit_cast(bf16x8, s16x8v(lane + i + kt));
-#pragma unroll
-          for (int j = 0; j < 4; ++j) bf[j] = __builtin_bit_cast(bf16x8, s16x8v(lane - j - kt));
-        }
-        if constexpr (kAbl & 1) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) asm volatile("" ::"v"(af[i]));
-#pragma unroll
-          for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(bf[j]));
-        } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af[i], acc[i][j], 0, 0, 0);
-        }
       } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           bf16x8 af;
           if constexpr (!A_T) af = frag_kc(As, wm * 128 + 16 * i + (lane & 15), 4 * kk + (lane >> 4));
           else af = frag_mc(As, 32 * kk, wm * 128 + 16 * i, lane);
-          if constexpr (kAbl & 2) {
-            af = __builtin_bit_cast(bf16x8, s16x8v(lane + i + kt));
-            if (i == 0) {
 #pragma unroll
-              for (int j = 0; j < 4; ++j) bf[j] = __builtin_bit_cast(bf16x8, s16x8v(lane - j - kt));
-            }
-          }
-          if constexpr (kAbl & 1) {
-            asm volatile("" ::"v"(af));
-            if (i == 0) {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) asm volatile("" ::"v"(bf[j]));
-            }
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af, acc[i][j], 0, 0, 0);
-          }
+          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[j], af, acc[i][j], 0, 0, 0);
         }
       }
     }
@@ -249,177 +208,28 @@ __global__ __launch_bounds__(kThreads, 1) void gemm256_kernel(GemmParams P) {
 }
 
 template <bool A_T, bool B_T, int EPI>
-int launch(const GemmParams& P, hipStream_t s, int splits) {
-  dim3 grid(((P.M + BM - 1) / BM) * (P.N / BN) * splits);
-  gemm256_kernel<A_T, B_T, EPI><<<grid, kThreads, 0, s>>>(P);
+int launch(const gpt2mi::GemmPlan& plan, const GemmParams& P, hipStream_t s) {
+  gemm256_kernel<A_T, B_T, EPI><<<dim3(plan.grid), kThreads, 0, s>>>(P);
   return gpt2mi::check_launch("gemm256");
-}
-
-// out[i] (+)= sum_z slab[z][i]   (fixed summation order: deterministic). The slabs' loads go out in groups of 8 before
-// their adds (in split order: the same bits as one load per add), so a thread keeps 8 loads in flight instead of one
-// (the 27-split proj reduction was latency-bound)
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, int splits, size_t n4,
-                                                            float* __restrict__ out, int accumulate) {
-  const f32x4* s4 = reinterpret_cast<const f32x4*>(slab);
-  for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    f32x4 s = accumulate ? reinterpret_cast<const f32x4*>(out)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int z = 0; z < splits; z += 8) {
-      const int nz = min(8, splits - z);  // (uniform)
-      f32x4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (u < nz) v[u] = s4[(size_t)(z + u) * n4 + i];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (u < nz) s += v[u];
-    }
-    reinterpret_cast<f32x4*>(out)[i] = s;
-  }
-}
-
-// The same sums for the problems of a grouped weight-gradient launch (gpt2mi_gemm_wgrad_grouped): blockIdx.y is the
-// problem, whose slabs / output / length come from the kernel arguments; the same per-element order as above
-struct ReduceGroup {
-  const float* slab[kGroupMax];
-  float* out[kGroupMax];
-  size_t n4[kGroupMax];
-};
-__global__ __launch_bounds__(256) void splitk_reduce_grouped_kernel(ReduceGroup R, int splits, int accumulate) {
-  const int g = blockIdx.y;
-  const f32x4* s4 = reinterpret_cast<const f32x4*>(R.slab[g]);
-  f32x4* o4 = reinterpret_cast<f32x4*>(R.out[g]);
-  const size_t n4 = R.n4[g];
-  for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    f32x4 s = accumulate ? o4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int z = 0; z < splits; z += 8) {
-      const int nz = min(8, splits - z);  // (uniform)
-      f32x4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (u < nz) v[u] = s4[(size_t)(z + u) * n4 + i];
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (u < nz) s += v[u];
-    }
-    o4[i] = s;
-  }
-}
-
-// bf16 slabs (GPT2MI_SCHED_BF16_SLABS): 8 elements per thread (one 16-B load per slab), each widened to fp32 and added
-// in the order above (the old value first when accumulating, then the slabs in split order)
-__global__ __launch_bounds__(256) void splitk_reduce16_kernel(const bf16* __restrict__ slab, int splits, size_t n8,
-                                                              float* __restrict__ out, int accumulate) {
-  for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
-    f32x4* o = reinterpret_cast<f32x4*>(out) + 2 * i;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0;
-    if (accumulate) {
-      s0 = o[0];
-      s1 = o[1];
-    }
-    for (int z = 0; z < splits; ++z) {
-      const bf16x8 v = reinterpret_cast<const bf16x8*>(slab + (size_t)z * n8 * 8)[i];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        s0[e] += bf2f(v[e]);
-        s1[e] += bf2f(v[4 + e]);
-      }
-    }
-    o[0] = s0;
-    o[1] = s1;
-  }
-}
-
-// 64 x 64 tile of the slabs per block, summed as splitk_reduce sums (the old value first when accumulating, then the
-// slabs in split order: the same bits), staged through LDS and written transposed: 16-B loads and stores, 16 lanes per
-// 256-B row segment on both sides
-template <typename TS>  // slab element: float, or bf16 (GPT2MI_SCHED_BF16_SLABS)
-__global__ __launch_bounds__(256) void splitk_reduce_t_kernel(const TS* __restrict__ slab, int splits, int rows,
-                                                              int cols, float* __restrict__ out, int accumulate) {
-  __shared__ float t[64][65];
-  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-  const int q = threadIdx.x & 15, p = threadIdx.x >> 4;  // 16 lanes x 4 floats per 64-float segment, 16 segments / pass
-  const size_t plane = (size_t)rows * cols;
-  if (accumulate) {  // t[r][c] = out[c][r]
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = 16 * i + p;
-      const f32x4 v = *reinterpret_cast<const f32x4*>(out + (size_t)(c0 + c) * rows + r0 + 4 * q);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) t[4 * q + e][c] = v[e];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = 16 * i + p;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (accumulate) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = t[r][4 * q + e];
-    }
-    const TS* src = slab + (size_t)(r0 + r) * cols + c0 + 4 * q;
-    for (int z = 0; z < splits; ++z) {
-      const f32x4 w = load4<TS>(src + z * plane);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] += w[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) t[r][4 * q + e] = v[e];  // (the lane's own elements: read above, by it alone)
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int c = 16 * i + p;
-    const f32x4 v = {t[4 * q][c], t[4 * q + 1][c], t[4 * q + 2][c], t[4 * q + 3][c]};
-    *reinterpret_cast<f32x4*>(out + (size_t)(c0 + c) * rows + r0 + 4 * q) = v;
-  }
 }
 
 }  // namespace
 
 namespace gpt2mi {
-// Layouts 0 (forward) and 1 (dgrad); N % 256 == 0, M % 64 == 0, K % 32 == 0, no split-K.
-int gemm256_dispatch(int layout, int epilogue, const GemmParams& P, hipStream_t s, int splits) {
-  switch (layout * 16 + epilogue) {
-    case 0 * 16 + EPI_BF16: return launch<false, false, EPI_BF16>(P, s, 1);
-    case 0 * 16 + EPI_F32: return launch<false, false, EPI_F32>(P, s, 1);
-    case 0 * 16 + EPI_RESID: return launch<false, false, EPI_RESID>(P, s, 1);
-    case 0 * 16 + EPI_GELU: return launch<false, false, EPI_GELU>(P, s, 1);
-    case 0 * 16 + EPI_GELU_BWD: return launch<false, false, EPI_GELU_BWD>(P, s, 1);
-    case 1 * 16 + EPI_BF16: return launch<false, true, EPI_BF16>(P, s, 1);
-    case 1 * 16 + EPI_F32: return launch<false, true, EPI_F32>(P, s, 1);
-    case 1 * 16 + EPI_GELU_BWD: return launch<false, true, EPI_GELU_BWD>(P, s, 1);
-    case 2 * 16 + EPI_F32: return launch<true, true, EPI_F32>(P, s, 1);
-    case 2 * 16 + EPI_SLAB: return launch<true, true, EPI_SLAB>(P, s, splits);
-    default: return -1;  // not built for this kernel: caller falls back to the 128x128 kernel
+// Full column tiles (layout 2: full row tiles too), M % 64 == 0, any K-tile count; split-K into fp32 slabs (layout 2)
+int gemm256_launch(const GemmPlan& plan, const GemmParams& P, hipStream_t s) {
+  switch ((plan.a_t ? 32 : plan.b_t ? 16 : 0) + plan.epi) {
+    case 0 * 16 + EPI_BF16: return launch<false, false, EPI_BF16>(plan, P, s);
+    case 0 * 16 + EPI_F32: return launch<false, false, EPI_F32>(plan, P, s);
+    case 0 * 16 + EPI_RESID: return launch<false, false, EPI_RESID>(plan, P, s);
+    case 0 * 16 + EPI_GELU: return launch<false, false, EPI_GELU>(plan, P, s);
+    case 0 * 16 + EPI_GELU_BWD: return launch<false, false, EPI_GELU_BWD>(plan, P, s);
+    case 1 * 16 + EPI_BF16: return launch<false, true, EPI_BF16>(plan, P, s);
+    case 1 * 16 + EPI_F32: return launch<false, true, EPI_F32>(plan, P, s);
+    case 1 * 16 + EPI_GELU_BWD: return launch<false, true, EPI_GELU_BWD>(plan, P, s);
+    case 2 * 16 + EPI_F32: return launch<true, true, EPI_F32>(plan, P, s);
+    case 2 * 16 + EPI_SLAB: return launch<true, true, EPI_SLAB>(plan, P, s);
+    default: return no_instance("gemm256", plan);
   }
-}
-
-int splitk_reduce_t(const float* slab, int splits, int rows, int cols, float* out, int accumulate, hipStream_t s) {
-  splitk_reduce_t_kernel<float><<<dim3(cols / 64, rows / 64), 256, 0, s>>>(slab, splits, rows, cols, out, accumulate);
-  return check_launch("splitk_reduce_t");
-}
-int splitk_reduce16_t(const bf16* slab, int splits, int rows, int cols, float* out, int accumulate, hipStream_t s) {
-  splitk_reduce_t_kernel<bf16><<<dim3(cols / 64, rows / 64), 256, 0, s>>>(slab, splits, rows, cols, out, accumulate);
-  return check_launch("splitk_reduce16_t");
-}
-int splitk_reduce16(const bf16* slab, int splits, size_t n, float* out, int accumulate, hipStream_t s) {
-  splitk_reduce16_kernel<<<2048, 256, 0, s>>>(slab, splits, n / 8, out, accumulate);
-  return check_launch("splitk_reduce16");
-}
-int splitk_reduce_grouped(const float* const* slab, float* const* out, const size_t* n, int count, int splits,
-                          int accumulate, hipStream_t s) {
-  ReduceGroup R{};
-  for (int g = 0; g < count; ++g) {
-    R.slab[g] = slab[g];
-    R.out[g] = out[g];
-    R.n4[g] = n[g] / 4;
-  }
-  splitk_reduce_grouped_kernel<<<dim3(2048 / count, count), 256, 0, s>>>(R, splits, accumulate);
-  return check_launch("splitk_reduce_grouped");
-}
-int splitk_reduce(const float* slab, int splits, size_t n, float* out, int accumulate, hipStream_t s) {
-  splitk_reduce_kernel<<<2048, 256, 0, s>>>(slab, splits, n / 4, out, accumulate);
-  return check_launch("splitk_reduce");
 }
 }  // namespace gpt2mi

@@ -1,6 +1,6 @@
 // bf16 MFMA GEMM, 256x256x64 block tile, "ping-pong" 4-phase K-step — the main GEMM of the step.
 //
-// Same contract and epilogues as gemm.hip / gemm256.hip (C = epi(alpha * A.B^T), layouts 0/1/2).
+// Same contract and epilogues as gemm.hip / gemm256.hip (C = epi(alpha * A.B^T), layouts 0/1/2; gemm_api.hip).
 //
 // Structure (CDNA4 idiom: 2 waves per SIMD that alternate MFMA and memory work):
 //  * 512 threads = 8 waves = 2 groups of 4 (group g = wave>>2, one wave of each group per SIMD).
@@ -37,7 +37,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "gemm_common.h"
+#include "gemm_epilogue.h"
 
 namespace {
 
@@ -59,9 +59,9 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 __device__ __forceinline__ int mc_swz(int k) { return 2 * ((k & 3) | (((k >> 3) & 1) << 2)); }
 
 // image row/col ir (0..127) of half `h` -> offset inside the 256-wide block dimension
-//   contiguous (default): A_h / B_h = rows / columns h*128 + ir
-//   interleaved (A/B experiments): A_h = 64-row slice h of each 128-row group, B_h = 32-column slice
-//   h of each 64-column group
+//   contiguous (k-contiguous operands): A_h / B_h = rows / columns h*128 + ir
+//   interleaved (m-contiguous, i.e. transposed, operands: default_map in gemm_plan.h): A_h = 64-row slice h of each
+//   128-row group, B_h = 32-column slice h of each 64-column group
 template <bool INTERLEAVED, bool IS_A>
 __device__ __forceinline__ int half_map(int ir, int h) {
   if constexpr (!INTERLEAVED) return (h << 7) + ir;
@@ -208,49 +208,24 @@ __device__ __forceinline__ void mfma_quadrant(f32x4 (&acc)[4][2], const Frags& f
 // s_waitcnt vmcnt takes 0..63: a count past that waits for a few more of the oldest operations (safe)
 constexpr int vm_cap(int n) { return n > 63 ? 63 : n; }
 
-// end of a phase's memory segment: retire the half-tile the next phase reads, then the ping-pong
-// MFMA segment between two barriers
-// PP_LGKM_AFTER_BARRIER=0 (A/B builds): no explicit lgkmcnt(0) ahead of the MFMA segment; the compiler's own counted
-// waits retire each fragment read before its first MFMA, and every fragment a memory segment reads is consumed by the
-// MFMA segment that follows it, so all reads still complete before the barrier that ends that segment
-#ifndef PP_LGKM_AFTER_BARRIER
-#define PP_LGKM_AFTER_BARRIER 1
-#endif
-GPT2MI_PRODUCT_KNOB(PP_LGKM_AFTER_BARRIER, 1);
-#if PP_LGKM_AFTER_BARRIER
-#define PP_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-#define PP_LGKM0()
-#endif
-#define PP_PRIO_HI() __builtin_amdgcn_s_setprio(1);
-#define PP_PRIO_LO() __builtin_amdgcn_s_setprio(0);
-#define PP_SYNC_MFMA(ACC, NI, VM)                          \
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory"); \
-  __builtin_amdgcn_sched_barrier(0);                       \
-  __builtin_amdgcn_s_barrier();                            \
-  PP_LGKM0()                                               \
-  __builtin_amdgcn_sched_barrier(0);                       \
-  PP_PRIO_HI()                                             \
-  mfma_quadrant<NI>(ACC, fr);                              \
-  PP_PRIO_LO()                                             \
-  __builtin_amdgcn_sched_barrier(0);                       \
-  __builtin_amdgcn_s_barrier();                            \
-  __builtin_amdgcn_sched_barrier(0);
-
-// the same with the wait chosen at run time: vmcnt(VM + kStores) when FIRST (persistent K-tile 0), else vmcnt(VM)
-#define PP_SYNC_MFMA_F(ACC, NI, VM, FIRST)                                             \
+// end of a phase's memory segment: retire the half-tile the next phase reads, then the ping-pong MFMA segment between
+// two barriers (an explicit lgkmcnt(0) after the first: every fragment read of the memory segment has landed before
+// the MFMA segment starts). The wait is vmcnt(VM + kStores) when FIRST (persistent K-tile 0, chosen at run time), else
+// vmcnt(VM)
+#define PP_SYNC_MFMA_F(ACC, NI, VM, FIRST)                                                 \
   if (FIRST) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(vm_cap((VM) + kStores)) : "memory"); \
-  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");                       \
-  __builtin_amdgcn_sched_barrier(0);                                                  \
-  __builtin_amdgcn_s_barrier();                                                       \
-  PP_LGKM0()                                                                          \
-  __builtin_amdgcn_sched_barrier(0);                                                  \
-  PP_PRIO_HI()                                                                        \
-  mfma_quadrant<NI>(ACC, fr);                                                         \
-  PP_PRIO_LO()                                                                        \
-  __builtin_amdgcn_sched_barrier(0);                                                  \
-  __builtin_amdgcn_s_barrier();                                                       \
+  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");                           \
+  __builtin_amdgcn_sched_barrier(0);                                                       \
+  __builtin_amdgcn_s_barrier();                                                            \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                       \
+  __builtin_amdgcn_sched_barrier(0);                                                       \
+  __builtin_amdgcn_s_setprio(1);                                                           \
+  mfma_quadrant<NI>(ACC, fr);                                                              \
+  __builtin_amdgcn_s_setprio(0);                                                           \
+  __builtin_amdgcn_sched_barrier(0);                                                       \
+  __builtin_amdgcn_s_barrier();                                                            \
   __builtin_amdgcn_sched_barrier(0);
+#define PP_SYNC_MFMA(ACC, NI, VM) PP_SYNC_MFMA_F(ACC, NI, VM, false)
 
 // workgroup barrier that orders LDS only (the epilogue's global stores stay in flight)
 __device__ __forceinline__ void lds_barrier() {
@@ -258,26 +233,6 @@ __device__ __forceinline__ void lds_barrier() {
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
 }
-
-// Timing instrumentation (tools/gemm_timing.py builds a separate library with -DGEMM_PP_TIMING): wave 0
-// of every block stamps s_memtime at kernel start (0), first operands landed (1), end of the main loop
-// (2) and end of the epilogue (3), plus its HW_ID / XCC_ID, into P.aux (BF16 epilogue only).
-#if defined(GEMM_PP_TIMING) && !defined(GPT2MI_AB_BUILD)
-#error "GEMM_PP_TIMING writes stamps into P.aux: an A/B build (make timing) only"
-#endif
-#ifdef GEMM_PP_TIMING
-#define PP_STAMP(I)                                                                                  \
-  if (EPI == EPI_BF16 && P.aux && threadIdx.x == 0) {                                               \
-    uint64_t* ts = reinterpret_cast<uint64_t*>(P.aux) + (size_t)blockIdx.x * 6;                    \
-    ts[I] = __builtin_amdgcn_s_memtime();                                                            \
-    if (I == 0) {                                                                                    \
-      ts[4] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4);                                  \
-      ts[5] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20);                                 \
-    }                                                                                                \
-  }
-#else
-#define PP_STAMP(I)
-#endif
 
 // Persistent schedule: the work queue. Items (output tiles) are dealt to the 8 XCD labels (blockIdx % 8) in contiguous
 // ranges, as xcd_remap does; the first item of every block is static (blockIdx / 8 within its label), every later one
@@ -351,10 +306,9 @@ __device__ __forceinline__ const GemmParams& pp_problem(const PPArg<GRP>& a, int
 template <bool A_T, bool B_T, int EPI, int MAP, bool PERSIST = false, bool BND = false, bool DYN = false,
           bool GRP = false>
 __global__ __launch_bounds__(kThreads, 1) void gemm_pp_kernel(PPArg<GRP> KA) {
-  PP_STAMP(0)
   int item0;
   const GemmParams& P = pp_problem<GRP>(KA, item0);
-  constexpr bool AIL = MAP & 1, BIL = MAP & 2;  // interleaved half-tile maps (A/B experiments)
+  constexpr bool AIL = MAP & 1, BIL = MAP & 2;  // interleaved half-tile maps (half_map; the transposed operands')
   static_assert(!PERSIST || MAP == 0, "the persistent epilogue assumes the contiguous half-tile map");
   // phase-4 B reads (see ktile): the persistent schedule and the weight gradients (both operands by buffer DMA); the
   // one-tile-per-block k-contiguous kernels keep the round-2 schedule (their per-lane flat DMA addresses would spill)
@@ -484,7 +438,6 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_pp_kernel(PPArg<GRP> KA) {
   }
   asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // A_0(0), B_0(0) landed
   __builtin_amdgcn_s_barrier();
-  PP_STAMP(1)
   if (wr == 1) __builtin_amdgcn_s_barrier();  // group 1 runs one barrier behind group 0
   __builtin_amdgcn_sched_barrier(0);
   for (;;) {  // PERSIST: one iteration per output tile (non-persistent: exactly one)
@@ -583,7 +536,6 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_pp_kernel(PPArg<GRP> KA) {
     asm volatile("" ::: "memory");
     nxt_item = __builtin_amdgcn_readfirstlane(s_next);
   }
-  PP_STAMP(2)
 
   // the thread index through an opaque copy: lane constants derived from it are formed here, per tile, instead of
   // being hoisted to kernel entry and spilled across the tile loop (whose reloads would wait vmcnt(0) behind the
@@ -694,17 +646,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_pp_kernel(PPArg<GRP> KA) {
     csum = f32x4{0.f, 0.f, 0.f, 0.f};
     csum1 = csum;
   }
-  if constexpr (GEMM_STORE_EXP == 3 && PERSIST) {
-    // A/B build only: no epilogue at all (the accumulators kept live): the main loop's share of a tile
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b)
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(acc[a][b][i][j]));
-  } else if constexpr (kBf16Acc) {
+  if constexpr (kBf16Acc) {
     // BF16 output: alpha and the bias applied in the accumulator layout, the tile rounded to bf16 into a [128][256]
     // bf16 image (64 KiB: all of buffer 1, so two 128-row passes of every wave instead of four 64-row fp32 passes; half
     // the LDS bytes). 8-B chunk c of image row r at c ^ 2(r & 15): conflict-free for the 16-row x 8-B writes and the
@@ -739,8 +681,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_pp_kernel(PPArg<GRP> KA) {
         const int r = 16 * it + (tid >> 5);
         const u32x4 v = *reinterpret_cast<const u32x4*>(img16 + r * 512 + 8 * ((2 * cu) ^ (2 * (r & 15))));
         bf16* C = reinterpret_cast<bf16*>(P.C) + out_idx(m0 + mi * 128 + r, P.ldc, n0 + 8 * cu);
-        if constexpr (GEMM_STORE_EXP == 1) asm volatile("" ::"v"(v));
-        else __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(C));
+        __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(C));
       }
     }
   } else if constexpr (kWide && PERSIST) {
@@ -937,8 +878,7 @@ write_image(mi, wr * 64);
         // default-policy stores, not the non-temporal ones of the other epilogues: the split-K reduction reads the
         // slabs right after this launch (same-process A/B, same bits: qkv / proj / fc2 wgrad + reduction 1-3.5 %
         // faster, fc1 within noise; profiles/r4fin/slab_store_ab.log)
-        if constexpr (GEMM_STORE_EXP == 1) asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
-        else *reinterpret_cast<f32x4*>(slab + (size_t)gm * P.ldc + gn) = v;
+        *reinterpret_cast<f32x4*>(slab + (size_t)gm * P.ldc + gn) = v;
       } else if constexpr (EPI == EPI_SLAB16) {  // 8 B per lane: one 512-B bf16 row per wave-instruction
         bf16* slab = reinterpret_cast<bf16*>(P.C) + (size_t)split * P.M * P.ldc;
         store4<bf16>(slab + (size_t)gm * P.ldc + gn, v);
@@ -998,7 +938,6 @@ write_image(mi, wr * 64);
       }
     }
   }
-  PP_STAMP(3)
   if constexpr (!PERSIST) {
     return;
   } else {
@@ -1042,32 +981,36 @@ write_image(mi, wr * 64);
 }
 
 
-// Default half-tile maps: interleaved for m-contiguous (transposed) operands, contiguous otherwise
-// (measured, tools/gemm_probe.py: 8192^3 dgrad 1195 vs 1022 TF with B interleaved; no effect on the
+// Default half-tile maps (gemm_plan.h default_map): interleaved for m-contiguous (transposed) operands, contiguous
+// otherwise (measured, tools/gemm_probe.py: 8192^3 dgrad 1195 vs 1022 TF with B interleaved; no effect on the
 // k-contiguous forward operands).
-template <bool A_T, bool B_T, int EPI, int MAP = (A_T ? 1 : 0) | (B_T ? 2 : 0)>
-int launch(const GemmParams& P, hipStream_t s, int splits) {
-  dim3 grid(((P.M + BM - 1) / BM) * ((P.N + BN - 1) / BN) * splits);
+template <bool A_T, bool B_T, int EPI, int MAP = gpt2mi::default_map(A_T, B_T)>
+int launch(const gpt2mi::GemmPlan& plan, const GemmParams& P, hipStream_t s) {
+  if (plan.map != MAP) return gpt2mi::no_instance("gemm_pp", plan);
   if constexpr (A_T || B_T) {  // a transposed operand with a partial last tile: the bounded DMA
-    if ((A_T && P.M % BM != 0) || (B_T && P.N % BN != 0)) {
-      gemm_pp_kernel<A_T, B_T, EPI, MAP, false, true><<<grid, kThreads, 0, s>>>(P);
+    if (plan.bnd) {
+      gemm_pp_kernel<A_T, B_T, EPI, MAP, false, true><<<dim3(plan.grid), kThreads, 0, s>>>(P);
       return gpt2mi::check_launch("gemm_pp");
     }
   }
-  gemm_pp_kernel<A_T, B_T, EPI, MAP><<<grid, kThreads, 0, s>>>(P);
+  gemm_pp_kernel<A_T, B_T, EPI, MAP><<<dim3(plan.grid), kThreads, 0, s>>>(P);
   return gpt2mi::check_launch("gemm_pp");
 }
 
-}  // namespace
-namespace gpt2mi {
-int gemm_pp_grouped(const GemmGroup& G, hipStream_t s) {
-  const int nsplit = (G.p[0].K + G.p[0].k_per_split - 1) / G.p[0].k_per_split;
-  gemm_pp_kernel<true, true, EPI_SLAB, 3, false, false, false, true><<<dim3(G.tiles * nsplit), kThreads, 0, s>>>(G);
-  return gpt2mi::check_launch("gemm_pp_grouped");
+// persistent variant: one block per CU, grid a multiple of 8 (or every tile)
+template <int EPI>
+int launch_persistent(const gpt2mi::GemmPlan& plan, const GemmParams& Pin, hipStream_t s) {
+  static std::atomic<unsigned> next_slot{0};
+  GemmParams P = Pin;
+  P.qslot = (int)(next_slot.fetch_add(1u, std::memory_order_relaxed) % kQueueSlots);
+  if (plan.dyn) gemm_pp_kernel<false, false, EPI, 0, true, false, true><<<dim3(plan.grid), kThreads, 0, s>>>(P);
+  else gemm_pp_kernel<false, false, EPI, 0, true><<<dim3(plan.grid), kThreads, 0, s>>>(P);
+  return gpt2mi::check_launch("gemm_pp_persistent");
 }
-}  // namespace gpt2mi
-namespace {
 
+}  // namespace
+
+namespace gpt2mi {
 int num_cus() {
   static int n = 0;
   if (!n) {
@@ -1080,106 +1023,42 @@ int num_cus() {
   return n;
 }
 
-// persistent variant: one block per CU, grid a multiple of 8
-#ifndef GPT2MI_PERSIST_GRID
-#define GPT2MI_PERSIST_GRID 0  // A/B builds: a fixed persistent grid (a CU-masked stream's CU count), 0 = every CU
-#endif
-GPT2MI_PRODUCT_KNOB(GPT2MI_PERSIST_GRID, 0);
-template <int EPI>
-int launch_persistent(const GemmParams& Pin, hipStream_t s, bool dyn) {
-  static std::atomic<unsigned> next_slot{0};
-  GemmParams P = Pin;
-  P.qslot = (int)(next_slot.fetch_add(1u, std::memory_order_relaxed) % kQueueSlots);
-  const int ntiles = ((P.M + BM - 1) / BM) * (P.N / BN);  // N % 256 == 0 (gemm_pp_dispatch)
-  dim3 grid(min(ntiles, GPT2MI_PERSIST_GRID > 0 ? GPT2MI_PERSIST_GRID : num_cus()));
-  if (dyn) gemm_pp_kernel<false, false, EPI, 0, true, false, true><<<grid, kThreads, 0, s>>>(P);
-  else gemm_pp_kernel<false, false, EPI, 0, true><<<grid, kThreads, 0, s>>>(P);
-  return gpt2mi::check_launch("gemm_pp_persistent");
+int gemm_pp_launch_grouped(const GemmPlan& plan, const GemmGroup& G, hipStream_t s) {
+  gemm_pp_kernel<true, true, EPI_SLAB, 3, false, false, false, true><<<dim3(plan.grid), kThreads, 0, s>>>(G);
+  return check_launch("gemm_pp_grouped");
 }
 
-}  // namespace
-
-namespace gpt2mi {
-#ifndef GPT2MI_PERSIST_KMAX
-#define GPT2MI_PERSIST_KMAX 4096
-#endif
-GPT2MI_PRODUCT_KNOB(GPT2MI_PERSIST_KMAX, 4096);
-// longest K that takes the persistent schedule by default: the step's K = 768 / 2304 / 3072 shapes (qkv / fc1 dgrad
-// and fc2 + residual 2-3 % faster than one tile per block since the persistent kernel reads the next K-tile's B
-// fragments in phase 4, tools/gemm_ab.py 0 7); the lm_head dgrad (K = 50 432) stays one tile per block
-constexpr int g_persist_kmax = GPT2MI_PERSIST_KMAX;
-// Layouts 0 / 1; N % 256 == 0, every split's K range an even number (>= 2) of 64-deep tiles.
-// Returns -1 when this kernel does not apply (the caller falls back).
-// bf16-slab weight gradients: half-tile map 2 (A contiguous, B interleaved) so that the epilogue takes the wide path
-// (8 columns per lane, one 16-B store per row); map 3 (both interleaved, the fp32-slab kernel's) stores 8 B per lane
-#ifndef PP_WGRAD16_MAP
-#define PP_WGRAD16_MAP 2
-#endif
-GPT2MI_PRODUCT_KNOB(PP_WGRAD16_MAP, 2);
-int gemm_pp_dispatch(int layout, int epilogue, const GemmParams& P, hipStream_t s, int splits, int map,
-                     bool persistent_ok, bool shared_cus) {
-  // N (and M) multiples of 64; without split-K any K-tile count >= 2 (an odd count ends in a single K-tile); with
-  // split-K an even count per split
-  if (P.N % 64 != 0 || P.M % 64 != 0 || P.K % BK != 0 || P.K < 2 * BK) return -1;
-  if (splits > 1 && (P.k_per_split % (2 * BK) != 0 || P.K % (2 * BK) != 0)) return -1;
-  if (splits == 1 && P.k_per_split != P.K) return -1;
-  // wgrad (both operands m-contiguous): this kernel since the LDS-DMA went to inline asm (lm_head wgrad 4046 vs
-  // 4485 us on the 2-stage gemm256 kernel, qkv 197 vs 230; before, hipcc's vmcnt(0) drains made it the slower
-  // one, 698-721 vs 765 TF). map 8 = the same (tools/lib_ab.py impl 8)
-  if (layout == 2) {
-    if (map != 0 && map != 8) return -1;
-    return epilogue == EPI_SLAB     ? launch<true, true, EPI_SLAB>(P, s, splits)
-           : epilogue == EPI_SLAB16 ? launch<true, true, EPI_SLAB16, PP_WGRAD16_MAP>(P, s, splits)
-           : epilogue == EPI_F32    ? launch<true, true, EPI_F32>(P, s, 1)
-                                    : -1;
-  }
-  // layout 1 split-K slabs: the weight gradient with its X operand transposed (gpt2mi_gemm_wgrad_kt)
-  if (layout == 1 && (epilogue == EPI_SLAB || epilogue == EPI_SLAB16)) {
-    if (P.N % BN != 0) return -1;
-    return epilogue == EPI_SLAB ? launch<false, true, EPI_SLAB>(P, s, splits) : launch<false, true, EPI_SLAB16>(P, s, splits);
-  }
-  if (map > 0 && epilogue == EPI_BF16 && layout <= 1 && P.N % BN == 0) {  // half-tile maps (tools/gemm_probe.py)
-    if (layout == 0) {
-      if (map == 1) return launch<false, false, EPI_BF16, 1>(P, s, 1);
-      if (map == 2) return launch<false, false, EPI_BF16, 2>(P, s, 1);
-      if (map == 3) return launch<false, false, EPI_BF16, 3>(P, s, 1);
-    } else {
-      if (map == 1) return launch<false, true, EPI_BF16, 1>(P, s, 1);
-      if (map == 2) return launch<false, true, EPI_BF16, 2>(P, s, 1);
-      if (map == 3) return launch<false, true, EPI_BF16, 3>(P, s, 1);
+// wgrad (both operands m-contiguous): this kernel since the LDS-DMA went to inline asm (lm_head wgrad 4046 vs
+// 4485 us on the 2-stage gemm256 kernel, qkv 197 vs 230; before, hipcc's vmcnt(0) drains made it the slower one).
+// Persistent schedule: epilogue operand loads (residual, GELU derivative) are issued after the next tile's asm DMAs, so
+// the compiler's wait for them retires those DMAs too — early, never late.
+int gemm_pp_launch(const GemmPlan& plan, const GemmParams& P, hipStream_t s) {
+  if (plan.family == GemmFamily::PingPongPersistent) {
+    if (plan.a_t || plan.b_t || plan.map != 0) return no_instance("gemm_pp", plan);
+    switch (plan.epi) {
+      case EPI_BF16: return launch_persistent<EPI_BF16>(plan, P, s);
+      case EPI_GELU: return launch_persistent<EPI_GELU>(plan, P, s);
+      case EPI_RESID: return launch_persistent<EPI_RESID>(plan, P, s);
+      case EPI_GELU_BWD: return launch_persistent<EPI_GELU_BWD>(plan, P, s);
+      default: return no_instance("gemm_pp", plan);
     }
   }
-  // short-K forward-layout shapes: the persistent schedule (map < 0 forces the one-tile-per-block kernel, map 7
-  // the persistent one at any K: tools/gemm_ab.py). Epilogue operand loads (residual, GELU derivative) are
-  // issued after the next tile's asm DMAs, so the compiler's wait for them retires those DMAs too — early,
-  // never late.
-  const int ntiles = ((P.M + BM - 1) / BM) * ((P.N + BN - 1) / BN);
-  // (full column tiles and an even K-tile count only: the persistent epilogue has no column guard, and its K-tile 0
-  // must be a steady-state tile)
-  if (layout == 0 && (map == 7 || (map == 0 && persistent_ok && P.K <= g_persist_kmax)) && P.K >= 4 * BK &&
-      P.N % BN == 0 && P.K % (2 * BK) == 0 &&
-      ntiles >= 2 * num_cus() &&
-      ((epilogue == EPI_BF16 && P.dbias == nullptr) || epilogue == EPI_GELU || epilogue == EPI_RESID ||
-       epilogue == EPI_GELU_BWD) &&
-      P.M % BM == 0 && (size_t)P.M * P.lda * 2 < (1ull << 31) && (size_t)P.N * P.ldb * 2 < (1ull << 31)) {
-    switch (epilogue) {
-      case EPI_BF16: return launch_persistent<EPI_BF16>(P, s, shared_cus);
-      case EPI_GELU: return launch_persistent<EPI_GELU>(P, s, shared_cus);
-      case EPI_RESID: return launch_persistent<EPI_RESID>(P, s, shared_cus);
-      default: return launch_persistent<EPI_GELU_BWD>(P, s, shared_cus);
-    }
-  }
-  if (map < 0 || map == 7) map = 0;
-  switch (layout * 16 + epilogue) {
-    case 0 * 16 + EPI_BF16: return launch<false, false, EPI_BF16>(P, s, 1);
-    case 0 * 16 + EPI_F32: return launch<false, false, EPI_F32>(P, s, 1);
-    case 0 * 16 + EPI_RESID: return launch<false, false, EPI_RESID>(P, s, 1);
-    case 0 * 16 + EPI_GELU: return launch<false, false, EPI_GELU>(P, s, 1);
-    case 0 * 16 + EPI_GELU_BWD: return launch<false, false, EPI_GELU_BWD>(P, s, 1);
-    case 1 * 16 + EPI_BF16: return launch<false, true, EPI_BF16>(P, s, 1);
-    case 1 * 16 + EPI_F32: return launch<false, true, EPI_F32>(P, s, 1);
-    case 1 * 16 + EPI_GELU_BWD: return launch<false, true, EPI_GELU_BWD>(P, s, 1);
-    default: return -1;
+  switch ((plan.a_t ? 32 : plan.b_t ? 16 : 0) + plan.epi) {
+    case 0 * 16 + EPI_BF16: return launch<false, false, EPI_BF16>(plan, P, s);
+    case 0 * 16 + EPI_F32: return launch<false, false, EPI_F32>(plan, P, s);
+    case 0 * 16 + EPI_RESID: return launch<false, false, EPI_RESID>(plan, P, s);
+    case 0 * 16 + EPI_GELU: return launch<false, false, EPI_GELU>(plan, P, s);
+    case 0 * 16 + EPI_GELU_BWD: return launch<false, false, EPI_GELU_BWD>(plan, P, s);
+    case 1 * 16 + EPI_BF16: return launch<false, true, EPI_BF16>(plan, P, s);
+    case 1 * 16 + EPI_F32: return launch<false, true, EPI_F32>(plan, P, s);
+    case 1 * 16 + EPI_GELU_BWD: return launch<false, true, EPI_GELU_BWD>(plan, P, s);
+    // layout 1 split-K slabs: the weight gradient with its X operand transposed (gpt2mi_gemm_wgrad_kt)
+    case 1 * 16 + EPI_SLAB: return launch<false, true, EPI_SLAB>(plan, P, s);
+    case 1 * 16 + EPI_SLAB16: return launch<false, true, EPI_SLAB16>(plan, P, s);
+    case 2 * 16 + EPI_F32: return launch<true, true, EPI_F32>(plan, P, s);
+    case 2 * 16 + EPI_SLAB: return launch<true, true, EPI_SLAB>(plan, P, s);
+    case 2 * 16 + EPI_SLAB16: return launch<true, true, EPI_SLAB16, PP_WGRAD16_MAP>(plan, P, s);
+    default: return no_instance("gemm_pp", plan);
   }
 }
 }  // namespace gpt2mi

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 14
+#define GPT2MI_ABI_VERSION 15
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -65,8 +65,9 @@ int gpt2mi_colsum_bf16(const uint16_t* g, float* db, int M, int N, int ld, void*
  *          4 GELU_BWD: C = bf16(acc * aux) (aux from the GELU forward)   5 ATOMIC: C fp32 += acc (split-K)
  * dbias (may be NULL; BF16 / GELU_BWD epilogues of layouts 0/1): dbias[n] += sum_m C[m][n] of the stored
  * output — the bias gradient of the Linear whose output grad C is (fused into the 256x256 epilogue).
- * Requires M, N multiples of 64 and K a multiple of 64*splits (layout 0: any N multiple of 64 and any K-tile count on
- * the 256x256 kernels; layouts 1 / 2 with N (and M) not multiples of 256 run on the 128x128 kernel).
+ * Requires M, N multiples of 64 and K a multiple of 64*splits. The kernel is chosen by csrc/gemm_plan.h (plan_gemm):
+ * the ping-pong 256x256 kernel for layout 0 (any N multiple of 64, K >= 128) and for layouts 1 / 2 with N (and, layout 2,
+ * M) multiples of 256; otherwise the 2-stage 256x256 kernel (full tiles, K = 64) or the 128x128 kernel.
  * `sched`: GPT2MI_SCHED_* below. */
 int gpt2mi_gemm(int layout, int epilogue, int M, int N, int K, const uint16_t* A, int lda, const uint16_t* B, int ldb,
                 void* C, int ldc, const float* bias, const float* resid, uint16_t* aux, int ldaux, float alpha,
@@ -80,9 +81,10 @@ int gpt2mi_gemm(int layout, int epilogue, int M, int N, int K, const uint16_t* A
  *  GPT2MI_SCHED_SHARED_CUS (flag, v11): other kernels (the data-parallel wrappers' RCCL collectives) may hold CUs while
  *    this GEMM runs. The persistent schedule then takes its tiles from per-XCD work queues instead of a static walk:
  *    a block whose CU a collective holds takes fewer tiles instead of making the grid end on its latest block.
- *  low byte (A/B experiments and the kernel-equivalence tests only): 1 = 128x128 kernel, 2 = 2-stage 256x256,
- *    3..5 = ping-pong with half-tile map 1..3, 6 = ping-pong one tile per block, 7 = persistent at any K,
- *    8 = weight gradients on the ping-pong kernel (= auto). */
+ *  low byte (the kernel-equivalence tests and A/B tools only): 0 = auto, 1 = 128x128 kernel, 2 = 2-stage 256x256,
+ *    6 = ping-pong one tile per block (forward / dgrad layouts; weight gradients take the 2-stage kernel). Any other
+ *    value is refused with 22 (v15 retired the experiment selectors 3, 4, 5, 7 and 8; gpt2mi_gemm_wgrad_kt has one
+ *    kernel and ignores the low byte). */
 #define GPT2MI_SCHED_AUTO 0
 #define GPT2MI_SCHED_NO_PERSISTENT 0x100
 #define GPT2MI_SCHED_SHARED_CUS 0x400

@@ -10,7 +10,7 @@ the dropout-on step checkable element for element against autograd of the refere
 
 Element indexing per site (the kernels' own):
   * embedding / attn proj / fc1 / fc2 outputs, logical [M, N] row-major: element e = row * N + col,
-    hash(seed, e >> 1), 16-bit half e & 1 (`csrc/norm_embed.hip`, `csrc/gemm_common.h`);
+    hash(seed, e >> 1), 16-bit half e & 1 (`csrc/norm_embed.hip`, `csrc/gemm_epilogue.h`);
   * attention probabilities [B*H, T(q), T(key)]: hash(seed, (bh * T + (q & ~16)) * T + key), half
     (q >> 4) & 1 (`csrc/attention.hip`, `csrc/fp32.hip`).
 keep = int16(uniform16) >= round(p * 2^16) - 2^15, i.e. (uniform16 ^ 0x8000) >= round(p * 2^16): P(keep) = 1 - p

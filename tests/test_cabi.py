@@ -70,6 +70,14 @@ def test_gemm_schedule_is_a_per_call_argument():
     assert b"sched" in lib.gpt2mi_last_error()
     assert lib.gpt2mi_gemm_wgrad(256, 256, 64, None, 256, None, 256, None, 256, 0, 1.0, None, None, 0, 1, 0x1ff,
                                  None) == 22
+    # ABI v15: the low bytes that selected concluded experiments are refused like any other bad value
+    for retired in (3, 4, 5, 7, 8):
+        assert lib.gpt2mi_gemm(0, 0, 256, 256, 128, None, 128, None, 128, None, 256, None, None, None, 0,
+                               1.0, None, 0, 1, 0.0, 1, None, retired, None) == 22, retired
+        assert b"sched" in lib.gpt2mi_last_error()
+        assert lib.gpt2mi_gemm_wgrad(256, 256, 128, None, 256, None, 256, None, 256, 0, 1.0, None, None, 0, 1,
+                                     retired, None) == 22, retired
+        assert b"sched" in lib.gpt2mi_last_error()
 
 
 def test_schedule_flags_match_the_header():

@@ -154,9 +154,9 @@ def test_embed_decode_and_decode_step_refuse_bad_arguments(lib):
 
 
 @needs_lib
-def test_abi_is_v14_and_binds_the_decode_entries(lib):
+def test_abi_is_v14_or_later_and_binds_the_decode_entries(lib):
     from gpt_2_distributed_amd import _lib
-    assert lib.gpt2mi_abi_version() == _lib.ABI_VERSION == 14
+    assert lib.gpt2mi_abi_version() == _lib.ABI_VERSION >= 14  # (the decode entries arrived with v14)
     for name in ("gpt2mi_gemm_skinny", "gpt2mi_kv_store", "gpt2mi_attn_decode", "gpt2mi_attn_decode_workspace",
                  "gpt2mi_embed_decode", "gpt2mi_decode_step"):
         assert name in _lib.EXPORTED and hasattr(lib, name)

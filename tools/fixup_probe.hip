@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void writer(float* slab, size_t n4, float v) {
     s[i] = f32x4{v, v + 1.f, v + 2.f, (float)(i & 7)};
 }
 
-// splitk_reduce_kernel's body (gemm256.hip), non-accumulating
+// splitk_reduce_kernel's body (splitk_reduce.hip), non-accumulating
 __global__ __launch_bounds__(256) void reduce(const float* __restrict__ slab, int splits, size_t n4, float* __restrict__ out) {
   const f32x4* s4 = reinterpret_cast<const f32x4*>(slab);
   for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {

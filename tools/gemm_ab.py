@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """A/B of GEMM schedules on the GPT-2 124M step shapes (B=64, T=1024): gpt2mi_gemm sched variants timed in
 interleaved rounds with HIP events (random data).  python tools/gemm_ab.py [impl_a impl_b ...]  (default 0 6:
-the persistent ping-pong schedule vs the one-tile-per-block kernel)."""
+the persistent ping-pong schedule vs the one-tile-per-block kernel; the sched low bytes gpt2mi.h lists: 0, 1, 2, 6)."""
 import os
 import sys
 

@@ -3,6 +3,8 @@ operands, one process (cdna_hip_programming.md §5.4 rule 24). Shapes: square 81
 reference point) and the GPT-2 step's extreme shapes.
 
     python tools/gemm_probe.py [impl,impl,...] [shape names]
+
+impl = the sched low byte (gpt2mi.h): 0 auto, 1 128x128, 2 2-stage 256x256, 6 ping-pong one tile per block.
 """
 import os
 import sys

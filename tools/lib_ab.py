@@ -39,7 +39,7 @@ def _sched(lib):
 
 def main():
     libs = [bind(p) for p in sys.argv[1:]]
-    # LIB_AB_IMPLS=0,2: the GEMM sched argument per library (the same .so may be listed twice)
+    # LIB_AB_IMPLS=0,2: the GEMM sched argument per library (the same .so may be listed twice; low bytes 0, 1, 2, 6)
     impls = [int(v) for v in os.environ.get("LIB_AB_IMPLS", "").split(",") if v]
     for lib, impl in zip(libs, impls):
         lib.sched = impl

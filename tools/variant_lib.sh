@@ -8,7 +8,7 @@ cd "$(dirname "$0")/../gpt_2_distributed_amd/csrc"
 make -s -j8
 mkdir -p ../../tools/ab
 OBJS=""
-for f in runtime.cpp norm_embed.hip xent_adamw.hip gemm.hip gemm256.hip gemm_pp.hip attention.hip fp32.hip transpose.hip aux_ops.hip; do
+for f in runtime.cpp norm_embed.hip xent_adamw.hip gemm_api.hip gemm.hip gemm256.hip gemm_pp.hip splitk_reduce.hip attention.hip fp32.hip transpose.hip aux_ops.hip decode.hip; do
   [ "$f" = "$SRC" ] || OBJS="$OBJS build/$f.o"
 done
 EXTRA=""; [ "$SRC" = attention.hip ] && EXTRA="-fno-honor-nans -fno-slp-vectorize"
