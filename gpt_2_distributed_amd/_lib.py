@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -41,6 +41,10 @@ _SIGS = {
     "gpt2mi_grad_norm": [_p, _c_size, _c_float, _p, _p, _p],
     "gpt2mi_norm_finalize": [_p, _c_int, _p, _p],
     "gpt2mi_norm_partials_size": [],
+    "gpt2mi_sumsq_partials": [_p, _c_size, _c_float, _p, _p],
+    "gpt2mi_clip_coef": [_p, _c_int, _c_float, _p, _p, _p, _p],
+    "gpt2mi_adamw_clipped": [_p, _p, _p, _p, _p, _c_size, _c_float, _c_float, _c_float, _c_float, _c_float, _c_int,
+                             _c_float, _p, _p, _p, _p],
     "gpt2mi_cast_f32_bf16": [_p, _p, _c_size, _p],
     "gpt2mi_transpose_bf16": [_p, _p, _c_int, _c_int, _c_int, _c_int, _p],
     "gpt2mi_transpose_bf16_batched": [_p, _p, _p, _c_int, ctypes.c_int64, _p],
@@ -288,6 +292,23 @@ def grad_norm(g, n, scale, partials, out):
 def norm_finalize(partials, n, out):
     """out[0] = sqrt(sum(partials[:n])) (the norm of adamw launches given grad_norm=None)."""
     _call("gpt2mi_norm_finalize", _ptr(partials), n, _ptr(out), _stream())
+
+
+def sumsq_partials(g, n, scale, partials):
+    """norm_partials_size() partial sums of (g*scale)^2 over g[:n] (no finalisation; slices of one buffer)."""
+    _call("gpt2mi_sumsq_partials", _ptr(g), n, scale, _ptr(partials), _stream())
+
+
+def clip_coef(partials, n, max_norm, sumsq_out, norm_out, coef_out):
+    """norm_out[0] = sqrt(sum(partials[:n])), coef_out[0] = min(1, max_norm / (norm + 1e-6)), sumsq_out[0] (or None) =
+    the sum: clip_grad_norm_'s coefficient, left on the device."""
+    _call("gpt2mi_clip_coef", _ptr(partials), n, max_norm, _ptr(sumsq_out), _ptr(norm_out), _ptr(coef_out), _stream())
+
+
+def adamw_clipped(p, g, m, v, p_bf16, n, lr, wd, b1, b2, eps, step, grad_scale, coef_dev, partials=None,
+                  grad_norm=None):
+    _call("gpt2mi_adamw_clipped", _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(p_bf16), n, lr, wd, b1, b2, eps, step,
+          grad_scale, _ptr(coef_dev), _ptr(partials), _ptr(grad_norm), _stream())
 
 
 def norm_partials_size() -> int:

@@ -282,11 +282,16 @@ __global__ __launch_bounds__(1024) void xent_finalize_kernel(const float* __rest
 //   p -= step_size * m / (sqrt(v)/bc2_sqrt + eps)       step_size = lr/(1-b1^t), bc2_sqrt = sqrt(1-b2^t)
 // Also: partial sums of g^2 (the clip_grad_norm_(inf) total norm, computed from the same read of g
 // before the update, as the reference computes it before optim.step()), and the bf16 shadow of p.
+// CLIP (gpt2mi_adamw_clipped): the gradient scale is grad_scale * coef_dev[0], the clip coefficient gpt2mi_clip_coef
+// left in device memory (formed once per thread; everything after it is the unclipped kernel's code).
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                     float* __restrict__ m, float* __restrict__ v,
                                                     bf16* __restrict__ pb, size_t n4, float lr, float wd, float b1,
                                                     float b2, float eps, float step_size, float bc2_sqrt,
-                                                    float grad_scale, float* __restrict__ partials) {
+                                                    float grad_scale, float* __restrict__ partials,
+                                                    const float* __restrict__ coef_dev) {
+  if constexpr (CLIP) grad_scale *= coef_dev[0];
   float sq = 0.f;
   const float decay = 1.f - lr * wd;
   auto upd = [&](f32x4& pv, f32x4 gv, f32x4& mv, f32x4& vv) {
@@ -381,6 +386,39 @@ __global__ __launch_bounds__(1024) void norm_finalize_kernel(const float* __rest
   if (threadIdx.x == 0) out[0] = (float)sqrt(r[0]);
 }
 
+// The clip_grad_norm_ coefficient from per-block partials, in device memory: norm_finalize_kernel's reduction (the
+// same bits for the norm), then coef = min(1, max_norm / (norm + 1e-6)) as torch forms it (clamp(max=1): a NaN norm
+// gives NaN, an infinite one 0). sumsq (may be NULL) = the fp32 sum, for a cross-rank all-reduce.
+__global__ __launch_bounds__(1024) void clip_coef_kernel(const float* __restrict__ partials, int n, float max_norm,
+                                                         float* __restrict__ sumsq, float* __restrict__ norm,
+                                                         float* __restrict__ coef) {
+  double s = 0.0;
+  int i = threadIdx.x;
+  for (; i + 3 * 1024 < n; i += 4 * 1024) {
+    const float a = partials[i], b = partials[i + 1024], c = partials[i + 2048], d = partials[i + 3072];
+    s += a;
+    s += b;
+    s += c;
+    s += d;
+  }
+  for (; i < n; i += 1024) s += partials[i];
+  __shared__ double r[1024];
+  r[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 512; o > 0; o >>= 1) {
+    if (threadIdx.x < o) r[threadIdx.x] += r[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double nrm = sqrt(r[0]);
+    if (sumsq) sumsq[0] = (float)r[0];
+    norm[0] = (float)nrm;
+    // from the double-precision norm: the coefficient every gradient is multiplied by carries one fp32 rounding
+    const double c = (double)max_norm / (nrm + 1e-6);
+    coef[0] = c > 1.0 ? 1.f : (float)c;  // NaN compares false and stays NaN; max_norm / inf = 0
+  }
+}
+
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ x, bf16* __restrict__ y, size_t n) {
   for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = f2bf(x[i]);
 }
@@ -436,12 +474,44 @@ GPT2MI_EXPORT int gpt2mi_adamw(float* p, const float* g, float* m, float* v, uin
   hipStream_t s = (hipStream_t)stream;
   const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
   const float step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
-  adamw_kernel<<<kNormBlocks, 256, 0, s>>>(p, g, m, v, (bf16*)p_bf16, n / 4, lr, wd, b1, b2, eps, step_size, bc2_sqrt,
-                                           grad_scale, partials);
+  adamw_kernel<false><<<kNormBlocks, 256, 0, s>>>(p, g, m, v, (bf16*)p_bf16, n / 4, lr, wd, b1, b2, eps, step_size,
+                                                  bc2_sqrt, grad_scale, partials, nullptr);
   int rc = gpt2mi::check_launch("adamw");
   if (rc || !grad_norm) return rc;
   norm_finalize_kernel<<<1, 1024, 0, s>>>(partials, kNormBlocks, grad_norm);
   return gpt2mi::check_launch("adamw_norm");
+}
+
+GPT2MI_EXPORT int gpt2mi_adamw_clipped(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, size_t n,
+                                       float lr, float wd, float b1, float b2, float eps, int step, float grad_scale,
+                                       const float* coef_dev, float* partials, float* grad_norm, void* stream) {
+  GPT2MI_REQUIRE(n % 4 == 0, "adamw_clipped: n=%zu must be a multiple of 4", n);
+  GPT2MI_REQUIRE(step >= 1, "adamw_clipped: step must be >= 1");
+  GPT2MI_REQUIRE(coef_dev != nullptr, "adamw_clipped: coef_dev is NULL");
+  GPT2MI_REQUIRE(partials != nullptr || grad_norm == nullptr, "adamw_clipped: grad_norm needs partials");
+  hipStream_t s = (hipStream_t)stream;
+  const double bc1 = 1.0 - pow((double)b1, step), bc2 = 1.0 - pow((double)b2, step);
+  const float step_size = (float)(lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+  adamw_kernel<true><<<kNormBlocks, 256, 0, s>>>(p, g, m, v, (bf16*)p_bf16, n / 4, lr, wd, b1, b2, eps, step_size,
+                                                 bc2_sqrt, grad_scale, partials, coef_dev);
+  int rc = gpt2mi::check_launch("adamw_clipped");
+  if (rc || !grad_norm) return rc;
+  norm_finalize_kernel<<<1, 1024, 0, s>>>(partials, kNormBlocks, grad_norm);
+  return gpt2mi::check_launch("adamw_clipped_norm");
+}
+
+GPT2MI_EXPORT int gpt2mi_sumsq_partials(const float* g, size_t n, float scale, float* partials, void* stream) {
+  GPT2MI_REQUIRE(n % 4 == 0, "sumsq_partials: n=%zu must be a multiple of 4", n);
+  sumsq_kernel<<<kNormBlocks, 256, 0, (hipStream_t)stream>>>(g, n / 4, scale, partials);
+  return gpt2mi::check_launch("sumsq_partials");
+}
+
+GPT2MI_EXPORT int gpt2mi_clip_coef(const float* partials, int n, float max_norm, float* sumsq_out, float* norm_out,
+                                   float* coef_out, void* stream) {
+  GPT2MI_REQUIRE(n > 0, "clip_coef: n=%d", n);
+  GPT2MI_REQUIRE(max_norm >= 0.f, "clip_coef: max_norm=%g", (double)max_norm);
+  clip_coef_kernel<<<1, 1024, 0, (hipStream_t)stream>>>(partials, n, max_norm, sumsq_out, norm_out, coef_out);
+  return gpt2mi::check_launch("clip_coef");
 }
 
 GPT2MI_EXPORT int gpt2mi_grad_norm(const float* g, size_t n, float scale, float* partials, float* out, void* stream) {

@@ -298,13 +298,16 @@ class GPT2(nn.Module):
 
     # ---- optimizer (nanoGPT-style name the north star uses) -----------------------------------------
     def configure_optimizers(self, weight_decay: float = 0.1, learning_rate: float = 1e-4,
-                             betas=(0.9, 0.95), device_type: Optional[str] = None, eps: float = 1e-8):
+                             betas=(0.9, 0.95), device_type: Optional[str] = None, eps: float = 1e-8,
+                             max_grad_norm: Optional[float] = None):
         """The reference builds ``torch.optim.AdamW(model.parameters(), lr, weight_decay=0.1,
         betas=(0.9, 0.95), fused=True)`` inline (train_gpt2_distributed.py:356-362): ONE param group,
         so decay also hits biases/LayerNorm/embeddings. This returns the same optimizer as one fused
-        HIP kernel over the flat arena."""
+        HIP kernel over the flat arena. ``max_grad_norm``: ``clip_grad_norm_(parameters, max_grad_norm)`` folded
+        into ``step()`` (None or inf: off, the reference's clip at inf)."""
         from .optim import FusedAdamW
-        return FusedAdamW(self, lr=learning_rate, betas=betas, eps=eps, weight_decay=weight_decay)
+        return FusedAdamW(self, lr=learning_rate, betas=betas, eps=eps, weight_decay=weight_decay,
+                          max_grad_norm=max_grad_norm)
 
 
 GPT = GPT2  # nanoGPT alias used by the north star

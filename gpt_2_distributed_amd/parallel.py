@@ -945,10 +945,11 @@ class FullyShardedDataParallel(nn.Module):
         self.engine.discard_grads()
 
     def configure_optimizers(self, weight_decay=0.1, learning_rate=1e-4, betas=(0.9, 0.95), device_type=None,
-                             eps=1e-8):
+                             eps=1e-8, max_grad_norm=None):
         from .optim import ShardedAdamW
         self._defer_tail = self.overlap_optimizer  # ShardedAdamW.step waits for the deferred unit itself
-        return ShardedAdamW(self, lr=learning_rate, betas=betas, eps=eps, weight_decay=weight_decay)
+        return ShardedAdamW(self, lr=learning_rate, betas=betas, eps=eps, weight_decay=weight_decay,
+                            max_grad_norm=max_grad_norm)
 
     # ---- full state (checkpointing): collective, every rank calls --------------------------------------
     @torch.no_grad()

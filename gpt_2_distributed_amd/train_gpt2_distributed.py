@@ -6,6 +6,8 @@
         [--save_every 1000] [--save_dir ./checkpoints] [--log_dir ./logs] [--workers 2]
     build-side extensions: --model {124M,350M,1.5B} --dropout P --max_steps N --synthetic N_SHARDS
         --resume STEP_DIR --log_every N
+    recipe: --max_grad_norm X (0 = off) --lr_schedule {constant,cosine} --warmup_steps N --lr_decay_steps N
+        --min_lr X (nanoGPT clips at 1.0 with linear warmup and cosine decay to lr/10; all off by default)
 
 Loop semantics follow the reference (:374-457): seed 42; loss/grad_accum; backward; every
 grad_accum micro-steps the fused AdamW step (which also yields the clip_grad_norm_(inf) value);
@@ -32,6 +34,7 @@ import torch
 import torch.distributed as dist
 
 from . import dataloader as gpt2_dataloader
+from .lr_schedule import KINDS, lr_at
 from .model import GPT2, GPT2Config, MODEL_SIZES
 from .parallel import DistributedDataParallel, FullyShardedDataParallel, init_distributed, is_primary
 
@@ -70,7 +73,33 @@ def build_parser():
                         "reshard after forward")
     p.add_argument("--fsdp_reshard", action="store_true",
                    help="fsdp: reshard after forward (the default; kept for command lines of earlier rounds)")
+    # the recipe (all off by default: the reference clips at inf and keeps lr constant)
+    p.add_argument("--max_grad_norm", type=float, default=0.0,
+                   help="clip the global gradient norm to this value in the optimizer step (0 = off)")
+    p.add_argument("--lr_schedule", choices=list(KINDS), default="constant")
+    p.add_argument("--warmup_steps", type=int, default=0, help="cosine: linear warmup over N optimizer steps")
+    p.add_argument("--lr_decay_steps", type=int, default=0,
+                   help="cosine: the step at which lr reaches --min_lr (0 = --max_steps)")
+    p.add_argument("--min_lr", type=float, default=None, help="cosine: the final lr (default lr/10)")
     return p
+
+
+def schedule_from_args(args) -> dict:
+    """lr_at's keyword arguments for these flags (validated once, before anything is built)."""
+    if args.max_grad_norm < 0:
+        raise SystemExit("--max_grad_norm must be >= 0 (0 = off)")
+    if args.lr_schedule == "constant":
+        return dict(lr=args.lr, kind="constant")
+    decay = args.lr_decay_steps or args.max_steps
+    if not decay:
+        raise SystemExit("--lr_schedule cosine needs --lr_decay_steps or --max_steps")
+    sched = dict(lr=args.lr, warmup_steps=args.warmup_steps, decay_steps=decay,
+                 min_lr=args.lr / 10 if args.min_lr is None else args.min_lr, kind="cosine")
+    try:
+        lr_at(0, **sched)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return sched
 
 
 def save_checkpoint(model, opt, step: int, out_dir: str, trainer_state: dict = None):
@@ -151,6 +180,9 @@ def main(argv=None):
     torch.manual_seed(SEED)
     os.environ.setdefault("PYTORCH_CUDA_ALLOC_CONF", "expandable_segments:True")
     args = build_parser().parse_args(argv)
+    sched = schedule_from_args(args)
+    scheduled = sched["kind"] != "constant"
+    clip = args.max_grad_norm > 0
     if args.training_mode in ("fsdp", "ddp"):
         init_distributed()
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -192,7 +224,8 @@ def main(argv=None):
         model = FullyShardedDataParallel(base, overlap_optimizer=True, reshard_after_forward=not args.fsdp_resident)
     else:
         model = base
-    optim = model.configure_optimizers(weight_decay=0.1, learning_rate=args.lr, betas=(0.9, 0.95))
+    optim = model.configure_optimizers(weight_decay=0.1, learning_rate=args.lr, betas=(0.9, 0.95),
+                                       **({"max_grad_norm": args.max_grad_norm} if clip else {}))
     global_step, start_epoch, skip = 0, 0, 0
     # the epoch the DataLoader's persistent workers were spawned with: they keep that dataset copy, so every later
     # epoch replays its order (SURVEY §5 "epoch freeze"); a resumed run must spawn its workers with the same one
@@ -246,6 +279,9 @@ def main(argv=None):
             micro += 1
             if not last:
                 continue
+            lr = args.lr
+            if scheduled:  # a function of the steps taken, which a resume restores: no schedule state of its own
+                lr = optim.param_groups[0]["lr"] = lr_at(global_step, **sched)
             optim.step()
             optim.zero_grad()
             global_step += 1
@@ -257,7 +293,8 @@ def main(argv=None):
                 mem = memory_metrics(world)
                 if is_primary():
                     print(json.dumps({"step": global_step, "loss": round(loss.item() * args.grad_accum_steps, 5),
-                                      "grad_norm": round(float(optim.grad_norm.item()), 5), "lr": args.lr,
+                                      "grad_norm": round(float(optim.grad_norm.item()), 5), "lr": lr,
+                                      **({"clip_coef": round(float(optim.clip_coef.item()), 6)} if clip else {}),
                                       "tok_per_s_node": round(tps, 1),
                                       "mfu": round(tps * fpt / (world * PEAK_BF16), 4),
                                       "epoch_time": round(now - t_epoch, 2), **mem}), flush=True)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 15
+#define GPT2MI_ABI_VERSION 16
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -155,6 +155,21 @@ int gpt2mi_grad_norm(const float* g, size_t n, float scale, float* partials, flo
  * consecutive gpt2mi_norm_partials_size()-float slices of one partials buffer (FSDP's AdamW runs once per unit). */
 int gpt2mi_norm_finalize(const float* partials, int n, float* out, void* stream);
 int gpt2mi_norm_partials_size(void);
+/* v16: global-norm gradient clipping with the coefficient kept in device memory (nothing here reads it back).
+ * gpt2mi_sumsq_partials: gpt2mi_norm_partials_size() partial sums of (g*scale)^2 over g[0..n), n % 4 == 0; several
+ *   ranges fill consecutive slices of one buffer (the pieces of the arena around a DDP bucket, the FSDP units).
+ * gpt2mi_clip_coef: over partials[0..n) (n >= 1): norm_out[0] = sqrt(sum), the bits gpt2mi_norm_finalize gives;
+ *   sumsq_out[0] (may be NULL) = the fp32 sum, for a cross-rank all-reduce (then call again with n = 1 on it);
+ *   coef_out[0] = min(1, max_norm / (norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s coefficient: NaN for a NaN norm,
+ *   0 for an infinite one.
+ * gpt2mi_adamw_clipped: gpt2mi_adamw with every gradient scaled by grad_scale * coef_dev[0]. partials and grad_norm
+ *   may be NULL (they would see the clipped gradients; the pre-clip norm is gpt2mi_clip_coef's). */
+int gpt2mi_sumsq_partials(const float* g, size_t n, float scale, float* partials, void* stream);
+int gpt2mi_clip_coef(const float* partials, int n, float max_norm, float* sumsq_out, float* norm_out, float* coef_out,
+                     void* stream);
+int gpt2mi_adamw_clipped(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, size_t n, float lr, float wd,
+                         float b1, float b2, float eps, int step, float grad_scale, const float* coef_dev,
+                         float* partials, float* grad_norm, void* stream);
 
 /* ---- fp32 mode: the reference model.py run WITHOUT torch.autocast (plain fp32 module; the CPU
  * trajectory goldens and the north star's "fp32 loss within 1e-4" gate). Same contracts as the bf16
