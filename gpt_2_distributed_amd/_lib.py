@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -84,6 +84,13 @@ _SIGS = {
     "gpt2mi_attn_decode_workspace": [_c_int, _c_int, _c_int],
     "gpt2mi_embed_decode": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _p],
     "gpt2mi_decode_step": [_p, _p, _c_int, _p],
+    # v17 sampling: logits, ldl, B, V, temperature, top_k, top_p, seed, pos, eos, done, tok_out, seq_out, ld_seq,
+    # probs_out, stream
+    "gpt2mi_sample": [_p, _c_int, _c_int, _c_int, _c_float, _c_int, _c_float, _c_u64, _c_int, ctypes.c_int64, _p, _p,
+                      _p, _c_int, _p, _p],
+    # plan, V, temperature, top_k, top_p, seed, eos, pos0, n, tok, seq, ld_seq, done, stream
+    "gpt2mi_decode_generate": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _c_int, _c_int, _p, _p,
+                               _c_int, _p, _p],
 }
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size}
@@ -427,3 +434,28 @@ def embed_decode(tok, wte, wpe, x, B, C, pos):
 def decode_step(plan: DecodePlan, tok, pos):
     """One token step of the whole network (gpt2mi_decode_step) into plan.logits."""
     _call("gpt2mi_decode_step", ctypes.byref(plan), _ptr(tok), pos, _stream())
+
+
+# ---- v17: device-side sampling (csrc/sample.hip) --------------------------------------------------
+SAMPLE_MAX_V = 51200  # gpt2mi.h GPT2MI_SAMPLE_MAX_V
+
+
+def _sampler_args(temperature, top_k, top_p, seed, eos):
+    """The sampler's scalars as the C entries take them (top_k <= 0 and top_p >= 1 mean off, eos -1 none)."""
+    return (float(temperature), 0 if top_k is None else int(top_k), 1.0 if top_p is None else float(top_p),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, -1 if eos is None else int(eos))
+
+
+def sample(logits, V, temperature, top_k, top_p, seed, pos, tok_out, eos=None, done=None, seq_out=None, probs_out=None):
+    """gpt2mi_sample: one token per row of fp32 logits [B, ldl] (V valid columns) into tok_out (int64 [B]), column pos
+    of seq_out (int64 [B, ld_seq]) and probs_out (fp32 [B, V], tests)."""
+    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
+    _call("gpt2mi_sample", _ptr(logits), logits.stride(0), logits.size(0), V, t, k, p, s, pos, e, _ptr(done),
+          _ptr(tok_out), _ptr(seq_out), 0 if seq_out is None else seq_out.stride(0), _ptr(probs_out), _stream())
+
+
+def decode_generate(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, eos=None, seq=None, done=None):
+    """gpt2mi_decode_generate: n sample-then-step rounds from plan.logits without leaving C."""
+    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
+    _call("gpt2mi_decode_generate", ctypes.byref(plan), V, t, k, p, s, e, pos0, n, _ptr(tok), _ptr(seq),
+          0 if seq is None else seq.stride(0), _ptr(done), _stream())

@@ -437,3 +437,26 @@ GPT2MI_EXPORT int gpt2mi_decode_step(const gpt2mi_decode_plan* P, const int64_t*
 #undef STEP
   return 0;
 }
+
+GPT2MI_EXPORT int gpt2mi_decode_generate(const gpt2mi_decode_plan* P, int V, float temperature, int top_k, float top_p,
+                                         uint64_t seed, int64_t eos, int pos0, int n, int64_t* tok, int64_t* seq,
+                                         int ld_seq, uint8_t* done, void* stream) {
+  GPT2MI_REQUIRE(P != nullptr, "decode_generate: plan is NULL");
+  GPT2MI_REQUIRE(V >= 1 && V <= P->Vp, "decode_generate: V=%d not in [1, Vp=%d]", V, P->Vp);
+  GPT2MI_REQUIRE(n >= 0 && pos0 >= 1, "decode_generate: n=%d must be >= 0 and pos0=%d >= 1 (after a prefill)", n, pos0);
+  GPT2MI_REQUIRE((long long)pos0 + n <= P->Tcap, "decode_generate: pos0=%d + n=%d exceeds the cache length Tcap=%d", pos0,
+                 n, P->Tcap);
+  GPT2MI_REQUIRE(!seq || (long long)pos0 + n <= ld_seq, "decode_generate: pos0=%d + n=%d exceeds ld_seq=%d", pos0, n,
+                 ld_seq);
+  GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr, "decode_generate: tok and plan->logits must not be NULL");
+  for (int i = 0; i < n; ++i) {
+    int rc = gpt2mi_sample(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, pos0 + i, eos, done, tok, seq,
+                           ld_seq, nullptr, stream);
+    if (rc) return rc;
+    if (i + 1 < n) {
+      rc = gpt2mi_decode_step(P, tok, pos0 + i, stream);
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}

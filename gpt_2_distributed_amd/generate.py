@@ -1,5 +1,5 @@
 """Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
---prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --seed S --batch B]``.
+--prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -25,6 +25,10 @@ def parse_args(argv=None):
     p.add_argument("--max_new_tokens", type=int, default=64)
     p.add_argument("--temperature", type=float, default=1.0)
     p.add_argument("--top_k", type=int, default=None)
+    p.add_argument("--top_p", type=float, default=None, help="nucleus filter in (0, 1); >= 1 or unset: off")
+    p.add_argument("--sampler", default="torch", choices=["torch", "device"],
+                   help="torch: sample_next with a torch.Generator seeded by --seed; device: the fused sampling kernel, "
+                        "drawing from (--seed, row, position), and the token loop issued from C")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--batch", type=int, default=1)
     p.add_argument("--eos_token_id", type=int, default=None)
@@ -57,9 +61,10 @@ def main(argv=None) -> int:
         raise SystemExit("--prompt_ids is empty")
     model = load_model(a.checkpoint, a.model)
     idx = torch.tensor([prompt] * a.batch, dtype=torch.int64, device="cuda:0")
-    gen = torch.Generator(device="cuda:0").manual_seed(a.seed)
-    out = model.generate(idx, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, generator=gen,
-                         eos_token_id=a.eos_token_id)
+    how = (dict(seed=a.seed) if a.sampler == "device"
+           else dict(generator=torch.Generator(device="cuda:0").manual_seed(a.seed)))
+    out = model.generate(idx, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
+                         eos_token_id=a.eos_token_id, **how)
     for row in out.tolist():
         print(json.dumps(row))
     return 0

@@ -4,7 +4,9 @@ The reference (model.py, train_gpt2_distributed.py) trains and evaluates only; c
 calling ``model(idx)`` on the whole growing sequence for every new token. Here a prompt is run once through the
 engine's trunk forward (``DecodeSession.prefill``), its keys and values are copied into the cache, and every further
 token is one call of ``gpt2mi_decode_step`` (csrc/decode.hip): weight-streaming skinny GEMMs and single-query attention
-over the cache, about 10 launches per layer issued from C.
+over the cache, about 10 launches per layer issued from C. The next token is drawn either on the host side in PyTorch
+(``sample_next``, from a ``torch.Generator``) or, with a ``seed``, by ``gpt2mi_sample`` on the device (csrc/sample.hip;
+``sample_reference`` and ``uniform_at`` state what it computes), in which case the whole loop is one C call.
 
 Numerics are the autocast path's whatever the autocast state: bf16 GEMM operands from the engine's weight shadow, fp32
 accumulation, fp32 residual stream / LayerNorm / softmax, dropout off (p = 0 whatever ``model.training`` is, and
@@ -29,12 +31,28 @@ F32 = torch.float32
 MAX_BATCH = 64  # rows of the skinny GEMM (gpt2mi_gemm_skinny)
 
 
+def _nucleus_keep(key: torch.Tensor, probs: torch.Tensor, top_p: float) -> torch.Tensor:
+    """The top-p rule on probabilities [B, V] (rows summing to 1), tokens ordered by ``key`` [B, V] (the probabilities
+    themselves, or the values they were formed from): token i is kept iff the total probability of the tokens with a
+    strictly larger key is < top_p (ties at the threshold all kept, the largest always kept)."""
+    sk, order = torch.sort(key, dim=-1, descending=True)
+    sp = probs.gather(-1, order)
+    before = sp.cumsum(-1) - sp                                  # mass ahead of each sorted position
+    pos = torch.arange(sk.size(-1), device=sk.device).expand_as(sk)
+    new = torch.ones_like(sk, dtype=torch.bool)
+    new[:, 1:] = sk[:, 1:] != sk[:, :-1]
+    first = torch.where(new, pos, torch.zeros_like(pos)).cummax(-1).values  # where a position's run of equals starts
+    keep_sorted = before.gather(-1, first) < top_p
+    return torch.zeros_like(keep_sorted).scatter(-1, order, keep_sorted)
+
+
 def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None,
-                generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                generator: Optional[torch.Generator] = None, top_p: Optional[float] = None) -> torch.Tensor:
     """Next token ids [B] from logits [B, V] (nanoGPT's rule; pure torch, any device).
 
     ``temperature == 0`` is greedy argmax. Otherwise ``logits / temperature``, optionally everything below the
-    ``top_k``-th largest logit of a row set to -inf, softmax, and one ``torch.multinomial`` draw per row from
+    ``top_k``-th largest logit of a row set to -inf, softmax, optionally (``top_p`` in (0, 1)) every token dropped whose
+    strictly more probable tokens already weigh ``top_p`` or more, and one ``torch.multinomial`` draw per row from
     ``generator``."""
     if logits.dim() != 2:
         raise ValueError(f"sample_next takes logits [B, V] (got {tuple(logits.shape)})")
@@ -42,6 +60,7 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[
         raise ValueError(f"temperature must be >= 0 (got {temperature})")
     if top_k is not None and top_k < 1:
         raise ValueError(f"top_k must be >= 1 (got {top_k})")
+    _check_top_p(top_p)
     logits = logits.float()
     if temperature == 0:
         return logits.argmax(dim=-1)
@@ -50,7 +69,60 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[
         kth = torch.topk(logits, top_k, dim=-1).values[:, -1:]
         logits = logits.masked_fill(logits < kth, float("-inf"))
     probs = torch.softmax(logits, dim=-1)
+    if top_p is not None and top_p < 1:
+        probs = probs.masked_fill(~_nucleus_keep(probs, probs, top_p), 0.0)  # (multinomial normalises what is left)
     return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
+
+
+def _check_top_p(top_p):
+    if top_p is not None and not top_p > 0:  # (NaN too)
+        raise ValueError(f"top_p must be > 0 (got {top_p}); >= 1 or None turns it off")
+
+
+# ---- the device sampler's contract (gpt2mi_sample, csrc/sample.hip), executable -------------------------------------
+_M64 = (1 << 64) - 1
+
+
+def uniform_at(seed: int, b: int, pos: int) -> float:
+    """The uniform in [0, 1) that row ``b`` draws with at position ``pos``: 24 bits of splitmix64's finaliser over
+    ``seed + 0x9E3779B97F4A7C15 * (1 + (b << 32 | pos))``. A pure function: no state, no dependence on the batch."""
+    c = ((seed & _M64) + 0x9E3779B97F4A7C15 * (1 + (((b & 0xFFFFFFFF) << 32) | (pos & 0xFFFFFFFF)))) & _M64
+    c ^= c >> 30
+    c = (c * 0xBF58476D1CE4E5B9) & _M64
+    c ^= c >> 27
+    c = (c * 0x94D049BB133111EB) & _M64
+    c ^= c >> 31
+    return (c >> 40) * 2.0 ** -24
+
+
+def sample_reference(logits: torch.Tensor, temperature: float, top_k: Optional[int], top_p: Optional[float],
+                     u: torch.Tensor):
+    """What gpt2mi_sample computes, in float64 (any device): ``(tokens [B], probs [B, V])`` from logits [B, V] and the
+    uniforms ``u`` [B] (``uniform_at``'s for the device's draw).
+
+    ``temperature == 0``: argmax, the lowest index among equal maxima (probs one-hot). Otherwise x = fp32
+    ``logits / temperature``; top-k keeps x >= the k-th largest value; top-p, on the softmax p of what top-k kept, keeps
+    token i iff the tokens with a strictly larger value weigh < top_p; the token is the first index, in vocabulary
+    order, whose inclusive cumulative kept probability exceeds u * Z (Z the kept mass). probs = p_i / Z, 0 if filtered."""
+    B, V = logits.shape
+    x = logits.float()
+    if temperature == 0:
+        mx = x.max(-1, keepdim=True).values
+        tok = (x == mx).int().argmax(-1)  # argmax of a 0/1 tensor: the first 1
+        return tok, torch.zeros(B, V, dtype=torch.float64, device=x.device).scatter_(1, tok[:, None], 1.0)
+    x = x / temperature
+    keep = torch.ones_like(x, dtype=torch.bool)
+    if top_k is not None and 1 <= top_k < V:
+        keep = x >= torch.topk(x, top_k, dim=-1).values[:, -1:]
+    xd = x.double()
+    p = torch.softmax(xd.masked_fill(~keep, float("-inf")), dim=-1)
+    if top_p is not None and top_p < 1:
+        keep = keep & _nucleus_keep(xd, p, top_p)  # (ties decided by the value, not by the p it rounds to)
+    pk = p * keep
+    Z = pk.sum(-1, keepdim=True)
+    cdf = pk.cumsum(-1)
+    tok = (cdf > u.double().to(x.device)[:, None] * Z).int().argmax(-1)
+    return tok, pk / Z
 
 
 def _check_model(model):
@@ -101,6 +173,8 @@ class DecodeSession:
         shapes = [(3 * C, C), (C, C), (4 * C, C), (C, 4 * C), (Vp, C)]
         self.gemm_ws = e(max(max(K.gemm_skinny_workspace(B, n, k) for n, k in shapes), 1), dt=F32)
         self.logits = e(B, Vp, dt=F32)
+        self._tok = e(B, dt=torch.int64)  # the device loop's newest tokens (DecodeSession.generate)
+        self._drawn = False               # True: generate() drew _tok from the logits in place and has not stepped it
         self._plan = self._build_plan()
 
     def _build_plan(self) -> K.DecodePlan:
@@ -168,7 +242,7 @@ class DecodeSession:
         last = ws.lnf.view(B, Tp, C)[:, P - 1]  # rows b*Tp + P-1: row stride Tp*C
         K.gemm_skinny(K.EPI_F32, B, Vp, C, last, Tp * C, eng.w16("transformer.wte.weight"), C, self.logits, Vp,
                       workspace=self.gemm_ws)
-        self.pos = P
+        self.pos, self._drawn = P, False
         return self.logits[:, :cfg.vocab_size].clone()
 
     @torch.no_grad()
@@ -186,12 +260,72 @@ class DecodeSession:
         tok = tokens.contiguous() if tokens.dtype == torch.int64 else tokens.long()
         K.decode_step(self._plan, tok, self.pos)
         self.pos += 1
+        self._drawn = False
         return self.logits[:, :self.cfg.vocab_size].clone()
+
+    # ---- device-side sampling (gpt2mi_sample, gpt2mi_decode_generate): nothing below returns to the host ----
+    def _check_sampler(self, temperature, top_p, seed):
+        if self.pos == 0:
+            raise RuntimeError("sampling before prefill: there are no logits")
+        if temperature < 0:
+            raise ValueError(f"temperature must be >= 0 (got {temperature})")
+        _check_top_p(top_p)
+        if not isinstance(seed, int):
+            raise ValueError(f"seed must be an int (got {seed!r})")
+        if self.cfg.vocab_size > K.SAMPLE_MAX_V:
+            raise NotImplementedError(f"the sampling kernel holds rows of up to {K.SAMPLE_MAX_V} logits "
+                                      f"(vocab_size {self.cfg.vocab_size})")
+        self._ready(False)
+
+    @torch.no_grad()
+    def sample(self, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+               seed: int = 0) -> torch.Tensor:
+        """Tokens [B] (int64, device) for position ``pos`` from the logits of the last ``prefill`` / ``step``: one
+        launch, no host synchronisation. Row b's token is a function of (its logits, the parameters, seed, b, pos):
+        ``sample_reference`` with ``uniform_at(seed, b, pos)``."""
+        self._check_sampler(temperature, top_p, seed)
+        if self._drawn:
+            raise RuntimeError("the logits are those generate() drew its last token from: step() that token first")
+        out = torch.empty(self.B, dtype=torch.int64, device=self.logits.device)
+        K.sample(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.pos, out)
+        return out
+
+    @torch.no_grad()
+    def generate(self, n: int, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                 seed: int = 0, eos_token_id: Optional[int] = None, seq: Optional[torch.Tensor] = None,
+                 done: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Draw the tokens of positions ``pos .. pos + n - 1`` in one C call (gpt2mi_decode_generate: sample, step,
+        sample, ... on the stream, no Python and no synchronisation in between). The tokens go to column ``pos + i`` of
+        ``seq`` (int64 [B, >= pos + n], optional); with ``eos_token_id``, ``done`` (uint8 [B]) marks finished rows, which
+        keep emitting eos. Returns the newest tokens [B] (a buffer the next call overwrites). The last token drawn is
+        not stepped until the next ``generate`` (which does it first) or ``step``."""
+        self._check_sampler(temperature, top_p, seed)
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"generate takes n >= 1 (got {n})")
+        if self.pos + int(self._drawn) + n > self.Tcap:
+            raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
+        if seq is not None and (seq.dtype != torch.int64 or seq.dim() != 2 or seq.size(0) != self.B or seq.stride(1) != 1):
+            raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
+        if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
+            raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
+        if self._drawn:  # the token the previous call ended on
+            K.decode_step(self._plan, self._tok, self.pos)
+            self.pos += 1
+        K.decode_generate(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.pos, n, self._tok,
+                          eos=eos_token_id, seq=seq, done=done if eos_token_id is not None else None)
+        self.pos += n - 1
+        self._drawn = True
+        return self._tok
+
+
+EOS_CHUNK = 32  # device loop with eos_token_id: tokens issued between two reads of the done flags
 
 
 @torch.no_grad()
 def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
-             generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None) -> torch.Tensor:
+             generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
+             top_p: Optional[float] = None, seed: Optional[int] = None) -> torch.Tensor:
     """``GPT2.generate``: see there."""
     if idx.dim() != 2:
         raise ValueError(f"generate takes idx [B, P] (got {tuple(idx.shape)})")
@@ -201,16 +335,21 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
         raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
     if P + n > model.config.n_positions:
         raise ValueError(f"prompt length {P} + max_new_tokens {n} > n_positions {model.config.n_positions}")
+    _check_top_p(top_p)
+    if seed is not None and generator is not None:
+        raise ValueError("seed selects the device sampler, which draws from (seed, row, position): it takes no generator")
     _check_model(model)
     idx = idx.long()
     if n == 0:
         return idx.clone()
     sess = DecodeSession(model, B, P + n)
+    if seed is not None:
+        return _generate_on_device(sess, idx, n, temperature, top_k, top_p, seed, eos_token_id)
     out = [idx]
     done = torch.zeros(B, dtype=torch.bool, device=idx.device)
     logits = sess.prefill(idx)
     for i in range(n):
-        nxt = sample_next(logits, temperature, top_k, generator)
+        nxt = sample_next(logits, temperature, top_k, generator, top_p)
         if eos_token_id is not None:
             nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)  # a finished row keeps emitting eos
             done = done | (nxt == eos_token_id)
@@ -220,3 +359,32 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
         if i + 1 < n:
             logits = sess.step(nxt)
     return torch.cat(out, dim=1)
+
+
+def _generate_on_device(sess: DecodeSession, idx, n, temperature, top_k, top_p, seed, eos_token_id):
+    """The loop of ``generate`` with the sampler on the device: one [B, P + n] buffer holds the prompt and receives the
+    tokens. Without eos nothing is read back; with eos the loop is issued EOS_CHUNK tokens at a time and the done flags
+    are read once per chunk, then the result is cut after the column by which every row has emitted eos (the shape and
+    padding of the host loop)."""
+    B, P = idx.shape
+    if eos_token_id is not None and not 0 <= eos_token_id < sess.cfg.vocab_size:
+        raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={sess.cfg.vocab_size})")
+    seq = torch.empty(B, P + n, dtype=torch.int64, device=idx.device)
+    seq[:, :P] = idx
+    sess.prefill(idx)
+    if eos_token_id is None:
+        sess.generate(n, temperature, top_k, top_p, seed, seq=seq)
+        return seq
+    done = torch.zeros(B, dtype=torch.uint8, device=idx.device)
+    made = 0
+    while made < n:
+        m = min(EOS_CHUNK, n - made)
+        sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done)
+        made += m
+        if bool(done.all()):
+            break
+    new = seq[:, P:P + made]
+    finished = ((new == eos_token_id).cumsum(1) > 0).all(0)  # columns by which every row has emitted eos
+    if bool(finished.any()):
+        made = int(finished.int().argmax()) + 1
+    return seq[:, :P + made].clone() if made < n else seq

@@ -279,12 +279,19 @@ class GPT2(nn.Module):
         return DecodeSession(self, batch_size, max_len)
 
     def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
-                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None) -> torch.Tensor:
+                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
+                 top_p: Optional[float] = None, seed: Optional[int] = None) -> torch.Tensor:
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
-        filter, softmax and ``torch.multinomial`` with ``generator`` (``generation.sample_next``). With
-        ``eos_token_id`` a finished row keeps emitting it and generation stops once every row has finished (n is then
-        smaller). ``P + max_new_tokens > n_positions`` raises ``ValueError``.
+        filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
+        (``generation.sample_next``). With ``eos_token_id`` a finished row keeps emitting it and generation stops once
+        every row has finished (n is then smaller). ``P + max_new_tokens > n_positions`` raises ``ValueError``.
+
+        With an integer ``seed`` the tokens are drawn on the device instead (``gpt2mi_sample``; the rule is
+        ``generation.sample_reference`` with ``generation.uniform_at(seed, row, position)``: reproducible per row and
+        position whatever the batch) and the whole loop is issued from C: without ``eos_token_id`` nothing synchronises
+        the host before the return, with it the done flags are read once per 32 tokens. Same output shape and padding.
+        ``seed`` together with ``generator``, or ``top_p <= 0``, raises ``ValueError``.
 
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
         the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
@@ -294,7 +301,7 @@ class GPT2(nn.Module):
         backward. Through ``DistributedDataParallel`` call ``.module.generate``; a ``FullyShardedDataParallel``-wrapped
         model holds only a shard of the parameters and raises ``NotImplementedError``."""
         from .generation import generate
-        return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id)
+        return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed)
 
     # ---- optimizer (nanoGPT-style name the north star uses) -----------------------------------------
     def configure_optimizers(self, weight_decay: float = 0.1, learning_rate: float = 1e-4,

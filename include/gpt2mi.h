@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 16
+#define GPT2MI_ABI_VERSION 17
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -299,6 +299,40 @@ typedef struct gpt2mi_decode_plan {
 /* embed -> per layer (LN1, qkv, attention at pos, proj + resid, LN2, fc1 + GELU, fc2 + resid) -> ln_f -> lm_head into
  * plan->logits, for the B tokens `tok` (device int64 [B]) at position pos (model.py:295-351 at one position). */
 int gpt2mi_decode_step(const gpt2mi_decode_plan* plan, const int64_t* tok, int pos, void* stream);
+
+/* ---- v17: device-side sampling (csrc/sample.hip) and the token loop around it. The executable specification of the
+ * rule is gpt_2_distributed_amd/generation.py sample_reference + uniform_at (nanoGPT's temperature / top-k rule, as
+ * generation.py sample_next, plus nucleus filtering and a counter-based draw). ---- */
+/* Largest vocabulary gpt2mi_sample takes: one 1024-thread workgroup holds a row in registers, 50 logits per thread. */
+#define GPT2MI_SAMPLE_MAX_V 51200
+/* One token per row b < B from logits fp32 [B][ldl] (columns V..ldl-1 are padding and are not read). One launch, one
+ * workgroup per row; the row is read once.
+ *  temperature == 0: the argmax, the lowest index among equal maxima (top_k, top_p, seed ignored; probs_out one-hot).
+ *  otherwise x = logits / temperature (IEEE fp32 division), then
+ *   top_k (1 <= top_k < V; else off): keep x >= the k-th largest value of the row (ties at it all kept);
+ *   top_p (0 < top_p < 1; >= 1 off), on p = softmax of what top-k kept: keep token i iff the total p of the tokens
+ *     with a value strictly larger than x_i is < top_p (ties at the threshold all kept, the largest always kept);
+ *   draw: u = (h >> 40) * 2^-24 with h = splitmix64's finaliser of seed + 0x9E3779B97F4A7C15 * (1 + (b << 32 | pos));
+ *     the token is the first kept index i, in vocabulary order, whose inclusive cumulative p exceeds u * Z (Z = the kept
+ *     mass): a pure function of (row, parameters, seed, b, pos), whatever B is.
+ *  eos (-1: none) / done (uint8 [B], may be NULL): a row whose done flag is set emits eos; otherwise a row that draws eos
+ *   sets its flag.
+ *  Writes tok_out[b], seq_out[b*ld_seq + pos] (seq_out may be NULL) and, for tests, probs_out [B][V] (may be NULL): the
+ *   kept distribution, p_i / Z, zero where filtered.
+ * No float atomics; every float reduction and scan runs in a fixed order: two calls give the same bits.
+ * Refused with 22 before any launch: B < 1, V < 1 or > GPT2MI_SAMPLE_MAX_V, ldl < V, temperature < 0 or NaN,
+ * top_p <= 0 or NaN, pos < 0, eos outside [-1, V), ld_seq <= pos with seq_out, NULL logits or tok_out. */
+int gpt2mi_sample(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p, uint64_t seed,
+                  int pos, int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out,
+                  void* stream);
+/* n tokens per sequence without returning to the caller: for i < n, gpt2mi_sample from plan->logits (V valid columns)
+ * at position pos0 + i into tok (device int64 [B]) and seq[:, pos0 + i] (seq may be NULL), then, if i + 1 < n,
+ * gpt2mi_decode_step(plan, tok, pos0 + i). On entry plan->logits holds the logits for position pos0 (the prefill's or
+ * the previous step's); on return the token of position pos0 + n - 1 is in tok and has not been stepped. A host loop of
+ * launches on `stream`: nothing is synchronised or read back. n = 0 does nothing. */
+int gpt2mi_decode_generate(const gpt2mi_decode_plan* plan, int V, float temperature, int top_k, float top_p,
+                           uint64_t seed, int64_t eos, int pos0, int n, int64_t* tok, int64_t* seq, int ld_seq,
+                           uint8_t* done, void* stream);
 
 #ifdef __cplusplus
 }
