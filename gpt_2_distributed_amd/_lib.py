@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -91,9 +91,14 @@ _SIGS = {
     # plan, V, temperature, top_k, top_p, seed, eos, pos0, n, tok, seq, ld_seq, done, stream
     "gpt2mi_decode_generate": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _c_int, _c_int, _p, _p,
                                _c_int, _p, _p],
+    # v18 evaluation: x, ldx, w, ldw, w_rows, labels, M, V, K, ignore_index, loss_rows, lse, loss_sum, count, accumulate,
+    # loss_mean, workspace, stream
+    "gpt2mi_lm_loss": [_p, _c_int, _p, _c_int, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p,
+                       _p, _p],
+    "gpt2mi_lm_loss_workspace": [_c_int, _c_int],
 }
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
-             "gpt2mi_attn_decode_workspace": _c_size}
+             "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size}
 
 EXPORTED = tuple(_SIGS)
 
@@ -459,3 +464,22 @@ def decode_generate(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, 
     t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
     _call("gpt2mi_decode_generate", ctypes.byref(plan), V, t, k, p, s, e, pos0, n, _ptr(tok), _ptr(seq),
           0 if seq is None else seq.stride(0), _ptr(done), _stream())
+
+
+# ---- v18: evaluation (csrc/lm_loss.hip) -------------------------------------------------------------
+def lm_loss_workspace(M, V) -> int:
+    """fp32 elements of workspace lm_loss needs for M rows over a vocabulary of V."""
+    return load().gpt2mi_lm_loss_workspace(M, V) // 4
+
+
+def lm_loss(x, ldx, w, ldw, w_rows, labels, M, V, K, loss_rows, lse, workspace, loss_sum=None, count=None,
+            accumulate=False, loss_mean=None, ignore_index=-100):
+    """gpt2mi_lm_loss: the rows of F.cross_entropy(x @ w[:V].T, labels) from bf16 x [M, ldx] and w [w_rows, ldw] without
+    forming the logits; loss_sum / count (+)= this call's sum and number of valid labels, loss_mean = their ratio."""
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise KernelError(f"lm_loss takes bf16 operands (got {x.dtype}, {w.dtype})")
+    if workspace.dtype != torch.float32 or workspace.numel() < lm_loss_workspace(M, V):
+        raise KernelError(f"lm_loss: workspace of {workspace.numel()} {workspace.dtype} elements, needs "
+                          f"{lm_loss_workspace(M, V)} fp32")
+    _call("gpt2mi_lm_loss", _ptr(x), ldx, _ptr(w), ldw, w_rows, _ptr(labels), M, V, K, ignore_index, _ptr(loss_rows),
+          _ptr(lse), _ptr(loss_sum), _ptr(count), int(accumulate), _ptr(loss_mean), _ptr(workspace), _stream())

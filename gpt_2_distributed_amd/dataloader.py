@@ -15,6 +15,8 @@ Shards are raw little-endian uint16 files (memory-mapped, never loaded whole).
 Beyond the reference: ``iter_batches`` is an in-process, vectorised iterator over the same order
 (one fancy-indexed gather per batch instead of B per-sample copies + collate), used by the trainer
 when ``--workers 0`` (the reference crashes there: prefetch_factor with 0 workers).
+``iter_eval_batches`` walks a validation split in order, its windows dealt round-robin to the ranks (the training
+order assigns whole shards to ranks: with one validation shard every rank but 0 would get nothing).
 """
 from __future__ import annotations
 
@@ -140,3 +142,38 @@ def iter_batches(shard_paths, seq_len: int, batch_size: int, num_workers: int = 
             except StopIteration:
                 pass
         alive = nxt
+
+
+def eval_windows(shard_paths, seq_len: int) -> List[Tuple[pathlib.Path, int]]:
+    """(shard, offset) of every evaluation window: the non-overlapping ``seq_len + 1``-token windows of the sorted
+    shards, in order, at the offsets ``range(0, n - (seq_len + 1), seq_len)`` the training loader uses."""
+    out = []
+    for path in sorted(shard_paths):
+        n = os.path.getsize(path) // 2
+        out.extend((path, o) for o in range(0, n - (seq_len + 1), seq_len))
+    return out
+
+
+def iter_eval_batches(shard_paths, seq_len: int, batch_size: int, rank: int = 0, world: int = 1,
+                      max_batches: int = None) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+    """Evaluation batches of rank ``rank`` of ``world``: window i of ``eval_windows`` belongs to rank i % world, no
+    shuffle, and every rank yields the same number of full int64 ``(x, y)`` batches [batch_size, seq_len]:
+    min(max_batches, floor(floor(n_windows / world) / batch_size)) (the windows past that are not evaluated). A pure
+    function of its arguments: evaluation has no position to checkpoint."""
+    if not (0 <= rank < world) or batch_size < 1 or seq_len < 1:
+        raise ValueError(f"iter_eval_batches: rank {rank} of {world}, batch_size {batch_size}, seq_len {seq_len}")
+    wins = eval_windows(shard_paths, seq_len)
+    n_batches = (len(wins) // world) // batch_size
+    if max_batches is not None:
+        n_batches = min(n_batches, max(0, max_batches))
+    ar = np.arange(seq_len + 1)
+    maps = {}
+    for b in range(n_batches):
+        out = np.empty((batch_size, seq_len + 1), dtype=np.int64)
+        for j in range(batch_size):
+            path, o = wins[(b * batch_size + j) * world + rank]
+            if path not in maps:
+                maps[path] = _open(path)[0]
+            out[j] = maps[path][o + ar]
+        t = torch.from_numpy(out)
+        yield t[:, :-1].contiguous(), t[:, 1:].contiguous()

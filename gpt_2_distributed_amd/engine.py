@@ -29,6 +29,10 @@ HBM layout per (B, T) workspace (M = B*T tokens, C = n_embd, Vp = vocab padded t
              (returned as a [B,T,V] view that stays valid as long as the caller holds it)
   backward scratch: dres fp32 [M,C], dres_bf bf16 [M,C], dln bf16 [M,C], dU bf16 [M,4C],
              dqkv bf16 [M,3C], delta fp32 [B*H,T], dqkv_cs fp32 [M/32,3C]
+
+Evaluation (``Engine.score``) is forward-only and has its own, small workspace (``EvalWorkspace``: two residual
+buffers, ONE block's activations, ln_f, the loss rows): no logits tensor (bf16: the lm_head runs fused with the
+cross-entropy, ``gpt2mi_lm_loss``), dropout off, and nothing of the training state above is read or written.
 """
 from __future__ import annotations
 
@@ -182,6 +186,68 @@ class Workspace(Scratch):
         self.lse_ce = e(M, dt=F32)
         self.inv_count = e(1, dt=F32)
         self.dscale = e(1, dt=F32)
+
+
+class _Alternating:
+    """x[l] of a forward that keeps nothing for a backward: two buffers used alternately."""
+
+    def __init__(self, a, b):
+        self.bufs = (a, b)
+
+    def __getitem__(self, l):
+        return self.bufs[l & 1]
+
+
+class _Shared:
+    """blocks[l] of a forward that keeps nothing for a backward: every layer writes the same activations."""
+
+    def __init__(self, acts):
+        self.acts = acts
+
+    def __getitem__(self, l):
+        return self.acts
+
+
+EVAL_F32_CHUNK = 4096  # rows of fp32 logits the fp32 evaluation head holds at a time
+
+
+class EvalWorkspace:
+    """Activations of the forward-only evaluation path (Engine.score) for one (B, T): what ONE block writes, two
+    residual buffers, the ln_f output and the loss rows. It presents ``x[l]`` / ``blocks[l]`` as a Workspace does, so
+    Engine._trunk_fwd runs on it unchanged. No term in n_layer and no [M, Vp] logits: bf16 has the fused head's split
+    partials (gpt2mi_lm_loss_workspace), fp32 a logits buffer of at most EVAL_F32_CHUNK rows."""
+
+    @staticmethod
+    def shapes(cfg, B, T, V, vpad, act):
+        """name -> (shape, dtype) of every buffer (the BlockActs aside)."""
+        M, C = B * T, cfg.n_embd
+        sh = {"x0": ((M, C), F32), "x1": ((M, C), F32), "lnf": ((M, C), act), "mf": ((M,), F32), "rf": ((M,), F32),
+              "loss_rows": ((M,), F32), "lse_ce": ((M,), F32), "loss_mean": ((1,), F32), "inv_count": ((1,), F32)}
+        if act == BF16:
+            sh["head_ws"] = ((K.lm_loss_workspace(M, V),), F32)
+        else:
+            sh["head_ws"] = ((min(M, EVAL_F32_CHUNK), vpad), F32)
+        return sh
+
+    @classmethod
+    def nbytes(cls, cfg, B, T, V, vpad, act):
+        """Bytes of the tensors the constructor allocates, counted on the same construction without storage."""
+        ws = cls(cfg, B, T, V, vpad, torch.device("meta"), act)
+        return sum(t.numel() * t.element_size() for t in ws.tensors())
+
+    def tensors(self):
+        own = [getattr(self, name) for name in self._names]
+        return own + [t for t in vars(self.blocks.acts).values() if t is not None]
+
+    def __init__(self, cfg, B, T, V, vpad, device, act=BF16):
+        self.act = act
+        self.B, self.T, self.M = B, T, B * T
+        sh = self.shapes(cfg, B, T, V, vpad, act)
+        self._names = tuple(sh)
+        for name, (shape, dt) in sh.items():
+            setattr(self, name, act_empty(*shape, dtype=dt, device=device))
+        self.x = _Alternating(self.x0, self.x1)
+        self.blocks = _Shared(BlockActs.alloc(cfg, B, T, device, act))
 
 
 class _NullCtxT:
@@ -345,6 +411,7 @@ class Engine:
         self._shadow_versions = None
         self._tdesc_cache: Dict[tuple, tuple] = {}
         self._ws: Dict[tuple, Workspace] = {}
+        self._eval_ws: Dict[tuple, EvalWorkspace] = {}  # its own slot: evaluation never evicts the training workspace
         self._fwd_token = 0
         self._step_seed = 0
         self.base_seed = 1234
@@ -610,6 +677,18 @@ class Engine:
             torch.cuda.empty_cache()
             self._ws[key] = Workspace(self.cfg, B, T, self.vpad, self.device, act)
         return self._ws[key]
+
+    def eval_workspace(self, B, T, act=BF16) -> EvalWorkspace:
+        key = (B, T, act)
+        if key not in self._eval_ws:
+            self._eval_ws.clear()  # one live evaluation shape at a time
+            self._eval_ws[key] = EvalWorkspace(self.cfg, B, T, self.cfg.vocab_size, self.vpad, self.device, act)
+        return self._eval_ws[key]
+
+    def eval_workspace_bytes(self, B, T, act=BF16) -> int:
+        """Bytes of the evaluation workspace of a [B, T] batch (T as the caller passes it; padded to the attention
+        tile here): independent of n_layer, and without an [M, Vp] term."""
+        return EvalWorkspace.nbytes(self.cfg, B, padded_len(T), self.cfg.vocab_size, self.vpad, act)
 
     # ---- precision ----------------------------------------------------------------------------------
     def compute_dtype(self) -> torch.dtype:
@@ -895,6 +974,64 @@ class Engine:
         if Tp != T:  # compact rows, so the reference's own logits.view(-1, V) (model.py:357-358) merges B and T
             out = out[:, :T].contiguous()
         return out[..., :V], loss
+
+    # ---- evaluation: forward only, nothing kept, nothing of the training state touched --------------------
+    def score(self, idx, labels, acc=None):
+        """Per-token negative log-likelihoods of ``labels`` [B, T] without a backward, a logits tensor or the training
+        workspace. Dropout is off whatever ``model.training`` is (fixed seeds, p = 0), and the dropout stream
+        (_step_seed), _fwd_token, _saved, gemm_sched and the grad arena are left as found: no state that a later
+        training step reads is changed by a call of this between two steps (two runs of the training steps themselves
+        are not bit-reproducible, their LayerNorm and embedding backwards add with float atomics, so that, not equal
+        bits of two runs, is the guarantee; not between a forward and its backward when an FSDP wrapper reshards: the
+        forward re-gathers units). Returns device tensors, no host sync: (loss [B, T] fp32, a
+        view of the workspace valid until the next score of this shape, 0 at ignore_index; sum [1]; count [1];
+        mean [1]). acc = (sum, count) fp32 [1] tensors: this call's sum and count are ADDED to them (and returned).
+        bf16: the fused lm_head + cross-entropy kernel (gpt2mi_lm_loss). fp32: the fp32 lm_head GEMM + cross-entropy
+        over chunks of at most EVAL_F32_CHUNK rows into one reused buffer."""
+        sched = self.gemm_sched
+        self.gemm_sched = self.base_sched
+        try:
+            with torch.no_grad():
+                return self._score(idx, labels, acc)
+        finally:
+            self.gemm_sched = sched
+
+    def _score(self, idx, labels, acc):
+        cfg = self.cfg
+        V, Vp, C = cfg.vocab_size, self.vpad, cfg.n_embd
+        idx, labels, T = self._pad(idx, labels)
+        B, Tp = idx.shape
+        M = B * Tp
+        act = self.compute_dtype()
+        self._sync_shadows(act, False)
+        ws = self.eval_workspace(B, Tp, act)
+        self._trunk_fwd(ws, idx, B, Tp, T, act, 0.0, 0.0, self._seeds(0))
+        wte = self.w("transformer.wte.weight", act)
+        if acc is None:
+            s, n = torch.empty(1, dtype=F32, device=self.device), torch.empty(1, dtype=F32, device=self.device)
+        else:
+            s, n = acc
+        if act == BF16:
+            with self._probe("lm_loss"):
+                K.lm_loss(ws.lnf, C, wte, C, Vp, labels, M, V, C, ws.loss_rows, ws.lse_ce, ws.head_ws, loss_sum=s,
+                          count=n, accumulate=acc is not None, loss_mean=ws.loss_mean)
+            mean = ws.loss_mean.clone()
+        else:
+            flat = labels.view(-1)
+            for r0 in range(0, M, EVAL_F32_CHUNK):
+                m = min(EVAL_F32_CHUNK, M - r0)
+                self._gemm(K.FWD, K.EPI_BF16, m, Vp, C, ws.lnf[r0:r0 + m], C, wte, C, ws.head_ws, Vp)
+                K.xent_fwd(ws.head_ws, Vp, flat[r0:r0 + m], ws.loss_rows[r0:r0 + m], ws.lse_ce[r0:r0 + m], None, Vp, m,
+                           V, ws.loss_mean, ws.inv_count)  # (the chunk's mean and 1/count are not used)
+            cs, cn = ws.loss_rows.sum().reshape(1), (flat != -100).sum().to(F32).reshape(1)
+            mean = cs / cn
+            if acc is None:
+                s, n = cs, cn
+            else:
+                s += cs
+                n += cn
+        rows = ws.loss_rows.view(B, Tp)
+        return (rows[:, :T] if Tp != T else rows), s, n, mean
 
     def _backward(self, grad_logits, grad_loss):
         cfg = self.cfg

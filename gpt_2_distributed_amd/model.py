@@ -271,6 +271,69 @@ class GPT2(nn.Module):
                                "inputs to a cuda device (there is no CPU fallback)")
         return self.engine().forward(idx, labels)
 
+    # ---- evaluation (the reference has none) ----------------------------------------------------------------
+    def _check_inputs(self, idx):
+        B, T = idx.size()
+        if T > self.config.n_positions:
+            raise ValueError(f"Sequence length {T} > model max {self.config.n_positions}")
+        if not idx.is_cuda or not self._arena.is_cuda:
+            raise RuntimeError("gpt_2_distributed_amd.GPT2 runs only on the MI355X HIP path: move the model and "
+                               "inputs to a cuda device (there is no CPU fallback)")
+
+    def score(self, idx: torch.Tensor, labels: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
+        """The negative log-likelihood of ``labels`` [B, T] under the model, forward only: ``"none"`` the fp32 per-token
+        values [B, T] (0 where the label is -100), ``"sum"`` their sum, ``"mean"`` sum / number of labels != -100 (what
+        ``forward(idx, labels)[1]`` computes in eval mode). Same argument checks as ``forward``.
+
+        Under bf16 autocast (or ``precision == "bf16"``) the lm_head runs fused with the cross-entropy
+        (``gpt2mi_lm_loss``): no logits tensor exists and the label's logit and the log-sum-exp are taken from the fp32
+        accumulators, not from bf16-rounded logits. It needs neither the training workspace nor ``model.eval()``:
+        dropout is off whatever ``self.training`` is, which is not changed, and the dropout stream and everything a
+        later backward needs are left alone: a call between two training steps changes no state that a later step
+        reads (weights, shadows, gradients, optimizer state, dropout stream, training workspace). Not differentiable: the results carry no graph, whatever the grad mode."""
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
+        self._check_inputs(idx)
+        rows, s, _, mean = self.engine().score(idx, labels)
+        if reduction == "none":
+            return rows.clone()
+        return (s if reduction == "sum" else mean).reshape(()).clone()
+
+    def evaluate(self, batches, max_batches: Optional[int] = None) -> dict:
+        """``{"loss", "ppl", "tokens"}`` over the ``(idx, labels)`` pairs of ``batches`` (at most ``max_batches``):
+        loss = sum of the token losses / number of tokens over ALL batches (token-weighted, not a mean of batch means),
+        ppl = exp(loss). The sums stay on the device (``gpt2mi_lm_loss``'s accumulate mode) and the host synchronises
+        once, at the end. With ``torch.distributed`` initialised the two sums are all-reduced before the division, so
+        every rank returns the same numbers; every rank must then be given the same number of batches (a collective)."""
+        import torch.distributed as dist
+        dev = self._arena.device
+        eng = self.engine()
+        acc = (torch.zeros(1, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
+        total = torch.zeros(2, dtype=torch.float64, device=dev)
+        pending = 0
+        for n, (idx, labels) in enumerate(batches):
+            if max_batches is not None and n >= max_batches:
+                break
+            idx, labels = idx.to(dev, non_blocking=True), labels.to(dev, non_blocking=True)
+            self._check_inputs(idx)
+            # the kernel adds into fp32 running sums; they move to fp64 before they pass 2^20 tokens (a batch of the
+            # bench shape: every batch), so the count stays exact and a batch's sum is rounded against a small total
+            if pending and pending + idx.numel() > 1 << 20:
+                total += torch.cat(acc).double()
+                acc[0].zero_()
+                acc[1].zero_()
+                pending = 0
+            eng.score(idx, labels, acc=acc)
+            pending += idx.numel()
+        total += torch.cat(acc).double()
+        if dist.is_available() and dist.is_initialized():
+            from .parallel import use_collectives
+            if use_collectives(dist.get_world_size()):
+                dist.all_reduce(total)
+        s, c = total.tolist()  # the one host sync
+        loss = s / c if c else float("nan")
+        return {"loss": loss, "ppl": math.exp(loss) if loss < 700 else float("inf"), "tokens": int(c)}
+
     # ---- generation (nanoGPT's surface; the reference has none) ----------------------------------------
     def decoder(self, batch_size: int, max_len: Optional[int] = None):
         """A ``generation.DecodeSession``: the per-layer key/value cache (L x 2 x bf16 ``[B][H][Tcap][64]``,

@@ -276,6 +276,14 @@ class DistributedDataParallel(nn.Module):
     def forward(self, *args, **kwargs):
         return self.module(*args, **kwargs)
 
+    def score(self, *args, **kwargs):
+        """GPT2.score of the wrapped module (forward only: no collective)."""
+        return self.module.score(*args, **kwargs)
+
+    def evaluate(self, *args, **kwargs):
+        """GPT2.evaluate of the wrapped module: the sums are all-reduced, every rank calls it with as many batches."""
+        return self.module.evaluate(*args, **kwargs)
+
     def finish_gradient_sync(self):
         """Make the gradients final on the current stream: a no-op unless overlap_optimizer left the last bucket in
         flight (the backward itself completes every other bucket)."""
@@ -928,6 +936,15 @@ class FullyShardedDataParallel(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.module(*args, **kwargs)
+
+    def score(self, *args, **kwargs):
+        """GPT2.score through this wrapper's unit gathers (a collective: every rank calls it), resident or resharding:
+        the forward's unit hooks are the ones a training forward uses. Not between a forward and its backward."""
+        return self.module.score(*args, **kwargs)
+
+    def evaluate(self, *args, **kwargs):
+        """GPT2.evaluate through this wrapper's unit gathers; every rank calls it with as many batches."""
+        return self.module.evaluate(*args, **kwargs)
 
     def finish_gradient_sync(self):
         """Make the gradient shard final on the current stream: a no-op unless overlap_optimizer left the last unit's

@@ -8,6 +8,10 @@
         --resume STEP_DIR --log_every N
     recipe: --max_grad_norm X (0 = off) --lr_schedule {constant,cosine} --warmup_steps N --lr_decay_steps N
         --min_lr X (nanoGPT clips at 1.0 with linear warmup and cosine decay to lr/10; all off by default)
+    validation: --eval_every N (0 = off) --eval_steps K --eval_batch B --val_split NAME: after optimizer steps N, 2N, ...
+        and after the last one every rank runs model.evaluate over the first K batches of its share of the split's
+        windows (dataloader.iter_eval_batches) and rank 0 prints one more JSON line {"step", "val_loss", "val_ppl",
+        "val_tokens", "eval_s"}; the evaluation changes no state that a later training step reads
 
 Loop semantics follow the reference (:374-457): seed 42; loss/grad_accum; backward; every
 grad_accum micro-steps the fused AdamW step (which also yields the clip_grad_norm_(inf) value);
@@ -81,7 +85,48 @@ def build_parser():
     p.add_argument("--lr_decay_steps", type=int, default=0,
                    help="cosine: the step at which lr reaches --min_lr (0 = --max_steps)")
     p.add_argument("--min_lr", type=float, default=None, help="cosine: the final lr (default lr/10)")
+    # validation (off by default)
+    p.add_argument("--eval_every", type=int, default=0, help="evaluate the val split every N optimizer steps (0 = off)")
+    p.add_argument("--eval_steps", type=int, default=20, help="batches per rank per evaluation")
+    p.add_argument("--eval_batch", type=int, default=None, help="evaluation batch size (default --batch)")
+    p.add_argument("--val_split", type=str, default="val", help="shards whose file name contains this are the val split")
     return p
+
+
+def eval_from_args(args) -> dict:
+    """The validation flags, checked once before anything is built: {} when off, else every, steps, batch, split."""
+    if args.eval_every < 0:
+        raise SystemExit("--eval_every must be >= 0 (0 = off)")
+    if not args.eval_every:
+        return {}
+    batch = args.batch if args.eval_batch is None else args.eval_batch
+    if args.eval_steps < 1 or batch < 1:
+        raise SystemExit("--eval_steps and --eval_batch must be >= 1")
+    if not args.val_split or args.val_split == "train":
+        raise SystemExit(f"--val_split {args.val_split!r} would select the training shards")
+    return dict(every=args.eval_every, steps=args.eval_steps, batch=batch, split=args.val_split)
+
+
+def val_shards(data_dir, ev: dict, seq_len: int, world: int):
+    """The val split's shards; SystemExit unless they hold at least one batch for every rank."""
+    d = pathlib.Path(data_dir)
+    paths = gpt2_dataloader.get_shard_paths(d, split=ev["split"]) if d.is_dir() else []
+    if not paths:
+        raise SystemExit(f"--eval_every {ev['every']}: no '{ev['split']}' shard (*{ev['split']}*.bin) in {data_dir}")
+    n = len(gpt2_dataloader.eval_windows(paths, seq_len))
+    if n // world < ev["batch"]:
+        raise SystemExit(f"--eval_every {ev['every']}: the '{ev['split']}' split has {n} windows of {seq_len + 1} "
+                         f"tokens, fewer than one batch of {ev['batch']} for each of {world} ranks")
+    return paths
+
+
+def run_eval(model, paths, ev: dict, seq_len: int, rank: int, world: int):
+    """model.evaluate over this rank's first ev["steps"] validation batches; (result, seconds). Collective."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        res = model.evaluate(gpt2_dataloader.iter_eval_batches(paths, seq_len, ev["batch"], rank, world, ev["steps"]))
+    return res, time.perf_counter() - t0
 
 
 def schedule_from_args(args) -> dict:
@@ -183,6 +228,10 @@ def main(argv=None):
     sched = schedule_from_args(args)
     scheduled = sched["kind"] != "constant"
     clip = args.max_grad_norm > 0
+    ev = eval_from_args(args)
+    if ev and not args.synthetic:  # (synthetic runs write their val shard below)
+        val_paths = val_shards(args.data_dir or "", ev, args.seq_len, int(os.environ.get("WORLD_SIZE", 1))
+                               if args.training_mode != "local" else 1)
     if args.training_mode in ("fsdp", "ddp"):
         init_distributed()
     rank = dist.get_rank() if dist.is_initialized() else 0
@@ -199,8 +248,12 @@ def main(argv=None):
         data_dir = data_dir or tempfile.mkdtemp(prefix="gpt2_synth_")
         if is_primary():
             write_shards(data_dir, args.synthetic, args.synthetic_tokens, dist="zipf", seed=1234)
+            if ev:
+                write_shards(data_dir, 1, args.synthetic_tokens, dist="zipf", seed=4321, split=ev["split"])
         if dist.is_initialized():
             dist.barrier()
+        if ev:
+            val_paths = val_shards(data_dir, ev, args.seq_len, world)
     if not data_dir:
         raise SystemExit("--data_dir is required (or --synthetic N)")
     if is_primary():
@@ -246,6 +299,16 @@ def main(argv=None):
     tok_per_step = args.batch * args.grad_accum_steps * args.seq_len * world
     t_last, steps_since = time.perf_counter(), 0
     done, epoch, micro = False, start_epoch, 0
+    evaluated_at = None
+
+    def validate():
+        nonlocal t_last, evaluated_at
+        res, secs = run_eval(model, val_paths, ev, args.seq_len, rank, world)
+        evaluated_at = global_step
+        t_last += secs  # the logged tok/s stays the training throughput
+        if is_primary():
+            print(json.dumps({"step": global_step, "val_loss": res["loss"], "val_ppl": res["ppl"],
+                              "val_tokens": res["tokens"], "eval_s": round(secs, 3)}), flush=True)
     for epoch in range(start_epoch, args.epochs):
         t_epoch = time.perf_counter()  # the reference's epoch_time (stats_tracker.py:265-275): time in this epoch
         ds.set_epoch(epoch)  # as the reference; persistent workers keep the epoch they were spawned with
@@ -299,6 +362,8 @@ def main(argv=None):
                                       "mfu": round(tps * fpt / (world * PEAK_BF16), 4),
                                       "epoch_time": round(now - t_epoch, 2), **mem}), flush=True)
                 t_last, steps_since = now, 0
+            if ev and global_step % ev["every"] == 0:
+                validate()
             if global_step % args.save_every == 0:
                 save_checkpoint(model, optim, global_step, args.save_dir,
                                 {"epoch": epoch, "micro": micro, "worker_epoch": worker_epoch})
@@ -307,6 +372,8 @@ def main(argv=None):
                 break
         if done:
             break
+    if ev and evaluated_at != global_step:  # after the last step
+        validate()
     pos = {"epoch": epoch, "micro": micro} if done else {"epoch": args.epochs, "micro": 0}
     pos["worker_epoch"] = worker_epoch
     save_checkpoint(model, optim, global_step, args.save_dir, pos)

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 17
+#define GPT2MI_ABI_VERSION 18
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -333,6 +333,25 @@ int gpt2mi_sample(const float* logits, int ldl, int B, int V, float temperature,
 int gpt2mi_decode_generate(const gpt2mi_decode_plan* plan, int V, float temperature, int top_k, float top_p,
                            uint64_t seed, int64_t eos, int pos0, int n, int64_t* tok, int64_t* seq, int ld_seq,
                            uint8_t* done, void* stream);
+
+/* ---- v18: evaluation (csrc/lm_loss.hip). The loss rows of F.cross_entropy(x @ w[:V].T, labels, ignore_index) without
+ * forming the logits: the tied lm_head GEMM (bf16 operands, fp32 accumulation) fused with the cross-entropy reduction,
+ * so the semantics are gpt2mi_xent_fwd's on the un-rounded fp32 logits. ----
+ *  x bf16 [M][ldx] (K valid columns: the ln_f output), w bf16 [w_rows][ldw] (the tied wte shadow; rows V..w_rows-1 are
+ *   padding whose contents do not matter: columns >= V of the logits never contribute, rows >= w_rows are never read).
+ *  loss_rows [M] = lse - logit[label], 0 where label == ignore_index, NaN where the label is outside [0, V) otherwise
+ *   (the sums are then NaN too); lse [M] = log-sum-exp of the row. Either may be NULL.
+ *  loss_sum[0] / count[0] (may be NULL): the sum of loss_rows and the number of labels != ignore_index of THIS call,
+ *   written (accumulate = 0) or added to what they hold (accumulate = 1: a running token-weighted total over calls).
+ *  loss_mean[0] (may be NULL) = this call's sum / count (NaN when every label is ignored, as gpt2mi_xent_fwd's loss).
+ *  workspace: gpt2mi_lm_loss_workspace(M, V) bytes of fp32 (per-split row partials; a function of M and V only).
+ * Two launches, no float atomics, every reduction in a fixed order: two calls give the same bits.
+ * Refused with 22 before any launch: M or K not a positive multiple of 64, V < 1, w_rows < V, a row stride < K or not
+ * a multiple of 8, NULL x / w / labels / workspace. */
+int gpt2mi_lm_loss(const uint16_t* x, int ldx, const uint16_t* w, int ldw, int w_rows, const int64_t* labels, int M,
+                   int V, int K, int ignore_index, float* loss_rows, float* lse, float* loss_sum, float* count,
+                   int accumulate, float* loss_mean, float* workspace, void* stream);
+size_t gpt2mi_lm_loss_workspace(int M, int V); /* bytes; 0 for M < 1 or V < 1 */
 
 #ifdef __cplusplus
 }
