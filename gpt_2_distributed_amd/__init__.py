@@ -9,10 +9,11 @@ dataloader.py / train_gpt2_distributed.py surfaces, running on hand-written gfx9
 
 from .model import (GPT, GPT2, GPT2Backbone, GPT2Block, GPT2Config, MLP, MODEL_SIZES,  # noqa: F401
                     CausalMultiHeadSelfAttention, NewGELU)
+from .generation import generate_many  # noqa: F401
 from .parallel import DistributedDataParallel, ShardedDataParallel, init_distributed  # noqa: F401
 
 DEFAULT_CONFIG = GPT2Config()  # train_gpt2_distributed.py:42-44 (124M; --seq_len replaces n_positions)
 
 __all__ = ["GPT", "GPT2", "GPT2Backbone", "GPT2Block", "GPT2Config", "MLP", "CausalMultiHeadSelfAttention",
            "NewGELU", "MODEL_SIZES", "DEFAULT_CONFIG", "DistributedDataParallel", "ShardedDataParallel",
-           "init_distributed"]
+           "init_distributed", "generate_many"]

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -96,6 +96,15 @@ _SIGS = {
     "gpt2mi_lm_loss": [_p, _c_int, _p, _c_int, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p,
                        _p, _p],
     "gpt2mi_lm_loss_workspace": [_c_int, _c_int],
+    # v19 ragged decode: the scalar twins' lists with pos -> const int* pos (HOST array of B ints) and, for the sampler
+    # and the loop, const uint32_t* row_id (HOST array, may be NULL) after it
+    "gpt2mi_attn_decode_ragged": [_p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _p, _p],
+    "gpt2mi_embed_decode_ragged": [_p, _p, _p, _p, _c_int, _c_int, _p, _p],
+    "gpt2mi_sample_ragged": [_p, _c_int, _c_int, _c_int, _c_float, _c_int, _c_float, _c_u64, _p, _p, ctypes.c_int64, _p,
+                             _p, _p, _c_int, _p, _p],
+    "gpt2mi_decode_step_ragged": [_p, _p, _p, _p],
+    "gpt2mi_decode_generate_ragged": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _p, _p, _c_int,
+                                      _p, _p, _c_int, _p, _p],
 }
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size}
@@ -483,3 +492,61 @@ def lm_loss(x, ldx, w, ldw, w_rows, labels, M, V, K, loss_rows, lse, workspace, 
                           f"{lm_loss_workspace(M, V)} fp32")
     _call("gpt2mi_lm_loss", _ptr(x), ldx, _ptr(w), ldw, w_rows, _ptr(labels), M, V, K, ignore_index, _ptr(loss_rows),
           _ptr(lse), _ptr(loss_sum), _ptr(count), int(accumulate), _ptr(loss_mean), _ptr(workspace), _stream())
+
+
+# ---- v19: ragged decode (csrc/decode.hip, csrc/sample.hip) ------------------------------------------
+DECODE_MAX_B = 64  # gpt2mi.h GPT2MI_DECODE_MAX_B
+
+
+def _host_ints(vals, ctype=_c_int):
+    """A host array for a `const int* pos` / `const uint32_t* row_id` argument (None: NULL). The entry reads it before it
+    returns, so the temporary need not outlive the call."""
+    if vals is None:
+        return None
+    vals = [int(v) for v in vals]
+    return (ctype * len(vals))(*vals)
+
+
+def _row_ids(row_id, B):
+    if row_id is not None and len(row_id) != B:
+        raise KernelError(f"row_id has {len(row_id)} entries for B={B} rows")
+    return _host_ints(row_id, ctypes.c_uint32)
+
+
+def _positions(pos, B):
+    if len(pos) != B:
+        raise KernelError(f"the position array has {len(pos)} entries for B={B} rows")
+    return _host_ints(pos)
+
+
+def attn_decode_ragged(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos):
+    """attn_decode with row b at pos[b] (a host sequence of B ints)."""
+    _call("gpt2mi_attn_decode_ragged", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(workspace),
+          workspace.numel(), B, H, D, Tcap, _positions(pos, B), _stream())
+
+
+def embed_decode_ragged(tok, wte, wpe, x, B, C, pos):
+    _call("gpt2mi_embed_decode_ragged", _ptr(tok), _ptr(wte), _ptr(wpe), _ptr(x), B, C, _positions(pos, B), _stream())
+
+
+def decode_step_ragged(plan: DecodePlan, tok, pos):
+    """gpt2mi_decode_step_ragged: one token step with row b at pos[b], into plan.logits."""
+    _call("gpt2mi_decode_step_ragged", ctypes.byref(plan), _ptr(tok), _positions(pos, plan.B), _stream())
+
+
+def sample_ragged(logits, V, temperature, top_k, top_p, seed, pos, tok_out, row_id=None, eos=None, done=None,
+                  seq_out=None, probs_out=None):
+    """gpt2mi_sample_ragged: `sample` with row b drawing from (seed, row_id[b] (None: b), pos[b]) into column pos[b]."""
+    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
+    B = logits.size(0)
+    _call("gpt2mi_sample_ragged", _ptr(logits), logits.stride(0), B, V, t, k, p, s, _positions(pos, B),
+          _row_ids(row_id, B), e, _ptr(done), _ptr(tok_out), _ptr(seq_out), 0 if seq_out is None else seq_out.stride(0),
+          _ptr(probs_out), _stream())
+
+
+def decode_generate_ragged(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, row_id=None, eos=None,
+                           seq=None, done=None):
+    """gpt2mi_decode_generate_ragged: n sample-then-step rounds with row b starting at pos0[b]."""
+    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
+    _call("gpt2mi_decode_generate_ragged", ctypes.byref(plan), V, t, k, p, s, e, _positions(pos0, plan.B),
+          _row_ids(row_id, plan.B), n, _ptr(tok), _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(done), _stream())

@@ -43,12 +43,13 @@ __device__ __forceinline__ float keyf(uint32_t k) {
 
 // GREEDY (temperature == 0) is a kernel of its own: as one branch of the sampling kernel it kept the row live to the
 // end of the other branch, beside the exponentials.
+// The body of both kernels below: row b = blockIdx.x of the buffers, drawn with the key (draw_row, pos) and written to
+// column pos of seq_out.
 template <bool GREEDY>
-__global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restrict__ logits, int ldl, int V,
-                                                            float temperature, int top_k, float top_p, uint64_t seed,
-                                                            int pos, int64_t eos, uint8_t* __restrict__ done,
-                                                            int64_t* __restrict__ tok_out, int64_t* __restrict__ seq_out,
-                                                            int ld_seq, float* __restrict__ probs_out) {
+__device__ __forceinline__ void sample_row(const float* __restrict__ logits, int ldl, int V, float temperature,
+                                           int top_k, float top_p, uint64_t seed, uint32_t draw_row, int pos,
+                                           int64_t eos, uint8_t* __restrict__ done, int64_t* __restrict__ tok_out,
+                                           int64_t* __restrict__ seq_out, int ld_seq, float* __restrict__ probs_out) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const float* lp = logits + (size_t)b * ldl;
   __shared__ uint32_t red[2][SM_WAVES];
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restr
 #pragma unroll 1  // (rolled: unrolled, the 50 running sums of these scans are all live beside the row)
     for (int i = 0; i < SM_NE; ++i) Z += ctot[i];
 
-    uint64_t h = seed + 0x9E3779B97F4A7C15ull * (1ull + (((uint64_t)(uint32_t)b << 32) | (uint32_t)pos));
+    uint64_t h = seed + 0x9E3779B97F4A7C15ull * (1ull + (((uint64_t)draw_row << 32) | (uint32_t)pos));
     h ^= h >> 30;
     h *= 0xBF58476D1CE4E5B9ull;
     h ^= h >> 27;
@@ -316,6 +317,34 @@ __global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restr
   }
 }
 
+template <bool GREEDY>
+__global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restrict__ logits, int ldl, int V,
+                                                            float temperature, int top_k, float top_p, uint64_t seed,
+                                                            int pos, int64_t eos, uint8_t* __restrict__ done,
+                                                            int64_t* __restrict__ tok_out, int64_t* __restrict__ seq_out,
+                                                            int ld_seq, float* __restrict__ probs_out) {
+  sample_row<GREEDY>(logits, ldl, V, temperature, top_k, top_p, seed, blockIdx.x, pos, eos, done, tok_out, seq_out,
+                     ld_seq, probs_out);
+}
+
+// Per-row position and draw key (gpt2mi_sample_ragged): the entry's validated host arrays, by value; two scalar loads.
+struct RowKeys {
+  int pos[GPT2MI_DECODE_MAX_B];
+  uint32_t row_id[GPT2MI_DECODE_MAX_B];
+};
+
+template <bool GREEDY>
+__global__ __launch_bounds__(SM_THREADS) void sample_ragged_kernel(const float* __restrict__ logits, int ldl, int V,
+                                                                   float temperature, int top_k, float top_p,
+                                                                   uint64_t seed, RowKeys keys, int64_t eos,
+                                                                   uint8_t* __restrict__ done,
+                                                                   int64_t* __restrict__ tok_out,
+                                                                   int64_t* __restrict__ seq_out, int ld_seq,
+                                                                   float* __restrict__ probs_out) {
+  sample_row<GREEDY>(logits, ldl, V, temperature, top_k, top_p, seed, keys.row_id[blockIdx.x], keys.pos[blockIdx.x], eos,
+                     done, tok_out, seq_out, ld_seq, probs_out);
+}
+
 }  // namespace
 
 GPT2MI_EXPORT int gpt2mi_sample(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
@@ -337,4 +366,34 @@ GPT2MI_EXPORT int gpt2mi_sample(const float* logits, int ldl, int B, int V, floa
     sample_kernel<false><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(logits, ldl, V, temperature, top_k, top_p, seed, pos,
                                                                     eos, done, tok_out, seq_out, ld_seq, probs_out);
   return gpt2mi::check_launch("sample");
+}
+
+GPT2MI_EXPORT int gpt2mi_sample_ragged(const float* logits, int ldl, int B, int V, float temperature, int top_k,
+                                       float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos,
+                                       uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out,
+                                       void* stream) {
+  GPT2MI_REQUIRE(B >= 1 && B <= GPT2MI_DECODE_MAX_B && V >= 1, "sample_ragged: B=%d not in [1, %d] or V=%d not positive",
+                 B, GPT2MI_DECODE_MAX_B, V);
+  GPT2MI_REQUIRE(V <= GPT2MI_SAMPLE_MAX_V, "sample_ragged: V=%d above the kernel's row capacity %d", V,
+                 GPT2MI_SAMPLE_MAX_V);
+  GPT2MI_REQUIRE(ldl >= V, "sample_ragged: ldl=%d < V=%d", ldl, V);
+  GPT2MI_REQUIRE(temperature >= 0.f, "sample_ragged: temperature=%g must be >= 0", (double)temperature);  // (NaN too)
+  GPT2MI_REQUIRE(top_p > 0.f, "sample_ragged: top_p=%g must be > 0 (>= 1: off)", (double)top_p);
+  GPT2MI_REQUIRE(pos != nullptr, "sample_ragged: the position array (host, B ints) is NULL");
+  GPT2MI_REQUIRE(eos >= -1 && eos < V, "sample_ragged: eos=%lld not in [-1, V=%d)", (long long)eos, V);
+  RowKeys keys = {};
+  for (int b = 0; b < B; ++b) {
+    GPT2MI_REQUIRE(pos[b] >= 0, "sample_ragged: pos[%d]=%d is negative", b, pos[b]);
+    GPT2MI_REQUIRE(!seq_out || ld_seq > pos[b], "sample_ragged: ld_seq=%d does not reach pos[%d]=%d", ld_seq, b, pos[b]);
+    keys.pos[b] = pos[b];
+    keys.row_id[b] = row_id ? row_id[b] : (uint32_t)b;
+  }
+  GPT2MI_REQUIRE(logits && tok_out, "sample_ragged: logits and tok_out must not be NULL");
+  if (temperature == 0.f)
+    sample_ragged_kernel<true><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(
+        logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out);
+  else
+    sample_ragged_kernel<false><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(
+        logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out);
+  return gpt2mi::check_launch("sample_ragged");
 }

@@ -3,7 +3,11 @@
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
-included). No tokenizer is shipped: prompts and outputs are GPT-2 BPE ids (50256 = <|endoftext|>)."""
+included). No tokenizer is shipped: prompts and outputs are GPT-2 BPE ids (50256 = <|endoftext|>).
+
+Several prompts: repeat ``--prompt_ids`` or give ``--prompts_file`` (one comma-separated prompt per line). They go
+through ``GPT2.generate_many`` (continuous batching on the device sampler, ``--batch`` rows at a time; prompt i draws from
+(``--seed``, i, position)) and one JSON list per prompt is printed, in input order."""
 from __future__ import annotations
 
 import argparse
@@ -21,7 +25,9 @@ def parse_args(argv=None):
     p.add_argument("--checkpoint", required=True, help="a step_XXXXXXX directory written by save_checkpoint")
     p.add_argument("--model", default="124M", choices=sorted(MODEL_SIZES) + ["auto"],
                    help="model size; auto: widths and depth from the checkpoint (n_head = n_embd / 64)")
-    p.add_argument("--prompt_ids", default="50256", help="comma-separated token ids")
+    p.add_argument("--prompt_ids", action="append", default=None,
+                   help="comma-separated token ids (default 50256); may be given several times")
+    p.add_argument("--prompts_file", default=None, help="a file with one comma-separated prompt per line")
     p.add_argument("--max_new_tokens", type=int, default=64)
     p.add_argument("--temperature", type=float, default=1.0)
     p.add_argument("--top_k", type=int, default=None)
@@ -30,7 +36,8 @@ def parse_args(argv=None):
                    help="torch: sample_next with a torch.Generator seeded by --seed; device: the fused sampling kernel, "
                         "drawing from (--seed, row, position), and the token loop issued from C")
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--batch", type=int, default=1)
+    p.add_argument("--batch", type=int, default=1,
+                   help="one prompt: the number of copies; several prompts: the rows of generate_many's session")
     p.add_argument("--eos_token_id", type=int, default=None)
     return p.parse_args(argv)
 
@@ -56,10 +63,24 @@ def load_model(ckpt_dir: str, size: str) -> GPT2:
 
 def main(argv=None) -> int:
     a = parse_args(argv)
-    prompt = [int(t) for t in a.prompt_ids.split(",") if t.strip()]
-    if not prompt:
-        raise SystemExit("--prompt_ids is empty")
+    lines = list(a.prompt_ids or [])
+    if a.prompts_file:
+        with open(a.prompts_file) as f:
+            lines += [line for line in f.read().splitlines() if line.strip()]
+    prompts = [[int(t) for t in line.split(",") if t.strip()] for line in lines or ["50256"]]
+    if not all(prompts):
+        raise SystemExit("an empty prompt (--prompt_ids / --prompts_file)")
     model = load_model(a.checkpoint, a.model)
+    if len(prompts) > 1:
+        if a.sampler != "device" and a.temperature != 0:
+            raise SystemExit("several prompts are served by generate_many, which draws on the device: --sampler device")
+        outs = model.generate_many([torch.tensor(q, dtype=torch.int64, device="cuda:0") for q in prompts],
+                                   a.max_new_tokens, batch_size=a.batch, temperature=a.temperature, top_k=a.top_k,
+                                   top_p=a.top_p, seed=a.seed, eos_token_id=a.eos_token_id)
+        for row in outs:
+            print(json.dumps(row.tolist()))
+        return 0
+    prompt = prompts[0]
     idx = torch.tensor([prompt] * a.batch, dtype=torch.int64, device="cuda:0")
     how = (dict(seed=a.seed) if a.sampler == "device"
            else dict(generator=torch.Generator(device="cuda:0").manual_seed(a.seed)))

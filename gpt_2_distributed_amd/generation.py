@@ -8,6 +8,10 @@ over the cache, about 10 launches per layer issued from C. The next token is dra
 (``sample_next``, from a ``torch.Generator``) or, with a ``seed``, by ``gpt2mi_sample`` on the device (csrc/sample.hip;
 ``sample_reference`` and ``uniform_at`` state what it computes), in which case the whole loop is one C call.
 
+The sequences of a session need not be equally long: ``DecodeSession.lens`` holds one position per row, ``prefill`` takes
+right-padded prompts with their lengths, ``refill`` replaces one row while the others go on, and ``generate_many`` serves
+any number of prompts through one session that way (the ``gpt2mi_*_ragged`` entries; DESIGN.md "Ragged batches").
+
 Numerics are the autocast path's whatever the autocast state: bf16 GEMM operands from the engine's weight shadow, fp32
 accumulation, fp32 residual stream / LayerNorm / softmax, dropout off (p = 0 whatever ``model.training`` is, and
 ``.training`` is not touched). Logits are fp32. ``model.precision == "fp32"`` has no decode kernels and raises.
@@ -20,7 +24,7 @@ forward re-allocates, and (b) it must not be called between a forward and its ba
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import List, Optional, Sequence
 
 import torch
 
@@ -125,6 +129,25 @@ def sample_reference(logits: torch.Tensor, temperature: float, top_k: Optional[i
     return tok, pk / Z
 
 
+def _check_lens(lens, B: int, P: int) -> List[int]:
+    """``lens`` as a list of B ints in [1, P], or a ValueError."""
+    lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
+    if len(lens) != B:
+        raise ValueError(f"{len(lens)} prompt lengths for B={B} rows")
+    if not all(1 <= n <= P for n in lens):
+        raise ValueError(f"prompt lengths {lens} not all in [1, P={P}]")
+    return lens
+
+
+def _check_row_id(row_id, B: int) -> Optional[List[int]]:
+    if row_id is None:
+        return None
+    row_id = [int(r) for r in row_id]
+    if len(row_id) != B or not all(0 <= r < 1 << 32 for r in row_id):
+        raise ValueError(f"row_id must be B={B} ints in [0, 2^32) (got {row_id})")
+    return row_id
+
+
 def _check_model(model):
     """The engine of a model generation can run on (see the module docstring), or the reason it cannot."""
     if getattr(model, "precision", "auto") == "fp32":
@@ -149,7 +172,10 @@ class DecodeSession:
 
     Cache: per layer ``kcache`` and ``vcache``, bf16 ``[B][H][Tcap][64]`` (a (b, h) stream is contiguous 128-byte rows).
     ``prefill(idx)`` starts the sequences from a prompt, ``step(tokens)`` appends one token to each; both return the fp32
-    logits ``[B, V]`` of the newest position. ``pos`` is the number of cached tokens."""
+    logits ``[B, V]`` of the newest position. ``lens`` (a host list of B ints) is the number of cached tokens of each
+    row; ``pos`` is their common value (None while the rows disagree). While they agree every call goes through the
+    scalar C entries (one position for the batch); once they disagree (``prefill`` with ``lens``, ``refill``) through
+    their ``_ragged`` twins, which give each row the bits the scalar entry gives it at that row's position."""
 
     def __init__(self, model, batch_size: int, max_len: Optional[int] = None):
         eng = _check_model(model)
@@ -160,7 +186,8 @@ class DecodeSession:
         if not 1 <= Tcap <= cfg.n_positions:
             raise ValueError(f"max_len {Tcap} not in [1, n_positions={cfg.n_positions}]")
         self.model, self.engine, self.cfg = model, eng, cfg
-        self.B, self.Tcap, self.pos = int(batch_size), Tcap, 0
+        self.B, self.Tcap = int(batch_size), Tcap
+        self.lens: List[int] = [0] * self.B
         B, C, H, L, Vp = self.B, cfg.n_embd, cfg.n_head, cfg.n_layer, model.vpad
         dev = eng.device
         e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
@@ -175,7 +202,25 @@ class DecodeSession:
         self.logits = e(B, Vp, dt=F32)
         self._tok = e(B, dt=torch.int64)  # the device loop's newest tokens (DecodeSession.generate)
         self._drawn = False               # True: generate() drew _tok from the logits in place and has not stepped it
+        self._refill_ws = None            # (Tp, engine.Workspace) of the last refill's one-sequence prefill
         self._plan = self._build_plan()
+
+    @property
+    def pos(self) -> Optional[int]:
+        """The number of cached tokens when every row has the same, else None (see ``lens``)."""
+        return self.lens[0] if self.uniform else None
+
+    @pos.setter
+    def pos(self, value: int) -> None:
+        self.lens = [int(value)] * self.B
+
+    @property
+    def uniform(self) -> bool:
+        return min(self.lens) == max(self.lens)
+
+    @property
+    def device(self):
+        return self.logits.device
 
     def _build_plan(self) -> K.DecodePlan:
         eng, cfg = self.engine, self.cfg
@@ -212,21 +257,30 @@ class DecodeSession:
 
     def reset(self) -> None:
         """Rewind to an empty cache (the next call is ``prefill``)."""
-        self.pos = 0
+        self.pos, self._drawn = 0, False
 
     @torch.no_grad()
-    def prefill(self, idx: torch.Tensor) -> torch.Tensor:
+    def prefill(self, idx: torch.Tensor, lens: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Run the prompt ``idx`` [B, P] and cache its keys and values; fp32 logits [B, V] of its last position.
 
         The prompt goes through the engine's trunk forward (the training kernels at bf16, p = 0, padded to the attention
         tile), the K / V columns of each layer's qkv activations are copied into the cache, and the lm_head runs on the
-        last valid row of each sequence only."""
+        last valid row of each sequence only.
+
+        With ``lens`` (B ints, ``1 <= lens[b] <= P``) row b's prompt is ``idx[b, :lens[b]]`` and the rest of the row is
+        padding: any valid token id. The trunk runs once on the padded batch (causal attention keeps positions
+        ``< lens[b]`` independent of what follows them) and all P positions are copied into the cache: positions
+        ``>= lens[b]`` then hold the padding's keys and values, which no step reads (row b attends over
+        ``0..lens[b]`` only) and which are overwritten one by one as the row grows. The logits are those of position
+        ``lens[b] - 1`` of each row."""
         eng, cfg = self.engine, self.cfg
         if idx.dim() != 2 or idx.size(0) != self.B:
             raise ValueError(f"prefill takes idx [B={self.B}, P] (got {tuple(idx.shape)})")
         P = idx.size(1)
         if not 1 <= P <= self.Tcap:
             raise ValueError(f"prompt length {P} not in [1, max_len={self.Tcap}]")
+        if lens is not None:
+            lens = _check_lens(lens, self.B, P)
         if not idx.is_cuda:
             raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
         self._ready(True)
@@ -239,18 +293,81 @@ class DecodeSession:
         eng._trunk_fwd(ws, idx_p, B, Tp, P, BF16, 0.0, 0.0, eng._seeds(0))
         for l in range(cfg.n_layer):
             K.kv_store(ws.blocks[l].qkv, self.kcache[l], self.vcache[l], B, Tp, P, 0, H, 64, self.Tcap)
-        last = ws.lnf.view(B, Tp, C)[:, P - 1]  # rows b*Tp + P-1: row stride Tp*C
-        K.gemm_skinny(K.EPI_F32, B, Vp, C, last, Tp * C, eng.w16("transformer.wte.weight"), C, self.logits, Vp,
-                      workspace=self.gemm_ws)
-        self.pos, self._drawn = P, False
+        if lens is None:
+            last = ws.lnf.view(B, Tp, C)[:, P - 1]  # rows b*Tp + P-1: row stride Tp*C
+            K.gemm_skinny(K.EPI_F32, B, Vp, C, last, Tp * C, eng.w16("transformer.wte.weight"), C, self.logits, Vp,
+                          workspace=self.gemm_ws)
+            self.pos = P
+        else:  # rows b*Tp + lens[b]-1, gathered into the session's [B, C] buffer
+            rows = torch.tensor([b * Tp + n - 1 for b, n in enumerate(lens)], device=idx.device)
+            torch.index_select(ws.lnf, 0, rows, out=self.ln)
+            K.gemm_skinny(K.EPI_F32, B, Vp, C, self.ln, C, eng.w16("transformer.wte.weight"), C, self.logits, Vp,
+                          workspace=self.gemm_ws)
+            self.lens = lens
+        self._drawn = False
         return self.logits[:, :cfg.vocab_size].clone()
+
+    def _one_sequence_workspace(self, Tp: int):
+        """The trunk workspace of refill's one-sequence prefill: the session's own (the engine's holds one shape at a
+        time, the training step's), kept while the padded length repeats."""
+        if self._refill_ws is None or self._refill_ws[0] != Tp:
+            from .engine import Workspace
+            self._refill_ws = None
+            self._refill_ws = (Tp, Workspace(self.cfg, 1, Tp, self.model.vpad, self.engine.device, BF16))
+        return self._refill_ws[1]
+
+    @torch.no_grad()
+    def refill(self, row: int, prompt: torch.Tensor) -> None:
+        """Replace sequence ``row`` by the 1-D ``prompt`` while the other rows keep their cache, logits and position.
+
+        The prompt runs as a prefill of one sequence: its keys and values go to the row's slices of the caches
+        (contiguous ``[H][Tcap][64]``: kv_store at B = 1), its last position's logits to ``logits[row]`` (gemm_skinny at
+        M = 1) and ``lens[row]`` becomes its length. Every shape of that prefill depends on the prompt alone, so the
+        row's cache and logits are a function of (weights, prompt) only: not of the row, the batch size or what the
+        other rows hold. ``generate_many``'s guarantee rests on this. A token ``generate`` drew and has not stepped is
+        stepped first (``flush``), so that afterwards every row's logits are those of its next position."""
+        eng, cfg = self.engine, self.cfg
+        if not 0 <= int(row) < self.B:
+            raise ValueError(f"row {row} not in [0, B={self.B})")
+        if prompt.dim() != 1 or not 1 <= prompt.numel() <= self.Tcap:
+            raise ValueError(f"refill takes a 1-D prompt of 1..max_len={self.Tcap} tokens (got {tuple(prompt.shape)})")
+        if not prompt.is_cuda:
+            raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
+        self.flush()
+        self._ready(True)
+        eng.gemm_sched = eng.base_sched
+        row, P = int(row), prompt.numel()
+        idx_p, _, _ = eng._pad(prompt.view(1, P), None)
+        Tp = idx_p.size(1)
+        C, H, Vp = cfg.n_embd, cfg.n_head, self.model.vpad
+        ws = self._one_sequence_workspace(Tp)
+        eng._trunk_fwd(ws, idx_p, 1, Tp, P, BF16, 0.0, 0.0, eng._seeds(0))
+        for l in range(cfg.n_layer):
+            K.kv_store(ws.blocks[l].qkv, self.kcache[l, row], self.vcache[l, row], 1, Tp, P, 0, H, 64, self.Tcap)
+        K.gemm_skinny(K.EPI_F32, 1, Vp, C, ws.lnf[P - 1], Tp * C, eng.w16("transformer.wte.weight"), C, self.logits[row],
+                      Vp, workspace=self.gemm_ws)
+        self.lens[row] = P
+
+    @torch.no_grad()
+    def flush(self) -> None:
+        """Step the token the last ``generate`` ended on, if it has not been (the next ``generate`` would do it first)."""
+        if self._drawn:
+            self._step(self._tok)
+            self._drawn = False
+
+    def _step(self, tok: torch.Tensor) -> None:
+        if self.uniform:
+            K.decode_step(self._plan, tok, self.lens[0])
+        else:
+            K.decode_step_ragged(self._plan, tok, self.lens)
+        self.lens = [n + 1 for n in self.lens]
 
     @torch.no_grad()
     def step(self, tokens: torch.Tensor) -> torch.Tensor:
-        """Append ``tokens`` [B] (one per sequence) at position ``pos``; fp32 logits [B, V] for the position after."""
-        if self.pos == 0:
+        """Append ``tokens`` [B] (one per sequence) at position ``lens[b]``; fp32 logits [B, V] for the position after."""
+        if min(self.lens) == 0:
             raise RuntimeError("step before prefill: the cache is empty")
-        if self.pos >= self.Tcap:
+        if max(self.lens) >= self.Tcap:
             raise ValueError(f"the cache is full ({self.Tcap} positions): reset() or a larger max_len")
         if tokens.shape != (self.B,):
             raise ValueError(f"step takes tokens [B={self.B}] (got {tuple(tokens.shape)})")
@@ -258,14 +375,13 @@ class DecodeSession:
             raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
         self._ready(False)  # (the weights are those of the prefill: the shadow is synced there)
         tok = tokens.contiguous() if tokens.dtype == torch.int64 else tokens.long()
-        K.decode_step(self._plan, tok, self.pos)
-        self.pos += 1
+        self._step(tok)
         self._drawn = False
         return self.logits[:, :self.cfg.vocab_size].clone()
 
     # ---- device-side sampling (gpt2mi_sample, gpt2mi_decode_generate): nothing below returns to the host ----
     def _check_sampler(self, temperature, top_p, seed):
-        if self.pos == 0:
+        if min(self.lens) == 0:
             raise RuntimeError("sampling before prefill: there are no logits")
         if temperature < 0:
             raise ValueError(f"temperature must be >= 0 (got {temperature})")
@@ -279,42 +395,52 @@ class DecodeSession:
 
     @torch.no_grad()
     def sample(self, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
-               seed: int = 0) -> torch.Tensor:
-        """Tokens [B] (int64, device) for position ``pos`` from the logits of the last ``prefill`` / ``step``: one
-        launch, no host synchronisation. Row b's token is a function of (its logits, the parameters, seed, b, pos):
-        ``sample_reference`` with ``uniform_at(seed, b, pos)``."""
+               seed: int = 0, row_id: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Tokens [B] (int64, device) for position ``lens[b]`` from the logits of the last ``prefill`` / ``step``: one
+        launch, no host synchronisation. Row b's token is a function of (its logits, the parameters, seed, its draw key,
+        its position): ``sample_reference`` with ``uniform_at(seed, row_id[b], lens[b])``; ``row_id`` (B ints, default
+        the row numbers) lets a sequence keep its draw stream whichever row it sits in."""
         self._check_sampler(temperature, top_p, seed)
         if self._drawn:
             raise RuntimeError("the logits are those generate() drew its last token from: step() that token first")
         out = torch.empty(self.B, dtype=torch.int64, device=self.logits.device)
-        K.sample(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.pos, out)
+        if self.uniform and row_id is None:
+            K.sample(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens[0], out)
+        else:
+            K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, out,
+                            row_id=_check_row_id(row_id, self.B))
         return out
 
     @torch.no_grad()
     def generate(self, n: int, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  seed: int = 0, eos_token_id: Optional[int] = None, seq: Optional[torch.Tensor] = None,
-                 done: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 done: Optional[torch.Tensor] = None, row_id: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Draw the tokens of positions ``pos .. pos + n - 1`` in one C call (gpt2mi_decode_generate: sample, step,
         sample, ... on the stream, no Python and no synchronisation in between). The tokens go to column ``pos + i`` of
         ``seq`` (int64 [B, >= pos + n], optional); with ``eos_token_id``, ``done`` (uint8 [B]) marks finished rows, which
         keep emitting eos. Returns the newest tokens [B] (a buffer the next call overwrites). The last token drawn is
-        not stepped until the next ``generate`` (which does it first) or ``step``."""
+        not stepped until the next ``generate`` (which does it first), ``flush`` or ``step``. With rows at different
+        positions ``pos`` reads ``lens[b]`` throughout (gpt2mi_decode_generate_ragged); ``row_id`` as for ``sample``."""
         self._check_sampler(temperature, top_p, seed)
         n = int(n)
         if n < 1:
             raise ValueError(f"generate takes n >= 1 (got {n})")
-        if self.pos + int(self._drawn) + n > self.Tcap:
+        row_id = _check_row_id(row_id, self.B)
+        if max(self.lens) + int(self._drawn) + n > self.Tcap:
             raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
         if seq is not None and (seq.dtype != torch.int64 or seq.dim() != 2 or seq.size(0) != self.B or seq.stride(1) != 1):
             raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
         if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
             raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
-        if self._drawn:  # the token the previous call ended on
-            K.decode_step(self._plan, self._tok, self.pos)
-            self.pos += 1
-        K.decode_generate(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.pos, n, self._tok,
-                          eos=eos_token_id, seq=seq, done=done if eos_token_id is not None else None)
-        self.pos += n - 1
+        self.flush()  # the token the previous call ended on
+        done = done if eos_token_id is not None else None
+        if self.uniform and row_id is None:
+            K.decode_generate(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens[0], n,
+                              self._tok, eos=eos_token_id, seq=seq, done=done)
+        else:
+            K.decode_generate_ragged(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
+                                     self._tok, row_id=row_id, eos=eos_token_id, seq=seq, done=done)
+        self.lens = [m + n - 1 for m in self.lens]
         self._drawn = True
         return self._tok
 
@@ -322,17 +448,40 @@ class DecodeSession:
 EOS_CHUNK = 32  # device loop with eos_token_id: tokens issued between two reads of the done flags
 
 
+def _pad_prompts(prompts, pad: int):
+    """A list of 1-D token tensors as one right-padded [B, Pmax] int64 tensor and the list of their lengths."""
+    if not prompts or any(p.dim() != 1 or p.numel() < 1 for p in prompts):
+        raise ValueError("prompts must be a non-empty list of non-empty 1-D token tensors")
+    lens = [p.numel() for p in prompts]
+    idx = torch.full((len(prompts), max(lens)), pad, dtype=torch.int64, device=prompts[0].device)
+    for b, p in enumerate(prompts):
+        idx[b, :lens[b]] = p
+    return idx, lens
+
+
 @torch.no_grad()
-def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
+def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
              generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
-             top_p: Optional[float] = None, seed: Optional[int] = None) -> torch.Tensor:
+             top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens: Optional[Sequence[int]] = None,
+             pad_token_id: Optional[int] = None) -> torch.Tensor:
     """``GPT2.generate``: see there."""
+    pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
+    if isinstance(idx, (list, tuple)):
+        if prompt_lens is not None:
+            raise ValueError("a list of prompts carries its own lengths: prompt_lens goes with a padded idx [B, P]")
+        idx, prompt_lens = _pad_prompts(idx, pad)
     if idx.dim() != 2:
         raise ValueError(f"generate takes idx [B, P] (got {tuple(idx.shape)})")
     B, P = idx.shape
     n = int(max_new_tokens)
     if n < 0:
         raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
+    if prompt_lens is not None:
+        prompt_lens = _check_lens(prompt_lens, B, P)
+        if not 0 <= pad < model.config.vocab_size:
+            raise ValueError(f"pad_token_id {pad} not in [0, vocab_size={model.config.vocab_size})")
+        P = max(prompt_lens)
+        idx = idx[:, :P]
     if P + n > model.config.n_positions:
         raise ValueError(f"prompt length {P} + max_new_tokens {n} > n_positions {model.config.n_positions}")
     _check_top_p(top_p)
@@ -340,6 +489,9 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
         raise ValueError("seed selects the device sampler, which draws from (seed, row, position): it takes no generator")
     _check_model(model)
     idx = idx.long()
+    if prompt_lens is not None:
+        return _generate_ragged(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id,
+                                pad)
     if n == 0:
         return idx.clone()
     sess = DecodeSession(model, B, P + n)
@@ -359,6 +511,62 @@ def generate(model, idx: torch.Tensor, max_new_tokens: int, temperature: float =
         if i + 1 < n:
             logits = sess.step(nxt)
     return torch.cat(out, dim=1)
+
+
+def _generate_ragged(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad):
+    """``generate`` with ``prompt_lens``: [B, Pmax + m], row b = its prompt, its m new tokens from column lens[b] on, then
+    ``pad``. m = n, or with eos the number of tokens by which every row has emitted it (the cut of the equal-length
+    paths). Host sampler: new tokens are collected per step; device sampler: gpt2mi_sample_ragged writes row b's token
+    of step i to column lens[b] + i of the buffer that holds the prompts."""
+    B, P = idx.shape
+    dev = idx.device
+    if eos_token_id is not None and seed is not None and not 0 <= eos_token_id < model.config.vocab_size:
+        raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={model.config.vocab_size})")
+    lens_t = torch.tensor(lens, device=dev)
+    cols = torch.arange(P + n, device=dev)[None]
+    seq = torch.full((B, P + n), pad, dtype=torch.int64, device=dev)
+    seq[:, :P] = torch.where(cols[:, :P] < lens_t[:, None], idx, seq[:, :P])  # the callers' padding may be anything
+    if n == 0:
+        return seq
+    idx = torch.where(cols[:, :P] < lens_t[:, None], idx, torch.zeros_like(idx))  # (a valid token id as padding)
+    sess = DecodeSession(model, B, P + n)
+    if seed is not None:
+        sess.prefill(idx, lens)
+        if eos_token_id is None:
+            sess.generate(n, temperature, top_k, top_p, seed, seq=seq)
+            return seq
+        done = torch.zeros(B, dtype=torch.uint8, device=dev)
+        made = 0
+        while made < n:
+            m = min(EOS_CHUNK, n - made)
+            sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done)
+            made += m
+            if bool(done.all()):
+                break
+        new = seq.gather(1, lens_t[:, None] + torch.arange(made, device=dev)[None])
+    else:
+        toks = []
+        done = torch.zeros(B, dtype=torch.bool, device=dev)
+        logits = sess.prefill(idx, lens)
+        for i in range(n):
+            nxt = sample_next(logits, temperature, top_k, generator, top_p)
+            if eos_token_id is not None:
+                nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)
+                done = done | (nxt == eos_token_id)
+            toks.append(nxt)
+            if eos_token_id is not None and bool(done.all()):
+                break
+            if i + 1 < n:
+                logits = sess.step(nxt)
+        new = torch.stack(toks, dim=1)
+        made = new.size(1)
+        seq.scatter_(1, lens_t[:, None] + torch.arange(made, device=dev)[None], new)
+    if eos_token_id is not None:
+        finished = ((new == eos_token_id).cumsum(1) > 0).all(0)  # steps by which every row has emitted eos
+        if bool(finished.any()):
+            made = int(finished.int().argmax()) + 1
+    keep = cols[:, :P + made] < (lens_t + made)[:, None]
+    return torch.where(keep, seq[:, :P + made], torch.full_like(seq[:, :P + made], pad))
 
 
 def _generate_on_device(sess: DecodeSession, idx, n, temperature, top_k, top_p, seed, eos_token_id):
@@ -388,3 +596,84 @@ def _generate_on_device(sess: DecodeSession, idx, n, temperature, top_k, top_p, 
     if bool(finished.any()):
         made = int(finished.int().argmax()) + 1
     return seq[:, :P + made].clone() if made < n else seq
+
+
+@torch.no_grad()
+def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
+                  top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
+                  eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None) -> List[torch.Tensor]:
+    """``GPT2.generate_many``: see there."""
+    if generator is not None:
+        raise ValueError("generate_many draws on the device from (seed, prompt index, position): a torch.Generator is "
+                         "one stream shared by the rows of a batch, so its draws would depend on the batching")
+    prompts = list(prompts)
+    if any(not isinstance(p, torch.Tensor) or p.dim() != 1 or p.numel() < 1 for p in prompts):
+        raise ValueError("prompts must be non-empty 1-D token tensors")
+    n = int(max_new_tokens)
+    if n < 0:
+        raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
+    if not 1 <= int(batch_size) <= MAX_BATCH:
+        raise ValueError(f"batch_size {batch_size} not in [1, {MAX_BATCH}] (the decode GEMM's row limit)")
+    longest = max((p.numel() for p in prompts), default=0)
+    if longest + n > model.config.n_positions:
+        raise ValueError(f"prompt length {longest} + max_new_tokens {n} > n_positions {model.config.n_positions}")
+    _check_top_p(top_p)
+    if not isinstance(seed, int):
+        raise ValueError(f"seed must be an int (got {seed!r})")
+    if eos_token_id is not None and not 0 <= eos_token_id < model.config.vocab_size:
+        raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={model.config.vocab_size})")
+    if not prompts or n == 0:
+        return [p.long().clone() for p in prompts]
+    _check_model(model)
+    # (at least a chunk and two positions, so that a dummy row of one token need not start over within a chunk)
+    sess = DecodeSession(model, int(batch_size), min(model.config.n_positions, max(longest + n, EOS_CHUNK + 2)))
+    return serve_prompts(sess, [p.long() for p in prompts], n, temperature, top_k, top_p, seed, eos_token_id)
+
+
+def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, eos_token_id) -> List[torch.Tensor]:
+    """The loop of ``generate_many`` over a session (anything with DecodeSession's ``B``, ``Tcap``, ``lens``,
+    ``device``, ``refill``, ``generate`` and ``flush``). Rows are slots: a slot holds prompt ``owner[row]`` (None: a
+    dummy of one token whose output is dropped) and draws with ``row_id = owner[row]``. The device loop runs in chunks
+    of at most EOS_CHUNK tokens, cut so that no live row passes its ``n`` tokens; after a chunk the done flags and the
+    tokens are read once, finished rows (eos, or n tokens) are harvested, cut after their first eos, and refilled with
+    the next pending prompt."""
+    B, dev = sess.B, sess.device
+    out: List[Optional[torch.Tensor]] = [None] * len(prompts)
+    pending = list(range(len(prompts)))[::-1]  # (pop() serves them in input order)
+    owner: List[Optional[int]] = [None] * B
+    start, made = [0] * B, [0] * B  # the prompt length and the tokens drawn so far of each slot
+    seq = torch.zeros(B, sess.Tcap, dtype=torch.int64, device=dev)
+    done = torch.zeros(B, dtype=torch.uint8, device=dev)
+    dummy = torch.zeros(1, dtype=torch.int64, device=dev)
+    DUMMY_ID = 0xFFFFFFFF
+
+    def fill(row):
+        owner[row] = pending.pop() if pending else None
+        prompt = dummy if owner[row] is None else prompts[owner[row]].to(dev)
+        sess.refill(row, prompt)
+        start[row], made[row] = prompt.numel(), 0
+        done[row] = 0
+
+    for row in range(B):
+        fill(row)
+    while any(o is not None for o in owner):
+        m = min([EOS_CHUNK] + [n - made[r] for r in range(B) if owner[r] is not None])
+        for r in range(B):  # a dummy row that a chunk would take past the cache starts over
+            if owner[r] is None and sess.lens[r] + m + 1 > sess.Tcap:
+                fill(r)
+        sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done,
+                      row_id=[DUMMY_ID if o is None else o for o in owner])
+        sess.flush()  # every row's logits are now those of its next position: a refilled row joins on equal terms
+        host = torch.cat([done.to(torch.int64)[:, None], seq], dim=1).cpu()  # the one read of the chunk
+        for r in range(B):
+            made[r] += m
+            if owner[r] is None or not (made[r] >= n or (eos_token_id is not None and bool(host[r, 0]))):
+                continue
+            new = host[r, 1 + start[r]:1 + start[r] + made[r]]
+            if eos_token_id is not None:
+                hits = (new == eos_token_id).nonzero()
+                if hits.numel():
+                    new = new[:int(hits[0]) + 1]
+            out[owner[r]] = torch.cat([prompts[owner[r]].to(dev), new.to(dev)])
+            fill(r)
+    return out

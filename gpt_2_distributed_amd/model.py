@@ -341,9 +341,10 @@ class GPT2(nn.Module):
         from .generation import DecodeSession
         return DecodeSession(self, batch_size, max_len)
 
-    def generate(self, idx: torch.Tensor, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
+    def generate(self, idx, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
-                 top_p: Optional[float] = None, seed: Optional[int] = None) -> torch.Tensor:
+                 top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens=None,
+                 pad_token_id: Optional[int] = None) -> torch.Tensor:
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
         filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
@@ -356,6 +357,14 @@ class GPT2(nn.Module):
         the host before the return, with it the done flags are read once per 32 tokens. Same output shape and padding.
         ``seed`` together with ``generator``, or ``top_p <= 0``, raises ``ValueError``.
 
+        Prompts of unequal length: ``prompt_lens`` (B ints, ``1 <= prompt_lens[b] <= P``) says that row b's prompt is
+        ``idx[b, :prompt_lens[b]]`` and the rest of the row padding; ``idx`` may also be a list of 1-D tensors, which is
+        padded here. The result is then ``[B, Pmax + m]`` with ``Pmax = max(prompt_lens)``: row b holds its prompt, its
+        m new tokens from column ``prompt_lens[b]`` on, and ``pad_token_id`` (default ``eos_token_id``, else 0) after
+        them; m = ``max_new_tokens`` unless every row emitted eos earlier. Both samplers work; with ``seed`` row b's
+        tokens are those it gets in an equal-length batch (one position per row: ``gpt2mi_decode_step_ragged``).
+        ``Pmax + max_new_tokens > n_positions`` raises ``ValueError``. Without ``prompt_lens`` nothing changes.
+
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
         the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
         ``NotImplementedError``. It does not advance the dropout stream or touch what a later backward needs, so a
@@ -364,7 +373,29 @@ class GPT2(nn.Module):
         backward. Through ``DistributedDataParallel`` call ``.module.generate``; a ``FullyShardedDataParallel``-wrapped
         model holds only a shard of the parameters and raises ``NotImplementedError``."""
         from .generation import generate
-        return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed)
+        return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed,
+                        prompt_lens, pad_token_id)
+
+    def generate_many(self, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
+                      top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
+                      eos_token_id: Optional[int] = None, generator=None):
+        """Continue any number of 1-D ``prompts`` of any lengths by up to ``max_new_tokens`` tokens each; returns a list
+        in input order, each entry the prompt plus its new tokens, cut after the first ``eos_token_id``.
+
+        One ``DecodeSession`` of ``batch_size`` rows serves them all (continuous batching): every prompt enters a row
+        through ``DecodeSession.refill``, the device loop runs in chunks of up to 32 tokens, and after each chunk the
+        rows that have finished (eos, or ``max_new_tokens``) are harvested and refilled with the next prompt while the
+        others go on. Prompt i draws with ``generation.uniform_at(seed, i, position)``.
+
+        Guarantee: prompt i's output is a function of (weights, prompt i, the sampler parameters, seed, i). It does not
+        depend on ``batch_size``, on the other prompts or on the order in which they finish (every kernel of the
+        decode step forms a row from that row's data alone, in an order that does not depend on the batch; a refill's
+        shapes depend on its prompt alone). Device sampler only: ``generator=`` raises ``ValueError``.
+        ``max(len) + max_new_tokens > n_positions`` raises ``ValueError``. Training is left untouched as by
+        ``generate``."""
+        from .generation import generate_many
+        return generate_many(self, prompts, max_new_tokens, batch_size, temperature, top_k, top_p, seed, eos_token_id,
+                             generator)
 
     # ---- optimizer (nanoGPT-style name the north star uses) -----------------------------------------
     def configure_optimizers(self, weight_decay: float = 0.1, learning_rate: float = 1e-4,

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 18
+#define GPT2MI_ABI_VERSION 19
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -352,6 +352,47 @@ int gpt2mi_lm_loss(const uint16_t* x, int ldx, const uint16_t* w, int ldw, int w
                    int V, int K, int ignore_index, float* loss_rows, float* lse, float* loss_sum, float* count,
                    int accumulate, float* loss_mean, float* workspace, void* stream);
 size_t gpt2mi_lm_loss_workspace(int M, int V); /* bytes; 0 for M < 1 or V < 1 */
+
+/* ---- v19: ragged decode (csrc/decode.hip, csrc/sample.hip). The entries above put every sequence of a batch at one
+ * position; these take one position per row, so prompts of unequal length share a batch and a finished row can be
+ * replaced while the others go on (generation.py DecodeSession.refill, generate_many).
+ * A position array is `const int* pos`: a HOST array of B ints, 1 <= B <= GPT2MI_DECODE_MAX_B. The entry checks every
+ * element before any launch and passes the array to its kernels by value, as a kernel argument: there is no device-side
+ * position array, so no position reaches a kernel unchecked, nothing is copied to the device and the caller's array may
+ * be reused as soon as the call returns.
+ * Refused with 22 before any launch, beside what the scalar twin refuses: B outside [1, GPT2MI_DECODE_MAX_B], a NULL
+ * position array, a pos[b] outside the range stated at the entry, ld_seq <= pos[b] with a seq_out. ---- */
+#define GPT2MI_DECODE_MAX_B 64
+/* gpt2mi_attn_decode with row b at pos[b] in [0, Tcap) (model.py:124-155 for the newest position of each row): row b's
+ * k and v are written to position pos[b] of its streams and out[b] attends over positions 0..pos[b]. The grid covers
+ * max_b pos[b] / 32 + 1 key ranges; a wave whose range starts beyond its row's position exits before any load or
+ * store, and the combine merges pos[b] / 32 + 1 ranges of row b in range order. Workspace: size and layout of
+ * gpt2mi_attn_decode_workspace(B, H, Tcap). Per row: cache positions != pos[b] are not written, positions > pos[b] are
+ * not read; no atomics. The bits of out[b] and of row b's cache are those gpt2mi_attn_decode gives that row at
+ * pos = pos[b] (one per-range body serves both kernels). */
+int gpt2mi_attn_decode_ragged(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out, float* workspace,
+                              size_t workspace_floats, int B, int H, int head_dim, int Tcap, const int* pos,
+                              void* stream);
+/* K1 for one new token per sequence at its own position: x[b,:] = wte[tok[b],:] + wpe[pos[b],:] (model.py:295-304
+ * at one position per row; fp32, no dropout), pos[b] >= 0. */
+int gpt2mi_embed_decode_ragged(const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C,
+                               const int* pos, void* stream);
+/* gpt2mi_sample with a position and a draw key per row: row b draws u from (seed, row_id[b], pos[b]) in place of
+ * (seed, b, pos) and writes seq_out[b*ld_seq + pos[b]]; pos[b] >= 0. row_id is a HOST array of B values and may be NULL
+ * (row_id[b] = b): it lets a sequence keep its draw stream whichever row of the batch it occupies. Everything else
+ * (filtering, scan, draw, eos / done indexed by b, tok_out[b], probs_out) is gpt2mi_sample's code. */
+int gpt2mi_sample_ragged(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
+                         uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
+                         int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, void* stream);
+/* gpt2mi_decode_step with row b at pos[b] in [0, plan->Tcap) (model.py:295-351 at one position per row): the same
+ * sequence with gpt2mi_embed_decode_ragged and gpt2mi_attn_decode_ragged; LayerNorm and the skinny GEMMs are unchanged. */
+int gpt2mi_decode_step_ragged(const gpt2mi_decode_plan* plan, const int64_t* tok, const int* pos, void* stream);
+/* gpt2mi_decode_generate with row b starting at pos0[b] >= 1: for i < n, gpt2mi_sample_ragged at pos0[b] + i (draw key
+ * row_id[b], may be NULL), then, if i + 1 < n, gpt2mi_decode_step_ragged at pos0[b] + i. max_b pos0[b] + n <= Tcap (and
+ * <= ld_seq with seq) is checked before the first launch. */
+int gpt2mi_decode_generate_ragged(const gpt2mi_decode_plan* plan, int V, float temperature, int top_k, float top_p,
+                                  uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
+                                  int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream);
 
 #ifdef __cplusplus
 }
