@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -96,8 +96,9 @@ _SIGS = {
     "gpt2mi_lm_loss": [_p, _c_int, _p, _c_int, _c_int, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p, _c_int, _p,
                        _p, _p],
     "gpt2mi_lm_loss_workspace": [_c_int, _c_int],
-    # v19 ragged decode: the scalar twins' lists with pos -> const int* pos (HOST array of B ints) and, for the sampler
-    # and the loop, const uint32_t* row_id (HOST array, may be NULL) after it
+    # v19 ragged decode: the scalar entries' lists with pos -> const int* pos (HOST array of B ints) and, for the sampler
+    # and the loop, const uint32_t* row_id (HOST array, may be NULL) after it. v20: these are the implementation, the
+    # scalar entries above forward to them (and take B <= DECODE_MAX_B like them)
     "gpt2mi_attn_decode_ragged": [_p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _p, _p],
     "gpt2mi_embed_decode_ragged": [_p, _p, _p, _p, _c_int, _c_int, _p, _p],
     "gpt2mi_sample_ragged": [_p, _c_int, _c_int, _c_int, _c_float, _c_int, _c_float, _c_u64, _p, _p, ctypes.c_int64, _p,
@@ -436,7 +437,8 @@ def attn_decode_workspace(B, H, Tcap) -> int:
 
 
 def attn_decode(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos):
-    """The new token's attention over cache positions 0..pos (its own k / v are written at pos first)."""
+    """The new token's attention over cache positions 0..pos (its own k / v are written at pos first): attn_decode_ragged
+    with every row at pos."""
     _call("gpt2mi_attn_decode", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(workspace), workspace.numel(),
           B, H, D, Tcap, pos, _stream())
 
@@ -446,7 +448,8 @@ def embed_decode(tok, wte, wpe, x, B, C, pos):
 
 
 def decode_step(plan: DecodePlan, tok, pos):
-    """One token step of the whole network (gpt2mi_decode_step) into plan.logits."""
+    """One token step of the whole network (gpt2mi_decode_step) into plan.logits: decode_step_ragged with every row at
+    pos. The package steps through decode_step_ragged; this binding serves the test that holds the two equal."""
     _call("gpt2mi_decode_step", ctypes.byref(plan), _ptr(tok), pos, _stream())
 
 
@@ -469,7 +472,8 @@ def sample(logits, V, temperature, top_k, top_p, seed, pos, tok_out, eos=None, d
 
 
 def decode_generate(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, eos=None, seq=None, done=None):
-    """gpt2mi_decode_generate: n sample-then-step rounds from plan.logits without leaving C."""
+    """gpt2mi_decode_generate: n sample-then-step rounds from plan.logits without leaving C: decode_generate_ragged with
+    every row starting at pos0 (as decode_step, kept for the test of that)."""
     t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
     _call("gpt2mi_decode_generate", ctypes.byref(plan), V, t, k, p, s, e, pos0, n, _ptr(tok), _ptr(seq),
           0 if seq is None else seq.stride(0), _ptr(done), _stream())

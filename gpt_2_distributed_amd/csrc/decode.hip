@@ -178,19 +178,25 @@ __device__ __forceinline__ void unpack8(bf16x8 v, float* f) {
   for (int j = 0; j < 8; ++j) f[j] = bf2f(v[j]);
 }
 
-// A position per row (gpt2mi_*_ragged): the host array of the C entry, validated there and passed by value as a kernel
-// argument, so a kernel never indexes memory with a position nobody checked. Indexed by blockIdx: scalar loads.
+// A position per row: the host array of the C entry, validated there and passed by value as a kernel argument, so a
+// kernel never indexes memory with a position nobody checked. Indexed by blockIdx: scalar loads.
 struct RowPos {
   int v[GPT2MI_DECODE_MAX_B];
 };
 
-// The body of one (range, b, h) wave at position pos: shared by both kernels below, so a row's bits are the same.
-__device__ __forceinline__ void attn_decode_range(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                  bf16* __restrict__ vc, float* __restrict__ ws_ml,
-                                                  float* __restrict__ ws_acc, int H, int Tcap, int pos, int nr_max,
-                                                  int range, int bh) {
+// Grid (ranges, H, B): row b at rows.v[b]; the x extent is that of the longest row. A wave whose range starts beyond
+// its row's position leaves before any load or store (wave-uniform: one wave per block, range and row from blockIdx; the
+// body has no barrier), so its workspace slot stays unwritten and attn_combine_kernel does not read it. b is a grid
+// index of its own so that the position is one scalar load from the start of the wave: behind a division of a
+// (b, h) index by H every cache load waited for it.
+__global__ __launch_bounds__(64) void attn_decode_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
+                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
+                                                         float* __restrict__ ws_acc, int H, int Tcap, RowPos rows,
+                                                         int nr_max) {
+  const int range = blockIdx.x, h = blockIdx.y, b = blockIdx.z, bh = b * H + h;
+  const int pos = rows.v[b];
+  if (range * AD_KEYS > pos) return;
   const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
-  const int b = bh / H, h = bh % H;
   const int C = H * 64;
   const bf16* tok = qkv + (size_t)b * 3 * C + h * 64 + 8 * dg;  // q; k at + C, v at + 2C
   float q[8];
@@ -262,29 +268,13 @@ __device__ __forceinline__ void attn_decode_range(const bf16* __restrict__ qkv, 
   }
 }
 
-__global__ __launch_bounds__(64) void attn_decode_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
-                                                         float* __restrict__ ws_acc, int H, int Tcap, int pos,
-                                                         int nr_max) {
-  attn_decode_range(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, pos, nr_max, blockIdx.x, blockIdx.y);
-}
-
-// Row b at pos.v[b]; the grid's x extent is that of the longest row. A wave whose range starts beyond its row's
-// position leaves before any load or store (wave-uniform: one wave per block, range and row from blockIdx; the body has
-// no barrier), so its workspace slot stays unwritten and attn_combine_ragged_kernel does not read it.
-__global__ __launch_bounds__(64) void attn_decode_ragged_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                                bf16* __restrict__ vc, float* __restrict__ ws_ml,
-                                                                float* __restrict__ ws_acc, int H, int Tcap,
-                                                                RowPos pos, int nr_max) {
-  const int p = pos.v[blockIdx.y / H];
-  if ((int)blockIdx.x * AD_KEYS > p) return;
-  attn_decode_range(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, p, nr_max, blockIdx.x, blockIdx.y);
-}
-
-// out[b, h*64 + d] = sum_r e^(m_r - m) acc_r[d] / sum_r e^(m_r - m) l_r, r in range order; lane d.
-__device__ __forceinline__ void attn_combine_row(const float* __restrict__ ws_ml, const float* __restrict__ ws_acc,
-                                                 bf16* __restrict__ out, int H, int nr, int nr_max) {
-  const int d = threadIdx.x, bh = blockIdx.x;
+// out[b, h*64 + d] = sum_r e^(m_r - m) acc_r[d] / sum_r e^(m_r - m) l_r over the pos[b] / 32 + 1 ranges of row b, in
+// range order; lane d, grid (H, B).
+__global__ __launch_bounds__(64) void attn_combine_kernel(const float* __restrict__ ws_ml,
+                                                          const float* __restrict__ ws_acc, bf16* __restrict__ out,
+                                                          int H, RowPos rows, int nr_max) {
+  const int d = threadIdx.x, h = blockIdx.x, b = blockIdx.y, bh = b * H + h;
+  const int nr = rows.v[b] / AD_KEYS + 1;
   const size_t slot0 = (size_t)bh * nr_max;
   float m = -INFINITY;
   for (int r = 0; r < nr; ++r) m = fmaxf(m, ws_ml[2 * (slot0 + r)]);
@@ -294,44 +284,18 @@ __device__ __forceinline__ void attn_combine_row(const float* __restrict__ ws_ml
     l = __builtin_fmaf(w, ws_ml[2 * (slot0 + r) + 1], l);
     o = __builtin_fmaf(w, ws_acc[(slot0 + r) * 64 + d], o);
   }
-  out[(size_t)(bh / H) * H * 64 + (bh % H) * 64 + d] = f2bf(o / l);
-}
-
-__global__ __launch_bounds__(64) void attn_combine_kernel(const float* __restrict__ ws_ml,
-                                                          const float* __restrict__ ws_acc, bf16* __restrict__ out,
-                                                          int H, int nr, int nr_max) {
-  attn_combine_row(ws_ml, ws_acc, out, H, nr, nr_max);
-}
-
-__global__ __launch_bounds__(64) void attn_combine_ragged_kernel(const float* __restrict__ ws_ml,
-                                                                 const float* __restrict__ ws_acc,
-                                                                 bf16* __restrict__ out, int H, RowPos pos,
-                                                                 int nr_max) {
-  attn_combine_row(ws_ml, ws_acc, out, H, pos.v[blockIdx.x / H] / AD_KEYS + 1, nr_max);
-}
-
-__global__ __launch_bounds__(256) void embed_decode_kernel(const int64_t* __restrict__ tok,
-                                                           const float* __restrict__ wte,
-                                                           const float* __restrict__ wpe, float* __restrict__ x, int B,
-                                                           int C, int pos) {
-  const int i = blockIdx.x * 256 + threadIdx.x;  // one thread per 4 floats
-  const int c4 = C / 4;
-  if (i >= B * c4) return;
-  const int b = i / c4, c = 4 * (i % c4);
-  const f32x4 e = *reinterpret_cast<const f32x4*>(wte + (size_t)tok[b] * C + c);
-  const f32x4 p = *reinterpret_cast<const f32x4*>(wpe + (size_t)pos * C + c);
-  *reinterpret_cast<f32x4*>(x + (size_t)b * C + c) = e + p;
+  out[(size_t)bh * 64 + d] = f2bf(o / l);
 }
 
 // One row per blockIdx.y, so that the row's position is a scalar load of the argument.
-__global__ __launch_bounds__(256) void embed_decode_ragged_kernel(const int64_t* __restrict__ tok,
-                                                                  const float* __restrict__ wte,
-                                                                  const float* __restrict__ wpe, float* __restrict__ x,
-                                                                  int C, RowPos pos) {
+__global__ __launch_bounds__(256) void embed_decode_kernel(const int64_t* __restrict__ tok,
+                                                           const float* __restrict__ wte,
+                                                           const float* __restrict__ wpe, float* __restrict__ x, int C,
+                                                           RowPos rows) {
   const int b = blockIdx.y, c = 4 * (blockIdx.x * 256 + threadIdx.x);  // one thread per 4 floats
   if (c >= C) return;
   const f32x4 e = *reinterpret_cast<const f32x4*>(wte + (size_t)tok[b] * C + c);
-  const f32x4 p = *reinterpret_cast<const f32x4*>(wpe + (size_t)pos.v[b] * C + c);
+  const f32x4 p = *reinterpret_cast<const f32x4*>(wpe + (size_t)rows.v[b] * C + c);
   *reinterpret_cast<f32x4*>(x + (size_t)b * C + c) = e + p;
 }
 
@@ -414,33 +378,9 @@ GPT2MI_EXPORT size_t gpt2mi_attn_decode_workspace(int B, int H, int Tcap) {
   return (size_t)B * H * attn_ranges(Tcap) * 66;  // (max, sum) + acc[64] per range
 }
 
-GPT2MI_EXPORT int gpt2mi_attn_decode(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
-                                     float* workspace, size_t workspace_floats, int B, int H, int head_dim, int Tcap,
-                                     int pos, void* stream) {
-  GPT2MI_REQUIRE(head_dim == 64, "attn_decode: head_dim=%d (the decode kernels implement 64)", head_dim);
-  GPT2MI_REQUIRE(B >= 1 && H >= 1 && Tcap >= 1 && (long long)B * H <= 65535,
-                 "attn_decode: B=%d, H=%d, Tcap=%d must be positive and B*H <= 65535", B, H, Tcap);
-  GPT2MI_REQUIRE(pos >= 0 && pos < Tcap, "attn_decode: pos=%d not in [0, Tcap=%d)", pos, Tcap);
-  const size_t need = gpt2mi_attn_decode_workspace(B, H, Tcap);
-  GPT2MI_REQUIRE(workspace_floats >= need,
-                 "attn_decode: workspace too small (%zu floats given, %zu needed)", workspace_floats, need);
-  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
-                 "attn_decode: qkv, the caches, out and workspace must not be NULL");
-  hipStream_t s = (hipStream_t)stream;
-  const int nr_max = attn_ranges(Tcap), nr = pos / AD_KEYS + 1;
-  float* ws_ml = workspace;
-  float* ws_acc = workspace + (size_t)B * H * nr_max * 2;
-  attn_decode_kernel<<<dim3(nr, B * H), 64, 0, s>>>((const bf16*)qkv, (bf16*)kcache, (bf16*)vcache, ws_ml, ws_acc, H,
-                                                    Tcap, pos, nr_max);
-  int rc = gpt2mi::check_launch("attn_decode");
-  if (rc) return rc;
-  attn_combine_kernel<<<B * H, 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, nr, nr_max);
-  return gpt2mi::check_launch("attn_decode combine");
-}
-
 namespace {
-// The position array of a ragged entry: B in [1, GPT2MI_DECODE_MAX_B] host ints, each in [0, limit). 22 with a message
-// naming `what` otherwise; on success *out holds them (entries >= B are 0) and *max_pos the largest.
+// The position array of an entry: B in [1, GPT2MI_DECODE_MAX_B] host ints, each in [0, limit). 22 with a message naming
+// `what` otherwise; on success *out holds them (entries >= B are 0) and *max_pos the largest.
 int row_positions(const char* what, const int* pos, int B, int limit, RowPos* out, int* max_pos) {
   GPT2MI_REQUIRE(B >= 1 && B <= GPT2MI_DECODE_MAX_B, "%s: B=%d not in [1, %d]", what, B, GPT2MI_DECODE_MAX_B);
   GPT2MI_REQUIRE(pos != nullptr, "%s: the position array (host, B ints) is NULL", what);
@@ -453,72 +393,90 @@ int row_positions(const char* what, const int* pos, int B, int limit, RowPos* ou
   }
   return 0;
 }
+
+// What a scalar-position entry hands to the per-row implementation: every row at `pos`. All GPT2MI_DECODE_MAX_B
+// entries are filled, so B is checked where the array is read and nowhere else.
+struct SamePos {
+  int v[GPT2MI_DECODE_MAX_B];
+  explicit SamePos(int pos) { std::fill_n(v, GPT2MI_DECODE_MAX_B, pos); }
+};
+
+// Each operation below is written once, for one position per row; `what` is the entry's name in its messages.
+int attn_decode_rows(const char* what, const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
+                     float* workspace, size_t workspace_floats, int B, int H, int head_dim, int Tcap, const int* pos,
+                     void* stream) {
+  GPT2MI_REQUIRE(head_dim == 64, "%s: head_dim=%d (the decode kernels implement 64)", what, head_dim);
+  GPT2MI_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && Tcap >= 1, "%s: B=%d, H=%d (<= 65535), Tcap=%d must be positive", what,
+                 B, H, Tcap);
+  RowPos rp;
+  int max_pos;
+  if (const int rc = row_positions(what, pos, B, Tcap, &rp, &max_pos)) return rc;
+  const size_t need = gpt2mi_attn_decode_workspace(B, H, Tcap);
+  GPT2MI_REQUIRE(workspace_floats >= need, "%s: workspace too small (%zu floats given, %zu needed)", what,
+                 workspace_floats, need);
+  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
+                 "%s: qkv, the caches, out and workspace must not be NULL", what);
+  hipStream_t s = (hipStream_t)stream;
+  const int nr_max = attn_ranges(Tcap);
+  float* ws_ml = workspace;
+  float* ws_acc = workspace + (size_t)B * H * nr_max * 2;
+  attn_decode_kernel<<<dim3(max_pos / AD_KEYS + 1, H, B), 64, 0, s>>>((const bf16*)qkv, (bf16*)kcache, (bf16*)vcache,
+                                                                     ws_ml, ws_acc, H, Tcap, rp, nr_max);
+  if (const int rc = gpt2mi::check_launch(what)) return rc;
+  attn_combine_kernel<<<dim3(H, B), 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, rp, nr_max);
+  return gpt2mi::check_launch(what);
+}
+
+int embed_decode_rows(const char* what, const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C,
+                      const int* pos, void* stream) {
+  GPT2MI_REQUIRE(C >= 4 && C % 4 == 0, "%s: C=%d must be a positive multiple of 4", what, C);
+  RowPos rp;
+  int max_pos;
+  if (const int rc = row_positions(what, pos, B, INT_MAX, &rp, &max_pos)) return rc;
+  GPT2MI_REQUIRE(tok && wte && wpe && x, "%s: tok, wte, wpe and x must not be NULL", what);
+  embed_decode_kernel<<<dim3((C / 4 + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(tok, wte, wpe, x, C, rp);
+  return gpt2mi::check_launch(what);
+}
 }  // namespace
 
 GPT2MI_EXPORT int gpt2mi_attn_decode_ragged(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
                                             float* workspace, size_t workspace_floats, int B, int H, int head_dim,
                                             int Tcap, const int* pos, void* stream) {
-  GPT2MI_REQUIRE(head_dim == 64, "attn_decode_ragged: head_dim=%d (the decode kernels implement 64)", head_dim);
-  GPT2MI_REQUIRE(B >= 1 && H >= 1 && Tcap >= 1 && (long long)B * H <= 65535,
-                 "attn_decode_ragged: B=%d, H=%d, Tcap=%d must be positive and B*H <= 65535", B, H, Tcap);
-  RowPos rp;
-  int max_pos;
-  if (const int rc = row_positions("attn_decode_ragged", pos, B, Tcap, &rp, &max_pos)) return rc;
-  const size_t need = gpt2mi_attn_decode_workspace(B, H, Tcap);
-  GPT2MI_REQUIRE(workspace_floats >= need,
-                 "attn_decode_ragged: workspace too small (%zu floats given, %zu needed)", workspace_floats, need);
-  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
-                 "attn_decode_ragged: qkv, the caches, out and workspace must not be NULL");
-  hipStream_t s = (hipStream_t)stream;
-  const int nr_max = attn_ranges(Tcap);
-  float* ws_ml = workspace;
-  float* ws_acc = workspace + (size_t)B * H * nr_max * 2;
-  attn_decode_ragged_kernel<<<dim3(max_pos / AD_KEYS + 1, B * H), 64, 0, s>>>(
-      (const bf16*)qkv, (bf16*)kcache, (bf16*)vcache, ws_ml, ws_acc, H, Tcap, rp, nr_max);
-  int rc = gpt2mi::check_launch("attn_decode_ragged");
-  if (rc) return rc;
-  attn_combine_ragged_kernel<<<B * H, 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, rp, nr_max);
-  return gpt2mi::check_launch("attn_decode_ragged combine");
+  return attn_decode_rows("attn_decode_ragged", qkv, kcache, vcache, out, workspace, workspace_floats, B, H, head_dim,
+                          Tcap, pos, stream);
 }
 
-GPT2MI_EXPORT int gpt2mi_embed_decode(const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C,
-                                      int pos, void* stream) {
-  GPT2MI_REQUIRE(B >= 1 && C >= 4 && C % 4 == 0, "embed_decode: B=%d must be positive and C=%d a multiple of 4", B, C);
-  GPT2MI_REQUIRE(pos >= 0, "embed_decode: pos=%d is negative", pos);
-  GPT2MI_REQUIRE(tok && wte && wpe && x, "embed_decode: tok, wte, wpe and x must not be NULL");
-  embed_decode_kernel<<<(B * (C / 4) + 255) / 256, 256, 0, (hipStream_t)stream>>>(tok, wte, wpe, x, B, C, pos);
-  return gpt2mi::check_launch("embed_decode");
+GPT2MI_EXPORT int gpt2mi_attn_decode(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
+                                     float* workspace, size_t workspace_floats, int B, int H, int head_dim, int Tcap,
+                                     int pos, void* stream) {
+  GPT2MI_REQUIRE(pos >= 0 && pos < Tcap, "attn_decode: pos=%d not in [0, Tcap=%d)", pos, Tcap);
+  return attn_decode_rows("attn_decode", qkv, kcache, vcache, out, workspace, workspace_floats, B, H, head_dim, Tcap,
+                          SamePos(pos).v, stream);
 }
 
 GPT2MI_EXPORT int gpt2mi_embed_decode_ragged(const int64_t* tok, const float* wte, const float* wpe, float* x, int B,
                                              int C, const int* pos, void* stream) {
-  GPT2MI_REQUIRE(C >= 4 && C % 4 == 0, "embed_decode_ragged: C=%d must be a positive multiple of 4", C);
-  RowPos rp;
-  int max_pos;
-  if (const int rc = row_positions("embed_decode_ragged", pos, B, INT_MAX, &rp, &max_pos)) return rc;
-  GPT2MI_REQUIRE(tok && wte && wpe && x, "embed_decode_ragged: tok, wte, wpe and x must not be NULL");
-  embed_decode_ragged_kernel<<<dim3((C / 4 + 255) / 256, B), 256, 0, (hipStream_t)stream>>>(tok, wte, wpe, x, C, rp);
-  return gpt2mi::check_launch("embed_decode_ragged");
+  return embed_decode_rows("embed_decode_ragged", tok, wte, wpe, x, B, C, pos, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_embed_decode(const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C,
+                                      int pos, void* stream) {
+  GPT2MI_REQUIRE(pos >= 0, "embed_decode: pos=%d is negative", pos);
+  return embed_decode_rows("embed_decode", tok, wte, wpe, x, B, C, SamePos(pos).v, stream);
 }
 
 namespace {
-// gpt2mi_decode_step (rpos == NULL: every row at pos) and gpt2mi_decode_step_ragged (row b at rpos[b]): one sequence,
-// which differs in the embedding and attention entries only.
-int decode_step_impl(const char* what, const gpt2mi_decode_plan* P, const int64_t* tok, int pos, const int* rpos,
-                     bool ragged, void* stream) {
+// One step with row b at pos[b]: gpt2mi_decode_step_ragged, and gpt2mi_decode_step with every pos[b] equal.
+int decode_step_rows(const char* what, const gpt2mi_decode_plan* P, const int64_t* tok, const int* pos, void* stream) {
   GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
   const int B = P->B, C = P->C, H = P->H;
   GPT2MI_REQUIRE(B >= 1 && B <= 64, "%s: B=%d not in [1, 64]", what, B);
   GPT2MI_REQUIRE(H >= 1 && C == 64 * H, "%s: head_dim = C/H must be 64 (C=%d, H=%d)", what, C, H);
   GPT2MI_REQUIRE(P->L >= 1 && P->Vp >= 64 && P->Vp % 64 == 0, "%s: L=%d, Vp=%d (a multiple of 64) invalid", what, P->L,
                  P->Vp);
-  if (ragged) {
-    RowPos rp;
-    int max_pos;
-    if (const int rc = row_positions(what, rpos, B, P->Tcap, &rp, &max_pos)) return rc;
-  } else {
-    GPT2MI_REQUIRE(pos >= 0 && pos < P->Tcap, "%s: pos=%d not in [0, Tcap=%d)", what, pos, P->Tcap);
-  }
+  RowPos rp;
+  int max_pos;
+  if (const int rc = row_positions(what, pos, B, P->Tcap, &rp, &max_pos)) return rc;
   GPT2MI_REQUIRE(P->attn_ws_floats >= gpt2mi_attn_decode_workspace(B, H, P->Tcap),
                  "%s: attention workspace too small (%zu floats)", what, P->attn_ws_floats);
   size_t need = 0;
@@ -535,20 +493,13 @@ int decode_step_impl(const char* what, const gpt2mi_decode_plan* P, const int64_
   float *x = P->x, *xmid = P->xmid;
   float* gws = P->gemm_ws;
   const size_t gwn = P->gemm_ws_floats;
-  if (ragged)
-    STEP(gpt2mi_embed_decode_ragged(tok, P->wte, P->wpe, x, B, C, rpos, stream));
-  else
-    STEP(gpt2mi_embed_decode(tok, P->wte, P->wpe, x, B, C, pos, stream));
+  STEP(embed_decode_rows(what, tok, P->wte, P->wpe, x, B, C, pos, stream));
   for (int l = 0; l < P->L; ++l) {
     const gpt2mi_decode_layer& Y = P->layers[l];
     STEP(gpt2mi_layernorm_fwd(x, Y.ln1_w, Y.ln1_b, P->ln, nullptr, P->mean, P->rstd, B, C, P->eps, stream));
     STEP(gpt2mi_gemm_skinny(SK_BF16, B, 3 * C, C, P->ln, C, Y.qkv_w, C, P->qkv, 3 * C, Y.qkv_b, nullptr, gws, gwn, stream));
-    if (ragged)
-      STEP(gpt2mi_attn_decode_ragged(P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64,
-                                     P->Tcap, rpos, stream));
-    else
-      STEP(gpt2mi_attn_decode(P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap, pos,
-                              stream));
+    STEP(attn_decode_rows(what, P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap,
+                          pos, stream));
     STEP(gpt2mi_gemm_skinny(SK_RESID, B, C, C, P->ao, C, Y.proj_w, C, xmid, C, Y.proj_b, x, gws, gwn, stream));
     STEP(gpt2mi_layernorm_fwd(xmid, Y.ln2_w, Y.ln2_b, P->ln, nullptr, P->mean, P->rstd, B, C, P->eps, stream));
     STEP(gpt2mi_gemm_skinny(SK_GELU, B, 4 * C, C, P->ln, C, Y.fc1_w, C, P->h, 4 * C, Y.fc1_b, nullptr, gws, gwn, stream));
@@ -562,65 +513,64 @@ int decode_step_impl(const char* what, const gpt2mi_decode_plan* P, const int64_
 }
 }  // namespace
 
-GPT2MI_EXPORT int gpt2mi_decode_step(const gpt2mi_decode_plan* P, const int64_t* tok, int pos, void* stream) {
-  return decode_step_impl("decode_step", P, tok, pos, nullptr, false, stream);
-}
-
 GPT2MI_EXPORT int gpt2mi_decode_step_ragged(const gpt2mi_decode_plan* P, const int64_t* tok, const int* pos,
                                             void* stream) {
-  return decode_step_impl("decode_step_ragged", P, tok, 0, pos, true, stream);
+  return decode_step_rows("decode_step_ragged", P, tok, pos, stream);
 }
 
-GPT2MI_EXPORT int gpt2mi_decode_generate(const gpt2mi_decode_plan* P, int V, float temperature, int top_k, float top_p,
-                                         uint64_t seed, int64_t eos, int pos0, int n, int64_t* tok, int64_t* seq,
-                                         int ld_seq, uint8_t* done, void* stream) {
-  GPT2MI_REQUIRE(P != nullptr, "decode_generate: plan is NULL");
-  GPT2MI_REQUIRE(V >= 1 && V <= P->Vp, "decode_generate: V=%d not in [1, Vp=%d]", V, P->Vp);
-  GPT2MI_REQUIRE(n >= 0 && pos0 >= 1, "decode_generate: n=%d must be >= 0 and pos0=%d >= 1 (after a prefill)", n, pos0);
-  GPT2MI_REQUIRE((long long)pos0 + n <= P->Tcap, "decode_generate: pos0=%d + n=%d exceeds the cache length Tcap=%d", pos0,
-                 n, P->Tcap);
-  GPT2MI_REQUIRE(!seq || (long long)pos0 + n <= ld_seq, "decode_generate: pos0=%d + n=%d exceeds ld_seq=%d", pos0, n,
-                 ld_seq);
-  GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr, "decode_generate: tok and plan->logits must not be NULL");
-  for (int i = 0; i < n; ++i) {
-    int rc = gpt2mi_sample(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, pos0 + i, eos, done, tok, seq,
-                           ld_seq, nullptr, stream);
-    if (rc) return rc;
-    if (i + 1 < n) {
-      rc = gpt2mi_decode_step(P, tok, pos0 + i, stream);
-      if (rc) return rc;
-    }
-  }
-  return 0;
+GPT2MI_EXPORT int gpt2mi_decode_step(const gpt2mi_decode_plan* P, const int64_t* tok, int pos, void* stream) {
+  GPT2MI_REQUIRE(P != nullptr, "decode_step: plan is NULL");
+  GPT2MI_REQUIRE(pos >= 0 && pos < P->Tcap, "decode_step: pos=%d not in [0, Tcap=%d)", pos, P->Tcap);
+  return decode_step_rows("decode_step", P, tok, SamePos(pos).v, stream);
 }
 
-GPT2MI_EXPORT int gpt2mi_decode_generate_ragged(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
-                                                float top_p, uint64_t seed, int64_t eos, const int* pos0,
-                                                const uint32_t* row_id, int n, int64_t* tok, int64_t* seq, int ld_seq,
-                                                uint8_t* done, void* stream) {
-  GPT2MI_REQUIRE(P != nullptr, "decode_generate_ragged: plan is NULL");
-  GPT2MI_REQUIRE(V >= 1 && V <= P->Vp, "decode_generate_ragged: V=%d not in [1, Vp=%d]", V, P->Vp);
-  GPT2MI_REQUIRE(n >= 0, "decode_generate_ragged: n=%d must be >= 0", n);
+namespace {
+// The token loop with row b starting at pos0[b]: sample, then (but for the last token) step, n times.
+int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
+                         float top_p, uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
+                         int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream) {
+  GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
+  GPT2MI_REQUIRE(V >= 1 && V <= P->Vp, "%s: V=%d not in [1, Vp=%d]", what, V, P->Vp);
+  GPT2MI_REQUIRE(n >= 0, "%s: n=%d must be >= 0", what, n);
   RowPos rp;
   int max_pos;
-  if (const int rc = row_positions("decode_generate_ragged", pos0, P->B, P->Tcap, &rp, &max_pos)) return rc;
+  if (const int rc = row_positions(what, pos0, P->B, P->Tcap, &rp, &max_pos)) return rc;
   for (int b = 0; b < P->B; ++b)
-    GPT2MI_REQUIRE(pos0[b] >= 1, "decode_generate_ragged: pos0[%d]=%d must be >= 1 (after a prefill)", b, pos0[b]);
-  GPT2MI_REQUIRE((long long)max_pos + n <= P->Tcap,
-                 "decode_generate_ragged: max pos0=%d + n=%d exceeds the cache length Tcap=%d", max_pos, n, P->Tcap);
-  GPT2MI_REQUIRE(!seq || (long long)max_pos + n <= ld_seq, "decode_generate_ragged: max pos0=%d + n=%d exceeds ld_seq=%d",
-                 max_pos, n, ld_seq);
-  GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr,
-                 "decode_generate_ragged: tok and plan->logits must not be NULL");
+    GPT2MI_REQUIRE(pos0[b] >= 1, "%s: pos0[%d]=%d must be >= 1 (after a prefill)", what, b, pos0[b]);
+  GPT2MI_REQUIRE((long long)max_pos + n <= P->Tcap, "%s: max pos0=%d + n=%d exceeds the cache length Tcap=%d", what,
+                 max_pos, n, P->Tcap);
+  GPT2MI_REQUIRE(!seq || (long long)max_pos + n <= ld_seq, "%s: max pos0=%d + n=%d exceeds ld_seq=%d", what, max_pos, n,
+                 ld_seq);
+  GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr, "%s: tok and plan->logits must not be NULL", what);
   for (int i = 0; i < n; ++i) {
     for (int b = 0; b < P->B; ++b) rp.v[b] = pos0[b] + i;
     int rc = gpt2mi_sample_ragged(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos, done,
                                   tok, seq, ld_seq, nullptr, stream);
     if (rc) return rc;
     if (i + 1 < n) {
-      rc = gpt2mi_decode_step_ragged(P, tok, rp.v, stream);
+      rc = decode_step_rows(what, P, tok, rp.v, stream);
       if (rc) return rc;
     }
   }
   return 0;
+}
+}  // namespace
+
+GPT2MI_EXPORT int gpt2mi_decode_generate_ragged(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
+                                                float top_p, uint64_t seed, int64_t eos, const int* pos0,
+                                                const uint32_t* row_id, int n, int64_t* tok, int64_t* seq, int ld_seq,
+                                                uint8_t* done, void* stream) {
+  return decode_generate_rows("decode_generate_ragged", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n, tok,
+                              seq, ld_seq, done, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_decode_generate(const gpt2mi_decode_plan* P, int V, float temperature, int top_k, float top_p,
+                                         uint64_t seed, int64_t eos, int pos0, int n, int64_t* tok, int64_t* seq,
+                                         int ld_seq, uint8_t* done, void* stream) {
+  GPT2MI_REQUIRE(P != nullptr, "decode_generate: plan is NULL");
+  GPT2MI_REQUIRE(n >= 0 && pos0 >= 1, "decode_generate: n=%d must be >= 0 and pos0=%d >= 1 (after a prefill)", n, pos0);
+  GPT2MI_REQUIRE((long long)pos0 + n <= P->Tcap, "decode_generate: pos0=%d + n=%d exceeds the cache length Tcap=%d", pos0,
+                 n, P->Tcap);
+  return decode_generate_rows("decode_generate", P, V, temperature, top_k, top_p, seed, eos, SamePos(pos0).v, nullptr, n,
+                              tok, seq, ld_seq, done, stream);
 }

@@ -43,8 +43,8 @@ __device__ __forceinline__ float keyf(uint32_t k) {
 
 // GREEDY (temperature == 0) is a kernel of its own: as one branch of the sampling kernel it kept the row live to the
 // end of the other branch, beside the exponentials.
-// The body of both kernels below: row b = blockIdx.x of the buffers, drawn with the key (draw_row, pos) and written to
-// column pos of seq_out.
+// The kernel's body: row b = blockIdx.x of the buffers, drawn with the key (draw_row, pos) and written to column pos of
+// seq_out.
 template <bool GREEDY>
 __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int ldl, int V, float temperature,
                                            int top_k, float top_p, uint64_t seed, uint32_t draw_row, int pos,
@@ -317,83 +317,68 @@ __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int
   }
 }
 
-template <bool GREEDY>
-__global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restrict__ logits, int ldl, int V,
-                                                            float temperature, int top_k, float top_p, uint64_t seed,
-                                                            int pos, int64_t eos, uint8_t* __restrict__ done,
-                                                            int64_t* __restrict__ tok_out, int64_t* __restrict__ seq_out,
-                                                            int ld_seq, float* __restrict__ probs_out) {
-  sample_row<GREEDY>(logits, ldl, V, temperature, top_k, top_p, seed, blockIdx.x, pos, eos, done, tok_out, seq_out,
-                     ld_seq, probs_out);
-}
-
-// Per-row position and draw key (gpt2mi_sample_ragged): the entry's validated host arrays, by value; two scalar loads.
+// Per-row position and draw key: the entry's validated host arrays, by value; two scalar loads.
 struct RowKeys {
   int pos[GPT2MI_DECODE_MAX_B];
   uint32_t row_id[GPT2MI_DECODE_MAX_B];
 };
 
 template <bool GREEDY>
-__global__ __launch_bounds__(SM_THREADS) void sample_ragged_kernel(const float* __restrict__ logits, int ldl, int V,
-                                                                   float temperature, int top_k, float top_p,
-                                                                   uint64_t seed, RowKeys keys, int64_t eos,
-                                                                   uint8_t* __restrict__ done,
-                                                                   int64_t* __restrict__ tok_out,
-                                                                   int64_t* __restrict__ seq_out, int ld_seq,
-                                                                   float* __restrict__ probs_out) {
+__global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restrict__ logits, int ldl, int V,
+                                                            float temperature, int top_k, float top_p, uint64_t seed,
+                                                            RowKeys keys, int64_t eos, uint8_t* __restrict__ done,
+                                                            int64_t* __restrict__ tok_out, int64_t* __restrict__ seq_out,
+                                                            int ld_seq, float* __restrict__ probs_out) {
   sample_row<GREEDY>(logits, ldl, V, temperature, top_k, top_p, seed, keys.row_id[blockIdx.x], keys.pos[blockIdx.x], eos,
                      done, tok_out, seq_out, ld_seq, probs_out);
 }
 
-}  // namespace
-
-GPT2MI_EXPORT int gpt2mi_sample(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
-                                uint64_t seed, int pos, int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out,
-                                int ld_seq, float* probs_out, void* stream) {
-  GPT2MI_REQUIRE(B >= 1 && V >= 1, "sample: B=%d and V=%d must be positive", B, V);
-  GPT2MI_REQUIRE(V <= GPT2MI_SAMPLE_MAX_V, "sample: V=%d above the kernel's row capacity %d", V, GPT2MI_SAMPLE_MAX_V);
-  GPT2MI_REQUIRE(ldl >= V, "sample: ldl=%d < V=%d", ldl, V);
-  GPT2MI_REQUIRE(temperature >= 0.f, "sample: temperature=%g must be >= 0", (double)temperature);  // (NaN fails too)
-  GPT2MI_REQUIRE(top_p > 0.f, "sample: top_p=%g must be > 0 (>= 1: off)", (double)top_p);
-  GPT2MI_REQUIRE(pos >= 0, "sample: pos=%d is negative", pos);
-  GPT2MI_REQUIRE(eos >= -1 && eos < V, "sample: eos=%lld not in [-1, V=%d)", (long long)eos, V);
-  GPT2MI_REQUIRE(!seq_out || ld_seq > pos, "sample: ld_seq=%d does not reach pos=%d", ld_seq, pos);
-  GPT2MI_REQUIRE(logits && tok_out, "sample: logits and tok_out must not be NULL");
+// gpt2mi_sample_ragged, and gpt2mi_sample with every pos[b] equal and no row_id; `what` is the entry's name in messages.
+int sample_rows(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
+                uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done, int64_t* tok_out,
+                int64_t* seq_out, int ld_seq, float* probs_out, void* stream) {
+  GPT2MI_REQUIRE(B >= 1 && B <= GPT2MI_DECODE_MAX_B && V >= 1, "%s: B=%d not in [1, %d] or V=%d not positive", what, B,
+                 GPT2MI_DECODE_MAX_B, V);
+  GPT2MI_REQUIRE(V <= GPT2MI_SAMPLE_MAX_V, "%s: V=%d above the kernel's row capacity %d", what, V, GPT2MI_SAMPLE_MAX_V);
+  GPT2MI_REQUIRE(ldl >= V, "%s: ldl=%d < V=%d", what, ldl, V);
+  GPT2MI_REQUIRE(temperature >= 0.f, "%s: temperature=%g must be >= 0", what, (double)temperature);  // (NaN fails too)
+  GPT2MI_REQUIRE(top_p > 0.f, "%s: top_p=%g must be > 0 (>= 1: off)", what, (double)top_p);
+  GPT2MI_REQUIRE(pos != nullptr, "%s: the position array (host, B ints) is NULL", what);
+  GPT2MI_REQUIRE(eos >= -1 && eos < V, "%s: eos=%lld not in [-1, V=%d)", what, (long long)eos, V);
+  RowKeys keys = {};
+  for (int b = 0; b < B; ++b) {
+    GPT2MI_REQUIRE(pos[b] >= 0, "%s: pos[%d]=%d is negative", what, b, pos[b]);
+    GPT2MI_REQUIRE(!seq_out || ld_seq > pos[b], "%s: ld_seq=%d does not reach pos[%d]=%d", what, ld_seq, b, pos[b]);
+    keys.pos[b] = pos[b];
+    keys.row_id[b] = row_id ? row_id[b] : (uint32_t)b;
+  }
+  GPT2MI_REQUIRE(logits && tok_out, "%s: logits and tok_out must not be NULL", what);
   if (temperature == 0.f)
-    sample_kernel<true><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(logits, ldl, V, temperature, top_k, top_p, seed, pos,
+    sample_kernel<true><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(logits, ldl, V, temperature, top_k, top_p, seed, keys,
                                                                    eos, done, tok_out, seq_out, ld_seq, probs_out);
   else
-    sample_kernel<false><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(logits, ldl, V, temperature, top_k, top_p, seed, pos,
-                                                                    eos, done, tok_out, seq_out, ld_seq, probs_out);
-  return gpt2mi::check_launch("sample");
+    sample_kernel<false><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(logits, ldl, V, temperature, top_k, top_p, seed,
+                                                                    keys, eos, done, tok_out, seq_out, ld_seq, probs_out);
+  return gpt2mi::check_launch(what);
 }
+
+}  // namespace
 
 GPT2MI_EXPORT int gpt2mi_sample_ragged(const float* logits, int ldl, int B, int V, float temperature, int top_k,
                                        float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos,
                                        uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out,
                                        void* stream) {
-  GPT2MI_REQUIRE(B >= 1 && B <= GPT2MI_DECODE_MAX_B && V >= 1, "sample_ragged: B=%d not in [1, %d] or V=%d not positive",
-                 B, GPT2MI_DECODE_MAX_B, V);
-  GPT2MI_REQUIRE(V <= GPT2MI_SAMPLE_MAX_V, "sample_ragged: V=%d above the kernel's row capacity %d", V,
-                 GPT2MI_SAMPLE_MAX_V);
-  GPT2MI_REQUIRE(ldl >= V, "sample_ragged: ldl=%d < V=%d", ldl, V);
-  GPT2MI_REQUIRE(temperature >= 0.f, "sample_ragged: temperature=%g must be >= 0", (double)temperature);  // (NaN too)
-  GPT2MI_REQUIRE(top_p > 0.f, "sample_ragged: top_p=%g must be > 0 (>= 1: off)", (double)top_p);
-  GPT2MI_REQUIRE(pos != nullptr, "sample_ragged: the position array (host, B ints) is NULL");
-  GPT2MI_REQUIRE(eos >= -1 && eos < V, "sample_ragged: eos=%lld not in [-1, V=%d)", (long long)eos, V);
-  RowKeys keys = {};
-  for (int b = 0; b < B; ++b) {
-    GPT2MI_REQUIRE(pos[b] >= 0, "sample_ragged: pos[%d]=%d is negative", b, pos[b]);
-    GPT2MI_REQUIRE(!seq_out || ld_seq > pos[b], "sample_ragged: ld_seq=%d does not reach pos[%d]=%d", ld_seq, b, pos[b]);
-    keys.pos[b] = pos[b];
-    keys.row_id[b] = row_id ? row_id[b] : (uint32_t)b;
-  }
-  GPT2MI_REQUIRE(logits && tok_out, "sample_ragged: logits and tok_out must not be NULL");
-  if (temperature == 0.f)
-    sample_ragged_kernel<true><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(
-        logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out);
-  else
-    sample_ragged_kernel<false><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(
-        logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out);
-  return gpt2mi::check_launch("sample_ragged");
+  return sample_rows("sample_ragged", logits, ldl, B, V, temperature, top_k, top_p, seed, pos, row_id, eos, done,
+                     tok_out, seq_out, ld_seq, probs_out, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_sample(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
+                                uint64_t seed, int pos, int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out,
+                                int ld_seq, float* probs_out, void* stream) {
+  GPT2MI_REQUIRE(pos >= 0, "sample: pos=%d is negative", pos);
+  GPT2MI_REQUIRE(!seq_out || ld_seq > pos, "sample: ld_seq=%d does not reach pos=%d", ld_seq, pos);
+  int same[GPT2MI_DECODE_MAX_B];  // every row at pos (all entries: B is checked where they are read)
+  for (int& p : same) p = pos;
+  return sample_rows("sample", logits, ldl, B, V, temperature, top_k, top_p, seed, same, nullptr, eos, done, tok_out,
+                     seq_out, ld_seq, probs_out, stream);
 }

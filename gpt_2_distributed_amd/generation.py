@@ -3,14 +3,16 @@
 The reference (model.py, train_gpt2_distributed.py) trains and evaluates only; continuing a prompt with it means
 calling ``model(idx)`` on the whole growing sequence for every new token. Here a prompt is run once through the
 engine's trunk forward (``DecodeSession.prefill``), its keys and values are copied into the cache, and every further
-token is one call of ``gpt2mi_decode_step`` (csrc/decode.hip): weight-streaming skinny GEMMs and single-query attention
-over the cache, about 10 launches per layer issued from C. The next token is drawn either on the host side in PyTorch
-(``sample_next``, from a ``torch.Generator``) or, with a ``seed``, by ``gpt2mi_sample`` on the device (csrc/sample.hip;
-``sample_reference`` and ``uniform_at`` state what it computes), in which case the whole loop is one C call.
+token is one call of ``gpt2mi_decode_step_ragged`` (csrc/decode.hip): weight-streaming skinny GEMMs and single-query
+attention over the cache, about 10 launches per layer issued from C. The next token is drawn either on the host side in
+PyTorch (``sample_next``, from a ``torch.Generator``) or, with a ``seed``, by ``gpt2mi_sample_ragged`` on the device
+(csrc/sample.hip; ``sample_reference`` and ``uniform_at`` state what it computes), in which case the whole loop is one
+C call (``gpt2mi_decode_generate_ragged``).
 
-The sequences of a session need not be equally long: ``DecodeSession.lens`` holds one position per row, ``prefill`` takes
-right-padded prompts with their lengths, ``refill`` replaces one row while the others go on, and ``generate_many`` serves
-any number of prompts through one session that way (the ``gpt2mi_*_ragged`` entries; DESIGN.md "Ragged batches").
+Every row of a session has its own position: ``DecodeSession.lens`` holds one per row, ``prefill`` takes right-padded
+prompts with their lengths, ``refill`` replaces one row while the others go on, and ``generate_many`` serves any number
+of prompts through one session that way. Equally long sequences are the case where the positions agree: there is one
+set of kernels and one code path (the ``gpt2mi_*_ragged`` entries; DESIGN.md "Ragged batches").
 
 Numerics are the autocast path's whatever the autocast state: bf16 GEMM operands from the engine's weight shadow, fp32
 accumulation, fp32 residual stream / LayerNorm / softmax, dropout off (p = 0 whatever ``model.training`` is, and
@@ -173,9 +175,9 @@ class DecodeSession:
     Cache: per layer ``kcache`` and ``vcache``, bf16 ``[B][H][Tcap][64]`` (a (b, h) stream is contiguous 128-byte rows).
     ``prefill(idx)`` starts the sequences from a prompt, ``step(tokens)`` appends one token to each; both return the fp32
     logits ``[B, V]`` of the newest position. ``lens`` (a host list of B ints) is the number of cached tokens of each
-    row; ``pos`` is their common value (None while the rows disagree). While they agree every call goes through the
-    scalar C entries (one position for the batch); once they disagree (``prefill`` with ``lens``, ``refill``) through
-    their ``_ragged`` twins, which give each row the bits the scalar entry gives it at that row's position."""
+    row; ``pos`` is their common value (None while the rows disagree: ``prefill`` with ``lens``, ``refill``). Every call
+    goes through the per-row C entries (``gpt2mi_*_ragged``) with ``lens``, whether the rows agree or not: a row's bits
+    depend on its own position only."""
 
     def __init__(self, model, batch_size: int, max_len: Optional[int] = None):
         eng = _check_model(model)
@@ -356,10 +358,7 @@ class DecodeSession:
             self._drawn = False
 
     def _step(self, tok: torch.Tensor) -> None:
-        if self.uniform:
-            K.decode_step(self._plan, tok, self.lens[0])
-        else:
-            K.decode_step_ragged(self._plan, tok, self.lens)
+        K.decode_step_ragged(self._plan, tok, self.lens)
         self.lens = [n + 1 for n in self.lens]
 
     @torch.no_grad()
@@ -379,7 +378,7 @@ class DecodeSession:
         self._drawn = False
         return self.logits[:, :self.cfg.vocab_size].clone()
 
-    # ---- device-side sampling (gpt2mi_sample, gpt2mi_decode_generate): nothing below returns to the host ----
+    # ---- device-side sampling (gpt2mi_sample_ragged, gpt2mi_decode_generate_ragged): nothing below returns to the host ----
     def _check_sampler(self, temperature, top_p, seed):
         if min(self.lens) == 0:
             raise RuntimeError("sampling before prefill: there are no logits")
@@ -404,23 +403,20 @@ class DecodeSession:
         if self._drawn:
             raise RuntimeError("the logits are those generate() drew its last token from: step() that token first")
         out = torch.empty(self.B, dtype=torch.int64, device=self.logits.device)
-        if self.uniform and row_id is None:
-            K.sample(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens[0], out)
-        else:
-            K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, out,
-                            row_id=_check_row_id(row_id, self.B))
+        K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, out,
+                        row_id=_check_row_id(row_id, self.B))
         return out
 
     @torch.no_grad()
     def generate(self, n: int, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  seed: int = 0, eos_token_id: Optional[int] = None, seq: Optional[torch.Tensor] = None,
                  done: Optional[torch.Tensor] = None, row_id: Optional[Sequence[int]] = None) -> torch.Tensor:
-        """Draw the tokens of positions ``pos .. pos + n - 1`` in one C call (gpt2mi_decode_generate: sample, step,
-        sample, ... on the stream, no Python and no synchronisation in between). The tokens go to column ``pos + i`` of
-        ``seq`` (int64 [B, >= pos + n], optional); with ``eos_token_id``, ``done`` (uint8 [B]) marks finished rows, which
-        keep emitting eos. Returns the newest tokens [B] (a buffer the next call overwrites). The last token drawn is
-        not stepped until the next ``generate`` (which does it first), ``flush`` or ``step``. With rows at different
-        positions ``pos`` reads ``lens[b]`` throughout (gpt2mi_decode_generate_ragged); ``row_id`` as for ``sample``."""
+        """Draw row b's tokens of positions ``lens[b] .. lens[b] + n - 1`` in one C call (gpt2mi_decode_generate_ragged:
+        sample, step, sample, ... on the stream, no Python and no synchronisation in between). The tokens go to column
+        ``lens[b] + i`` of ``seq`` (int64 [B, >= max(lens) + n], optional); with ``eos_token_id``, ``done`` (uint8 [B])
+        marks finished rows, which keep emitting eos. Returns the newest tokens [B] (a buffer the next call overwrites).
+        The last token drawn is not stepped until the next ``generate`` (which does it first), ``flush`` or ``step``.
+        ``row_id`` as for ``sample``."""
         self._check_sampler(temperature, top_p, seed)
         n = int(n)
         if n < 1:
@@ -434,12 +430,8 @@ class DecodeSession:
             raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
         self.flush()  # the token the previous call ended on
         done = done if eos_token_id is not None else None
-        if self.uniform and row_id is None:
-            K.decode_generate(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens[0], n,
-                              self._tok, eos=eos_token_id, seq=seq, done=done)
-        else:
-            K.decode_generate_ragged(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
-                                     self._tok, row_id=row_id, eos=eos_token_id, seq=seq, done=done)
+        K.decode_generate_ragged(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
+                                 self._tok, row_id=row_id, eos=eos_token_id, seq=seq, done=done)
         self.lens = [m + n - 1 for m in self.lens]
         self._drawn = True
         return self._tok
@@ -489,40 +481,21 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
         raise ValueError("seed selects the device sampler, which draws from (seed, row, position): it takes no generator")
     _check_model(model)
     idx = idx.long()
-    if prompt_lens is not None:
-        return _generate_ragged(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id,
-                                pad)
-    if n == 0:
+    if prompt_lens is None and n == 0:
         return idx.clone()
-    sess = DecodeSession(model, B, P + n)
-    if seed is not None:
-        return _generate_on_device(sess, idx, n, temperature, top_k, top_p, seed, eos_token_id)
-    out = [idx]
-    done = torch.zeros(B, dtype=torch.bool, device=idx.device)
-    logits = sess.prefill(idx)
-    for i in range(n):
-        nxt = sample_next(logits, temperature, top_k, generator, top_p)
-        if eos_token_id is not None:
-            nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)  # a finished row keeps emitting eos
-            done = done | (nxt == eos_token_id)
-        out.append(nxt[:, None])
-        if eos_token_id is not None and bool(done.all()):
-            break
-        if i + 1 < n:
-            logits = sess.step(nxt)
-    return torch.cat(out, dim=1)
+    return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad)
 
 
-def _generate_ragged(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad):
-    """``generate`` with ``prompt_lens``: [B, Pmax + m], row b = its prompt, its m new tokens from column lens[b] on, then
-    ``pad``. m = n, or with eos the number of tokens by which every row has emitted it (the cut of the equal-length
-    paths). Host sampler: new tokens are collected per step; device sampler: gpt2mi_sample_ragged writes row b's token
-    of step i to column lens[b] + i of the buffer that holds the prompts."""
+def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad):
+    """The token loop of ``generate``: [B, P + m], row b = its prompt, its m new tokens from column lens[b] on, then
+    ``pad`` (``lens`` None: every row holds P tokens and nothing is padded). m = n, or with eos the number of tokens by
+    which every row has emitted it. Host sampler: new tokens are collected per step and scattered into the buffer that
+    holds the prompts; device sampler: gpt2mi_sample_ragged writes row b's token of step i to column lens[b] + i of it."""
     B, P = idx.shape
     dev = idx.device
     if eos_token_id is not None and seed is not None and not 0 <= eos_token_id < model.config.vocab_size:
         raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={model.config.vocab_size})")
-    lens_t = torch.tensor(lens, device=dev)
+    lens_t = torch.tensor([P] * B if lens is None else lens, device=dev)
     cols = torch.arange(P + n, device=dev)[None]
     seq = torch.full((B, P + n), pad, dtype=torch.int64, device=dev)
     seq[:, :P] = torch.where(cols[:, :P] < lens_t[:, None], idx, seq[:, :P])  # the callers' padding may be anything
@@ -530,28 +503,20 @@ def _generate_ragged(model, idx, lens, n, temperature, top_k, top_p, generator, 
         return seq
     idx = torch.where(cols[:, :P] < lens_t[:, None], idx, torch.zeros_like(idx))  # (a valid token id as padding)
     sess = DecodeSession(model, B, P + n)
+    logits = sess.prefill(idx, lens)
     if seed is not None:
-        sess.prefill(idx, lens)
+        done = None if eos_token_id is None else torch.zeros(B, dtype=torch.uint8, device=dev)
+        made = _device_loop(sess, n, temperature, top_k, top_p, seed, eos_token_id, seq, done)
         if eos_token_id is None:
-            sess.generate(n, temperature, top_k, top_p, seed, seq=seq)
             return seq
-        done = torch.zeros(B, dtype=torch.uint8, device=dev)
-        made = 0
-        while made < n:
-            m = min(EOS_CHUNK, n - made)
-            sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done)
-            made += m
-            if bool(done.all()):
-                break
         new = seq.gather(1, lens_t[:, None] + torch.arange(made, device=dev)[None])
     else:
         toks = []
         done = torch.zeros(B, dtype=torch.bool, device=dev)
-        logits = sess.prefill(idx, lens)
         for i in range(n):
             nxt = sample_next(logits, temperature, top_k, generator, top_p)
             if eos_token_id is not None:
-                nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)
+                nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)  # a finished row keeps emitting eos
                 done = done | (nxt == eos_token_id)
             toks.append(nxt)
             if eos_token_id is not None and bool(done.all()):
@@ -569,33 +534,18 @@ def _generate_ragged(model, idx, lens, n, temperature, top_k, top_p, generator, 
     return torch.where(keep, seq[:, :P + made], torch.full_like(seq[:, :P + made], pad))
 
 
-def _generate_on_device(sess: DecodeSession, idx, n, temperature, top_k, top_p, seed, eos_token_id):
-    """The loop of ``generate`` with the sampler on the device: one [B, P + n] buffer holds the prompt and receives the
-    tokens. Without eos nothing is read back; with eos the loop is issued EOS_CHUNK tokens at a time and the done flags
-    are read once per chunk, then the result is cut after the column by which every row has emitted eos (the shape and
-    padding of the host loop)."""
-    B, P = idx.shape
-    if eos_token_id is not None and not 0 <= eos_token_id < sess.cfg.vocab_size:
-        raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={sess.cfg.vocab_size})")
-    seq = torch.empty(B, P + n, dtype=torch.int64, device=idx.device)
-    seq[:, :P] = idx
-    sess.prefill(idx)
-    if eos_token_id is None:
-        sess.generate(n, temperature, top_k, top_p, seed, seq=seq)
-        return seq
-    done = torch.zeros(B, dtype=torch.uint8, device=idx.device)
+def _device_loop(sess: DecodeSession, n, temperature, top_k, top_p, seed, eos_token_id, seq, done) -> int:
+    """``n`` tokens per row with the sampler on the device, into ``seq``; the number issued. Without eos one C call and
+    nothing read back; with eos EOS_CHUNK tokens at a time, the done flags read once per chunk, until every row has
+    emitted it (the caller cuts the result after the column by which they all have)."""
     made = 0
     while made < n:
-        m = min(EOS_CHUNK, n - made)
+        m = n - made if eos_token_id is None else min(EOS_CHUNK, n - made)
         sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done)
         made += m
-        if bool(done.all()):
+        if eos_token_id is not None and bool(done.all()):
             break
-    new = seq[:, P:P + made]
-    finished = ((new == eos_token_id).cumsum(1) > 0).all(0)  # columns by which every row has emitted eos
-    if bool(finished.any()):
-        made = int(finished.int().argmax()) + 1
-    return seq[:, :P + made].clone() if made < n else seq
+    return made
 
 
 @torch.no_grad()

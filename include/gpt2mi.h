@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 19
+#define GPT2MI_ABI_VERSION 20
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -243,7 +243,11 @@ int gpt2mi_zero_ranges(float* base, const int64_t* ranges, int n, void* stream);
 /* ---- v14: autoregressive decode (csrc/decode.hip). The reference has no generation loop; these are the nanoGPT /
  * llm.c style `generate` of the model.py forward (model.py:335-351) with a per-layer key/value cache, one token per
  * sequence and step. bf16 operands, fp32 accumulation, head_dim 64, no dropout, no atomics: every reduction runs in
- * a fixed order, so outputs are bitwise reproducible. ---- */
+ * a fixed order, so outputs are bitwise reproducible.
+ * v20: the entries of this block that take one position `pos` for the whole batch (gpt2mi_attn_decode,
+ * gpt2mi_embed_decode, gpt2mi_decode_step) are forwarders: they check pos, then call the per-row implementation of the
+ * v19 block below with pos[b] = pos for every row. So they take 1 <= B <= GPT2MI_DECODE_MAX_B like it (before v20
+ * gpt2mi_attn_decode took any B * H <= 65535 and gpt2mi_embed_decode any B) and refuse a larger B with 22. ---- */
 /* Skinny forward GEMM (nn.Linear at M = batch rows): C[m][n] = epi(sum_k A[m][k] W[n][k] + bias[n]), A bf16 [M][K]
  * (row stride lda), W bf16 [N][K] (row stride ldw: the forward layout of the weight shadow), 1 <= M <= 64, N and K
  * multiples of 64 (N need not be a multiple of 256). epilogue: 0 BF16 (+bias), 1 F32 (+bias), 2 RESID: C fp32 =
@@ -265,11 +269,13 @@ int gpt2mi_kv_store(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, int
  * token; its k and v are written to position pos of the caches, and out[b, h*64..] = softmax(q.K[0..pos]^T / 8)
  * V[0..pos] (bf16 [B, C]). Keys are split in ranges of 32 across workgroups; the partial (max, sum, acc) go through
  * `workspace` (>= gpt2mi_attn_decode_workspace(B, H, Tcap) floats) and are combined in range order. Cache positions
- * > pos are neither read nor written. */
+ * > pos are neither read nor written. A forwarder (v20): gpt2mi_attn_decode_ragged with every pos[b] = pos, after
+ * "pos=%d not in [0, Tcap)"; B <= GPT2MI_DECODE_MAX_B. */
 int gpt2mi_attn_decode(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out, float* workspace,
                        size_t workspace_floats, int B, int H, int head_dim, int Tcap, int pos, void* stream);
 size_t gpt2mi_attn_decode_workspace(int B, int H, int Tcap);
-/* K1 for one new token per sequence: x[b,:] = wte[tok[b],:] + wpe[pos,:] (fp32, no dropout). */
+/* K1 for one new token per sequence: x[b,:] = wte[tok[b],:] + wpe[pos,:] (fp32, no dropout). A forwarder (v20):
+ * gpt2mi_embed_decode_ragged with every pos[b] = pos >= 0; B <= GPT2MI_DECODE_MAX_B. */
 int gpt2mi_embed_decode(const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C, int pos,
                         void* stream);
 
@@ -297,12 +303,15 @@ typedef struct gpt2mi_decode_plan {
   float* logits;                                          /* fp32 [B][Vp] */
 } gpt2mi_decode_plan;
 /* embed -> per layer (LN1, qkv, attention at pos, proj + resid, LN2, fc1 + GELU, fc2 + resid) -> ln_f -> lm_head into
- * plan->logits, for the B tokens `tok` (device int64 [B]) at position pos (model.py:295-351 at one position). */
+ * plan->logits, for the B tokens `tok` (device int64 [B]) at position pos (model.py:295-351 at one position). A
+ * forwarder (v20): gpt2mi_decode_step_ragged with every pos[b] = pos in [0, plan->Tcap). */
 int gpt2mi_decode_step(const gpt2mi_decode_plan* plan, const int64_t* tok, int pos, void* stream);
 
 /* ---- v17: device-side sampling (csrc/sample.hip) and the token loop around it. The executable specification of the
  * rule is gpt_2_distributed_amd/generation.py sample_reference + uniform_at (nanoGPT's temperature / top-k rule, as
- * generation.py sample_next, plus nucleus filtering and a counter-based draw). ---- */
+ * generation.py sample_next, plus nucleus filtering and a counter-based draw).
+ * v20: gpt2mi_sample and gpt2mi_decode_generate are forwarders to their v19 per-row forms (one kernel, one loop), so
+ * gpt2mi_sample takes 1 <= B <= GPT2MI_DECODE_MAX_B (before v20: any B) and refuses a larger B with 22. ---- */
 /* Largest vocabulary gpt2mi_sample takes: one 1024-thread workgroup holds a row in registers, 50 logits per thread. */
 #define GPT2MI_SAMPLE_MAX_V 51200
 /* One token per row b < B from logits fp32 [B][ldl] (columns V..ldl-1 are padding and are not read). One launch, one
@@ -320,8 +329,10 @@ int gpt2mi_decode_step(const gpt2mi_decode_plan* plan, const int64_t* tok, int p
  *  Writes tok_out[b], seq_out[b*ld_seq + pos] (seq_out may be NULL) and, for tests, probs_out [B][V] (may be NULL): the
  *   kept distribution, p_i / Z, zero where filtered.
  * No float atomics; every float reduction and scan runs in a fixed order: two calls give the same bits.
- * Refused with 22 before any launch: B < 1, V < 1 or > GPT2MI_SAMPLE_MAX_V, ldl < V, temperature < 0 or NaN,
- * top_p <= 0 or NaN, pos < 0, eos outside [-1, V), ld_seq <= pos with seq_out, NULL logits or tok_out. */
+ * Refused with 22 before any launch: B outside [1, GPT2MI_DECODE_MAX_B], V < 1 or > GPT2MI_SAMPLE_MAX_V, ldl < V,
+ * temperature < 0 or NaN, top_p <= 0 or NaN, pos < 0, eos outside [-1, V), ld_seq <= pos with seq_out, NULL logits or
+ * tok_out. A forwarder (v20): gpt2mi_sample_ragged with every pos[b] = pos and row_id = NULL (the draw key of row b is
+ * b). */
 int gpt2mi_sample(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p, uint64_t seed,
                   int pos, int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out,
                   void* stream);
@@ -329,7 +340,9 @@ int gpt2mi_sample(const float* logits, int ldl, int B, int V, float temperature,
  * at position pos0 + i into tok (device int64 [B]) and seq[:, pos0 + i] (seq may be NULL), then, if i + 1 < n,
  * gpt2mi_decode_step(plan, tok, pos0 + i). On entry plan->logits holds the logits for position pos0 (the prefill's or
  * the previous step's); on return the token of position pos0 + n - 1 is in tok and has not been stepped. A host loop of
- * launches on `stream`: nothing is synchronised or read back. n = 0 does nothing. */
+ * launches on `stream`: nothing is synchronised or read back. n = 0 launches nothing. pos0 >= 1 (after a prefill) and
+ * pos0 + n <= plan->Tcap; pos0 < plan->Tcap also when n = 0. A forwarder (v20): gpt2mi_decode_generate_ragged with every
+ * pos0[b] = pos0 and row_id = NULL. */
 int gpt2mi_decode_generate(const gpt2mi_decode_plan* plan, int V, float temperature, int top_k, float top_p,
                            uint64_t seed, int64_t eos, int pos0, int n, int64_t* tok, int64_t* seq, int ld_seq,
                            uint8_t* done, void* stream);
@@ -355,21 +368,23 @@ size_t gpt2mi_lm_loss_workspace(int M, int V); /* bytes; 0 for M < 1 or V < 1 */
 
 /* ---- v19: ragged decode (csrc/decode.hip, csrc/sample.hip). The entries above put every sequence of a batch at one
  * position; these take one position per row, so prompts of unequal length share a batch and a finished row can be
- * replaced while the others go on (generation.py DecodeSession.refill, generate_many).
+ * replaced while the others go on (generation.py DecodeSession.refill, generate_many). Since v20 these are the one
+ * implementation of each operation, with one set of kernels: the scalar-position entries above forward to them, and
+ * the package calls only these.
  * A position array is `const int* pos`: a HOST array of B ints, 1 <= B <= GPT2MI_DECODE_MAX_B. The entry checks every
  * element before any launch and passes the array to its kernels by value, as a kernel argument: there is no device-side
  * position array, so no position reaches a kernel unchecked, nothing is copied to the device and the caller's array may
  * be reused as soon as the call returns.
- * Refused with 22 before any launch, beside what the scalar twin refuses: B outside [1, GPT2MI_DECODE_MAX_B], a NULL
- * position array, a pos[b] outside the range stated at the entry, ld_seq <= pos[b] with a seq_out. ---- */
+ * Refused with 22 before any launch, beside the checks stated at the scalar entry: B outside [1, GPT2MI_DECODE_MAX_B], a
+ * NULL position array, a pos[b] outside the range stated at the entry, ld_seq <= pos[b] with a seq_out. ---- */
 #define GPT2MI_DECODE_MAX_B 64
 /* gpt2mi_attn_decode with row b at pos[b] in [0, Tcap) (model.py:124-155 for the newest position of each row): row b's
  * k and v are written to position pos[b] of its streams and out[b] attends over positions 0..pos[b]. The grid covers
  * max_b pos[b] / 32 + 1 key ranges; a wave whose range starts beyond its row's position exits before any load or
  * store, and the combine merges pos[b] / 32 + 1 ranges of row b in range order. Workspace: size and layout of
  * gpt2mi_attn_decode_workspace(B, H, Tcap). Per row: cache positions != pos[b] are not written, positions > pos[b] are
- * not read; no atomics. The bits of out[b] and of row b's cache are those gpt2mi_attn_decode gives that row at
- * pos = pos[b] (one per-range body serves both kernels). */
+ * not read; no atomics. The bits of out[b] and of row b's cache depend on row b's inputs and pos[b] only: they are
+ * those gpt2mi_attn_decode gives that row at pos = pos[b] (the same kernels). */
 int gpt2mi_attn_decode_ragged(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out, float* workspace,
                               size_t workspace_floats, int B, int H, int head_dim, int Tcap, const int* pos,
                               void* stream);
@@ -380,12 +395,12 @@ int gpt2mi_embed_decode_ragged(const int64_t* tok, const float* wte, const float
 /* gpt2mi_sample with a position and a draw key per row: row b draws u from (seed, row_id[b], pos[b]) in place of
  * (seed, b, pos) and writes seq_out[b*ld_seq + pos[b]]; pos[b] >= 0. row_id is a HOST array of B values and may be NULL
  * (row_id[b] = b): it lets a sequence keep its draw stream whichever row of the batch it occupies. Everything else
- * (filtering, scan, draw, eos / done indexed by b, tok_out[b], probs_out) is gpt2mi_sample's code. */
+ * (filtering, scan, draw, eos / done indexed by b, tok_out[b], probs_out) is as stated at gpt2mi_sample. */
 int gpt2mi_sample_ragged(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
                          uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
                          int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, void* stream);
-/* gpt2mi_decode_step with row b at pos[b] in [0, plan->Tcap) (model.py:295-351 at one position per row): the same
- * sequence with gpt2mi_embed_decode_ragged and gpt2mi_attn_decode_ragged; LayerNorm and the skinny GEMMs are unchanged. */
+/* gpt2mi_decode_step with row b at pos[b] in [0, plan->Tcap) (model.py:295-351 at one position per row): the sequence
+ * stated there with the embedding and the attention of this block; LayerNorm and the skinny GEMMs do not see positions. */
 int gpt2mi_decode_step_ragged(const gpt2mi_decode_plan* plan, const int64_t* tok, const int* pos, void* stream);
 /* gpt2mi_decode_generate with row b starting at pos0[b] >= 1: for i < n, gpt2mi_sample_ragged at pos0[b] + i (draw key
  * row_id[b], may be NULL), then, if i + 1 < n, gpt2mi_decode_step_ragged at pos0[b] + i. max_b pos0[b] + n <= Tcap (and

@@ -134,6 +134,32 @@ def test_step_raises_when_the_cache_is_full_and_reset_rewinds(tiny):
         model.decoder(65)
 
 
+def test_scalar_step_and_generate_entries_are_the_per_row_ones_at_equal_positions(tiny):
+    """gpt2mi_decode_step / gpt2mi_decode_generate have no caller in the package (a session always passes lens): called
+    here directly against their _ragged forms on a second session, across the 32-key range edge. Bitwise."""
+    from gpt_2_distributed_amd import _lib as K
+    model, S, _, _ = tiny
+    B, V = 3, TINY["vocab_size"]
+    a, b = model.decoder(B, max_len=70), model.decoder(B, max_len=70)
+    assert torch.equal(a.prefill(S[:, :31]), b.prefill(S[:, :31]))
+
+    def same_state(n):  # the logits and the n cached positions (the caches are torch.empty beyond them)
+        return (torch.equal(a.logits, b.logits) and torch.equal(a.kcache[:, :, :, :n], b.kcache[:, :, :, :n])
+                and torch.equal(a.vcache[:, :, :, :n], b.vcache[:, :, :, :n]))
+    for pos in (31, 32, 33):
+        tok = S[:, pos].contiguous()
+        K.decode_step(a._plan, tok, pos)
+        K.decode_step_ragged(b._plan, tok, [pos] * B)
+        assert same_state(pos + 1), pos
+    assert not torch.equal(a.kcache[:, :, :, 33], a.kcache[:, :, :, 30])  # (the steps did write their positions)
+    tok_a, tok_b = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
+    seq_a, seq_b = (torch.zeros(B, 70, dtype=torch.int64, device=dev) for _ in range(2))
+    K.decode_generate(a._plan, V, 0.8, 8, None, 5, 34, 4, tok_a, seq=seq_a)
+    K.decode_generate_ragged(b._plan, V, 0.8, 8, None, 5, [34] * B, 4, tok_b, row_id=None, seq=seq_b)
+    assert torch.equal(tok_a, tok_b) and torch.equal(seq_a, seq_b) and same_state(37)  # (token 37 is not stepped)
+    assert bool((seq_a[:, 34:38] < V).all()) and torch.equal(seq_a[:, 37], tok_a) and not bool(seq_a[:, 38:].any())
+
+
 # ---- generate --------------------------------------------------------------------------------------------------
 def test_greedy_generate_emits_an_argmax_of_the_full_forward(tiny):
     """Every emitted token's logit in the existing full forward of the sequence so far is within 2 E_full |row|_inf of

@@ -101,6 +101,27 @@ def test_sample_ragged_refuses_bad_arguments(lib):
     refused(lib, call(pos=ints(3, 4), B=2, row_id=(ctypes.c_uint32 * 2)(7, 9)), b"NULL")
 
 
+@needs_lib
+def test_scalar_entries_forward_and_take_at_most_64_rows(lib):
+    """v20: gpt2mi_attn_decode and gpt2mi_sample are forwarders to the per-row implementation, so B stops at
+    GPT2MI_DECODE_MAX_B (before: B * H <= 65535, any B); B = 64 still reaches the pointer check."""
+    from gpt_2_distributed_amd import _lib
+    assert lib.gpt2mi_abi_version() == _lib.ABI_VERSION >= 20
+    H, Tcap = 4, 256
+
+    def attn(B):
+        return lib.gpt2mi_attn_decode(None, None, None, None, None, lib.gpt2mi_attn_decode_workspace(B, H, Tcap), B, H,
+                                      64, Tcap, 5, None)
+
+    def sample(B):
+        return lib.gpt2mi_sample(None, 50432, B, 50257, 1.0, 0, 1.0, 0, 3, -1, None, None, None, 0, None, None)
+    for call in (attn, sample):
+        refused(lib, call(65), b"B=65")
+        refused(lib, call(1000), b"B=1000")
+        refused(lib, call(64), b"NULL")
+    refused(lib, lib.gpt2mi_embed_decode(None, None, None, None, 65, 128, 0, None), b"B=65")
+
+
 def _plan(B=2, Tcap=64):
     from gpt_2_distributed_amd import _lib
     plan = _lib.DecodePlan()
@@ -306,12 +327,15 @@ def test_serving_loop_at_the_end_of_the_cache():
 # ---- register budget ---------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")
 def test_ragged_kernels_have_no_scratch_and_no_spills():
-    """The position arrays arrive as kernel arguments and are indexed by blockIdx: a scalar load, not a private array."""
+    """The position arrays arrive as kernel arguments and are indexed by blockIdx: a scalar load, not a private array.
+    The per-row kernels are the only ones (the scalar entries forward to them), under the plain names."""
+    subs = ("attn_decode_kernel", "attn_combine_kernel", "embed_decode_kernel", "sample_kernel")
     found = {}
     for src in ("decode.hip", "sample.hip"):
-        found.update({k: v for k, v in _resources(src).items() if "ragged" in k})
-    for sub in ("attn_decode_ragged_kernel", "attn_combine_ragged_kernel", "embed_decode_ragged_kernel",
-                "sample_ragged_kernel"):
+        res = _resources(src)
+        assert not any("ragged" in k for k in res), sorted(res)
+        found.update({k: v for k, v in res.items() if any(sub in k for sub in subs)})
+    for sub in subs:
         assert any(sub in k for k in found), f"{sub} not found"
     assert len(found) == 5, sorted(found)  # (the sampler: greedy and sampling)
     for k, v in found.items():

@@ -43,6 +43,8 @@ def main():
     impls = [int(v) for v in os.environ.get("LIB_AB_IMPLS", "").split(",") if v]
     for lib, impl in zip(libs, impls):
         lib.sched = impl
+    if os.environ.get("LIB_AB_OP") == "decode":
+        return decode_mode(libs, torch.cuda.current_stream().cuda_stream)
     Mt, C, Vp = 65536, 768, 50432
     shapes = {"lm_head wgrad": (Vp, C), "qkv wgrad": (3 * C, C), "fc1 wgrad": (4 * C, C), "fc2 wgrad": (C, 4 * C),
               "proj wgrad": (C, C)}
@@ -303,6 +305,162 @@ def xent_mode(libs, g, st):
     gb = 2 * 2 * M * ld / 1e9
     print("xent " + "  ".join(f"lib{i}: {sorted(t)[2] * 1e3:8.1f} us {gb / sorted(t)[2]:5.2f} TB/s"
                               for i, t in times.items()), flush=True)
+
+
+def decode_mode(libs, st):
+    """LIB_AB_OP=decode: the decode entries with a scalar position (gpt2mi_attn_decode, gpt2mi_embed_decode,
+    gpt2mi_sample greedy and at temperature 0.8 / top_k 50 / top_p 0.95, gpt2mi_decode_step on a random-weight plan) and
+    their _ragged forms at equal and at mixed positions. Small shapes (B = 4, H = 2, Tcap = 70, positions 0 / 31 / 32 / 69,
+    V = 509 and 50257) and GPT-2 124M's widths at B = 1, 8, 64 with pos = 575 in a 1024-position cache. Every library
+    gets clones of the same seeded inputs; every output (out, both caches, x, tok, seq, probs_out, logits) is compared
+    bitwise against the first library's; each row is timed in interleaved rounds (HIP events around back-to-back
+    launches, the median round). A row whose symbol a library lacks is skipped for that library, and says so."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    bf = torch.bfloat16
+    rn = lambda *s, scale=1.0, dt=torch.float32: (torch.randn(*s, device=dev, generator=g) * scale).to(dt)  # noqa: E731
+    ints = lambda v: (ctypes.c_int * len(v))(*v)  # noqa: E731
+    stats = {"rows": 0, "mismatches": 0, "skipped": 0}
+
+    def row(label, symbol, make, call, rounds=5, reps=20):
+        """make() -> a fresh state (dict of tensors, clones of the shared inputs); call(lib, state) -> rc."""
+        have = [i for i, lib in enumerate(libs) if hasattr(lib, symbol)]
+        for i in set(range(len(libs))) - set(have):
+            print(f"{label:44s} SKIPPED for lib{i}: no {symbol}", flush=True)
+            stats["skipped"] += 1
+        if not have or have[0] != 0:
+            return
+        states = {i: make() for i in have}
+        for i in have:
+            rc = call(libs[i], states[i])
+            assert rc == 0, (label, i, rc, libs[i].gpt2mi_last_error())
+        torch.cuda.synchronize()
+        bad = [f"lib{i} {k}" for i in have[1:] for k, v in states[i].items() if not torch.equal(v, states[0][k])]
+        stats["rows"] += 1
+        stats["mismatches"] += len(bad)
+        times = {i: [] for i in have}
+        for _ in range(rounds):
+            for i in have:
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _r in range(reps):
+                    call(libs[i], states[i])
+                e.record()
+                torch.cuda.synchronize()
+                times[i].append(s.elapsed_time(e) / reps)
+        verdict = "MISMATCH " + ", ".join(bad) if bad else f"bitwise equal ({', '.join(states[0])})"
+        print(f"{label:44s} " + "  ".join(f"lib{i}: {sorted(t)[rounds // 2] * 1e3:8.1f} us" for i, t in times.items()) +
+              f"  {verdict}", flush=True)
+
+    def variants(B, positions, mixed):
+        """(label suffix, scalar position or None, position list) of a case: scalar and _ragged at each equal position,
+        _ragged at the mixed ones."""
+        out = []
+        for p in positions:
+            out += [(f"pos={p}", p, [p] * B), (f"ragged pos={p}", None, [p] * B)]
+        return out + [("ragged mixed", None, mixed)]
+
+    def attn(B, H, Tcap, vs):
+        C = 64 * H
+        qkv, kc0, vc0 = rn(B, 3 * C, dt=bf), rn(B, H, Tcap, 64, dt=bf), rn(B, H, Tcap, 64, dt=bf)
+        ws_n = libs[0].gpt2mi_attn_decode_workspace(B, H, Tcap)
+        make = lambda: dict(out=torch.zeros(B, C, dtype=bf, device=dev), kcache=kc0.clone(), vcache=vc0.clone(),  # noqa
+                            ws=torch.zeros(ws_n, device=dev))
+        for name, p, plist in vs:
+            sym = "gpt2mi_attn_decode" + ("" if p is not None else "_ragged")
+            arg = p if p is not None else ints(plist)
+            row(f"attn_decode B={B} H={H} Tcap={Tcap} {name}", sym, make,
+                lambda lib, s, sym=sym, arg=arg: getattr(lib, sym)(
+                    qkv.data_ptr(), s["kcache"].data_ptr(), s["vcache"].data_ptr(), s["out"].data_ptr(),
+                    s["ws"].data_ptr(), ws_n, B, H, 64, Tcap, arg, st))
+
+    def embed(B, C, V, Tcap, vs):
+        tok = torch.randint(0, V, (B,), device=dev, generator=g)
+        wte, wpe = rn(V, C), rn(Tcap, C)
+        make = lambda: dict(x=torch.zeros(B, C, device=dev))  # noqa: E731
+        for name, p, plist in vs:
+            sym = "gpt2mi_embed_decode" + ("" if p is not None else "_ragged")
+            arg = p if p is not None else ints(plist)
+            row(f"embed_decode B={B} C={C} {name}", sym, make,
+                lambda lib, s, sym=sym, arg=arg: getattr(lib, sym)(tok.data_ptr(), wte.data_ptr(), wpe.data_ptr(),
+                                                                   s["x"].data_ptr(), B, C, arg, st))
+
+    def sample(B, V, ldl, Tcap, vs):
+        logits = rn(B, ldl, scale=3.0)
+        make = lambda: dict(tok=torch.zeros(B, dtype=torch.int64, device=dev),  # noqa: E731
+                            seq=torch.zeros(B, Tcap, dtype=torch.int64, device=dev),
+                            probs_out=torch.zeros(B, V, device=dev))
+        for mode, (t, k, tp) in {"greedy": (0.0, 0, 1.0), "t0.8 k50 p0.95": (0.8, 50, 0.95)}.items():
+            for name, p, plist in vs:
+                def call(lib, s, p=p, arr=ints(plist), t=t, k=k, tp=tp):
+                    a = (logits.data_ptr(), ldl, B, V, t, k, tp, 7)
+                    z = (-1, None, s["tok"].data_ptr(), s["seq"].data_ptr(), Tcap, s["probs_out"].data_ptr(), st)
+                    if p is not None:
+                        return lib.gpt2mi_sample(*a, p, *z)
+                    return lib.gpt2mi_sample_ragged(*a, arr, None, *z)  # (row_id NULL: the row number)
+                row(f"sample {mode} B={B} V={V} {name}", "gpt2mi_sample" + ("" if p is not None else "_ragged"), make, call)
+
+    def step(B, C, H, L, V, Vp, Tcap, vs, reps):
+        """gpt2mi_decode_step on random weights (shared by the libraries) with each library's own buffers and caches."""
+        w = dict(wte=rn(Vp, C, scale=0.02), wpe=rn(Tcap, C, scale=0.02), lnf_w=1 + rn(C, scale=0.1), lnf_b=rn(C, scale=0.1))
+        w["wte"][V:] = 0
+        w["wte_bf16"] = w["wte"].to(bf)
+        lw = []
+        for _ in range(L):
+            d = {n: (1 if n.endswith("_w") else 0) + rn(C, scale=0.1) for n in ("ln1_w", "ln1_b", "ln2_w", "ln2_b")}
+            for n, (o, i) in dict(qkv=(3 * C, C), proj=(C, C), fc1=(4 * C, C), fc2=(C, 4 * C)).items():
+                d[n + "_w"], d[n + "_b"] = rn(o, i, scale=0.02, dt=bf), rn(o, scale=0.02)
+            lw.append(d)
+        tok = torch.randint(0, V, (B,), device=dev, generator=g)
+        kc0, vc0 = rn(L, B, H, Tcap, 64, dt=bf), rn(L, B, H, Tcap, 64, dt=bf)
+        aws = libs[0].gpt2mi_attn_decode_workspace(B, H, Tcap)
+        gws = max(libs[0].gpt2mi_gemm_skinny_workspace(B, n, k)
+                  for n, k in ((3 * C, C), (C, C), (4 * C, C), (C, 4 * C), (Vp, C)))
+        plans = {}  # id(state) -> (plan, layers): ctypes structures of a state, kept alive with it
+
+        def make():
+            z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
+            s = dict(logits=z(B, Vp), kcache=kc0.clone(), vcache=vc0.clone(), x=z(B, C), xmid=z(B, C), ln=z(B, C, dt=bf),
+                     qkv=z(B, 3 * C, dt=bf), ao=z(B, C, dt=bf), h=z(B, 4 * C, dt=bf), mean=z(B), rstd=z(B),
+                     attn_ws=z(max(aws, 1)), gemm_ws=z(max(gws, 1)))
+            layers = (K.DecodeLayer * L)()
+            for l, Y in enumerate(layers):
+                for n, t in lw[l].items():
+                    setattr(Y, n, t.data_ptr())
+                Y.kcache, Y.vcache = s["kcache"][l].data_ptr(), s["vcache"][l].data_ptr()
+            P = K.DecodePlan()
+            P.B, P.C, P.H, P.L, P.Vp, P.Tcap, P.eps = B, C, H, L, Vp, Tcap, 1e-5
+            for n, t in w.items():
+                setattr(P, n, t.data_ptr())
+            P.layers = ctypes.cast(layers, ctypes.POINTER(K.DecodeLayer))
+            for n in ("x", "xmid", "ln", "qkv", "ao", "h", "mean", "rstd", "attn_ws", "gemm_ws", "logits"):
+                setattr(P, n, s[n].data_ptr())
+            P.attn_ws_floats, P.gemm_ws_floats = s["attn_ws"].numel(), s["gemm_ws"].numel()
+            plans[id(s)] = (P, layers)
+            return s
+        for name, p, plist in vs:
+            sym = "gpt2mi_decode_step" + ("" if p is not None else "_ragged")
+            arg = p if p is not None else ints(plist)
+            row(f"decode_step B={B} C={C} L={L} Vp={Vp} {name}", sym, make,
+                lambda lib, s, sym=sym, arg=arg: getattr(lib, sym)(ctypes.byref(plans[id(s)][0]), tok.data_ptr(), arg, st),
+                reps=reps)
+            plans.clear()
+
+    small = variants(4, (0, 31, 32, 69), [0, 31, 32, 69])
+    attn(4, 2, 70, small)
+    embed(4, 128, 509, 70, small)
+    for V, ldl in ((509, 512), (50257, 50432)):
+        sample(4, V, ldl, 70, small)
+    step(4, 128, 2, 2, 509, 512, 70, small, reps=5)
+    for B in (1, 8, 64):
+        big = variants(B, (575,), [575 - (37 * b) % 576 for b in range(B)])
+        attn(B, 12, 1024, big)
+        embed(B, 768, 50257, 1024, big)
+        sample(B, 50257, 50432, 1024, big)
+        step(B, 768, 12, 12, 50257, 50432, 1024, big, reps=5)
+    print(f"decode A/B: {stats['rows']} rows compared against lib0, {stats['mismatches']} mismatching outputs, "
+          f"{stats['skipped']} skipped", flush=True)
+    if stats["mismatches"]:
+        raise SystemExit(1)
 
 
 def embed_mode(libs, g, st):
