@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -106,6 +106,10 @@ _SIGS = {
     "gpt2mi_decode_step_ragged": [_p, _p, _p, _p],
     "gpt2mi_decode_generate_ragged": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _p, _p, _c_int,
                                       _p, _p, _c_int, _p, _p],
+    # v21 extend: qkv, kcache, vcache, out, workspace, workspace_floats, R, B, H, head_dim, Tcap, seq, pos (HOST arrays
+    # of R ints), stream; plan, R, tok, seq, pos, stream
+    "gpt2mi_attn_extend": [_p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p],
+    "gpt2mi_decode_extend": [_p, _c_int, _p, _p, _p, _p],
 }
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size}
@@ -412,7 +416,7 @@ class DecodePlan(ctypes.Structure):
                 [("layers", ctypes.POINTER(DecodeLayer))] +
                 [(n, _p) for n in ("x", "xmid", "ln", "qkv", "ao", "h", "mean", "rstd")] +
                 [("attn_ws", _p), ("attn_ws_floats", _c_size), ("gemm_ws", _p), ("gemm_ws_floats", _c_size),
-                 ("logits", _p)])
+                 ("logits", _p), ("rows", _c_int)])
 
 
 def gemm_skinny_workspace(M, N, K) -> int:
@@ -554,3 +558,16 @@ def decode_generate_ragged(plan: DecodePlan, V, temperature, top_k, top_p, seed,
     t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
     _call("gpt2mi_decode_generate_ragged", ctypes.byref(plan), V, t, k, p, s, e, _positions(pos0, plan.B),
           _row_ids(row_id, plan.B), n, _ptr(tok), _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(done), _stream())
+
+
+# ---- v21: several rows of a launch in one sequence (csrc/decode.hip) -----------------------------------
+def attn_extend(qkv, kcache, vcache, out, workspace, R, B, H, D, Tcap, seq, pos):
+    """gpt2mi_attn_extend: attention of R rows, row r at position pos[r] of sequence seq[r] (host sequences of R ints)."""
+    _call("gpt2mi_attn_extend", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(workspace), workspace.numel(),
+          R, B, H, D, Tcap, _positions(seq, R), _positions(pos, R), _stream())
+
+
+def decode_extend(plan: DecodePlan, tok, seq, pos):
+    """gpt2mi_decode_extend: the step's launch list on len(pos) rows of the row map (seq, pos), into plan.logits."""
+    R = len(pos)
+    _call("gpt2mi_decode_extend", ctypes.byref(plan), R, _ptr(tok), _positions(seq, R), _positions(pos, R), _stream())

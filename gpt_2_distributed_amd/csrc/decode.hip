@@ -287,6 +287,105 @@ __global__ __launch_bounds__(64) void attn_combine_kernel(const float* __restric
   out[(size_t)bh * 64 + d] = f2bf(o / l);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Several rows of one launch in the same sequence (gpt2mi_attn_extend): row r is (sequence seq[r], position pos[r]),
+// the rows of a sequence are one contiguous run at consecutive positions and first[r] is the position of the run's
+// first row. Validated on the host and passed by value like RowPos; indexed by blockIdx only.
+struct RowMap {
+  int seq[GPT2MI_DECODE_MAX_B], pos[GPT2MI_DECODE_MAX_B], first[GPT2MI_DECODE_MAX_B];
+};
+
+// attn_decode_kernel, lane for lane, for grid (ranges, H, R) with the keys of a row coming from two places: a key
+// below first[r] from the cache stream of seq[r] (written by an earlier call), a key in first[r]..pos[r] from the qkv
+// row of the run that sits at that position, r - (pos[r] - key) >= the run's first row. The keys of this call are
+// never read from the cache: other waves of this launch are writing them. The row at position t alone writes k / v
+// to position t of its stream, so every position has one writer, and nothing above pos[r] is read. The bits of a
+// key are the same from either source (the cache holds what the qkv row held), so row r gets what
+// attn_decode_kernel gives it when the rows are fed one call at a time. The workspace slot is that of row r, not of
+// the sequence: the combine is attn_combine_kernel over R rows at pos[r].
+__global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
+                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
+                                                         float* __restrict__ ws_acc, int H, int Tcap, RowMap rows,
+                                                         int nr_max) {
+  const int range = blockIdx.x, h = blockIdx.y, r = blockIdx.z;
+  const int pos = rows.pos[r];
+  if (range * AD_KEYS > pos) return;
+  const int first = rows.first[r];
+  const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
+  const int C = H * 64;
+  const bf16* tok = qkv + (size_t)r * 3 * C + h * 64 + 8 * dg;  // q; k at + C, v at + 2C
+  float q[8];
+  unpack8(*reinterpret_cast<const bf16x8*>(tok), q);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) q[j] *= 0.125f;  // 1/sqrt(64), exact
+
+  const size_t base = ((size_t)rows.seq[r] * H + h) * Tcap * 64 + 8 * dg;
+  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+  bf16x8 kv[4], vv[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int key = range * AD_KEYS + kk + 8 * i;
+    kv[i] = zero;
+    vv[i] = zero;
+    if (key < first) {
+      kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
+      vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
+    } else if (key <= pos) {
+      const bf16* src = tok - (ptrdiff_t)(pos - key) * 3 * C;  // the run's row at position key
+      kv[i] = *reinterpret_cast<const bf16x8*>(src + C);
+      vv[i] = *reinterpret_cast<const bf16x8*>(src + 2 * C);
+      if (key == pos) {
+        *reinterpret_cast<bf16x8*>(kc + base + (size_t)key * 64) = kv[i];
+        *reinterpret_cast<bf16x8*>(vc + base + (size_t)key * 64) = vv[i];
+      }
+    }
+  }
+
+  float s[4], mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float kf[8], d = 0.f;
+    unpack8(kv[i], kf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], kf[j], d);
+    d += __shfl_xor(d, 1, 64);
+    d += __shfl_xor(d, 2, 64);
+    d += __shfl_xor(d, 4, 64);
+    s[i] = (range * AD_KEYS + kk + 8 * i <= pos) ? d : -INFINITY;
+    mx = fmaxf(mx, s[i]);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 8, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // finite: the range's first key is <= pos
+
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float p = __expf(s[i] - mx);  // 0 for a masked key
+    float vf[8];
+    unpack8(vv[i], vf);
+    l += p;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(p, vf[j], acc[j]);
+  }
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) {
+    l += __shfl_xor(l, o, 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], o, 64);
+  }
+  const size_t slot = ((size_t)r * H + h) * nr_max + range;
+  if (kk == 0) {
+    float* a = ws_acc + slot * 64 + 8 * dg;
+    *reinterpret_cast<f32x4*>(a) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+    *reinterpret_cast<f32x4*>(a + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    if (dg == 0) {
+      ws_ml[2 * slot] = mx;
+      ws_ml[2 * slot + 1] = l;
+    }
+  }
+}
+
 // One row per blockIdx.y, so that the row's position is a scalar load of the argument.
 __global__ __launch_bounds__(256) void embed_decode_kernel(const int64_t* __restrict__ tok,
                                                            const float* __restrict__ wte,
@@ -466,6 +565,92 @@ GPT2MI_EXPORT int gpt2mi_embed_decode(const int64_t* tok, const float* wte, cons
 }
 
 namespace {
+// The row map of an extend entry: R in [1, GPT2MI_DECODE_MAX_B] rows, seq and pos HOST arrays of R ints. seq[r] in
+// [0, B) and non-decreasing, pos[r] in [0, Tcap), and within a sequence pos ascends by 1: so the rows of a sequence are
+// one contiguous run, the run's row at position t (first[r] <= t <= pos[r]) is row r - (pos[r] - t) >= the run's first
+// row, and every cache index (seq[r], h, t <= pos[r]) lies inside [B][H][Tcap]. 22 with a message otherwise.
+int row_map(const char* what, const int* seq, const int* pos, int R, int B, int Tcap, RowMap* out, int* max_pos) {
+  GPT2MI_REQUIRE(R >= 1 && R <= GPT2MI_DECODE_MAX_B, "%s: R=%d not in [1, %d]", what, R, GPT2MI_DECODE_MAX_B);
+  GPT2MI_REQUIRE(seq != nullptr, "%s: the sequence array (host, R ints) is NULL", what);
+  GPT2MI_REQUIRE(pos != nullptr, "%s: the position array (host, R ints) is NULL", what);
+  *out = RowMap{};
+  *max_pos = 0;
+  for (int r = 0; r < R; ++r) {
+    GPT2MI_REQUIRE(seq[r] >= 0 && seq[r] < B, "%s: seq[%d]=%d not in [0, B=%d)", what, r, seq[r], B);
+    GPT2MI_REQUIRE(r == 0 || seq[r] >= seq[r - 1], "%s: seq[%d]=%d after seq[%d]=%d: the sequences must not decrease",
+                   what, r, seq[r], r - 1, r ? seq[r - 1] : 0);
+    GPT2MI_REQUIRE(pos[r] >= 0 && pos[r] < Tcap, "%s: pos[%d]=%d not in [0, %d)", what, r, pos[r], Tcap);
+    const bool same = r > 0 && seq[r] == seq[r - 1];
+    GPT2MI_REQUIRE(!same || pos[r] == pos[r - 1] + 1,
+                   "%s: pos[%d]=%d does not follow pos[%d]=%d in sequence %d (a run ascends by 1)", what, r, pos[r],
+                   r - 1, r ? pos[r - 1] : 0, seq[r]);
+    out->seq[r] = seq[r];
+    out->pos[r] = pos[r];
+    out->first[r] = same ? out->first[r - 1] : pos[r];
+    *max_pos = std::max(*max_pos, pos[r]);
+  }
+  return 0;
+}
+
+int attn_extend_rows(const char* what, const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
+                     float* workspace, size_t workspace_floats, int R, int B, int H, int head_dim, int Tcap,
+                     const int* seq, const int* pos, void* stream) {
+  GPT2MI_REQUIRE(head_dim == 64, "%s: head_dim=%d (the decode kernels implement 64)", what, head_dim);
+  GPT2MI_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && Tcap >= 1, "%s: B=%d, H=%d (<= 65535), Tcap=%d must be positive", what,
+                 B, H, Tcap);
+  RowMap rm;
+  int max_pos;
+  if (const int rc = row_map(what, seq, pos, R, B, Tcap, &rm, &max_pos)) return rc;
+  const size_t need = gpt2mi_attn_decode_workspace(R, H, Tcap);
+  GPT2MI_REQUIRE(workspace_floats >= need, "%s: workspace too small (%zu floats given, %zu needed)", what,
+                 workspace_floats, need);
+  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
+                 "%s: qkv, the caches, out and workspace must not be NULL", what);
+  hipStream_t s = (hipStream_t)stream;
+  const int nr_max = attn_ranges(Tcap);
+  float* ws_ml = workspace;
+  float* ws_acc = workspace + (size_t)R * H * nr_max * 2;
+  attn_extend_kernel<<<dim3(max_pos / AD_KEYS + 1, H, R), 64, 0, s>>>((const bf16*)qkv, (bf16*)kcache, (bf16*)vcache,
+                                                                     ws_ml, ws_acc, H, Tcap, rm, nr_max);
+  if (const int rc = gpt2mi::check_launch(what)) return rc;
+  RowPos rp{};  // the combine is per row: row r merges its own pos[r] / 32 + 1 ranges
+  std::copy_n(rm.pos, R, rp.v);
+  attn_combine_kernel<<<dim3(H, R), 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, rp, nr_max);
+  return gpt2mi::check_launch(what);
+}
+
+// The launch list of a step over M rows at pos[m], shared by the step and the extend: they differ in the attention
+// (`attn`, called once per layer between the qkv and the proj GEMM) and in what they checked before.
+template <class Attn>
+int decode_launches(const char* what, const gpt2mi_decode_plan* P, int M, const int64_t* tok, const int* pos,
+                    void* stream, Attn attn) {
+#define STEP(call)       \
+  do {                   \
+    const int rc = call; \
+    if (rc) return rc;   \
+  } while (0)
+  const int C = P->C;
+  float *x = P->x, *xmid = P->xmid;
+  float* gws = P->gemm_ws;
+  const size_t gwn = P->gemm_ws_floats;
+  STEP(embed_decode_rows(what, tok, P->wte, P->wpe, x, M, C, pos, stream));
+  for (int l = 0; l < P->L; ++l) {
+    const gpt2mi_decode_layer& Y = P->layers[l];
+    STEP(gpt2mi_layernorm_fwd(x, Y.ln1_w, Y.ln1_b, P->ln, nullptr, P->mean, P->rstd, M, C, P->eps, stream));
+    STEP(gpt2mi_gemm_skinny(SK_BF16, M, 3 * C, C, P->ln, C, Y.qkv_w, C, P->qkv, 3 * C, Y.qkv_b, nullptr, gws, gwn, stream));
+    STEP(attn(Y));
+    STEP(gpt2mi_gemm_skinny(SK_RESID, M, C, C, P->ao, C, Y.proj_w, C, xmid, C, Y.proj_b, x, gws, gwn, stream));
+    STEP(gpt2mi_layernorm_fwd(xmid, Y.ln2_w, Y.ln2_b, P->ln, nullptr, P->mean, P->rstd, M, C, P->eps, stream));
+    STEP(gpt2mi_gemm_skinny(SK_GELU, M, 4 * C, C, P->ln, C, Y.fc1_w, C, P->h, 4 * C, Y.fc1_b, nullptr, gws, gwn, stream));
+    STEP(gpt2mi_gemm_skinny(SK_RESID, M, C, 4 * C, P->h, 4 * C, Y.fc2_w, 4 * C, x, C, Y.fc2_b, xmid, gws, gwn, stream));
+  }
+  STEP(gpt2mi_layernorm_fwd(x, P->lnf_w, P->lnf_b, P->ln, nullptr, P->mean, P->rstd, M, C, P->eps, stream));
+  STEP(gpt2mi_gemm_skinny(SK_F32, M, P->Vp, C, P->ln, C, P->wte_bf16, C, P->logits, P->Vp, nullptr, nullptr, gws, gwn,
+                          stream));
+#undef STEP
+  return 0;
+}
+
 // One step with row b at pos[b]: gpt2mi_decode_step_ragged, and gpt2mi_decode_step with every pos[b] equal.
 int decode_step_rows(const char* what, const gpt2mi_decode_plan* P, const int64_t* tok, const int* pos, void* stream) {
   GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
@@ -485,31 +670,10 @@ int decode_step_rows(const char* what, const gpt2mi_decode_plan* P, const int64_
   GPT2MI_REQUIRE(P->gemm_ws_floats >= need, "%s: GEMM workspace too small (%zu floats given, %zu needed)", what,
                  P->gemm_ws_floats, need);
   GPT2MI_REQUIRE(P->layers && tok, "%s: layers and tok must not be NULL", what);
-#define STEP(call)       \
-  do {                   \
-    const int rc = call; \
-    if (rc) return rc;   \
-  } while (0)
-  float *x = P->x, *xmid = P->xmid;
-  float* gws = P->gemm_ws;
-  const size_t gwn = P->gemm_ws_floats;
-  STEP(embed_decode_rows(what, tok, P->wte, P->wpe, x, B, C, pos, stream));
-  for (int l = 0; l < P->L; ++l) {
-    const gpt2mi_decode_layer& Y = P->layers[l];
-    STEP(gpt2mi_layernorm_fwd(x, Y.ln1_w, Y.ln1_b, P->ln, nullptr, P->mean, P->rstd, B, C, P->eps, stream));
-    STEP(gpt2mi_gemm_skinny(SK_BF16, B, 3 * C, C, P->ln, C, Y.qkv_w, C, P->qkv, 3 * C, Y.qkv_b, nullptr, gws, gwn, stream));
-    STEP(attn_decode_rows(what, P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap,
-                          pos, stream));
-    STEP(gpt2mi_gemm_skinny(SK_RESID, B, C, C, P->ao, C, Y.proj_w, C, xmid, C, Y.proj_b, x, gws, gwn, stream));
-    STEP(gpt2mi_layernorm_fwd(xmid, Y.ln2_w, Y.ln2_b, P->ln, nullptr, P->mean, P->rstd, B, C, P->eps, stream));
-    STEP(gpt2mi_gemm_skinny(SK_GELU, B, 4 * C, C, P->ln, C, Y.fc1_w, C, P->h, 4 * C, Y.fc1_b, nullptr, gws, gwn, stream));
-    STEP(gpt2mi_gemm_skinny(SK_RESID, B, C, 4 * C, P->h, 4 * C, Y.fc2_w, 4 * C, x, C, Y.fc2_b, xmid, gws, gwn, stream));
-  }
-  STEP(gpt2mi_layernorm_fwd(x, P->lnf_w, P->lnf_b, P->ln, nullptr, P->mean, P->rstd, B, C, P->eps, stream));
-  STEP(gpt2mi_gemm_skinny(SK_F32, B, P->Vp, C, P->ln, C, P->wte_bf16, C, P->logits, P->Vp, nullptr, nullptr, gws, gwn,
-                          stream));
-#undef STEP
-  return 0;
+  return decode_launches(what, P, B, tok, pos, stream, [&](const gpt2mi_decode_layer& Y) {
+    return attn_decode_rows(what, P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap,
+                            pos, stream);
+  });
 }
 }  // namespace
 
@@ -522,6 +686,41 @@ GPT2MI_EXPORT int gpt2mi_decode_step(const gpt2mi_decode_plan* P, const int64_t*
   GPT2MI_REQUIRE(P != nullptr, "decode_step: plan is NULL");
   GPT2MI_REQUIRE(pos >= 0 && pos < P->Tcap, "decode_step: pos=%d not in [0, Tcap=%d)", pos, P->Tcap);
   return decode_step_rows("decode_step", P, tok, SamePos(pos).v, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_extend(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
+                                     float* workspace, size_t workspace_floats, int R, int B, int H, int head_dim,
+                                     int Tcap, const int* seq, const int* pos, void* stream) {
+  return attn_extend_rows("attn_extend", qkv, kcache, vcache, out, workspace, workspace_floats, R, B, H, head_dim, Tcap,
+                          seq, pos, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_decode_extend(const gpt2mi_decode_plan* P, int R, const int64_t* tok, const int* seq,
+                                       const int* pos, void* stream) {
+  const char* what = "decode_extend";
+  GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
+  const int B = P->B, C = P->C, H = P->H;
+  GPT2MI_REQUIRE(B >= 1 && B <= 64, "%s: B=%d not in [1, 64]", what, B);
+  GPT2MI_REQUIRE(H >= 1 && C == 64 * H, "%s: head_dim = C/H must be 64 (C=%d, H=%d)", what, C, H);
+  GPT2MI_REQUIRE(P->L >= 1 && P->Vp >= 64 && P->Vp % 64 == 0, "%s: L=%d, Vp=%d (a multiple of 64) invalid", what, P->L,
+                 P->Vp);
+  RowMap rm;
+  int max_pos;
+  if (const int rc = row_map(what, seq, pos, R, B, P->Tcap, &rm, &max_pos)) return rc;
+  const int cap = P->rows ? P->rows : B;
+  GPT2MI_REQUIRE(R <= cap, "%s: R=%d exceeds the plan's row capacity %d (plan->rows, 0: B)", what, R, cap);
+  GPT2MI_REQUIRE(P->attn_ws_floats >= gpt2mi_attn_decode_workspace(R, H, P->Tcap),
+                 "%s: attention workspace too small (%zu floats)", what, P->attn_ws_floats);
+  size_t need = 0;
+  const int shapes[5][2] = {{3 * C, C}, {C, C}, {4 * C, C}, {C, 4 * C}, {P->Vp, C}};
+  for (const auto& sh : shapes) need = std::max(need, gpt2mi_gemm_skinny_workspace(R, sh[0], sh[1]));
+  GPT2MI_REQUIRE(P->gemm_ws_floats >= need, "%s: GEMM workspace too small (%zu floats given, %zu needed)", what,
+                 P->gemm_ws_floats, need);
+  GPT2MI_REQUIRE(P->layers && tok, "%s: layers and tok must not be NULL", what);
+  return decode_launches(what, P, R, tok, pos, stream, [&](const gpt2mi_decode_layer& Y) {
+    return attn_extend_rows(what, P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, R, B, H, 64,
+                            P->Tcap, seq, pos, stream);
+  });
 }
 
 namespace {

@@ -1,5 +1,6 @@
 """Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
---prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B]``.
+--prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B
+--draft_tokens K]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -39,6 +40,9 @@ def parse_args(argv=None):
     p.add_argument("--batch", type=int, default=1,
                    help="one prompt: the number of copies; several prompts: the rows of generate_many's session")
     p.add_argument("--eos_token_id", type=int, default=None)
+    p.add_argument("--draft_tokens", type=int, default=None,
+                   help="one prompt, --sampler device: verify up to this many prompt-lookup draft tokens per pass over "
+                        "the weights (the same tokens as without; batch * (draft_tokens + 1) <= 64)")
     return p.parse_args(argv)
 
 
@@ -82,7 +86,9 @@ def main(argv=None) -> int:
         return 0
     prompt = prompts[0]
     idx = torch.tensor([prompt] * a.batch, dtype=torch.int64, device="cuda:0")
-    how = (dict(seed=a.seed) if a.sampler == "device"
+    if a.draft_tokens is not None and a.sampler != "device":
+        raise SystemExit("--draft_tokens compares drafts with the device sampler's draws: --sampler device")
+    how = (dict(seed=a.seed, draft_tokens=a.draft_tokens) if a.sampler == "device"
            else dict(generator=torch.Generator(device="cuda:0").manual_seed(a.seed)))
     out = model.generate(idx, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
                          eos_token_id=a.eos_token_id, **how)

@@ -14,6 +14,11 @@ prompts with their lengths, ``refill`` replaces one row while the others go on, 
 of prompts through one session that way. Equally long sequences are the case where the positions agree: there is one
 set of kernels and one code path (the ``gpt2mi_*_ragged`` entries; DESIGN.md "Ragged batches").
 
+A step appends one token per row. ``DecodeSession.extend`` appends several to a live row in one pass over the weights
+(``gpt2mi_decode_extend``: the rows of a launch may be consecutive positions of one sequence), with the bits of as many
+steps; ``DecodeSession.speculate`` uses it to verify drafted tokens (``ngram_draft``, or any callable) and returns
+exactly the tokens of the device loop (DESIGN.md "Multi-token decode step").
+
 Numerics are the autocast path's whatever the autocast state: bf16 GEMM operands from the engine's weight shadow, fp32
 accumulation, fp32 residual stream / LayerNorm / softmax, dropout off (p = 0 whatever ``model.training`` is, and
 ``.training`` is not touched). Logits are fp32. ``model.precision == "fp32"`` has no decode kernels and raises.
@@ -35,6 +40,7 @@ from . import _lib as K
 BF16 = torch.bfloat16
 F32 = torch.float32
 MAX_BATCH = 64  # rows of the skinny GEMM (gpt2mi_gemm_skinny)
+SCRATCH = ("x", "xmid", "ln", "qkv", "ao", "h", "mean", "rstd", "attn_ws", "gemm_ws", "logits")  # a plan's buffers
 
 
 def _nucleus_keep(key: torch.Tensor, probs: torch.Tensor, top_p: float) -> torch.Tensor:
@@ -195,17 +201,25 @@ class DecodeSession:
         e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
         self.kcache = e(L, B, H, Tcap, 64)
         self.vcache = e(L, B, H, Tcap, 64)
-        self.x, self.xmid = e(B, C, dt=F32), e(B, C, dt=F32)
-        self.ln, self.qkv, self.ao, self.h = e(B, C), e(B, 3 * C), e(B, C), e(B, 4 * C)
-        self.mean, self.rstd = e(B, dt=F32), e(B, dt=F32)
-        self.attn_ws = e(max(K.attn_decode_workspace(B, H, Tcap), 1), dt=F32)
-        shapes = [(3 * C, C), (C, C), (4 * C, C), (C, 4 * C), (Vp, C)]
-        self.gemm_ws = e(max(max(K.gemm_skinny_workspace(B, n, k) for n, k in shapes), 1), dt=F32)
-        self.logits = e(B, Vp, dt=F32)
+        for name, t in self._scratch(B).items():  # x, xmid, ln, qkv, ao, h, mean, rstd, attn_ws, gemm_ws, logits
+            setattr(self, name, t)
         self._tok = e(B, dt=torch.int64)  # the device loop's newest tokens (DecodeSession.generate)
         self._drawn = False               # True: generate() drew _tok from the logits in place and has not stepped it
         self._refill_ws = None            # (Tp, engine.Workspace) of the last refill's one-sequence prefill
-        self._plan = self._build_plan()
+        self._plan = self._build_plan({n: getattr(self, n) for n in SCRATCH}, 0)
+        self._rows = None                 # (scratch of MAX_BATCH rows, its plan): extend / speculate, on first use
+
+    def _scratch(self, M: int) -> dict:
+        """The buffers a step over M rows writes (gpt2mi_decode_plan's x .. logits)."""
+        cfg = self.cfg
+        C, H, Vp = cfg.n_embd, cfg.n_head, self.model.vpad
+        e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=self.engine.device)  # noqa: E731
+        shapes = [(3 * C, C), (C, C), (4 * C, C), (C, 4 * C), (Vp, C)]
+        return dict(x=e(M, C, dt=F32), xmid=e(M, C, dt=F32), ln=e(M, C), qkv=e(M, 3 * C), ao=e(M, C), h=e(M, 4 * C),
+                    mean=e(M, dt=F32), rstd=e(M, dt=F32),
+                    attn_ws=e(max(K.attn_decode_workspace(M, H, self.Tcap), 1), dt=F32),
+                    gemm_ws=e(max(max(K.gemm_skinny_workspace(M, n, k) for n, k in shapes), 1), dt=F32),
+                    logits=e(M, Vp, dt=F32))
 
     @property
     def pos(self) -> Optional[int]:
@@ -224,7 +238,8 @@ class DecodeSession:
     def device(self):
         return self.logits.device
 
-    def _build_plan(self) -> K.DecodePlan:
+    def _build_plan(self, scratch: dict, rows: int) -> K.DecodePlan:
+        """The plan over the session's weights and caches with ``scratch`` as its buffers, holding ``rows`` rows (0: B)."""
         eng, cfg = self.engine, self.cfg
         p = lambda n: eng.p(n).data_ptr()  # noqa: E731  fp32 master view
         w = lambda n: eng.w16(n).data_ptr()  # noqa: E731  bf16 shadow
@@ -245,9 +260,10 @@ class DecodeSession:
         P.lnf_w, P.lnf_b = p("transformer.ln_f.weight"), p("transformer.ln_f.bias")
         P.wte_bf16 = w("transformer.wte.weight")  # the zero-padded [Vp, C] slot: the tied lm_head
         P.layers = ctypes.cast(self._layers, ctypes.POINTER(K.DecodeLayer))
-        for n in ("x", "xmid", "ln", "qkv", "ao", "h", "mean", "rstd", "attn_ws", "gemm_ws", "logits"):
-            setattr(P, n, getattr(self, n).data_ptr())
-        P.attn_ws_floats, P.gemm_ws_floats = self.attn_ws.numel(), self.gemm_ws.numel()
+        for n in SCRATCH:
+            setattr(P, n, scratch[n].data_ptr())
+        P.attn_ws_floats, P.gemm_ws_floats = scratch["attn_ws"].numel(), scratch["gemm_ws"].numel()
+        P.rows = rows
         return P
 
     def _ready(self, sync: bool):
@@ -436,6 +452,191 @@ class DecodeSession:
         self._drawn = True
         return self._tok
 
+    # ---- several tokens of a sequence per launch (gpt2mi_decode_extend) ----------------------------------------------
+    def _rows_plan(self):
+        """The plan whose buffers hold MAX_BATCH rows (same weights and caches), allocated on first use."""
+        if self._rows is None:
+            scratch = self._scratch(MAX_BATCH)
+            self._rows = (scratch, self._build_plan(scratch, MAX_BATCH))
+        return self._rows
+
+    @torch.no_grad()
+    def extend(self, tokens: torch.Tensor, counts: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """Append ``tokens[b, :counts[b]]`` (int64 [B, n] on the device; ``counts[b]`` in [0, n], default n) to row b at
+        positions ``lens[b] ..``; fp32 logits [B, n, V] after each appended position, NaN where ``j >= counts[b]``.
+
+        The rows of a call are (sequence, position) pairs of one ``gpt2mi_decode_extend``: the weights stream once for
+        up to 64 of them, and a call is split along the token axis when ``sum(counts) > 64``. Every logits row, the
+        cache and the final state (``lens[b] += counts[b]``, ``logits[b]`` those of the last appended position) have the
+        bits of ``counts[b]`` ``step`` calls; a row with count 0 keeps its cache, logits and length. Works from an empty
+        cache (``prefill`` is the fast path for long prompts: this one runs every position as a decode row). A token
+        ``generate`` drew and has not stepped is stepped first, as in ``refill``."""
+        if tokens.dim() != 2 or tokens.size(0) != self.B or tokens.dtype != torch.int64:
+            raise ValueError(f"extend takes int64 tokens [B={self.B}, n] (got {tokens.dtype} {tuple(tokens.shape)})")
+        if not tokens.is_cuda:
+            raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
+        n = tokens.size(1)
+        counts = [n] * self.B if counts is None else [int(c) for c in counts]
+        if len(counts) != self.B or not all(0 <= c <= n for c in counts):
+            raise ValueError(f"counts {counts} must be B={self.B} ints in [0, n={n}]")
+        drawn = int(self._drawn)
+        if any(m + drawn + c > self.Tcap for m, c in zip(self.lens, counts)):
+            raise ValueError(f"lens {self.lens} + counts {counts} do not fit the cache ({self.Tcap} positions)")
+        self.flush()
+        self._ready(True)
+        V = self.cfg.vocab_size
+        out = torch.full((self.B, n, V), float("nan"), dtype=F32, device=self.device)
+        scratch, plan = self._rows_plan()
+        flat = tokens.reshape(-1)
+        j0 = 0
+        while j0 < max(counts, default=0):
+            w = 1  # the widest slice of token columns whose rows fit one call
+            while sum(max(0, min(c, j0 + w + 1) - j0) for c in counts) <= MAX_BATCH and j0 + w < max(counts):
+                w += 1
+            rows = [(b, j) for b in range(self.B) for j in range(j0, min(counts[b], j0 + w))]
+            at = torch.tensor([b * n + j for b, j in rows], device=self.device)
+            K.decode_extend(plan, flat[at], [b for b, _ in rows], [self.lens[b] + j for b, j in rows])
+            got = scratch["logits"][:len(rows)]
+            out.view(self.B * n, V)[at] = got[:, :V]
+            last = [(r, b) for r, (b, j) in enumerate(rows) if j == counts[b] - 1]
+            if last:
+                self._accept([r for r, _ in last], [b for _, b in last])
+            j0 += w
+        self.lens = [m + c for m, c in zip(self.lens, counts)]
+        return out
+
+    def _accept(self, src: List[int], dst: List[int]) -> None:
+        """``logits[dst[i]]`` = row ``src[i]`` of the last extend call's logits."""
+        rows = self._rows[0]["logits"]
+        self.logits.index_copy_(0, torch.tensor(dst, device=self.device),
+                                rows.index_select(0, torch.tensor(src, device=self.device)))
+
+    def _verify(self, toks: List[int], seqs: List[int], poss: List[int], keys: List[int], sampler) -> List[int]:
+        """One ``gpt2mi_decode_extend`` over the rows (token, sequence, position) and one ``gpt2mi_sample_ragged`` over
+        their logits, row r at position ``poss[r] + 1`` with draw key ``keys[r]``; the R tokens, read back."""
+        V = self.cfg.vocab_size
+        if not all(0 <= t < V for t in toks):
+            raise ValueError(f"draft tokens must lie in [0, vocab_size={V}) (got {toks})")
+        scratch, plan = self._rows_plan()
+        R = len(toks)
+        K.decode_extend(plan, torch.tensor(toks, dtype=torch.int64, device=self.device), seqs, poss)
+        out = torch.empty(R, dtype=torch.int64, device=self.device)
+        temperature, top_k, top_p, seed = sampler
+        K.sample_ragged(scratch["logits"][:R], V, temperature, top_k, top_p, seed, [p + 1 for p in poss], out,
+                        row_id=keys)
+        return out.tolist()
+
+    @torch.no_grad()
+    def speculate(self, n: int, k: int, draft_fn=None, temperature: float = 1.0, top_k: Optional[int] = None,
+                  top_p: Optional[float] = None, seed: int = 0, eos_token_id: Optional[int] = None,
+                  seq: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
+                  row_id: Optional[Sequence[int]] = None) -> dict:
+        """``generate(n, ...)`` with up to ``k`` drafted tokens of every row verified per pass over the weights: the same
+        tokens in ``seq``, the same ``done`` flags and, with the last token drawn and not stepped, the same ``_tok``,
+        ``lens`` and ``logits``, in fewer passes when the drafts are right. ``B * (k + 1) <= 64``.
+
+        Each iteration, for every live row, ``draft_fn(history, m)`` (default ``ngram_draft``) proposes up to
+        ``m = min(k, tokens the row still needs - 1)`` tokens; one ``gpt2mi_decode_extend`` runs the rows [the row's
+        current token, its drafts ...], one ``gpt2mi_sample_ragged`` draws a token from each of their logits rows at the
+        position after it with the sequence's draw key, and the tokens are read back. A draft is right iff it equals
+        the token drawn before it: the sampler's token is a function of (logits row, parameters, seed, key, position)
+        and a logits row has the bits the one-token step gives it, so the comparison of integers is exact for greedy and
+        sampled decoding alike. The row advances by the accepted drafts + 1; cache entries of rejected drafts stay above
+        ``lens[b]``, where no kernel reads them before they are overwritten. ``history`` is the row's tokens so far:
+        ``seq[b, :lens[b]]`` on entry if ``seq`` is given (else empty), then what this call drew.
+
+        A row that draws eos stops being stepped: its ``lens`` is then the position of that eos and its ``logits`` those
+        the eos was drawn from (the plain call goes on stepping eos to ``lens + n - 1``); ``seq`` holds eos from there on
+        as after the plain call. One host synchronisation per iteration is inherent: the positions of the next call are
+        host arrays that depend on the tokens read back. Returns ``{"calls", "drafted", "accepted", "tokens"}``: verify
+        calls, draft tokens proposed and accepted, tokens drawn."""
+        n, k = int(n), int(k)
+        if n < 1 or k < 0:
+            raise ValueError(f"speculate takes n >= 1 and k >= 0 (got n={n}, k={k})")
+        if self.B * (k + 1) > MAX_BATCH:
+            raise ValueError(f"B={self.B} rows of {k} drafts + 1 exceed the {MAX_BATCH} rows of a call")
+        self._check_sampler(temperature, top_p, seed)
+        row_id = _check_row_id(row_id, self.B)
+        if max(self.lens) + int(self._drawn) + n > self.Tcap:
+            raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
+        if seq is not None and (seq.dtype != torch.int64 or seq.dim() != 2 or seq.size(0) != self.B or seq.stride(1) != 1):
+            raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
+        if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
+            raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
+        self.flush()
+        done = done if eos_token_id is not None else None
+        lens0 = list(self.lens)
+        K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, self._tok,
+                        row_id=row_id, eos=eos_token_id, done=done)
+        first = self._tok.tolist()
+        history = [[] for _ in range(self.B)] if seq is None else [r[:m] for r, m in zip(seq.tolist(), lens0)]
+        keys = list(range(self.B)) if row_id is None else row_id
+        new, stats = speculate_loop(self, n, k, draft_fn or ngram_draft, eos_token_id, history, first, keys,
+                                    (temperature, top_k, top_p, seed))
+        self._tok.copy_(torch.tensor([t[-1] for t in new], dtype=torch.int64))
+        self._drawn = True
+        if eos_token_id is not None:
+            new = [t + [eos_token_id] * (n - len(t)) for t in new]  # a finished row keeps emitting eos
+            done.copy_(torch.tensor([int(eos_token_id in t) for t in new], dtype=torch.uint8))
+        if seq is not None:
+            cols = torch.tensor(lens0, device=self.device)[:, None] + torch.arange(n, device=self.device)[None]
+            seq.scatter_(1, cols, torch.tensor(new, dtype=torch.int64, device=self.device))
+        return stats
+
+
+def ngram_draft(history: List[int], k: int, max_ngram: int = 3) -> List[int]:
+    """Prompt-lookup drafting: the longest suffix of ``history`` of g tokens, g from ``max_ngram`` down to 1, that also
+    occurs earlier; of its earlier occurrences the most recent; the (up to) k tokens that followed it. ``[]`` if no
+    suffix recurs or k < 1."""
+    n = len(history)
+    if k < 1 or n < 2:
+        return []
+    # where an earlier occurrence of a suffix can end: the earlier positions of the last token, the latest first
+    ends = [j for j in range(n - 2, -1, -1) if history[j] == history[-1]]
+    for g in range(min(max_ngram, n - 1), 0, -1):
+        tail = history[n - g:]
+        for j in ends:
+            if j + 1 >= g and history[j + 1 - g:j + 1] == tail:
+                return history[j + 1:j + 1 + k]
+    return []
+
+
+def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first, keys, sampler):
+    """The bookkeeping of ``DecodeSession.speculate`` over a session (anything with ``B``, ``lens``, ``_verify`` and
+    ``_accept``): ``first[b]`` is row b's first token, drawn and not stepped. Returns (the tokens of each row: n of
+    them, or fewer ending in eos; the stats). A draft counts as accepted iff it equals the token drawn before it and
+    that token is not eos; the row then advances by accepted + 1 and takes the logits row of its last accepted draft."""
+    B = sess.B
+    new = [[int(first[b])] for b in range(B)]
+    stats = dict(calls=0, drafted=0, accepted=0, tokens=0)
+
+    def live(b):
+        return len(new[b]) < n and new[b][-1] != eos_token_id
+
+    while any(live(b) for b in range(B)):
+        toks, seqs, poss, ks, spans = [], [], [], [], []
+        for b in filter(live, range(B)):
+            m = min(k, n - len(new[b]) - 1)
+            drafts = [int(t) for t in draft_fn(history[b] + new[b], m)][:m] if m > 0 else []
+            spans.append((b, len(toks), drafts))
+            for i, t in enumerate([new[b][-1]] + drafts):
+                toks.append(t), seqs.append(b), poss.append(sess.lens[b] + i), ks.append(keys[b])
+        drawn = sess._verify(toks, seqs, poss, ks, sampler)
+        src, dst = [], []
+        for b, r0, drafts in spans:
+            a = 0
+            while a < len(drafts) and drafts[a] == drawn[r0 + a] != eos_token_id:
+                a += 1
+            new[b] += [int(t) for t in drawn[r0:r0 + a + 1]]
+            sess.lens[b] += a + 1
+            src.append(r0 + a), dst.append(b)
+            stats["drafted"] += len(drafts)
+            stats["accepted"] += a
+        sess._accept(src, dst)
+        stats["calls"] += 1
+    stats["tokens"] = sum(len(t) for t in new)
+    return new, stats
+
 
 EOS_CHUNK = 32  # device loop with eos_token_id: tokens issued between two reads of the done flags
 
@@ -455,7 +656,7 @@ def _pad_prompts(prompts, pad: int):
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
              generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
              top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens: Optional[Sequence[int]] = None,
-             pad_token_id: Optional[int] = None) -> torch.Tensor:
+             pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None, draft_fn=None) -> torch.Tensor:
     """``GPT2.generate``: see there."""
     pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
     if isinstance(idx, (list, tuple)):
@@ -479,14 +680,25 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
     _check_top_p(top_p)
     if seed is not None and generator is not None:
         raise ValueError("seed selects the device sampler, which draws from (seed, row, position): it takes no generator")
+    if draft_tokens is None and draft_fn is not None:
+        raise ValueError("draft_fn goes with draft_tokens=k")
+    if draft_tokens is not None:
+        if seed is None:
+            raise ValueError("draft_tokens needs the device sampler (seed=int): a draft is accepted by comparing it with "
+                             "the token drawn at its position, which the host sampler's torch.Generator, a stream and "
+                             "not a function of the position, cannot reproduce")
+        if int(draft_tokens) < 1 or B * (int(draft_tokens) + 1) > MAX_BATCH:
+            raise ValueError(f"draft_tokens={draft_tokens} must be >= 1 with B * (draft_tokens + 1) <= {MAX_BATCH} rows "
+                             f"(B={B})")
     _check_model(model)
     idx = idx.long()
     if prompt_lens is None and n == 0:
         return idx.clone()
-    return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad)
+    return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad,
+                     None if draft_tokens is None else (int(draft_tokens), draft_fn))
 
 
-def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad):
+def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad, draft=None):
     """The token loop of ``generate``: [B, P + m], row b = its prompt, its m new tokens from column lens[b] on, then
     ``pad`` (``lens`` None: every row holds P tokens and nothing is padded). m = n, or with eos the number of tokens by
     which every row has emitted it. Host sampler: new tokens are collected per step and scattered into the buffer that
@@ -506,7 +718,11 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     logits = sess.prefill(idx, lens)
     if seed is not None:
         done = None if eos_token_id is None else torch.zeros(B, dtype=torch.uint8, device=dev)
-        made = _device_loop(sess, n, temperature, top_k, top_p, seed, eos_token_id, seq, done)
+        if draft is None:
+            made = _device_loop(sess, n, temperature, top_k, top_p, seed, eos_token_id, seq, done)
+        else:  # (draft = (k, draft_fn): the same tokens, up to k + 1 of a row per pass over the weights)
+            sess.speculate(n, draft[0], draft[1], temperature, top_k, top_p, seed, eos_token_id, seq, done)
+            made = n
         if eos_token_id is None:
             return seq
         new = seq.gather(1, lens_t[:, None] + torch.arange(made, device=dev)[None])

@@ -344,7 +344,8 @@ class GPT2(nn.Module):
     def generate(self, idx, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
                  top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens=None,
-                 pad_token_id: Optional[int] = None) -> torch.Tensor:
+                 pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None,
+                 draft_fn=None) -> torch.Tensor:
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
         filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
@@ -365,6 +366,12 @@ class GPT2(nn.Module):
         tokens are those it gets in an equal-length batch (one position per row: ``gpt2mi_decode_step_ragged``).
         ``Pmax + max_new_tokens > n_positions`` raises ``ValueError``. Without ``prompt_lens`` nothing changes.
 
+        Speculative generation: with ``seed`` and ``draft_tokens=k`` up to k drafted tokens of every row are verified
+        per pass over the weights (``DecodeSession.speculate``, ``gpt2mi_decode_extend``) and the result is
+        ``torch.equal`` to the call without ``draft_tokens``, for greedy and sampled decoding alike. ``draft_fn(history,
+        k) -> tokens`` proposes them (default ``generation.ngram_draft``: what followed the most recent earlier
+        occurrence of the sequence's last tokens). Without ``seed``, or with ``B * (k + 1) > 64``, ``ValueError``.
+
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
         the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
         ``NotImplementedError``. It does not advance the dropout stream or touch what a later backward needs, so a
@@ -374,7 +381,7 @@ class GPT2(nn.Module):
         model holds only a shard of the parameters and raises ``NotImplementedError``."""
         from .generation import generate
         return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed,
-                        prompt_lens, pad_token_id)
+                        prompt_lens, pad_token_id, draft_tokens, draft_fn)
 
     def generate_many(self, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                       top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,

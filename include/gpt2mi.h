@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 20
+#define GPT2MI_ABI_VERSION 21
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -301,6 +301,9 @@ typedef struct gpt2mi_decode_plan {
   float* gemm_ws;                                         /* the largest gpt2mi_gemm_skinny_workspace of the step */
   size_t gemm_ws_floats;
   float* logits;                                          /* fp32 [B][Vp] */
+  int rows;                                               /* v21, appended (no earlier offset moved): the rows the
+                                                             scratch buffers above (x .. logits, the workspaces) hold;
+                                                             0 means B. Read by gpt2mi_decode_extend only. */
 } gpt2mi_decode_plan;
 /* embed -> per layer (LN1, qkv, attention at pos, proj + resid, LN2, fc1 + GELU, fc2 + resid) -> ln_f -> lm_head into
  * plan->logits, for the B tokens `tok` (device int64 [B]) at position pos (model.py:295-351 at one position). A
@@ -408,6 +411,40 @@ int gpt2mi_decode_step_ragged(const gpt2mi_decode_plan* plan, const int64_t* tok
 int gpt2mi_decode_generate_ragged(const gpt2mi_decode_plan* plan, int V, float temperature, int top_k, float top_p,
                                   uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
                                   int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream);
+
+/* ---- v21: several rows of one launch in the same sequence (csrc/decode.hip). A step appends one token per sequence;
+ * these append a run of tokens to a live sequence in one pass over the weights: a second user turn, a prompt suffix, or
+ * a chunk of draft tokens to verify (generation.py DecodeSession.extend, speculate).
+ * The row map is two HOST arrays of R ints, 1 <= R <= GPT2MI_DECODE_MAX_B: row r is (sequence seq[r] in [0, B), position
+ * pos[r] in [0, Tcap)). seq must not decrease, and where seq[r] == seq[r-1], pos[r] == pos[r-1] + 1: the rows of a
+ * sequence are one contiguous run at consecutive positions. A sequence may be absent and a run may start at 0. The entry
+ * checks every element before any launch and passes the map (with each run's first position, derived on the host) to
+ * the kernel by value, indexed by the block index only: there is no device-side index array. These checks are what
+ * make every derived index in range: the qkv row of the run's position t, r - (pos[r] - t) for first <= t <= pos[r],
+ * is never below the run's first row, and every cache index (seq[r], h, t <= pos[r]) lies inside [B][H][Tcap].
+ * Refused with 22 and a message before any launch: R outside [1, GPT2MI_DECODE_MAX_B], a NULL seq or pos array, seq[r]
+ * outside [0, B), a decreasing seq, pos[r] outside [0, Tcap), seq[r] == seq[r-1] with pos[r] != pos[r-1] + 1, a
+ * workspace or row capacity too small, a NULL pointer. ---- */
+/* Single-query attention for R rows, qkv bf16 [R][3C], caches bf16 [B][H][Tcap][64] (one layer), out bf16 [R][C]:
+ * out[r] = softmax(q_r . K[0..pos[r]]^T / 8) V[0..pos[r]] over sequence seq[r], with gpt2mi_attn_decode_ragged's
+ * arithmetic lane for lane (one wave per 32 keys, head and row; the in-order combine of pos[r] / 32 + 1 ranges). A key
+ * at a position below the run's first comes from the cache; a key at first..pos[r] comes from the qkv row of the run
+ * at that position and is never read from the cache (other waves of the launch are writing it). The row at position t
+ * writes its k / v to position t of its sequence's streams: one writer per position, nothing above pos[r] read, streams
+ * of absent sequences untouched, no atomics. Workspace: size and layout of gpt2mi_attn_decode_workspace(R, H, Tcap),
+ * slots indexed by row. out[r] and the caches have the bits that R calls of gpt2mi_attn_decode_ragged, one position at
+ * a time, give. */
+int gpt2mi_attn_extend(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out, float* workspace,
+                       size_t workspace_floats, int R, int B, int H, int head_dim, int Tcap, const int* seq,
+                       const int* pos, void* stream);
+/* gpt2mi_decode_step_ragged's launch list on R rows: the embedding of tok (device int64 [R]) at pos[r], LayerNorm and
+ * the skinny GEMMs at M = R, gpt2mi_attn_extend in place of the attention, and the lm_head of all R rows into
+ * plan->logits, fp32 [R][Vp]. plan->B is the number of sequences of the caches; the scratch buffers of the plan hold
+ * plan->rows rows (0: B) and R must not exceed that. A row's activations do not depend on the other rows of a launch
+ * (gpt2mi_gemm_skinny, LayerNorm), so logits row r and the caches have the bits of feeding the same tokens through
+ * gpt2mi_decode_step_ragged one position at a time. */
+int gpt2mi_decode_extend(const gpt2mi_decode_plan* plan, int R, const int64_t* tok, const int* seq, const int* pos,
+                         void* stream);
 
 #ifdef __cplusplus
 }
