@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -110,6 +110,12 @@ _SIGS = {
     # of R ints), stream; plan, R, tok, seq, pos, stream
     "gpt2mi_attn_extend": [_p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p],
     "gpt2mi_decode_extend": [_p, _c_int, _p, _p, _p, _p],
+    # v22 penalties: gpt2mi_sample_ragged's list with (const gpt2mi_penalties* pen, logits_out) before the stream;
+    # gpt2mi_decode_generate_ragged's list, then repetition, presence, frequency, gen_start (HOST array, may be NULL)
+    "gpt2mi_sample_penalized": [_p, _c_int, _c_int, _c_int, _c_float, _c_int, _c_float, _c_u64, _p, _p, ctypes.c_int64,
+                                _p, _p, _p, _c_int, _p, _p, _p, _p],
+    "gpt2mi_decode_generate_penalized": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _p, _p, _c_int,
+                                         _p, _p, _c_int, _p, _p, _c_float, _c_float, _c_float, _p],
 }
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size}
@@ -571,3 +577,44 @@ def decode_extend(plan: DecodePlan, tok, seq, pos):
     """gpt2mi_decode_extend: the step's launch list on len(pos) rows of the row map (seq, pos), into plan.logits."""
     R = len(pos)
     _call("gpt2mi_decode_extend", ctypes.byref(plan), R, _ptr(tok), _positions(seq, R), _positions(pos, R), _stream())
+
+
+# ---- v22: penalties in the sampler (csrc/sample.hip, csrc/decode.hip) -----------------------------------
+PENALTY_MAX_HISTORY = 8192  # gpt2mi.h GPT2MI_PENALTY_MAX_HISTORY
+
+
+class Penalties(ctypes.Structure):
+    """gpt2mi_penalties"""
+    _fields_ = [("repetition", _c_float), ("presence", _c_float), ("frequency", _c_float), ("hist", _p),
+                ("ld_hist", _c_int), ("hist_rows", _c_int), ("hist_row", _p), ("gen_start", _p)]
+
+
+def sample_penalized(logits, V, temperature, top_k, top_p, seed, pos, tok_out, row_id=None, eos=None, done=None,
+                     seq_out=None, probs_out=None, repetition=1.0, presence=0.0, frequency=0.0, hist=None,
+                     hist_row=None, gen_start=None, logits_out=None):
+    """gpt2mi_sample_penalized: `sample_ragged` with row b's logits moved by its history hist[hist_row[b], :pos[b]]
+    (int64 [rows, ld]; hist_row None: b), the generated part from gen_start[b] (None: 0); logits_out (fp32 [B, V]) takes
+    the penalised logits."""
+    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
+    B = logits.size(0)
+    rows, starts = _host_ints(hist_row), _host_ints(gen_start)  # (kept alive to the end of the call)
+    if any(a is not None and len(a) != B for a in (rows, starts)):
+        raise KernelError(f"hist_row / gen_start must have B={B} entries")
+    pen = Penalties(float(repetition), float(presence), float(frequency), _ptr(hist),
+                    0 if hist is None else hist.stride(0), 0 if hist is None else hist.size(0),
+                    ctypes.cast(rows, _p) if rows is not None else None,
+                    ctypes.cast(starts, _p) if starts is not None else None)
+    _call("gpt2mi_sample_penalized", _ptr(logits), logits.stride(0), B, V, t, k, p, s, _positions(pos, B),
+          _row_ids(row_id, B), e, _ptr(done), _ptr(tok_out), _ptr(seq_out), 0 if seq_out is None else seq_out.stride(0),
+          _ptr(probs_out), ctypes.byref(pen), _ptr(logits_out), _stream())
+
+
+def decode_generate_penalized(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, row_id=None, eos=None,
+                              seq=None, done=None, repetition=1.0, presence=0.0, frequency=0.0, gen_start=None):
+    """gpt2mi_decode_generate_penalized: `decode_generate_ragged` with seq as the history the sampler reads."""
+    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
+    if gen_start is not None and len(gen_start) != plan.B:
+        raise KernelError(f"gen_start has {len(gen_start)} entries for B={plan.B} rows")
+    _call("gpt2mi_decode_generate_penalized", ctypes.byref(plan), V, t, k, p, s, e, _positions(pos0, plan.B),
+          _row_ids(row_id, plan.B), n, _ptr(tok), _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(done), _stream(),
+          float(repetition), float(presence), float(frequency), _host_ints(gen_start))

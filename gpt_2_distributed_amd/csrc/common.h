@@ -30,6 +30,8 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 namespace gpt2mi {
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
+// the sampler's penalty values (gpt2mi.h v22), checked; *on = whether any of them is non-neutral (csrc/sample.hip)
+int check_penalty_values(const char* what, float repetition, float presence, float frequency, bool* on);
 }  // namespace gpt2mi
 
 #define GPT2MI_REQUIRE(cond, ...)                  \

@@ -724,10 +724,12 @@ GPT2MI_EXPORT int gpt2mi_decode_extend(const gpt2mi_decode_plan* P, int R, const
 }
 
 namespace {
-// The token loop with row b starting at pos0[b]: sample, then (but for the last token) step, n times.
+// The token loop with row b starting at pos0[b]: sample, then (but for the last token) step, n times. With non-neutral
+// penalty values (gpt2mi_decode_generate_penalized) seq is the history the sampler reads, row b's own row of it.
 int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
                          float top_p, uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
-                         int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream) {
+                         int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream, float repetition = 1.f,
+                         float presence = 0.f, float frequency = 0.f, const int* gen_start = nullptr) {
   GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
   GPT2MI_REQUIRE(V >= 1 && V <= P->Vp, "%s: V=%d not in [1, Vp=%d]", what, V, P->Vp);
   GPT2MI_REQUIRE(n >= 0, "%s: n=%d must be >= 0", what, n);
@@ -740,11 +742,22 @@ int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, f
                  max_pos, n, P->Tcap);
   GPT2MI_REQUIRE(!seq || (long long)max_pos + n <= ld_seq, "%s: max pos0=%d + n=%d exceeds ld_seq=%d", what, max_pos, n,
                  ld_seq);
+  bool on;
+  if (const int rc = gpt2mi::check_penalty_values(what, repetition, presence, frequency, &on)) return rc;
+  const gpt2mi_penalties pen = {repetition, presence, frequency, seq, ld_seq, P->B, nullptr, gen_start};
+  if (on) {
+    GPT2MI_REQUIRE(seq != nullptr, "%s: penalties need seq, the history buffer: it is NULL", what);
+    for (int b = 0; b < P->B && gen_start; ++b)
+      GPT2MI_REQUIRE(gen_start[b] >= 0 && gen_start[b] <= pos0[b], "%s: gen_start[%d]=%d not in [0, pos0=%d]", what, b,
+                     gen_start[b], pos0[b]);
+    GPT2MI_REQUIRE((long long)max_pos + n - 1 <= GPT2MI_PENALTY_MAX_HISTORY,
+                   "%s: max pos0=%d + n=%d - 1 above the history cap %d", what, max_pos, n, GPT2MI_PENALTY_MAX_HISTORY);
+  }
   GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr, "%s: tok and plan->logits must not be NULL", what);
   for (int i = 0; i < n; ++i) {
     for (int b = 0; b < P->B; ++b) rp.v[b] = pos0[b] + i;
-    int rc = gpt2mi_sample_ragged(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos, done,
-                                  tok, seq, ld_seq, nullptr, stream);
+    int rc = gpt2mi_sample_penalized(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos, done,
+                                     tok, seq, ld_seq, nullptr, on ? &pen : nullptr, nullptr, stream);
     if (rc) return rc;
     if (i + 1 < n) {
       rc = decode_step_rows(what, P, tok, rp.v, stream);
@@ -761,6 +774,15 @@ GPT2MI_EXPORT int gpt2mi_decode_generate_ragged(const gpt2mi_decode_plan* P, int
                                                 uint8_t* done, void* stream) {
   return decode_generate_rows("decode_generate_ragged", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n, tok,
                               seq, ld_seq, done, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_decode_generate_penalized(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
+                                                   float top_p, uint64_t seed, int64_t eos, const int* pos0,
+                                                   const uint32_t* row_id, int n, int64_t* tok, int64_t* seq,
+                                                   int ld_seq, uint8_t* done, void* stream, float repetition,
+                                                   float presence, float frequency, const int* gen_start) {
+  return decode_generate_rows("decode_generate_penalized", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n,
+                              tok, seq, ld_seq, done, stream, repetition, presence, frequency, gen_start);
 }
 
 GPT2MI_EXPORT int gpt2mi_decode_generate(const gpt2mi_decode_plan* P, int V, float temperature, int top_k, float top_p,

@@ -21,6 +21,15 @@
 // 50 beside it spills; the comments at tid_here, mass_above and the rolled scans say where that had to be prevented.
 // Bound: not the 200 KB read but the dependent chain after it (up to 32 + 32 probes of a barrier, an LDS round trip and
 // 50 compares or exponentials per thread): DESIGN.md "Decode" has the timings.
+//
+// Penalties (PEN, v22: kernels of their own, the plain ones are compiled as before): between the load and the temperature
+// division the row's history window moves the logits of the tokens in it (gpt2mi.h v22, generation.py apply_penalties).
+// A per-thread count array beside the row would spill, so the counts live in LDS: 16 bits per vocabulary index (bit 15:
+// seen in the prompt part, bits 0..14: occurrences in the generated part), zeroed, filled from the window with integer
+// LDS atomics (thread j takes positions j, j + 1024, ...; integer adds commute, so the table does not depend on their
+// order) and read back once per register. A (wave, chunk) pair none of whose 64 tokens occurred skips the arithmetic on
+// a ballot, so the divisions are paid for the few pairs that hold a token of the window. The cost does not depend on
+// how often a token repeats and grows by one atomic per thread for every 1024 positions.
 #include <limits.h>
 #include <math.h>
 
@@ -40,16 +49,26 @@ __device__ __forceinline__ uint32_t fkey(float f) {
 __device__ __forceinline__ float keyf(uint32_t k) {
   return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu));
 }
+// One rounded fp32 operation each, the result pinned in a register: the compiler contracts x - f * c into an fma
+// otherwise, and the bits would not be apply_penalties'.
+__device__ __forceinline__ float pinned(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
 
 // GREEDY (temperature == 0) is a kernel of its own: as one branch of the sampling kernel it kept the row live to the
 // end of the other branch, beside the exponentials.
 // The kernel's body: row b = blockIdx.x of the buffers, drawn with the key (draw_row, pos) and written to column pos of
 // seq_out.
-template <bool GREEDY>
+// PEN: `hist` is the row's history (positions [0, pos) are read, [gen_start, pos) count as generated), rp / pp / fp the
+// repetition, presence and frequency values, logits_out the row-major [B][V] copy of the penalised row (may be NULL).
+template <bool GREEDY, bool PEN>
 __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int ldl, int V, float temperature,
                                            int top_k, float top_p, uint64_t seed, uint32_t draw_row, int pos,
                                            int64_t eos, uint8_t* __restrict__ done, int64_t* __restrict__ tok_out,
-                                           int64_t* __restrict__ seq_out, int ld_seq, float* __restrict__ probs_out) {
+                                           int64_t* __restrict__ seq_out, int ld_seq, float* __restrict__ probs_out,
+                                           const int64_t* hist = nullptr, int gen_start = 0, float rp = 1.f,
+                                           float pp = 0.f, float fp = 0.f, float* __restrict__ logits_out = nullptr) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const float* lp = logits + (size_t)b * ldl;
   __shared__ uint32_t red[2][SM_WAVES];
@@ -120,6 +139,42 @@ __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int
     const int t = tid_here();
 #pragma unroll
     for (int i = 0; i < SM_NE; ++i) x[i] = i * SM_THREADS + t < V ? x[i] : __builtin_nanf("");
+  }
+  if constexpr (PEN) {
+    __shared__ __attribute__((aligned(16))) uint32_t cnt[GPT2MI_SAMPLE_MAX_V / 2];  // two 16-bit entries a word
+    for (int i = tid; i < GPT2MI_SAMPLE_MAX_V / 8; i += SM_THREADS) reinterpret_cast<uint4*>(cnt)[i] = uint4{0, 0, 0, 0};
+    __syncthreads();
+    for (int j = tid; j < pos; j += SM_THREADS) {  // (pos <= ld_hist and <= the cap: the entry's checks)
+      const uint64_t t = (uint64_t)hist[j];
+      if (t < (uint64_t)V) {  // the one guard of a history value, before it forms any index (negative: huge unsigned)
+        const uint32_t sh = ((uint32_t)t & 1u) * 16u;
+        if (j >= gen_start)
+          atomicAdd(&cnt[(uint32_t)t >> 1], 1u << sh);  // (at most the cap, 8192 < 2^15: no carry into bit 15)
+        else
+          atomicOr(&cnt[(uint32_t)t >> 1], 0x8000u << sh);
+      }
+    }
+    __syncthreads();
+    const uint16_t* c16 = reinterpret_cast<const uint16_t*>(cnt);
+#pragma unroll
+    for (int i = 0; i < SM_NE; ++i) {
+      const uint32_t e = c16[i * SM_THREADS + tid_here()];
+      if (__ballot(e != 0)) {  // (wave-uniform) one of this wave's 64 tokens of chunk i is in the window
+        const float c = (float)(e & 0x7FFFu);
+        float v = x[i];
+        if (rp != 1.f && e != 0) v = pinned(v < 0.f ? v * rp : v / rp);
+        if (fp != 0.f && c > 0.f) v = pinned(v - pinned(fp * c));
+        if (pp != 0.f && c > 0.f) v = pinned(v - pp);
+        x[i] = v;
+      }
+    }
+    if (logits_out) {
+#pragma unroll
+      for (int i = 0; i < SM_NE; ++i) {
+        const int e = i * SM_THREADS + tid_here();
+        if (e < V) logits_out[(size_t)b * V + e] = x[i];
+      }
+    }
   }
   if constexpr (!GREEDY) {  // IEEE division: the bits of torch's logits / temperature
 #pragma unroll
@@ -329,14 +384,38 @@ __global__ __launch_bounds__(SM_THREADS) void sample_kernel(const float* __restr
                                                             RowKeys keys, int64_t eos, uint8_t* __restrict__ done,
                                                             int64_t* __restrict__ tok_out, int64_t* __restrict__ seq_out,
                                                             int ld_seq, float* __restrict__ probs_out) {
-  sample_row<GREEDY>(logits, ldl, V, temperature, top_k, top_p, seed, keys.row_id[blockIdx.x], keys.pos[blockIdx.x], eos,
-                     done, tok_out, seq_out, ld_seq, probs_out);
+  sample_row<GREEDY, false>(logits, ldl, V, temperature, top_k, top_p, seed, keys.row_id[blockIdx.x],
+                            keys.pos[blockIdx.x], eos, done, tok_out, seq_out, ld_seq, probs_out);
+}
+
+// The penalised form. Per row, the entry's validated host arrays by value again: which row of hist it reads and where
+// its generated part starts.
+struct PenRows {
+  int hist_row[GPT2MI_DECODE_MAX_B];
+  int gen_start[GPT2MI_DECODE_MAX_B];
+};
+
+template <bool GREEDY>
+__global__ __launch_bounds__(SM_THREADS) void penalized_kernel(const float* __restrict__ logits, int ldl, int V,
+                                                               float temperature, int top_k, float top_p,
+                                                               uint64_t seed, RowKeys keys, int64_t eos,
+                                                               uint8_t* __restrict__ done,
+                                                               int64_t* __restrict__ tok_out, int64_t* seq_out,
+                                                               int ld_seq, float* __restrict__ probs_out,
+                                                               const int64_t* hist, int ld_hist, PenRows rows, float rp,
+                                                               float pp, float fp, float* __restrict__ logits_out) {
+  const int b = blockIdx.x;
+  sample_row<GREEDY, true>(logits, ldl, V, temperature, top_k, top_p, seed, keys.row_id[b], keys.pos[b], eos, done,
+                           tok_out, seq_out, ld_seq, probs_out, hist + (size_t)rows.hist_row[b] * ld_hist,
+                           rows.gen_start[b], rp, pp, fp, logits_out);
 }
 
 // gpt2mi_sample_ragged, and gpt2mi_sample with every pos[b] equal and no row_id; `what` is the entry's name in messages.
+// `pen` (may be NULL) and logits_out: gpt2mi_sample_penalized's.
 int sample_rows(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
                 uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done, int64_t* tok_out,
-                int64_t* seq_out, int ld_seq, float* probs_out, void* stream) {
+                int64_t* seq_out, int ld_seq, float* probs_out, void* stream, const gpt2mi_penalties* pen = nullptr,
+                float* logits_out = nullptr) {
   GPT2MI_REQUIRE(B >= 1 && B <= GPT2MI_DECODE_MAX_B && V >= 1, "%s: B=%d not in [1, %d] or V=%d not positive", what, B,
                  GPT2MI_DECODE_MAX_B, V);
   GPT2MI_REQUIRE(V <= GPT2MI_SAMPLE_MAX_V, "%s: V=%d above the kernel's row capacity %d", what, V, GPT2MI_SAMPLE_MAX_V);
@@ -352,7 +431,42 @@ int sample_rows(const char* what, const float* logits, int ldl, int B, int V, fl
     keys.pos[b] = pos[b];
     keys.row_id[b] = row_id ? row_id[b] : (uint32_t)b;
   }
+  bool on = false;
+  PenRows rows = {};
+  if (pen) {
+    if (const int rc = gpt2mi::check_penalty_values(what, pen->repetition, pen->presence, pen->frequency, &on)) return rc;
+    if (on) {
+      GPT2MI_REQUIRE(pen->hist != nullptr, "%s: penalties need the history buffer: hist is NULL", what);
+      for (int b = 0; b < B; ++b) {
+        const int hr = pen->hist_row ? pen->hist_row[b] : b, gs = pen->gen_start ? pen->gen_start[b] : 0;
+        GPT2MI_REQUIRE(pos[b] <= GPT2MI_PENALTY_MAX_HISTORY, "%s: pos[%d]=%d above the history cap %d", what, b, pos[b],
+                       GPT2MI_PENALTY_MAX_HISTORY);
+        GPT2MI_REQUIRE(pen->ld_hist >= pos[b], "%s: ld_hist=%d < pos[%d]=%d", what, pen->ld_hist, b, pos[b]);
+        GPT2MI_REQUIRE(hr >= 0 && hr < pen->hist_rows, "%s: hist_row[%d]=%d not in [0, hist_rows=%d)", what, b, hr,
+                       pen->hist_rows);
+        GPT2MI_REQUIRE(gs >= 0 && gs <= pos[b], "%s: gen_start[%d]=%d not in [0, pos=%d]", what, b, gs, pos[b]);
+        rows.hist_row[b] = hr;
+        rows.gen_start[b] = gs;
+      }
+    }
+  }
   GPT2MI_REQUIRE(logits && tok_out, "%s: logits and tok_out must not be NULL", what);
+  if (on) {
+    if (temperature == 0.f)
+      penalized_kernel<true><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(
+          logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out,
+          pen->hist, pen->ld_hist, rows, pen->repetition, pen->presence, pen->frequency, logits_out);
+    else
+      penalized_kernel<false><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(
+          logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out,
+          pen->hist, pen->ld_hist, rows, pen->repetition, pen->presence, pen->frequency, logits_out);
+    return gpt2mi::check_launch(what);
+  }
+  if (logits_out) {  // neutral values: the logits themselves
+    const hipError_t e = hipMemcpy2DAsync(logits_out, sizeof(float) * V, logits, sizeof(float) * ldl, sizeof(float) * V,
+                                          B, hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    GPT2MI_REQUIRE(e == hipSuccess, "%s: copying the logits to logits_out: %s", what, hipGetErrorString(e));
+  }
   if (temperature == 0.f)
     sample_kernel<true><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(logits, ldl, V, temperature, top_k, top_p, seed, keys,
                                                                    eos, done, tok_out, seq_out, ld_seq, probs_out);
@@ -363,6 +477,26 @@ int sample_rows(const char* what, const float* logits, int ldl, int B, int V, fl
 }
 
 }  // namespace
+
+namespace gpt2mi {
+int check_penalty_values(const char* what, float repetition, float presence, float frequency, bool* on) {
+  GPT2MI_REQUIRE(repetition > 0.f && repetition < INFINITY, "%s: repetition=%g must be finite and > 0 (1: off)", what,
+                 (double)repetition);  // (NaN fails too)
+  GPT2MI_REQUIRE(fabsf(presence) < INFINITY, "%s: presence=%g must be finite (0: off)", what, (double)presence);
+  GPT2MI_REQUIRE(fabsf(frequency) < INFINITY, "%s: frequency=%g must be finite (0: off)", what, (double)frequency);
+  *on = repetition != 1.f || presence != 0.f || frequency != 0.f;
+  return 0;
+}
+}  // namespace gpt2mi
+
+GPT2MI_EXPORT int gpt2mi_sample_penalized(const float* logits, int ldl, int B, int V, float temperature, int top_k,
+                                          float top_p, uint64_t seed, const int* pos, const uint32_t* row_id,
+                                          int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq,
+                                          float* probs_out, const gpt2mi_penalties* pen, float* logits_out,
+                                          void* stream) {
+  return sample_rows("sample_penalized", logits, ldl, B, V, temperature, top_k, top_p, seed, pos, row_id, eos, done,
+                     tok_out, seq_out, ld_seq, probs_out, stream, pen, logits_out);
+}
 
 GPT2MI_EXPORT int gpt2mi_sample_ragged(const float* logits, int ldl, int B, int V, float temperature, int top_k,
                                        float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos,

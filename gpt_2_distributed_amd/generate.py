@@ -1,6 +1,6 @@
 """Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
 --prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B
---draft_tokens K]``.
+--draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -43,6 +43,13 @@ def parse_args(argv=None):
     p.add_argument("--draft_tokens", type=int, default=None,
                    help="one prompt, --sampler device: verify up to this many prompt-lookup draft tokens per pass over "
                         "the weights (the same tokens as without; batch * (draft_tokens + 1) <= 64)")
+    p.add_argument("--repetition_penalty", type=float, default=1.0,
+                   help="HF's rule: the logit of a token of the prompt or the output so far is divided by this "
+                        "(multiplied if negative); 1: off")
+    p.add_argument("--presence_penalty", type=float, default=0.0,
+                   help="subtracted from the logit of every token generated so far (OpenAI / vLLM); 0: off")
+    p.add_argument("--frequency_penalty", type=float, default=0.0,
+                   help="times the number of times a token was generated so far, subtracted from its logit; 0: off")
     return p.parse_args(argv)
 
 
@@ -75,12 +82,14 @@ def main(argv=None) -> int:
     if not all(prompts):
         raise SystemExit("an empty prompt (--prompt_ids / --prompts_file)")
     model = load_model(a.checkpoint, a.model)
+    pen = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
+               frequency_penalty=a.frequency_penalty)
     if len(prompts) > 1:
         if a.sampler != "device" and a.temperature != 0:
             raise SystemExit("several prompts are served by generate_many, which draws on the device: --sampler device")
         outs = model.generate_many([torch.tensor(q, dtype=torch.int64, device="cuda:0") for q in prompts],
                                    a.max_new_tokens, batch_size=a.batch, temperature=a.temperature, top_k=a.top_k,
-                                   top_p=a.top_p, seed=a.seed, eos_token_id=a.eos_token_id)
+                                   top_p=a.top_p, seed=a.seed, eos_token_id=a.eos_token_id, **pen)
         for row in outs:
             print(json.dumps(row.tolist()))
         return 0
@@ -91,7 +100,7 @@ def main(argv=None) -> int:
     how = (dict(seed=a.seed, draft_tokens=a.draft_tokens) if a.sampler == "device"
            else dict(generator=torch.Generator(device="cuda:0").manual_seed(a.seed)))
     out = model.generate(idx, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
-                         eos_token_id=a.eos_token_id, **how)
+                         eos_token_id=a.eos_token_id, **how, **pen)
     for row in out.tolist():
         print(json.dumps(row))
     return 0

@@ -137,6 +137,63 @@ def sample_reference(logits: torch.Tensor, temperature: float, top_k: Optional[i
     return tok, pk / Z
 
 
+# ---- penalties: the rule gpt2mi_sample_penalized applies in front of sample_reference, executable ---------------------
+def _check_penalties(repetition_penalty, presence_penalty, frequency_penalty):
+    """The three values as floats and whether any is non-neutral, or a ValueError."""
+    rp, pp, fp = float(repetition_penalty), float(presence_penalty), float(frequency_penalty)
+    if not 0 < rp < float("inf"):  # (NaN too)
+        raise ValueError(f"repetition_penalty must be finite and > 0 (got {repetition_penalty}); 1 turns it off")
+    if not abs(pp) < float("inf"):
+        raise ValueError(f"presence_penalty must be finite (got {presence_penalty}); 0 turns it off")
+    if not abs(fp) < float("inf"):
+        raise ValueError(f"frequency_penalty must be finite (got {frequency_penalty}); 0 turns it off")
+    return rp, pp, fp, (rp, pp, fp) != (1.0, 0.0, 0.0)
+
+
+def apply_penalties(logits: torch.Tensor, history: torch.Tensor, lens, gen_start, repetition_penalty: float = 1.0,
+                    presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> torch.Tensor:
+    """The logits a penalised draw is made from: fp32 [B, V] from logits [B, V] and the rows' token histories (pure
+    torch, any device; what csrc/sample.hip computes bit for bit).
+
+    Row b's history is ``history[b, :lens[b]]`` (integer [B, T]); entries outside [0, V) are ignored. For vocabulary
+    index i, seen_i = i occurs in it (prompt and generated tokens: the scope of HF's ``repetition_penalty``) and c_i =
+    its occurrences in ``history[b, gen_start[b]:lens[b]]`` (generated tokens: the OpenAI / vLLM scope of the other
+    two; ``gen_start`` None: 0). In this order, each operation one fp32 operation rounded to nearest:
+    ``repetition_penalty != 1`` and seen_i: ``x = x * rp if x < 0 else x / rp`` (0 is divided);
+    ``frequency_penalty != 0`` and c_i > 0: ``x = x - (fp * float(c_i))``; ``presence_penalty != 0`` and c_i > 0:
+    ``x = x - pp``. Neutral values (1, 0, 0) return the logits' bits."""
+    rp, pp, fp, on = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+    if logits.dim() != 2 or history.dim() != 2 or history.size(0) != logits.size(0):
+        raise ValueError(f"apply_penalties takes logits [B, V] and history [B, T] (got {tuple(logits.shape)}, "
+                         f"{tuple(history.shape)})")
+    x = logits.float()
+    if not on:
+        return x
+    B, V = x.shape
+    dev = x.device
+    as_t = lambda v: torch.as_tensor(v, device=dev).long().reshape(B)  # noqa: E731
+    lens_t = as_t(lens)
+    start_t = torch.zeros_like(lens_t) if gen_start is None else as_t(gen_start)
+    if bool((lens_t < 0).any() | (lens_t > history.size(1)).any() | (start_t < 0).any() | (start_t > lens_t).any()):
+        raise ValueError(f"lens must lie in [0, T={history.size(1)}] and gen_start in [0, lens]")
+    hist = history.to(dev).long()
+    at = torch.arange(hist.size(1), device=dev)[None]
+    valid = (at < lens_t[:, None]) & (hist >= 0) & (hist < V)
+    idx = hist.clamp(0, V - 1)
+    seen = torch.zeros(B, V, dtype=torch.int64, device=dev).scatter_add_(1, idx, valid.long()) > 0
+    generated = valid & (at >= start_t[:, None])
+    count = torch.zeros(B, V, dtype=torch.int64, device=dev).scatter_add_(1, idx, generated.long())
+    # (0-dim tensors: a Python scalar divisor would become a multiplication by its reciprocal on the device)
+    f32 = lambda v: torch.full((), v, dtype=F32, device=dev)  # noqa: E731
+    if rp != 1.0:
+        x = torch.where(seen, torch.where(x < 0, x * f32(rp), x / f32(rp)), x)
+    if fp != 0.0:
+        x = torch.where(count > 0, x - (f32(fp) * count.float()), x)
+    if pp != 0.0:
+        x = torch.where(count > 0, x - f32(pp), x)
+    return x
+
+
 def _check_lens(lens, B: int, P: int) -> List[int]:
     """``lens`` as a list of B ints in [1, P], or a ValueError."""
     lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
@@ -408,31 +465,71 @@ class DecodeSession:
                                       f"(vocab_size {self.cfg.vocab_size})")
         self._ready(False)
 
+    def _penalties(self, repetition_penalty, presence_penalty, frequency_penalty, gen_start, hist, name: str, last: int):
+        """The penalty keywords of the C entries (``{}`` when the values are neutral): ``hist`` is the history buffer
+        (argument ``name``), ``last`` the largest position a draw of the call reads its history up to."""
+        rp, pp, fp, on = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        if not on:
+            return {}
+        if hist is None:
+            raise ValueError(f"penalties read the rows' tokens: pass {name}, int64 [B={self.B}, T], holding row b's "
+                             f"tokens at [0, lens[b])")
+        if (hist.dtype != torch.int64 or hist.dim() != 2 or hist.size(0) != self.B or hist.stride(1) != 1
+                or not hist.is_cuda):
+            raise ValueError(f"{name} must be a device int64 [B={self.B}, T] with contiguous rows")
+        if last > K.PENALTY_MAX_HISTORY:
+            raise NotImplementedError(f"the penalised sampler reads a history of up to {K.PENALTY_MAX_HISTORY} tokens "
+                                      f"(GPT2MI_PENALTY_MAX_HISTORY); this call reaches position {last}")
+        if hist.size(1) < last:
+            raise ValueError(f"{name} holds {hist.size(1)} positions, the call reads up to {last}")
+        start = [0] * self.B if gen_start is None else [int(g) for g in gen_start]
+        if len(start) != self.B or not all(0 <= g <= m for g, m in zip(start, self.lens)):
+            raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
+        return dict(repetition=rp, presence=pp, frequency=fp, gen_start=start)
+
     @torch.no_grad()
     def sample(self, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
-               seed: int = 0, row_id: Optional[Sequence[int]] = None) -> torch.Tensor:
+               seed: int = 0, row_id: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
+               presence_penalty: float = 0.0, frequency_penalty: float = 0.0, gen_start: Optional[Sequence[int]] = None,
+               history: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Tokens [B] (int64, device) for position ``lens[b]`` from the logits of the last ``prefill`` / ``step``: one
         launch, no host synchronisation. Row b's token is a function of (its logits, the parameters, seed, its draw key,
         its position): ``sample_reference`` with ``uniform_at(seed, row_id[b], lens[b])``; ``row_id`` (B ints, default
-        the row numbers) lets a sequence keep its draw stream whichever row it sits in."""
+        the row numbers) lets a sequence keep its draw stream whichever row it sits in.
+
+        With a non-neutral ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` the logits are first
+        moved by ``apply_penalties`` over ``history[b, :lens[b]]`` (device int64 [B, T], required then: ``ValueError``
+        without), the generated part from ``gen_start[b]`` (default 0); ``logits`` itself is not modified."""
         self._check_sampler(temperature, top_p, seed)
         if self._drawn:
             raise RuntimeError("the logits are those generate() drew its last token from: step() that token first")
+        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, history, "history",
+                              max(self.lens))
         out = torch.empty(self.B, dtype=torch.int64, device=self.logits.device)
-        K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, out,
-                        row_id=_check_row_id(row_id, self.B))
+        if pen:
+            K.sample_penalized(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, out,
+                               row_id=_check_row_id(row_id, self.B), hist=history, **pen)
+        else:
+            K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, out,
+                            row_id=_check_row_id(row_id, self.B))
         return out
 
     @torch.no_grad()
     def generate(self, n: int, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  seed: int = 0, eos_token_id: Optional[int] = None, seq: Optional[torch.Tensor] = None,
-                 done: Optional[torch.Tensor] = None, row_id: Optional[Sequence[int]] = None) -> torch.Tensor:
+                 done: Optional[torch.Tensor] = None, row_id: Optional[Sequence[int]] = None,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                 gen_start: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Draw row b's tokens of positions ``lens[b] .. lens[b] + n - 1`` in one C call (gpt2mi_decode_generate_ragged:
         sample, step, sample, ... on the stream, no Python and no synchronisation in between). The tokens go to column
         ``lens[b] + i`` of ``seq`` (int64 [B, >= max(lens) + n], optional); with ``eos_token_id``, ``done`` (uint8 [B])
         marks finished rows, which keep emitting eos. Returns the newest tokens [B] (a buffer the next call overwrites).
         The last token drawn is not stepped until the next ``generate`` (which does it first), ``flush`` or ``step``.
-        ``row_id`` as for ``sample``."""
+        ``row_id`` as for ``sample``.
+
+        With non-neutral penalties (as for ``sample``) ``seq`` is the history and is required (``ValueError`` without):
+        row b holds its tokens at ``seq[b, :lens[b]]`` on entry, prompt included, and the loop reads what it appends
+        (gpt2mi_decode_generate_penalized); ``gen_start[b]`` (default 0) is where the row's generated part begins."""
         self._check_sampler(temperature, top_p, seed)
         n = int(n)
         if n < 1:
@@ -444,10 +541,16 @@ class DecodeSession:
             raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
         if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
             raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
+        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, seq, "seq",
+                              max(self.lens) + int(self._drawn) + n - 1)
         self.flush()  # the token the previous call ended on
         done = done if eos_token_id is not None else None
-        K.decode_generate_ragged(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
-                                 self._tok, row_id=row_id, eos=eos_token_id, seq=seq, done=done)
+        if pen:
+            K.decode_generate_penalized(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
+                                        self._tok, row_id=row_id, eos=eos_token_id, seq=seq, done=done, **pen)
+        else:
+            K.decode_generate_ragged(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
+                                     self._tok, row_id=row_id, eos=eos_token_id, seq=seq, done=done)
         self.lens = [m + n - 1 for m in self.lens]
         self._drawn = True
         return self._tok
@@ -513,24 +616,35 @@ class DecodeSession:
 
     def _verify(self, toks: List[int], seqs: List[int], poss: List[int], keys: List[int], sampler) -> List[int]:
         """One ``gpt2mi_decode_extend`` over the rows (token, sequence, position) and one ``gpt2mi_sample_ragged`` over
-        their logits, row r at position ``poss[r] + 1`` with draw key ``keys[r]``; the R tokens, read back."""
+        their logits, row r at position ``poss[r] + 1`` with draw key ``keys[r]``; the R tokens, read back.
+
+        ``sampler`` is (temperature, top_k, top_p, seed) or, penalised, those and (the penalty keywords, seq): see
+        ``verify_history``."""
         V = self.cfg.vocab_size
         if not all(0 <= t < V for t in toks):
             raise ValueError(f"draft tokens must lie in [0, vocab_size={V}) (got {toks})")
         scratch, plan = self._rows_plan()
         R = len(toks)
-        K.decode_extend(plan, torch.tensor(toks, dtype=torch.int64, device=self.device), seqs, poss)
+        tok_t = torch.tensor(toks, dtype=torch.int64, device=self.device)
+        K.decode_extend(plan, tok_t, seqs, poss)
         out = torch.empty(R, dtype=torch.int64, device=self.device)
-        temperature, top_k, top_p, seed = sampler
-        K.sample_ragged(scratch["logits"][:R], V, temperature, top_k, top_p, seed, [p + 1 for p in poss], out,
-                        row_id=keys)
+        temperature, top_k, top_p, seed = sampler[:4]
+        pen = verify_history(sampler, tok_t, seqs, poss)
+        if pen:
+            K.sample_penalized(scratch["logits"][:R], V, temperature, top_k, top_p, seed, [p + 1 for p in poss], out,
+                               row_id=keys, **pen)
+        else:
+            K.sample_ragged(scratch["logits"][:R], V, temperature, top_k, top_p, seed, [p + 1 for p in poss], out,
+                            row_id=keys)
         return out.tolist()
 
     @torch.no_grad()
     def speculate(self, n: int, k: int, draft_fn=None, temperature: float = 1.0, top_k: Optional[int] = None,
                   top_p: Optional[float] = None, seed: int = 0, eos_token_id: Optional[int] = None,
                   seq: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
-                  row_id: Optional[Sequence[int]] = None) -> dict:
+                  row_id: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
+                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                  gen_start: Optional[Sequence[int]] = None) -> dict:
         """``generate(n, ...)`` with up to ``k`` drafted tokens of every row verified per pass over the weights: the same
         tokens in ``seq``, the same ``done`` flags and, with the last token drawn and not stepped, the same ``_tok``,
         ``lens`` and ``logits``, in fewer passes when the drafts are right. ``B * (k + 1) <= 64``.
@@ -549,7 +663,11 @@ class DecodeSession:
         the eos was drawn from (the plain call goes on stepping eos to ``lens + n - 1``); ``seq`` holds eos from there on
         as after the plain call. One host synchronisation per iteration is inherent: the positions of the next call are
         host arrays that depend on the tokens read back. Returns ``{"calls", "drafted", "accepted", "tokens"}``: verify
-        calls, draft tokens proposed and accepted, tokens drawn."""
+        calls, draft tokens proposed and accepted, tokens drawn.
+
+        Penalties as for ``generate`` (``seq`` required), and as exact: the verify call's row r draws at ``poss[r] + 1``
+        from the history of its sequence up to and including the row's token (``_verify``), which is the history the
+        one-token loop has there."""
         n, k = int(n), int(k)
         if n < 1 or k < 0:
             raise ValueError(f"speculate takes n >= 1 and k >= 0 (got n={n}, k={k})")
@@ -563,16 +681,22 @@ class DecodeSession:
             raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
         if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
             raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
+        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, seq, "seq",
+                              max(self.lens) + int(self._drawn) + n - 1)
         self.flush()
         done = done if eos_token_id is not None else None
         lens0 = list(self.lens)
-        K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, self._tok,
-                        row_id=row_id, eos=eos_token_id, done=done)
+        if pen:
+            K.sample_penalized(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, self._tok,
+                               row_id=row_id, eos=eos_token_id, done=done, hist=seq, **pen)
+        else:
+            K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, self._tok,
+                            row_id=row_id, eos=eos_token_id, done=done)
         first = self._tok.tolist()
         history = [[] for _ in range(self.B)] if seq is None else [r[:m] for r, m in zip(seq.tolist(), lens0)]
         keys = list(range(self.B)) if row_id is None else row_id
         new, stats = speculate_loop(self, n, k, draft_fn or ngram_draft, eos_token_id, history, first, keys,
-                                    (temperature, top_k, top_p, seed))
+                                    (temperature, top_k, top_p, seed) + (((pen, seq),) if pen else ()))
         self._tok.copy_(torch.tensor([t[-1] for t in new], dtype=torch.int64))
         self._drawn = True
         if eos_token_id is not None:
@@ -582,6 +706,20 @@ class DecodeSession:
             cols = torch.tensor(lens0, device=self.device)[:, None] + torch.arange(n, device=self.device)[None]
             seq.scatter_(1, cols, torch.tensor(new, dtype=torch.int64, device=self.device))
         return stats
+
+
+def verify_history(sampler, tok_t: torch.Tensor, seqs: List[int], poss: List[int]) -> dict:
+    """The history of a penalised verify call (``{}`` when ``sampler`` has no fifth entry): row r draws at
+    ``poss[r] + 1`` from the tokens of sequence ``seqs[r]`` up to and including its own, ``tok_t[r]``, which one index
+    write puts at ``seq[seqs[r], poss[r]]`` (a rejected draft stays above ``lens``, where nothing reads it before it is
+    overwritten). That is the history the one-token loop has at that position, so the draws stay those of the loop.
+    Returns gpt2mi_sample_penalized's keywords: the values, ``hist = seq``, ``hist_row = seqs`` and each row's
+    ``gen_start``, its sequence's."""
+    if len(sampler) < 5:
+        return {}
+    pen, seq = sampler[4]
+    seq.index_put_((torch.tensor(seqs, device=seq.device), torch.tensor(poss, device=seq.device)), tok_t)
+    return dict(pen, hist=seq, hist_row=list(seqs), gen_start=[pen["gen_start"][b] for b in seqs])
 
 
 def ngram_draft(history: List[int], k: int, max_ngram: int = 3) -> List[int]:
@@ -656,8 +794,11 @@ def _pad_prompts(prompts, pad: int):
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
              generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
              top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens: Optional[Sequence[int]] = None,
-             pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None, draft_fn=None) -> torch.Tensor:
+             pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None, draft_fn=None,
+             repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+             frequency_penalty: float = 0.0) -> torch.Tensor:
     """``GPT2.generate``: see there."""
+    penalties = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
     pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
     if isinstance(idx, (list, tuple)):
         if prompt_lens is not None:
@@ -695,14 +836,18 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
     if prompt_lens is None and n == 0:
         return idx.clone()
     return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad,
-                     None if draft_tokens is None else (int(draft_tokens), draft_fn))
+                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties)
 
 
-def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad, draft=None):
+def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad, draft=None,
+              penalties=(1.0, 0.0, 0.0, False)):
     """The token loop of ``generate``: [B, P + m], row b = its prompt, its m new tokens from column lens[b] on, then
     ``pad`` (``lens`` None: every row holds P tokens and nothing is padded). m = n, or with eos the number of tokens by
     which every row has emitted it. Host sampler: new tokens are collected per step and scattered into the buffer that
-    holds the prompts; device sampler: gpt2mi_sample_ragged writes row b's token of step i to column lens[b] + i of it."""
+    holds the prompts; device sampler: gpt2mi_sample_ragged writes row b's token of step i to column lens[b] + i of it.
+    ``penalties`` = (repetition, presence, frequency, any non-neutral): that buffer is then the history too, with the
+    generated part starting at lens[b]; the host sampler writes each step's tokens into it as it goes and passes its
+    logits through apply_penalties."""
     B, P = idx.shape
     dev = idx.device
     if eos_token_id is not None and seed is not None and not 0 <= eos_token_id < model.config.vocab_size:
@@ -716,12 +861,15 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     idx = torch.where(cols[:, :P] < lens_t[:, None], idx, torch.zeros_like(idx))  # (a valid token id as padding)
     sess = DecodeSession(model, B, P + n)
     logits = sess.prefill(idx, lens)
+    rp, pp, fp, on = penalties
+    starts = lens_t.tolist()
+    pen = dict(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp, gen_start=starts) if on else {}
     if seed is not None:
         done = None if eos_token_id is None else torch.zeros(B, dtype=torch.uint8, device=dev)
         if draft is None:
-            made = _device_loop(sess, n, temperature, top_k, top_p, seed, eos_token_id, seq, done)
+            made = _device_loop(sess, n, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen)
         else:  # (draft = (k, draft_fn): the same tokens, up to k + 1 of a row per pass over the weights)
-            sess.speculate(n, draft[0], draft[1], temperature, top_k, top_p, seed, eos_token_id, seq, done)
+            sess.speculate(n, draft[0], draft[1], temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen)
             made = n
         if eos_token_id is None:
             return seq
@@ -730,11 +878,15 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
         toks = []
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         for i in range(n):
+            if on:
+                logits = apply_penalties(logits, seq, lens_t + i, lens_t, rp, pp, fp)
             nxt = sample_next(logits, temperature, top_k, generator, top_p)
             if eos_token_id is not None:
                 nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)  # a finished row keeps emitting eos
                 done = done | (nxt == eos_token_id)
             toks.append(nxt)
+            if on:  # the next step's history
+                seq.scatter_(1, (lens_t + i)[:, None], nxt[:, None])
             if eos_token_id is not None and bool(done.all()):
                 break
             if i + 1 < n:
@@ -750,14 +902,14 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     return torch.where(keep, seq[:, :P + made], torch.full_like(seq[:, :P + made], pad))
 
 
-def _device_loop(sess: DecodeSession, n, temperature, top_k, top_p, seed, eos_token_id, seq, done) -> int:
+def _device_loop(sess: DecodeSession, n, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen) -> int:
     """``n`` tokens per row with the sampler on the device, into ``seq``; the number issued. Without eos one C call and
     nothing read back; with eos EOS_CHUNK tokens at a time, the done flags read once per chunk, until every row has
     emitted it (the caller cuts the result after the column by which they all have)."""
     made = 0
     while made < n:
         m = n - made if eos_token_id is None else min(EOS_CHUNK, n - made)
-        sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done)
+        sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen)
         made += m
         if eos_token_id is not None and bool(done.all()):
             break
@@ -767,8 +919,11 @@ def _device_loop(sess: DecodeSession, n, temperature, top_k, top_p, seed, eos_to
 @torch.no_grad()
 def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                   top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
-                  eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None) -> List[torch.Tensor]:
+                  eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
+                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                  frequency_penalty: float = 0.0) -> List[torch.Tensor]:
     """``GPT2.generate_many``: see there."""
+    penalties = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
     if generator is not None:
         raise ValueError("generate_many draws on the device from (seed, prompt index, position): a torch.Generator is "
                          "one stream shared by the rows of a batch, so its draws would depend on the batching")
@@ -793,17 +948,24 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
     _check_model(model)
     # (at least a chunk and two positions, so that a dummy row of one token need not start over within a chunk)
     sess = DecodeSession(model, int(batch_size), min(model.config.n_positions, max(longest + n, EOS_CHUNK + 2)))
-    return serve_prompts(sess, [p.long() for p in prompts], n, temperature, top_k, top_p, seed, eos_token_id)
+    return serve_prompts(sess, [p.long() for p in prompts], n, temperature, top_k, top_p, seed, eos_token_id, penalties)
 
 
-def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, eos_token_id) -> List[torch.Tensor]:
+def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, eos_token_id,
+                  penalties=(1.0, 0.0, 0.0, False)) -> List[torch.Tensor]:
     """The loop of ``generate_many`` over a session (anything with DecodeSession's ``B``, ``Tcap``, ``lens``,
     ``device``, ``refill``, ``generate`` and ``flush``). Rows are slots: a slot holds prompt ``owner[row]`` (None: a
     dummy of one token whose output is dropped) and draws with ``row_id = owner[row]``. The device loop runs in chunks
     of at most EOS_CHUNK tokens, cut so that no live row passes its ``n`` tokens; after a chunk the done flags and the
     tokens are read once, finished rows (eos, or n tokens) are harvested, cut after their first eos, and refilled with
-    the next pending prompt."""
+    the next pending prompt.
+
+    ``penalties`` = (repetition, presence, frequency, any non-neutral). With them ``seq`` is the history the sampler
+    reads: a slot's prompt is written to ``seq[row, :len]`` when it is filled (otherwise seq holds generated tokens only)
+    and the generated part starts at the prompt's length. A row reads its own row below its own position only, so a
+    prompt's continuation still does not depend on what it is batched with."""
     B, dev = sess.B, sess.device
+    rp, pp, fp, on = penalties
     out: List[Optional[torch.Tensor]] = [None] * len(prompts)
     pending = list(range(len(prompts)))[::-1]  # (pop() serves them in input order)
     owner: List[Optional[int]] = [None] * B
@@ -819,6 +981,8 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
         sess.refill(row, prompt)
         start[row], made[row] = prompt.numel(), 0
         done[row] = 0
+        if on:
+            seq[row, :prompt.numel()] = prompt
 
     for row in range(B):
         fill(row)
@@ -827,8 +991,9 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
         for r in range(B):  # a dummy row that a chunk would take past the cache starts over
             if owner[r] is None and sess.lens[r] + m + 1 > sess.Tcap:
                 fill(r)
+        pen = dict(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp, gen_start=list(start)) if on else {}
         sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done,
-                      row_id=[DUMMY_ID if o is None else o for o in owner])
+                      row_id=[DUMMY_ID if o is None else o for o in owner], **pen)
         sess.flush()  # every row's logits are now those of its next position: a refilled row joins on equal terms
         host = torch.cat([done.to(torch.int64)[:, None], seq], dim=1).cpu()  # the one read of the chunk
         for r in range(B):

@@ -345,7 +345,8 @@ class GPT2(nn.Module):
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
                  top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens=None,
                  pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None,
-                 draft_fn=None) -> torch.Tensor:
+                 draft_fn=None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                 frequency_penalty: float = 0.0) -> torch.Tensor:
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
         filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
@@ -372,6 +373,14 @@ class GPT2(nn.Module):
         k) -> tokens`` proposes them (default ``generation.ngram_draft``: what followed the most recent earlier
         occurrence of the sequence's last tokens). Without ``seed``, or with ``B * (k + 1) > 64``, ``ValueError``.
 
+        Penalties, for both samplers, ``prompt_lens`` and ``draft_tokens`` alike (``generation.apply_penalties`` is the
+        rule; with ``seed`` it runs inside the sampling kernel, from the token buffer the device loop already keeps):
+        ``repetition_penalty`` (HF: a token that occurs in the row's prompt or among its new tokens has its logit
+        divided by it, multiplied if negative; 1 off), then ``frequency_penalty`` times the number of times the token
+        was generated in this call and ``presence_penalty`` if it was at all are subtracted (the OpenAI / vLLM
+        convention: the prompt does not count; 0 off). They move the logits in front of the greedy argmax, temperature,
+        ``top_k`` and ``top_p``. A value that is not finite, or ``repetition_penalty <= 0``, raises ``ValueError``.
+
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
         the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
         ``NotImplementedError``. It does not advance the dropout stream or touch what a later backward needs, so a
@@ -381,11 +390,13 @@ class GPT2(nn.Module):
         model holds only a shard of the parameters and raises ``NotImplementedError``."""
         from .generation import generate
         return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed,
-                        prompt_lens, pad_token_id, draft_tokens, draft_fn)
+                        prompt_lens, pad_token_id, draft_tokens, draft_fn, repetition_penalty, presence_penalty,
+                        frequency_penalty)
 
     def generate_many(self, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                       top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
-                      eos_token_id: Optional[int] = None, generator=None):
+                      eos_token_id: Optional[int] = None, generator=None, repetition_penalty: float = 1.0,
+                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
         """Continue any number of 1-D ``prompts`` of any lengths by up to ``max_new_tokens`` tokens each; returns a list
         in input order, each entry the prompt plus its new tokens, cut after the first ``eos_token_id``.
 
@@ -399,10 +410,11 @@ class GPT2(nn.Module):
         decode step forms a row from that row's data alone, in an order that does not depend on the batch; a refill's
         shapes depend on its prompt alone). Device sampler only: ``generator=`` raises ``ValueError``.
         ``max(len) + max_new_tokens > n_positions`` raises ``ValueError``. Training is left untouched as by
-        ``generate``."""
+        ``generate``. ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` as for ``generate``: a row's
+        history is its own prompt and new tokens, so the guarantee holds with them."""
         from .generation import generate_many
         return generate_many(self, prompts, max_new_tokens, batch_size, temperature, top_k, top_p, seed, eos_token_id,
-                             generator)
+                             generator, repetition_penalty, presence_penalty, frequency_penalty)
 
     # ---- optimizer (nanoGPT-style name the north star uses) -----------------------------------------
     def configure_optimizers(self, weight_decay: float = 0.1, learning_rate: float = 1e-4,

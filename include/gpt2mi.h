@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 21
+#define GPT2MI_ABI_VERSION 22
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -445,6 +445,51 @@ int gpt2mi_attn_extend(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, 
  * gpt2mi_decode_step_ragged one position at a time. */
 int gpt2mi_decode_extend(const gpt2mi_decode_plan* plan, int R, const int64_t* tok, const int* seq, const int* pos,
                          void* stream);
+
+/* ---- v22: repetition, presence and frequency penalties in the sampler (csrc/sample.hip, csrc/decode.hip). A token's
+ * history moves its logit before everything gpt2mi_sample states (the greedy argmax, the temperature division, top-k,
+ * top-p, the draw). The executable specification is gpt_2_distributed_amd/generation.py apply_penalties.
+ * Row b's history is hist[hist_row[b]][0 .. pos[b]) (values outside [0, V) are ignored). Per vocabulary index i,
+ * seen_i = i occurs in [0, pos[b]) (prompt and generated tokens: HF's scope of repetition_penalty) and c_i = its
+ * occurrences in [gen_start[b], pos[b]) (generated tokens: the OpenAI / vLLM scope). In this order, every operation one
+ * IEEE fp32 operation rounded to nearest, none contracted:
+ *   repetition != 1 and seen_i:  x = x < 0 ? x * repetition : x / repetition   (a logit of exactly 0 is divided)
+ *   frequency != 0 and c_i > 0:  x = x - (frequency * float(c_i))
+ *   presence != 0 and c_i > 0:   x = x - presence
+ * The kernels are instantiations of the sampling kernel of their own: the row is still read once and the logits buffer
+ * is not written; the counts live in LDS (16 bits per vocabulary index, integer LDS atomics: no table in global memory,
+ * no float atomics, two calls give the same bits). ---- */
+/* Longest history window (pos[b]) a penalised draw takes. */
+#define GPT2MI_PENALTY_MAX_HISTORY 8192
+typedef struct gpt2mi_penalties {
+  float repetition, presence, frequency; /* 1, 0, 0: off */
+  const int64_t* hist;                   /* device int64 [hist_rows][ld_hist] */
+  int ld_hist, hist_rows;
+  const int* hist_row;                   /* HOST [B], may be NULL (row b reads hist row b) */
+  const int* gen_start;                  /* HOST [B], may be NULL (0) */
+} gpt2mi_penalties;
+/* gpt2mi_sample_ragged with penalties: row b reads hist[hist_row[b]][0 .. pos[b]) and draws at pos[b]. seq_out may
+ * alias hist (a block reads positions < pos[b] of its row and writes position pos[b]). logits_out (fp32 [B][V], may be
+ * NULL) receives the penalised logits, before the temperature division. The host arrays travel to the kernel by value.
+ * pen == NULL or (1, 0, 0) launches gpt2mi_sample_ragged's kernels (its bits, launches and cost; hist may be NULL, the
+ * arrays are not read; a logits_out is then a device-to-device copy of the valid columns queued before the launch).
+ * Refused with 22 and a message before any launch, beside gpt2mi_sample_ragged's checks: repetition <= 0 or NaN, a
+ * non-finite presence or frequency; and with non-neutral values a NULL hist, ld_hist < pos[b], hist_row[b] outside
+ * [0, hist_rows) (hist_rows < B without a hist_row), gen_start[b] outside [0, pos[b]], pos[b] above
+ * GPT2MI_PENALTY_MAX_HISTORY. */
+int gpt2mi_sample_penalized(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
+                            uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
+                            int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out,
+                            const gpt2mi_penalties* pen, float* logits_out, void* stream);
+/* gpt2mi_decode_generate_ragged with penalties and seq as the history: row b must hold its tokens at seq[b][0 .. pos0[b])
+ * (the loop appends what it draws), gen_start (HOST [B], may be NULL: 0) is where its generated part starts. seq is
+ * required when a value is non-neutral; (1, 0, 0) is gpt2mi_decode_generate_ragged. Refused with 22 before any launch,
+ * beside its checks: the value checks above, a NULL seq or gen_start[b] outside [0, pos0[b]] with non-neutral values,
+ * max pos0 + n - 1 above GPT2MI_PENALTY_MAX_HISTORY. */
+int gpt2mi_decode_generate_penalized(const gpt2mi_decode_plan* plan, int V, float temperature, int top_k, float top_p,
+                                     uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
+                                     int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream,
+                                     float repetition, float presence, float frequency, const int* gen_start);
 
 #ifdef __cplusplus
 }
