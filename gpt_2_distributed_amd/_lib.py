@@ -548,22 +548,31 @@ def decode_step_ragged(plan: DecodePlan, tok, pos):
     _call("gpt2mi_decode_step_ragged", ctypes.byref(plan), _ptr(tok), _positions(pos, plan.B), _stream())
 
 
+def _sample_call(name, logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out, *tail):
+    """The argument list of the per-row sampler entries (`scalars`: _sampler_args'); `tail` goes before the stream."""
+    (t, k, p, s, e), B = scalars, logits.size(0)
+    _call(name, _ptr(logits), logits.stride(0), B, V, t, k, p, s, _positions(pos, B), _row_ids(row_id, B), e, _ptr(done),
+          _ptr(tok_out), _ptr(seq_out), 0 if seq_out is None else seq_out.stride(0), _ptr(probs_out), *tail, _stream())
+
+
+def _generate_call(name, plan, V, scalars, pos0, n, tok, row_id, seq, done, *tail):
+    """The argument list of the per-row generate loops; `tail` goes behind the stream."""
+    _call(name, ctypes.byref(plan), V, *scalars, _positions(pos0, plan.B), _row_ids(row_id, plan.B), n, _ptr(tok),
+          _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(done), _stream(), *tail)
+
+
 def sample_ragged(logits, V, temperature, top_k, top_p, seed, pos, tok_out, row_id=None, eos=None, done=None,
                   seq_out=None, probs_out=None):
     """gpt2mi_sample_ragged: `sample` with row b drawing from (seed, row_id[b] (None: b), pos[b]) into column pos[b]."""
-    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
-    B = logits.size(0)
-    _call("gpt2mi_sample_ragged", _ptr(logits), logits.stride(0), B, V, t, k, p, s, _positions(pos, B),
-          _row_ids(row_id, B), e, _ptr(done), _ptr(tok_out), _ptr(seq_out), 0 if seq_out is None else seq_out.stride(0),
-          _ptr(probs_out), _stream())
+    _sample_call("gpt2mi_sample_ragged", logits, V, _sampler_args(temperature, top_k, top_p, seed, eos), pos, tok_out,
+                 row_id, done, seq_out, probs_out)
 
 
 def decode_generate_ragged(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, row_id=None, eos=None,
                            seq=None, done=None):
     """gpt2mi_decode_generate_ragged: n sample-then-step rounds with row b starting at pos0[b]."""
-    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
-    _call("gpt2mi_decode_generate_ragged", ctypes.byref(plan), V, t, k, p, s, e, _positions(pos0, plan.B),
-          _row_ids(row_id, plan.B), n, _ptr(tok), _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(done), _stream())
+    _generate_call("gpt2mi_decode_generate_ragged", plan, V, _sampler_args(temperature, top_k, top_p, seed, eos), pos0,
+                   n, tok, row_id, seq, done)
 
 
 # ---- v21: several rows of a launch in one sequence (csrc/decode.hip) -----------------------------------
@@ -595,7 +604,7 @@ def sample_penalized(logits, V, temperature, top_k, top_p, seed, pos, tok_out, r
     """gpt2mi_sample_penalized: `sample_ragged` with row b's logits moved by its history hist[hist_row[b], :pos[b]]
     (int64 [rows, ld]; hist_row None: b), the generated part from gen_start[b] (None: 0); logits_out (fp32 [B, V]) takes
     the penalised logits."""
-    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
+    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
     B = logits.size(0)
     rows, starts = _host_ints(hist_row), _host_ints(gen_start)  # (kept alive to the end of the call)
     if any(a is not None and len(a) != B for a in (rows, starts)):
@@ -604,17 +613,15 @@ def sample_penalized(logits, V, temperature, top_k, top_p, seed, pos, tok_out, r
                     0 if hist is None else hist.stride(0), 0 if hist is None else hist.size(0),
                     ctypes.cast(rows, _p) if rows is not None else None,
                     ctypes.cast(starts, _p) if starts is not None else None)
-    _call("gpt2mi_sample_penalized", _ptr(logits), logits.stride(0), B, V, t, k, p, s, _positions(pos, B),
-          _row_ids(row_id, B), e, _ptr(done), _ptr(tok_out), _ptr(seq_out), 0 if seq_out is None else seq_out.stride(0),
-          _ptr(probs_out), ctypes.byref(pen), _ptr(logits_out), _stream())
+    _sample_call("gpt2mi_sample_penalized", logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out,
+                 ctypes.byref(pen), _ptr(logits_out))
 
 
 def decode_generate_penalized(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, row_id=None, eos=None,
                               seq=None, done=None, repetition=1.0, presence=0.0, frequency=0.0, gen_start=None):
     """gpt2mi_decode_generate_penalized: `decode_generate_ragged` with seq as the history the sampler reads."""
-    t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
+    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
     if gen_start is not None and len(gen_start) != plan.B:
         raise KernelError(f"gen_start has {len(gen_start)} entries for B={plan.B} rows")
-    _call("gpt2mi_decode_generate_penalized", ctypes.byref(plan), V, t, k, p, s, e, _positions(pos0, plan.B),
-          _row_ids(row_id, plan.B), n, _ptr(tok), _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(done), _stream(),
-          float(repetition), float(presence), float(frequency), _host_ints(gen_start))
+    _generate_call("gpt2mi_decode_generate_penalized", plan, V, scalars, pos0, n, tok, row_id, seq, done,
+                   float(repetition), float(presence), float(frequency), _host_ints(gen_start))

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "gpt2mi.h"
+
 typedef __bf16 bf16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
@@ -32,6 +34,15 @@ void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 // the sampler's penalty values (gpt2mi.h v22), checked; *on = whether any of them is non-neutral (csrc/sample.hip)
 int check_penalty_values(const char* what, float repetition, float presence, float frequency, bool* on);
+
+// What a scalar-position entry hands to the per-row implementation: every row at `pos`. All GPT2MI_DECODE_MAX_B
+// entries are filled, so B is checked where the array is read and nowhere else.
+struct SamePos {
+  int v[GPT2MI_DECODE_MAX_B];
+  explicit SamePos(int pos) {
+    for (int& p : v) p = pos;
+  }
+};
 }  // namespace gpt2mi
 
 #define GPT2MI_REQUIRE(cond, ...)                  \

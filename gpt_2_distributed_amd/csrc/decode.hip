@@ -6,6 +6,9 @@
 // the streamed operand straight to VGPRs in full 128-byte lines (no LDS round trip: nothing is shared between waves),
 // and split the reduction (K, or the keys) over enough waves to cover the chip. No atomics: partial results are
 // combined in a fixed order, so every output is bitwise reproducible.
+// The attention of the step and of the multi-row extend are two __global__ entries over one body (attn_row). Their
+// gfx950 disassemblies (the Makefile's flags, -S) were compared with those of the two separate kernels they replace:
+// same registers, no scratch, occupancy 8; what differs is listed in DESIGN.md "Multi-token decode step".
 #include <limits.h>
 
 #include <algorithm>
@@ -184,133 +187,25 @@ struct RowPos {
   int v[GPT2MI_DECODE_MAX_B];
 };
 
-// Grid (ranges, H, B): row b at rows.v[b]; the x extent is that of the longest row. A wave whose range starts beyond
-// its row's position leaves before any load or store (wave-uniform: one wave per block, range and row from blockIdx; the
-// body has no barrier), so its workspace slot stays unwritten and attn_combine_kernel does not read it. b is a grid
-// index of its own so that the position is one scalar load from the start of the wave: behind a division of a
-// (b, h) index by H every cache load waited for it.
-__global__ __launch_bounds__(64) void attn_decode_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
-                                                         float* __restrict__ ws_acc, int H, int Tcap, RowPos rows,
-                                                         int nr_max) {
-  const int range = blockIdx.x, h = blockIdx.y, b = blockIdx.z, bh = b * H + h;
-  const int pos = rows.v[b];
+// The work of one wave, written once for both entries: row r of the launch at position pos, keys range * 32 .. + 31 of
+// the cache stream `stream` = seq * H + h (formed by the entry, in the width its seq needs). The keys of a row come
+// from two places: a key below `first` from the cache (written by an earlier call), a key in first..pos from the qkv
+// row that sits at that position, r - (pos - key): the rows of a sequence in one launch are a contiguous run at
+// consecutive positions and `first` is the position of the run's first row. The keys of this call are never read from
+// the cache: other waves of this launch are writing them. The row at position t alone writes k / v to position t of
+// its stream, so every position has one writer, and nothing above pos is read. The bits of a key are the same from
+// either source (the cache holds what the qkv row held), so a row gets the same bits whether its run is fed in one
+// call or one row per call. RUN = false is the run of one (first == pos, the only qkv row read is the row's own) as a
+// compile-time choice: from first == pos alone the compiler does not drop the row offset (pos - key) * 3C.
+// A wave whose range starts beyond pos leaves before any load or store (wave-uniform: one wave per block, range and
+// row from blockIdx; the body has no barrier), so its workspace slot stays unwritten and attn_combine_kernel does not
+// read it. The workspace slot is that of row r, not of the sequence.
+template <bool RUN>
+__device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, bf16* __restrict__ kc, bf16* __restrict__ vc,
+                                         float* __restrict__ ws_ml, float* __restrict__ ws_acc, int H, int Tcap,
+                                         int nr_max, int r, size_t stream, int pos, int first) {
+  const int range = blockIdx.x, h = blockIdx.y;
   if (range * AD_KEYS > pos) return;
-  const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
-  const int C = H * 64;
-  const bf16* tok = qkv + (size_t)b * 3 * C + h * 64 + 8 * dg;  // q; k at + C, v at + 2C
-  float q[8];
-  unpack8(*reinterpret_cast<const bf16x8*>(tok), q);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) q[j] *= 0.125f;  // 1/sqrt(64), exact
-
-  const size_t base = (size_t)bh * Tcap * 64 + 8 * dg;
-  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-  bf16x8 kv[4], vv[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int key = range * AD_KEYS + kk + 8 * i;
-    kv[i] = zero;
-    vv[i] = zero;
-    if (key < pos) {
-      kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
-      vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
-    } else if (key == pos) {
-      kv[i] = *reinterpret_cast<const bf16x8*>(tok + C);
-      vv[i] = *reinterpret_cast<const bf16x8*>(tok + 2 * C);
-      *reinterpret_cast<bf16x8*>(kc + base + (size_t)key * 64) = kv[i];
-      *reinterpret_cast<bf16x8*>(vc + base + (size_t)key * 64) = vv[i];
-    }
-  }
-
-  float s[4], mx = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float kf[8], d = 0.f;
-    unpack8(kv[i], kf);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], kf[j], d);
-    d += __shfl_xor(d, 1, 64);
-    d += __shfl_xor(d, 2, 64);
-    d += __shfl_xor(d, 4, 64);
-    s[i] = (range * AD_KEYS + kk + 8 * i <= pos) ? d : -INFINITY;
-    mx = fmaxf(mx, s[i]);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 8, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // finite: the range's first key is <= pos
-
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, l = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float p = __expf(s[i] - mx);  // 0 for a masked key
-    float vf[8];
-    unpack8(vv[i], vf);
-    l += p;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(p, vf[j], acc[j]);
-  }
-#pragma unroll
-  for (int o = 8; o < 64; o <<= 1) {
-    l += __shfl_xor(l, o, 64);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], o, 64);
-  }
-  const size_t slot = (size_t)bh * nr_max + range;
-  if (kk == 0) {
-    float* a = ws_acc + slot * 64 + 8 * dg;
-    *reinterpret_cast<f32x4*>(a) = f32x4{acc[0], acc[1], acc[2], acc[3]};
-    *reinterpret_cast<f32x4*>(a + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
-    if (dg == 0) {
-      ws_ml[2 * slot] = mx;
-      ws_ml[2 * slot + 1] = l;
-    }
-  }
-}
-
-// out[b, h*64 + d] = sum_r e^(m_r - m) acc_r[d] / sum_r e^(m_r - m) l_r over the pos[b] / 32 + 1 ranges of row b, in
-// range order; lane d, grid (H, B).
-__global__ __launch_bounds__(64) void attn_combine_kernel(const float* __restrict__ ws_ml,
-                                                          const float* __restrict__ ws_acc, bf16* __restrict__ out,
-                                                          int H, RowPos rows, int nr_max) {
-  const int d = threadIdx.x, h = blockIdx.x, b = blockIdx.y, bh = b * H + h;
-  const int nr = rows.v[b] / AD_KEYS + 1;
-  const size_t slot0 = (size_t)bh * nr_max;
-  float m = -INFINITY;
-  for (int r = 0; r < nr; ++r) m = fmaxf(m, ws_ml[2 * (slot0 + r)]);
-  float l = 0.f, o = 0.f;
-  for (int r = 0; r < nr; ++r) {
-    const float w = __expf(ws_ml[2 * (slot0 + r)] - m);
-    l = __builtin_fmaf(w, ws_ml[2 * (slot0 + r) + 1], l);
-    o = __builtin_fmaf(w, ws_acc[(slot0 + r) * 64 + d], o);
-  }
-  out[(size_t)bh * 64 + d] = f2bf(o / l);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Several rows of one launch in the same sequence (gpt2mi_attn_extend): row r is (sequence seq[r], position pos[r]),
-// the rows of a sequence are one contiguous run at consecutive positions and first[r] is the position of the run's
-// first row. Validated on the host and passed by value like RowPos; indexed by blockIdx only.
-struct RowMap {
-  int seq[GPT2MI_DECODE_MAX_B], pos[GPT2MI_DECODE_MAX_B], first[GPT2MI_DECODE_MAX_B];
-};
-
-// attn_decode_kernel, lane for lane, for grid (ranges, H, R) with the keys of a row coming from two places: a key
-// below first[r] from the cache stream of seq[r] (written by an earlier call), a key in first[r]..pos[r] from the qkv
-// row of the run that sits at that position, r - (pos[r] - key) >= the run's first row. The keys of this call are
-// never read from the cache: other waves of this launch are writing them. The row at position t alone writes k / v
-// to position t of its stream, so every position has one writer, and nothing above pos[r] is read. The bits of a
-// key are the same from either source (the cache holds what the qkv row held), so row r gets what
-// attn_decode_kernel gives it when the rows are fed one call at a time. The workspace slot is that of row r, not of
-// the sequence: the combine is attn_combine_kernel over R rows at pos[r].
-__global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
-                                                         float* __restrict__ ws_acc, int H, int Tcap, RowMap rows,
-                                                         int nr_max) {
-  const int range = blockIdx.x, h = blockIdx.y, r = blockIdx.z;
-  const int pos = rows.pos[r];
-  if (range * AD_KEYS > pos) return;
-  const int first = rows.first[r];
   const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
   const int C = H * 64;
   const bf16* tok = qkv + (size_t)r * 3 * C + h * 64 + 8 * dg;  // q; k at + C, v at + 2C
@@ -319,7 +214,7 @@ __global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict_
 #pragma unroll
   for (int j = 0; j < 8; ++j) q[j] *= 0.125f;  // 1/sqrt(64), exact
 
-  const size_t base = ((size_t)rows.seq[r] * H + h) * Tcap * 64 + 8 * dg;
+  const size_t base = stream * Tcap * 64 + 8 * dg;
   const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
   bf16x8 kv[4], vv[4];
 #pragma unroll
@@ -330,11 +225,11 @@ __global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict_
     if (key < first) {
       kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
       vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
-    } else if (key <= pos) {
-      const bf16* src = tok - (ptrdiff_t)(pos - key) * 3 * C;  // the run's row at position key
+    } else if (RUN ? key <= pos : key == pos) {
+      const bf16* src = RUN ? tok - (ptrdiff_t)(pos - key) * 3 * C : tok;  // the run's row at position key
       kv[i] = *reinterpret_cast<const bf16x8*>(src + C);
       vv[i] = *reinterpret_cast<const bf16x8*>(src + 2 * C);
-      if (key == pos) {
+      if (!RUN || key == pos) {
         *reinterpret_cast<bf16x8*>(kc + base + (size_t)key * 64) = kv[i];
         *reinterpret_cast<bf16x8*>(vc + base + (size_t)key * 64) = vv[i];
       }
@@ -374,7 +269,7 @@ __global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict_
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], o, 64);
   }
-  const size_t slot = ((size_t)r * H + h) * nr_max + range;
+  const size_t slot = (size_t)(r * H + h) * nr_max + range;
   if (kk == 0) {
     float* a = ws_acc + slot * 64 + 8 * dg;
     *reinterpret_cast<f32x4*>(a) = f32x4{acc[0], acc[1], acc[2], acc[3]};
@@ -384,6 +279,55 @@ __global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict_
       ws_ml[2 * slot + 1] = l;
     }
   }
+}
+
+// Grid (ranges, H, B): row b at rows.v[b] of its own cache stream; the x extent is that of the longest row. b is a grid
+// index of its own so that the position is one scalar load from the start of the wave: behind a division of a
+// (b, h) index by H every cache load waited for it.
+__global__ __launch_bounds__(64) void attn_decode_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
+                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
+                                                         float* __restrict__ ws_acc, int H, int Tcap, RowPos rows,
+                                                         int nr_max) {
+  const int b = blockIdx.z, bh = b * H + blockIdx.y;  // (b < 64: int)
+  attn_row<false>(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, nr_max, b, bh, rows.v[b], rows.v[b]);
+}
+
+// out[b, h*64 + d] = sum_r e^(m_r - m) acc_r[d] / sum_r e^(m_r - m) l_r over the pos[b] / 32 + 1 ranges of row b, in
+// range order; lane d, grid (H, B).
+__global__ __launch_bounds__(64) void attn_combine_kernel(const float* __restrict__ ws_ml,
+                                                          const float* __restrict__ ws_acc, bf16* __restrict__ out,
+                                                          int H, RowPos rows, int nr_max) {
+  const int d = threadIdx.x, h = blockIdx.x, b = blockIdx.y, bh = b * H + h;
+  const int nr = rows.v[b] / AD_KEYS + 1;
+  const size_t slot0 = (size_t)bh * nr_max;
+  float m = -INFINITY;
+  for (int r = 0; r < nr; ++r) m = fmaxf(m, ws_ml[2 * (slot0 + r)]);
+  float l = 0.f, o = 0.f;
+  for (int r = 0; r < nr; ++r) {
+    const float w = __expf(ws_ml[2 * (slot0 + r)] - m);
+    l = __builtin_fmaf(w, ws_ml[2 * (slot0 + r) + 1], l);
+    o = __builtin_fmaf(w, ws_acc[(slot0 + r) * 64 + d], o);
+  }
+  out[(size_t)bh * 64 + d] = f2bf(o / l);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Several rows of one launch in the same sequence (gpt2mi_attn_extend): row r is (sequence seq[r], position pos[r]),
+// the rows of a sequence are one contiguous run at consecutive positions and first[r] is the position of the run's
+// first row. Validated on the host and passed by value like RowPos; indexed by blockIdx only.
+struct RowMap {
+  int seq[GPT2MI_DECODE_MAX_B], pos[GPT2MI_DECODE_MAX_B], first[GPT2MI_DECODE_MAX_B];
+};
+
+// Grid (ranges, H, R): several rows of one launch in the same sequence; the combine is attn_combine_kernel over R rows
+// at pos[r].
+__global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
+                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
+                                                         float* __restrict__ ws_acc, int H, int Tcap, RowMap rows,
+                                                         int nr_max) {
+  const int r = blockIdx.z;
+  attn_row<true>(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, nr_max, r, (size_t)rows.seq[r] * H + blockIdx.y, rows.pos[r],
+                 rows.first[r]);
 }
 
 // One row per blockIdx.y, so that the row's position is a scalar load of the argument.
@@ -493,12 +437,29 @@ int row_positions(const char* what, const int* pos, int B, int limit, RowPos* ou
   return 0;
 }
 
-// What a scalar-position entry hands to the per-row implementation: every row at `pos`. All GPT2MI_DECODE_MAX_B
-// entries are filled, so B is checked where the array is read and nowhere else.
-struct SamePos {
-  int v[GPT2MI_DECODE_MAX_B];
-  explicit SamePos(int pos) { std::fill_n(v, GPT2MI_DECODE_MAX_B, pos); }
-};
+using gpt2mi::SamePos;
+
+// The tail the two attention entries share, after their own row checks: M rows whose kernel argument is `rows`, at the
+// positions rp (the longest max_pos). The workspace is M * H * nr_max (max, sum) pairs, then as many acc[64].
+template <class Rows>
+int attn_launch(const char* what, void (*kernel)(const bf16*, bf16*, bf16*, float*, float*, int, int, Rows, int),
+                const Rows& rows, const RowPos& rp, int max_pos, const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache,
+                uint16_t* out, float* workspace, size_t workspace_floats, int M, int H, int Tcap, void* stream) {
+  const size_t need = gpt2mi_attn_decode_workspace(M, H, Tcap);
+  GPT2MI_REQUIRE(workspace_floats >= need, "%s: workspace too small (%zu floats given, %zu needed)", what,
+                 workspace_floats, need);
+  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
+                 "%s: qkv, the caches, out and workspace must not be NULL", what);
+  hipStream_t s = (hipStream_t)stream;
+  const int nr_max = attn_ranges(Tcap);
+  float* ws_ml = workspace;
+  float* ws_acc = workspace + (size_t)M * H * nr_max * 2;
+  kernel<<<dim3(max_pos / AD_KEYS + 1, H, M), 64, 0, s>>>((const bf16*)qkv, (bf16*)kcache, (bf16*)vcache, ws_ml, ws_acc,
+                                                         H, Tcap, rows, nr_max);
+  if (const int rc = gpt2mi::check_launch(what)) return rc;
+  attn_combine_kernel<<<dim3(H, M), 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, rp, nr_max);
+  return gpt2mi::check_launch(what);
+}
 
 // Each operation below is written once, for one position per row; `what` is the entry's name in its messages.
 int attn_decode_rows(const char* what, const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
@@ -510,20 +471,8 @@ int attn_decode_rows(const char* what, const uint16_t* qkv, uint16_t* kcache, ui
   RowPos rp;
   int max_pos;
   if (const int rc = row_positions(what, pos, B, Tcap, &rp, &max_pos)) return rc;
-  const size_t need = gpt2mi_attn_decode_workspace(B, H, Tcap);
-  GPT2MI_REQUIRE(workspace_floats >= need, "%s: workspace too small (%zu floats given, %zu needed)", what,
-                 workspace_floats, need);
-  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
-                 "%s: qkv, the caches, out and workspace must not be NULL", what);
-  hipStream_t s = (hipStream_t)stream;
-  const int nr_max = attn_ranges(Tcap);
-  float* ws_ml = workspace;
-  float* ws_acc = workspace + (size_t)B * H * nr_max * 2;
-  attn_decode_kernel<<<dim3(max_pos / AD_KEYS + 1, H, B), 64, 0, s>>>((const bf16*)qkv, (bf16*)kcache, (bf16*)vcache,
-                                                                     ws_ml, ws_acc, H, Tcap, rp, nr_max);
-  if (const int rc = gpt2mi::check_launch(what)) return rc;
-  attn_combine_kernel<<<dim3(H, B), 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, rp, nr_max);
-  return gpt2mi::check_launch(what);
+  return attn_launch(what, attn_decode_kernel, rp, rp, max_pos, qkv, kcache, vcache, out, workspace, workspace_floats,
+                     B, H, Tcap, stream);
 }
 
 int embed_decode_rows(const char* what, const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C,
@@ -601,22 +550,10 @@ int attn_extend_rows(const char* what, const uint16_t* qkv, uint16_t* kcache, ui
   RowMap rm;
   int max_pos;
   if (const int rc = row_map(what, seq, pos, R, B, Tcap, &rm, &max_pos)) return rc;
-  const size_t need = gpt2mi_attn_decode_workspace(R, H, Tcap);
-  GPT2MI_REQUIRE(workspace_floats >= need, "%s: workspace too small (%zu floats given, %zu needed)", what,
-                 workspace_floats, need);
-  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
-                 "%s: qkv, the caches, out and workspace must not be NULL", what);
-  hipStream_t s = (hipStream_t)stream;
-  const int nr_max = attn_ranges(Tcap);
-  float* ws_ml = workspace;
-  float* ws_acc = workspace + (size_t)R * H * nr_max * 2;
-  attn_extend_kernel<<<dim3(max_pos / AD_KEYS + 1, H, R), 64, 0, s>>>((const bf16*)qkv, (bf16*)kcache, (bf16*)vcache,
-                                                                     ws_ml, ws_acc, H, Tcap, rm, nr_max);
-  if (const int rc = gpt2mi::check_launch(what)) return rc;
   RowPos rp{};  // the combine is per row: row r merges its own pos[r] / 32 + 1 ranges
   std::copy_n(rm.pos, R, rp.v);
-  attn_combine_kernel<<<dim3(H, R), 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, rp, nr_max);
-  return gpt2mi::check_launch(what);
+  return attn_launch(what, attn_extend_kernel, rm, rp, max_pos, qkv, kcache, vcache, out, workspace, workspace_floats,
+                     R, H, Tcap, stream);
 }
 
 // The launch list of a step over M rows at pos[m], shared by the step and the extend: they differ in the attention
@@ -651,25 +588,38 @@ int decode_launches(const char* what, const gpt2mi_decode_plan* P, int M, const 
   return 0;
 }
 
-// One step with row b at pos[b]: gpt2mi_decode_step_ragged, and gpt2mi_decode_step with every pos[b] equal.
-int decode_step_rows(const char* what, const gpt2mi_decode_plan* P, const int64_t* tok, const int* pos, void* stream) {
+// The plan checks of the step and the extend, in two halves around the caller's own row checks: the shape of the plan,
+// then its buffers for M rows.
+int plan_shape(const char* what, const gpt2mi_decode_plan* P) {
   GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
-  const int B = P->B, C = P->C, H = P->H;
-  GPT2MI_REQUIRE(B >= 1 && B <= 64, "%s: B=%d not in [1, 64]", what, B);
-  GPT2MI_REQUIRE(H >= 1 && C == 64 * H, "%s: head_dim = C/H must be 64 (C=%d, H=%d)", what, C, H);
+  GPT2MI_REQUIRE(P->B >= 1 && P->B <= 64, "%s: B=%d not in [1, 64]", what, P->B);
+  GPT2MI_REQUIRE(P->H >= 1 && P->C == 64 * P->H, "%s: head_dim = C/H must be 64 (C=%d, H=%d)", what, P->C, P->H);
   GPT2MI_REQUIRE(P->L >= 1 && P->Vp >= 64 && P->Vp % 64 == 0, "%s: L=%d, Vp=%d (a multiple of 64) invalid", what, P->L,
                  P->Vp);
-  RowPos rp;
-  int max_pos;
-  if (const int rc = row_positions(what, pos, B, P->Tcap, &rp, &max_pos)) return rc;
-  GPT2MI_REQUIRE(P->attn_ws_floats >= gpt2mi_attn_decode_workspace(B, H, P->Tcap),
+  return 0;
+}
+
+int plan_buffers(const char* what, const gpt2mi_decode_plan* P, int M, const int64_t* tok) {
+  const int C = P->C;
+  GPT2MI_REQUIRE(P->attn_ws_floats >= gpt2mi_attn_decode_workspace(M, P->H, P->Tcap),
                  "%s: attention workspace too small (%zu floats)", what, P->attn_ws_floats);
   size_t need = 0;
   const int shapes[5][2] = {{3 * C, C}, {C, C}, {4 * C, C}, {C, 4 * C}, {P->Vp, C}};
-  for (const auto& sh : shapes) need = std::max(need, gpt2mi_gemm_skinny_workspace(B, sh[0], sh[1]));
+  for (const auto& sh : shapes) need = std::max(need, gpt2mi_gemm_skinny_workspace(M, sh[0], sh[1]));
   GPT2MI_REQUIRE(P->gemm_ws_floats >= need, "%s: GEMM workspace too small (%zu floats given, %zu needed)", what,
                  P->gemm_ws_floats, need);
   GPT2MI_REQUIRE(P->layers && tok, "%s: layers and tok must not be NULL", what);
+  return 0;
+}
+
+// One step with row b at pos[b]: gpt2mi_decode_step_ragged, and gpt2mi_decode_step with every pos[b] equal.
+int decode_step_rows(const char* what, const gpt2mi_decode_plan* P, const int64_t* tok, const int* pos, void* stream) {
+  if (const int rc = plan_shape(what, P)) return rc;
+  const int B = P->B, H = P->H;
+  RowPos rp;
+  int max_pos;
+  if (const int rc = row_positions(what, pos, B, P->Tcap, &rp, &max_pos)) return rc;
+  if (const int rc = plan_buffers(what, P, B, tok)) return rc;
   return decode_launches(what, P, B, tok, pos, stream, [&](const gpt2mi_decode_layer& Y) {
     return attn_decode_rows(what, P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap,
                             pos, stream);
@@ -698,25 +648,14 @@ GPT2MI_EXPORT int gpt2mi_attn_extend(const uint16_t* qkv, uint16_t* kcache, uint
 GPT2MI_EXPORT int gpt2mi_decode_extend(const gpt2mi_decode_plan* P, int R, const int64_t* tok, const int* seq,
                                        const int* pos, void* stream) {
   const char* what = "decode_extend";
-  GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
-  const int B = P->B, C = P->C, H = P->H;
-  GPT2MI_REQUIRE(B >= 1 && B <= 64, "%s: B=%d not in [1, 64]", what, B);
-  GPT2MI_REQUIRE(H >= 1 && C == 64 * H, "%s: head_dim = C/H must be 64 (C=%d, H=%d)", what, C, H);
-  GPT2MI_REQUIRE(P->L >= 1 && P->Vp >= 64 && P->Vp % 64 == 0, "%s: L=%d, Vp=%d (a multiple of 64) invalid", what, P->L,
-                 P->Vp);
+  if (const int rc = plan_shape(what, P)) return rc;
+  const int B = P->B, H = P->H;
   RowMap rm;
   int max_pos;
   if (const int rc = row_map(what, seq, pos, R, B, P->Tcap, &rm, &max_pos)) return rc;
   const int cap = P->rows ? P->rows : B;
   GPT2MI_REQUIRE(R <= cap, "%s: R=%d exceeds the plan's row capacity %d (plan->rows, 0: B)", what, R, cap);
-  GPT2MI_REQUIRE(P->attn_ws_floats >= gpt2mi_attn_decode_workspace(R, H, P->Tcap),
-                 "%s: attention workspace too small (%zu floats)", what, P->attn_ws_floats);
-  size_t need = 0;
-  const int shapes[5][2] = {{3 * C, C}, {C, C}, {4 * C, C}, {C, 4 * C}, {P->Vp, C}};
-  for (const auto& sh : shapes) need = std::max(need, gpt2mi_gemm_skinny_workspace(R, sh[0], sh[1]));
-  GPT2MI_REQUIRE(P->gemm_ws_floats >= need, "%s: GEMM workspace too small (%zu floats given, %zu needed)", what,
-                 P->gemm_ws_floats, need);
-  GPT2MI_REQUIRE(P->layers && tok, "%s: layers and tok must not be NULL", what);
+  if (const int rc = plan_buffers(what, P, R, tok)) return rc;
   return decode_launches(what, P, R, tok, pos, stream, [&](const gpt2mi_decode_layer& Y) {
     return attn_extend_rows(what, P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, R, B, H, 64,
                             P->Tcap, seq, pos, stream);

@@ -511,8 +511,6 @@ GPT2MI_EXPORT int gpt2mi_sample(const float* logits, int ldl, int B, int V, floa
                                 int ld_seq, float* probs_out, void* stream) {
   GPT2MI_REQUIRE(pos >= 0, "sample: pos=%d is negative", pos);
   GPT2MI_REQUIRE(!seq_out || ld_seq > pos, "sample: ld_seq=%d does not reach pos=%d", ld_seq, pos);
-  int same[GPT2MI_DECODE_MAX_B];  // every row at pos (all entries: B is checked where they are read)
-  for (int& p : same) p = pos;
-  return sample_rows("sample", logits, ldl, B, V, temperature, top_k, top_p, seed, same, nullptr, eos, done, tok_out,
-                     seq_out, ld_seq, probs_out, stream);
+  return sample_rows("sample", logits, ldl, B, V, temperature, top_k, top_p, seed, gpt2mi::SamePos(pos).v, nullptr, eos,
+                     done, tok_out, seq_out, ld_seq, probs_out, stream);
 }

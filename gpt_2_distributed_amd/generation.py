@@ -194,6 +194,13 @@ def apply_penalties(logits: torch.Tensor, history: torch.Tensor, lens, gen_start
     return x
 
 
+def _penalty_keywords(penalties, gen_start) -> dict:
+    """``DecodeSession.generate`` / ``speculate``'s penalty keywords from ``_check_penalties``' tuple (``{}`` when the
+    values are neutral), the rows' generated parts starting at ``gen_start``."""
+    rp, pp, fp, on = penalties
+    return dict(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp, gen_start=list(gen_start)) if on else {}
+
+
 def _check_lens(lens, B: int, P: int) -> List[int]:
     """``lens`` as a list of B ints in [1, P], or a ValueError."""
     lens = [int(n) for n in (lens.tolist() if isinstance(lens, torch.Tensor) else lens)]
@@ -487,6 +494,35 @@ class DecodeSession:
             raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
         return dict(repetition=rp, presence=pp, frequency=fp, gen_start=start)
 
+    def _draw(self, logits, pos, out, temperature, top_k, top_p, seed, pen: dict, hist=None, **kw) -> None:
+        """One token per row of ``logits`` at ``pos`` into ``out``: gpt2mi_sample_ragged, or with ``pen`` (``_penalties``'
+        keywords, not empty) gpt2mi_sample_penalized over the history ``hist``. ``kw``: row_id, eos, done."""
+        if pen:
+            K.sample_penalized(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **kw,
+                               **{"hist": hist, **pen})
+        else:
+            K.sample_ragged(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **kw)
+
+    def _loop(self, n: int, temperature, top_k, top_p, seed, pen: dict, **kw) -> None:
+        """``n`` sample-then-step rounds from ``lens`` into ``_tok``: gpt2mi_decode_generate_ragged, or with ``pen``
+        gpt2mi_decode_generate_penalized. ``kw``: row_id, eos, seq, done."""
+        loop = K.decode_generate_penalized if pen else K.decode_generate_ragged
+        loop(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n, self._tok, **kw, **pen)
+
+    def _check_run(self, n: int, row_id, eos_token_id, seq, done, penalties, gen_start):
+        """The argument checks ``generate`` and ``speculate`` share, then ``flush``; (row_id, done, pen) as checked:
+        ``done`` is None without eos, ``pen`` is ``_penalties``' keywords over ``seq``."""
+        row_id = _check_row_id(row_id, self.B)
+        if max(self.lens) + int(self._drawn) + n > self.Tcap:
+            raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
+        if seq is not None and (seq.dtype != torch.int64 or seq.dim() != 2 or seq.size(0) != self.B or seq.stride(1) != 1):
+            raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
+        if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
+            raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
+        pen = self._penalties(*penalties, gen_start, seq, "seq", max(self.lens) + int(self._drawn) + n - 1)
+        self.flush()  # the token the previous call ended on
+        return row_id, done if eos_token_id is not None else None, pen
+
     @torch.no_grad()
     def sample(self, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                seed: int = 0, row_id: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
@@ -506,12 +542,8 @@ class DecodeSession:
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, history, "history",
                               max(self.lens))
         out = torch.empty(self.B, dtype=torch.int64, device=self.logits.device)
-        if pen:
-            K.sample_penalized(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, out,
-                               row_id=_check_row_id(row_id, self.B), hist=history, **pen)
-        else:
-            K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, out,
-                            row_id=_check_row_id(row_id, self.B))
+        self._draw(self.logits, self.lens, out, temperature, top_k, top_p, seed, pen, history,
+                   row_id=_check_row_id(row_id, self.B))
         return out
 
     @torch.no_grad()
@@ -534,23 +566,9 @@ class DecodeSession:
         n = int(n)
         if n < 1:
             raise ValueError(f"generate takes n >= 1 (got {n})")
-        row_id = _check_row_id(row_id, self.B)
-        if max(self.lens) + int(self._drawn) + n > self.Tcap:
-            raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
-        if seq is not None and (seq.dtype != torch.int64 or seq.dim() != 2 or seq.size(0) != self.B or seq.stride(1) != 1):
-            raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
-        if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
-            raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
-        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, seq, "seq",
-                              max(self.lens) + int(self._drawn) + n - 1)
-        self.flush()  # the token the previous call ended on
-        done = done if eos_token_id is not None else None
-        if pen:
-            K.decode_generate_penalized(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
-                                        self._tok, row_id=row_id, eos=eos_token_id, seq=seq, done=done, **pen)
-        else:
-            K.decode_generate_ragged(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
-                                     self._tok, row_id=row_id, eos=eos_token_id, seq=seq, done=done)
+        row_id, done, pen = self._check_run(n, row_id, eos_token_id, seq, done,
+                                            (repetition_penalty, presence_penalty, frequency_penalty), gen_start)
+        self._loop(n, temperature, top_k, top_p, seed, pen, row_id=row_id, eos=eos_token_id, seq=seq, done=done)
         self.lens = [m + n - 1 for m in self.lens]
         self._drawn = True
         return self._tok
@@ -629,13 +647,8 @@ class DecodeSession:
         K.decode_extend(plan, tok_t, seqs, poss)
         out = torch.empty(R, dtype=torch.int64, device=self.device)
         temperature, top_k, top_p, seed = sampler[:4]
-        pen = verify_history(sampler, tok_t, seqs, poss)
-        if pen:
-            K.sample_penalized(scratch["logits"][:R], V, temperature, top_k, top_p, seed, [p + 1 for p in poss], out,
-                               row_id=keys, **pen)
-        else:
-            K.sample_ragged(scratch["logits"][:R], V, temperature, top_k, top_p, seed, [p + 1 for p in poss], out,
-                            row_id=keys)
+        self._draw(scratch["logits"][:R], [p + 1 for p in poss], out, temperature, top_k, top_p, seed,
+                   verify_history(sampler, tok_t, seqs, poss), row_id=keys)
         return out.tolist()
 
     @torch.no_grad()
@@ -674,24 +687,11 @@ class DecodeSession:
         if self.B * (k + 1) > MAX_BATCH:
             raise ValueError(f"B={self.B} rows of {k} drafts + 1 exceed the {MAX_BATCH} rows of a call")
         self._check_sampler(temperature, top_p, seed)
-        row_id = _check_row_id(row_id, self.B)
-        if max(self.lens) + int(self._drawn) + n > self.Tcap:
-            raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
-        if seq is not None and (seq.dtype != torch.int64 or seq.dim() != 2 or seq.size(0) != self.B or seq.stride(1) != 1):
-            raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
-        if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
-            raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
-        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, seq, "seq",
-                              max(self.lens) + int(self._drawn) + n - 1)
-        self.flush()
-        done = done if eos_token_id is not None else None
+        row_id, done, pen = self._check_run(n, row_id, eos_token_id, seq, done,
+                                            (repetition_penalty, presence_penalty, frequency_penalty), gen_start)
         lens0 = list(self.lens)
-        if pen:
-            K.sample_penalized(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, self._tok,
-                               row_id=row_id, eos=eos_token_id, done=done, hist=seq, **pen)
-        else:
-            K.sample_ragged(self.logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, self._tok,
-                            row_id=row_id, eos=eos_token_id, done=done)
+        self._draw(self.logits, self.lens, self._tok, temperature, top_k, top_p, seed, pen, seq, row_id=row_id,
+                   eos=eos_token_id, done=done)
         first = self._tok.tolist()
         history = [[] for _ in range(self.B)] if seq is None else [r[:m] for r, m in zip(seq.tolist(), lens0)]
         keys = list(range(self.B)) if row_id is None else row_id
@@ -862,8 +862,7 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     sess = DecodeSession(model, B, P + n)
     logits = sess.prefill(idx, lens)
     rp, pp, fp, on = penalties
-    starts = lens_t.tolist()
-    pen = dict(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp, gen_start=starts) if on else {}
+    pen = _penalty_keywords(penalties, lens_t.tolist())
     if seed is not None:
         done = None if eos_token_id is None else torch.zeros(B, dtype=torch.uint8, device=dev)
         if draft is None:
@@ -965,7 +964,7 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
     and the generated part starts at the prompt's length. A row reads its own row below its own position only, so a
     prompt's continuation still does not depend on what it is batched with."""
     B, dev = sess.B, sess.device
-    rp, pp, fp, on = penalties
+    on = penalties[3]
     out: List[Optional[torch.Tensor]] = [None] * len(prompts)
     pending = list(range(len(prompts)))[::-1]  # (pop() serves them in input order)
     owner: List[Optional[int]] = [None] * B
@@ -991,9 +990,8 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
         for r in range(B):  # a dummy row that a chunk would take past the cache starts over
             if owner[r] is None and sess.lens[r] + m + 1 > sess.Tcap:
                 fill(r)
-        pen = dict(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp, gen_start=list(start)) if on else {}
         sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done,
-                      row_id=[DUMMY_ID if o is None else o for o in owner], **pen)
+                      row_id=[DUMMY_ID if o is None else o for o in owner], **_penalty_keywords(penalties, start))
         sess.flush()  # every row's logits are now those of its next position: a refilled row joins on equal terms
         host = torch.cat([done.to(torch.int64)[:, None], seq], dim=1).cpu()  # the one read of the chunk
         for r in range(B):

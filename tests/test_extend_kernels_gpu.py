@@ -87,6 +87,25 @@ def test_attn_extend_has_the_bits_of_one_position_at_a_time(K, attn_inputs, name
     assert not torch.equal(bits(kc1), bits(attn_inputs[1]))  # (the call did write)
 
 
+def test_attn_extend_with_runs_of_one_is_attn_decode_ragged(K, attn_inputs):
+    """The relation the two entries' shared body encodes: the decode entry is the extend entry with first = pos. With
+    the identity map (row r is sequence r, every run one row) at positions 0 / 32 / 69 (the first key, a range edge, the
+    last and partly filled range) one gpt2mi_attn_extend gives what one gpt2mi_attn_decode_ragged over the same three
+    rows gives: out, both caches and the whole sentinel-filled workspace, bit for bit."""
+    qkv, kc, vc = attn_inputs
+    seq, pos = [0, 1, 2], [0, 32, 69]
+    out, kc1, vc1, ws = run_extend(K, qkv, kc, vc, seq, pos)
+    kc2, vc2 = kc.clone(), vc.clone()
+    want = torch.full((B, C), -12288.0, dtype=BF16, device=dev)
+    ws2 = torch.full_like(ws, WS_SENTINEL)
+    K.attn_decode_ragged(qkv[:B].contiguous(), kc2, vc2, want, ws2, B, H, 64, TCAP, pos)
+    torch.cuda.synchronize()
+    assert torch.equal(bits(out), bits(want))
+    assert torch.equal(bits(kc1), bits(kc2)) and torch.equal(bits(vc1), bits(vc2))
+    assert torch.equal(bits(ws), bits(ws2))
+    assert not torch.equal(bits(kc1), bits(kc)) and bool((ws != WS_SENTINEL).any())  # (the calls did write)
+
+
 @pytest.mark.parametrize("name", MAPS)
 def test_attn_extend_against_fp64(K, attn_inputs, name):
     seq, pos = MAPS[name]

@@ -310,7 +310,9 @@ def xent_mode(libs, g, st):
 def decode_mode(libs, st):
     """LIB_AB_OP=decode: the decode entries with a scalar position (gpt2mi_attn_decode, gpt2mi_embed_decode,
     gpt2mi_sample greedy and at temperature 0.8 / top_k 50 / top_p 0.95, gpt2mi_decode_step on a random-weight plan) and
-    their _ragged forms at equal and at mixed positions. Small shapes (B = 4, H = 2, Tcap = 70, positions 0 / 31 / 32 / 69,
+    their _ragged forms at equal and at mixed positions; gpt2mi_attn_extend and gpt2mi_decode_extend over row maps, and
+    gpt2mi_sample_penalized with neutral and non-neutral values.
+    Small shapes (B = 4, H = 2, Tcap = 70, positions 0 / 31 / 32 / 69,
     V = 509 and 50257) and GPT-2 124M's widths at B = 1, 8, 64 with pos = 575 in a 1024-position cache. Every library
     gets clones of the same seeded inputs; every output (out, both caches, x, tok, seq, probs_out, logits) is compared
     bitwise against the first library's; each row is timed in interleaved rounds (HIP events around back-to-back
@@ -373,6 +375,21 @@ def decode_mode(libs, st):
                     qkv.data_ptr(), s["kcache"].data_ptr(), s["vcache"].data_ptr(), s["out"].data_ptr(),
                     s["ws"].data_ptr(), ws_n, B, H, 64, Tcap, arg, st))
 
+    def attn_extend(B, H, Tcap, maps):
+        """gpt2mi_attn_extend over each row map (label, seq, pos): R rows of B sequences."""
+        C = 64 * H
+        for name, seq, pos in maps:
+            R = len(seq)
+            qkv, kc0, vc0 = rn(R, 3 * C, dt=bf), rn(B, H, Tcap, 64, dt=bf), rn(B, H, Tcap, 64, dt=bf)
+            ws_n = libs[0].gpt2mi_attn_decode_workspace(R, H, Tcap)
+            make = lambda R=R, kc0=kc0, vc0=vc0, ws_n=ws_n: dict(  # noqa: E731
+                out=torch.zeros(R, C, dtype=bf, device=dev), kcache=kc0.clone(), vcache=vc0.clone(),
+                ws=torch.zeros(ws_n, device=dev))
+            row(f"attn_extend B={B} H={H} Tcap={Tcap} {name}", "gpt2mi_attn_extend", make,
+                lambda lib, s, R=R, qkv=qkv, ws_n=ws_n, sa=ints(seq), pa=ints(pos): lib.gpt2mi_attn_extend(
+                    qkv.data_ptr(), s["kcache"].data_ptr(), s["vcache"].data_ptr(), s["out"].data_ptr(),
+                    s["ws"].data_ptr(), ws_n, R, B, H, 64, Tcap, sa, pa, st))
+
     def embed(B, C, V, Tcap, vs):
         tok = torch.randint(0, V, (B,), device=dev, generator=g)
         wte, wpe = rn(V, C), rn(Tcap, C)
@@ -399,8 +416,33 @@ def decode_mode(libs, st):
                     return lib.gpt2mi_sample_ragged(*a, arr, None, *z)  # (row_id NULL: the row number)
                 row(f"sample {mode} B={B} V={V} {name}", "gpt2mi_sample" + ("" if p is not None else "_ragged"), make, call)
 
-    def step(B, C, H, L, V, Vp, Tcap, vs, reps):
-        """gpt2mi_decode_step on random weights (shared by the libraries) with each library's own buffers and caches."""
+    def sample_penalized(B, V, ldl, T):
+        """gpt2mi_sample_penalized at position T - 1 over a random history of T - 1 tokens (seq is the history and takes
+        the token), with neutral values (the plain kernels, logits_out a copy) and with (1.3, 0.5, 0.25)."""
+        logits = rn(B, ldl, scale=3.0)
+        hist = torch.randint(0, V, (B, T), device=dev, generator=g)
+        pos, starts = ints([T - 1] * B), ints([(17 * b) % T for b in range(B)])
+        pens = {}  # id(state) -> its gpt2mi_penalties, kept alive with it
+
+        def make(vals):
+            s = dict(tok=torch.zeros(B, dtype=torch.int64, device=dev), seq=hist.clone(),
+                     probs_out=torch.zeros(B, V, device=dev), logits_out=torch.zeros(B, V, device=dev))
+            pens[id(s)] = K.Penalties(*vals, s["seq"].data_ptr(), T, B, None, ctypes.cast(starts, ctypes.c_void_p))
+            return s
+        for mode, (t, k, tp) in {"greedy": (0.0, 0, 1.0), "t0.8 k50 p0.95": (0.8, 50, 0.95)}.items():
+            for name, vals in {"neutral": (1.0, 0.0, 0.0), "rp1.3 pp0.5 fp0.25": (1.3, 0.5, 0.25)}.items():
+                row(f"sample_penalized {mode} B={B} V={V} {name}", "gpt2mi_sample_penalized",
+                    lambda vals=vals: make(vals),
+                    lambda lib, s, t=t, k=k, tp=tp: lib.gpt2mi_sample_penalized(
+                        logits.data_ptr(), ldl, B, V, t, k, tp, 7, pos, None, -1, None, s["tok"].data_ptr(),
+                        s["seq"].data_ptr(), T, s["probs_out"].data_ptr(), ctypes.byref(pens[id(s)]),
+                        s["logits_out"].data_ptr(), st))
+                pens.clear()
+
+    def step(B, C, H, L, V, Vp, Tcap, vs, reps, extends=()):
+        """gpt2mi_decode_step on random weights (shared by the libraries) with each library's own buffers and caches;
+        then gpt2mi_decode_extend over each row map of `extends` (label, seq, pos) on the same plan, its buffers and
+        plan->rows sized for the map's rows."""
         w = dict(wte=rn(Vp, C, scale=0.02), wpe=rn(Tcap, C, scale=0.02), lnf_w=1 + rn(C, scale=0.1), lnf_b=rn(C, scale=0.1))
         w["wte"][V:] = 0
         w["wte_bf16"] = w["wte"].to(bf)
@@ -412,15 +454,15 @@ def decode_mode(libs, st):
             lw.append(d)
         tok = torch.randint(0, V, (B,), device=dev, generator=g)
         kc0, vc0 = rn(L, B, H, Tcap, 64, dt=bf), rn(L, B, H, Tcap, 64, dt=bf)
-        aws = libs[0].gpt2mi_attn_decode_workspace(B, H, Tcap)
-        gws = max(libs[0].gpt2mi_gemm_skinny_workspace(B, n, k)
-                  for n, k in ((3 * C, C), (C, C), (4 * C, C), (C, 4 * C), (Vp, C)))
         plans = {}  # id(state) -> (plan, layers): ctypes structures of a state, kept alive with it
 
-        def make():
+        def make(M=B):
+            aws = libs[0].gpt2mi_attn_decode_workspace(M, H, Tcap)
+            gws = max(libs[0].gpt2mi_gemm_skinny_workspace(M, n, k)
+                      for n, k in ((3 * C, C), (C, C), (4 * C, C), (C, 4 * C), (Vp, C)))
             z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=dev)  # noqa: E731
-            s = dict(logits=z(B, Vp), kcache=kc0.clone(), vcache=vc0.clone(), x=z(B, C), xmid=z(B, C), ln=z(B, C, dt=bf),
-                     qkv=z(B, 3 * C, dt=bf), ao=z(B, C, dt=bf), h=z(B, 4 * C, dt=bf), mean=z(B), rstd=z(B),
+            s = dict(logits=z(M, Vp), kcache=kc0.clone(), vcache=vc0.clone(), x=z(M, C), xmid=z(M, C), ln=z(M, C, dt=bf),
+                     qkv=z(M, 3 * C, dt=bf), ao=z(M, C, dt=bf), h=z(M, 4 * C, dt=bf), mean=z(M), rstd=z(M),
                      attn_ws=z(max(aws, 1)), gemm_ws=z(max(gws, 1)))
             layers = (K.DecodeLayer * L)()
             for l, Y in enumerate(layers):
@@ -435,6 +477,7 @@ def decode_mode(libs, st):
             for n in ("x", "xmid", "ln", "qkv", "ao", "h", "mean", "rstd", "attn_ws", "gemm_ws", "logits"):
                 setattr(P, n, s[n].data_ptr())
             P.attn_ws_floats, P.gemm_ws_floats = s["attn_ws"].numel(), s["gemm_ws"].numel()
+            P.rows = 0 if M == B else M
             plans[id(s)] = (P, layers)
             return s
         for name, p, plist in vs:
@@ -444,19 +487,34 @@ def decode_mode(libs, st):
                 lambda lib, s, sym=sym, arg=arg: getattr(lib, sym)(ctypes.byref(plans[id(s)][0]), tok.data_ptr(), arg, st),
                 reps=reps)
             plans.clear()
+        for name, seq, pos in extends:
+            R = len(seq)
+            xtok = torch.randint(0, V, (R,), device=dev, generator=g)
+            row(f"decode_extend B={B} C={C} L={L} Vp={Vp} {name}", "gpt2mi_decode_extend", lambda R=R: make(R),
+                lambda lib, s, R=R, xtok=xtok, sa=ints(seq), pa=ints(pos): lib.gpt2mi_decode_extend(
+                    ctypes.byref(plans[id(s)][0]), R, xtok.data_ptr(), sa, pa, st), reps=reps)
+            plans.clear()
 
+    # the row maps of tests/test_extend_kernels_gpu.py (three runs; one sequence absent), and R rows of one sequence
+    maps = [("three-runs", [0, 0, 0, 0, 1, 1, 1, 2, 2, 2, 2], [30, 31, 32, 33, 0, 1, 2, 66, 67, 68, 69]),
+            ("one-absent", [0, 0, 0, 0, 2, 2, 2, 2], [30, 31, 32, 33, 66, 67, 68, 69])]
+    one_run = lambda R: (f"R={R} one run to pos=575", [0] * R, list(range(576 - R, 576)))  # noqa: E731
     small = variants(4, (0, 31, 32, 69), [0, 31, 32, 69])
     attn(4, 2, 70, small)
+    attn_extend(3, 2, 70, maps)
     embed(4, 128, 509, 70, small)
     for V, ldl in ((509, 512), (50257, 50432)):
         sample(4, V, ldl, 70, small)
-    step(4, 128, 2, 2, 509, 512, 70, small, reps=5)
+        sample_penalized(4, V, ldl, 70)
+    step(4, 128, 2, 2, 509, 512, 70, small, reps=5, extends=maps)
+    attn_extend(1, 12, 1024, [one_run(8)])
     for B in (1, 8, 64):
         big = variants(B, (575,), [575 - (37 * b) % 576 for b in range(B)])
         attn(B, 12, 1024, big)
         embed(B, 768, 50257, 1024, big)
         sample(B, 50257, 50432, 1024, big)
-        step(B, 768, 12, 12, 50257, 50432, 1024, big, reps=5)
+        step(B, 768, 12, 12, 50257, 50432, 1024, big, reps=5,
+             extends=[one_run(R) for R in (5, 8, 16)] if B == 1 else ())
     print(f"decode A/B: {stats['rows']} rows compared against lib0, {stats['mismatches']} mismatching outputs, "
           f"{stats['skipped']} skipped", flush=True)
     if stats["mismatches"]:
