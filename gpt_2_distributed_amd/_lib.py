@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -116,6 +116,11 @@ _SIGS = {
                                 _p, _p, _p, _c_int, _p, _p, _p, _p],
     "gpt2mi_decode_generate_penalized": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _p, _p, _c_int,
                                          _p, _p, _c_int, _p, _p, _c_float, _c_float, _c_float, _p],
+    # v23 fp8 cache: the bf16 siblings' lists with (kscale, vscale) behind (kcache, vcache)
+    "gpt2mi_kv_store_fp8": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p],
+    "gpt2mi_attn_decode_fp8_ragged": [_p, _p, _p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _p, _p],
+    "gpt2mi_attn_extend_fp8": [_p, _p, _p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p,
+                               _p],
 }
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size}
@@ -412,7 +417,7 @@ def zero_ranges(t: torch.Tensor, ranges: torch.Tensor):
 class DecodeLayer(ctypes.Structure):
     """gpt2mi_decode_layer (include/gpt2mi.h)."""
     _fields_ = [(n, _p) for n in ("ln1_w", "ln1_b", "ln2_w", "ln2_b", "qkv_w", "proj_w", "fc1_w", "fc2_w",
-                                  "qkv_b", "proj_b", "fc1_b", "fc2_b", "kcache", "vcache")]
+                                  "qkv_b", "proj_b", "fc1_b", "fc2_b", "kcache", "vcache", "kscale", "vscale")]
 
 
 class DecodePlan(ctypes.Structure):
@@ -423,6 +428,22 @@ class DecodePlan(ctypes.Structure):
                 [(n, _p) for n in ("x", "xmid", "ln", "qkv", "ao", "h", "mean", "rstd")] +
                 [("attn_ws", _p), ("attn_ws_floats", _c_size), ("gemm_ws", _p), ("gemm_ws_floats", _c_size),
                  ("logits", _p), ("rows", _c_int)])
+
+    # v23 appends `int kv_format` behind `rows`. An int behind a pointer-aligned struct's last int lands in what was the
+    # struct's tail padding: no offset moved and sizeof did not change. The field list above stays the one of v21
+    # (tests/test_extend_cpu.py pins its last two names), so the new field is a property over those four bytes, which
+    # ctypes allocates and zeroes with the rest of the structure: a plan that never sets it means bf16.
+    @property
+    def kv_format(self) -> int:
+        return _c_int.from_address(ctypes.addressof(self) + self.KV_FORMAT_OFFSET).value
+
+    @kv_format.setter
+    def kv_format(self, value: int) -> None:
+        _c_int.from_address(ctypes.addressof(self) + self.KV_FORMAT_OFFSET).value = value
+
+
+DecodePlan.KV_FORMAT_OFFSET = DecodePlan.rows.offset + ctypes.sizeof(_c_int)
+assert DecodePlan.KV_FORMAT_OFFSET + ctypes.sizeof(_c_int) <= ctypes.sizeof(DecodePlan)
 
 
 def gemm_skinny_workspace(M, N, K) -> int:
@@ -586,6 +607,28 @@ def decode_extend(plan: DecodePlan, tok, seq, pos):
     """gpt2mi_decode_extend: the step's launch list on len(pos) rows of the row map (seq, pos), into plan.logits."""
     R = len(pos)
     _call("gpt2mi_decode_extend", ctypes.byref(plan), R, _ptr(tok), _positions(seq, R), _positions(pos, R), _stream())
+
+
+# ---- v23: the fp8 key/value cache (csrc/decode.hip) ----------------------------------------------------
+KV_BF16, KV_FP8 = 0, 1  # gpt2mi.h GPT2MI_KV_*: gpt2mi_decode_plan.kv_format
+
+
+def kv_store_fp8(qkv, kcache, vcache, kscale, vscale, B, T_src, n, t0, H, D, Tcap):
+    """kv_store into an fp8 cache: uint8 codes [B][H][Tcap][64] and fp32 scales [B][H][Tcap] (generation.kv_quantize)."""
+    _call("gpt2mi_kv_store_fp8", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale), B, T_src, n, t0, H,
+          D, Tcap, _stream())
+
+
+def attn_decode_fp8_ragged(qkv, kcache, vcache, kscale, vscale, out, workspace, B, H, D, Tcap, pos):
+    """attn_decode_ragged over an fp8 cache."""
+    _call("gpt2mi_attn_decode_fp8_ragged", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale), _ptr(out),
+          _ptr(workspace), workspace.numel(), B, H, D, Tcap, _positions(pos, B), _stream())
+
+
+def attn_extend_fp8(qkv, kcache, vcache, kscale, vscale, out, workspace, R, B, H, D, Tcap, seq, pos):
+    """attn_extend over an fp8 cache."""
+    _call("gpt2mi_attn_extend_fp8", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale), _ptr(out),
+          _ptr(workspace), workspace.numel(), R, B, H, D, Tcap, _positions(seq, R), _positions(pos, R), _stream())
 
 
 # ---- v22: penalties in the sampler (csrc/sample.hip, csrc/decode.hip) -----------------------------------

@@ -9,6 +9,8 @@
 // The attention of the step and of the multi-row extend are two __global__ entries over one body (attn_row). Their
 // gfx950 disassemblies (the Makefile's flags, -S) were compared with those of the two separate kernels they replace:
 // same registers, no scratch, occupancy 8; what differs is listed in DESIGN.md "Multi-token decode step".
+// The cache is bf16 or, since v23, fp8 (e4m3 codes and a power-of-two scale per 64-wide row): attn_row is templated on
+// the format and kv_store has a second kernel; the bf16 instantiations are instruction for instruction what they were.
 #include <limits.h>
 
 #include <algorithm>
@@ -181,6 +183,79 @@ __device__ __forceinline__ void unpack8(bf16x8 v, float* f) {
   for (int j = 0; j < 8; ++j) f[j] = bf2f(v[j]);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The fp8 cache format (gpt2mi.h v23; generation.py kv_quantize / kv_dequantize are the rule, executable): a 64-wide
+// row of K or V is 64 OCP e4m3 codes and one fp32 scale 2^e, e the smallest exponent with amax <= 448 * 2^e and
+// >= -100. Scaling by a power of two is exact and |x * 2^-e| <= 448, so the conversion never saturates: the codes are
+// a pure function of the row's 64 bf16 values. This pair is the one quantiser and the one dequantiser of the file:
+// kv_store_fp8_kernel and attn_row both call it, so the two writers of a cache position cannot disagree.
+struct KvRow8 {
+  uint2 codes;  // this lane's 8 codes, dim 8 dg + j in byte j
+  float scale;  // 2^e of the whole row
+};
+
+// f: the lane's 8 values of a row held by 8 adjacent lanes (lane ^ 1, 2, 4 hold the rest of it).
+__device__ __forceinline__ KvRow8 kv_quantize8(const float* f) {
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
+  amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
+  amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
+  amax = fmaxf(amax, __shfl_xor(amax, 4, 64));
+  // amax = m 2^k, m in [1, 2): e = k - 8 + (m > 1.75). A zero or subnormal amax has exponent field 0 and clamps.
+  const unsigned u = __float_as_uint(amax);
+  const int e = max((int)(u >> 23) - 135 + ((u & 0x7FFFFFu) > 0x600000u ? 1 : 0), -100);
+  const float inv = __uint_as_float((unsigned)(127 - e) << 23);  // e in [-100, 121]: both are normal numbers
+  KvRow8 r;
+  r.scale = __uint_as_float((unsigned)(127 + e) << 23);
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * inv, f[1] * inv, lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * inv, f[3] * inv, lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * inv, f[5] * inv, hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * inv, f[7] * inv, hi, true);
+  r.codes = uint2{(unsigned)lo, (unsigned)hi};
+  return r;
+}
+
+// The 8 codes as fp32, without the scale (exact: every e4m3 value is an fp32 value).
+__device__ __forceinline__ void kv_codes8(uint2 c, float* f) {
+  const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.x, true);
+  const f32x2 d = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.y, false), g = __builtin_amdgcn_cvt_pk_f32_fp8((int)c.y, true);
+  f[0] = a[0], f[1] = a[1], f[2] = b[0], f[3] = b[1], f[4] = d[0], f[5] = d[1], f[6] = g[0], f[7] = g[1];
+}
+
+// code * 2^e: exact.
+__device__ __forceinline__ void kv_dequantize8(const KvRow8& r, float* f) {
+  kv_codes8(r.codes, f);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) f[j] *= r.scale;
+}
+
+// kv_store_kernel's indexing with the rows quantised: the 8 threads of a (b, t, K or V, h) row are 8 adjacent lanes
+// (a row is 8 consecutive values of i and blocks start at multiples of 8). Threads beyond the last row take part in
+// the shuffles on row 0's values and store nothing.
+__global__ __launch_bounds__(256) void kv_store_fp8_kernel(const bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
+                                                           uint8_t* __restrict__ vc, float* __restrict__ ks,
+                                                           float* __restrict__ vs, int B, int T_src, int n, int t0,
+                                                           int H, int Tcap) {
+  const int C = H * 64, per_row = 2 * C / 8;
+  const size_t at = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const bool live = at < (size_t)B * n * per_row;
+  const size_t i = live ? at : 0;
+  const int j = (int)(i % per_row);
+  const size_t row = i / per_row;
+  const int t = (int)(row % n), b = (int)(row / n);
+  const int col = 8 * j;  // in [0, 2C): K then V
+  const int which = col / C, c = col % C, h = c / 64, d = c % 64;
+  float f[8];
+  unpack8(*reinterpret_cast<const bf16x8*>(qkv + ((size_t)b * T_src + t) * 3 * C + C + col), f);
+  const KvRow8 q = kv_quantize8(f);
+  if (!live) return;
+  const size_t pos = ((size_t)b * H + h) * Tcap + t0 + t;
+  *reinterpret_cast<uint2*>((which ? vc : kc) + pos * 64 + d) = q.codes;
+  if (d == 0) (which ? vs : ks)[pos] = q.scale;
+}
+
 // A position per row: the host array of the C entry, validated there and passed by value as a kernel argument, so a
 // kernel never indexes memory with a position nobody checked. Indexed by blockIdx: scalar loads.
 struct RowPos {
@@ -200,10 +275,19 @@ struct RowPos {
 // A wave whose range starts beyond pos leaves before any load or store (wave-uniform: one wave per block, range and
 // row from blockIdx; the body has no barrier), so its workspace slot stays unwritten and attn_combine_kernel does not
 // read it. The workspace slot is that of row r, not of the sequence.
-template <bool RUN>
-__device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, bf16* __restrict__ kc, bf16* __restrict__ vc,
-                                         float* __restrict__ ws_ml, float* __restrict__ ws_acc, int H, int Tcap,
-                                         int nr_max, int r, size_t stream, int pos, int first) {
+//
+// FP8 = true is the body over the fp8 cache (kc / vc are the code bytes, ks / vs the scales [stream][Tcap]; FP8 = false
+// does not touch ks / vs and is the bf16 body unchanged). A key is then held as (8 codes, scale) whichever source it
+// has: a key below `first` is loaded that way, a key of the call is quantised in registers by kv_quantize8, the
+// quantiser of the store kernel, and the row at position t writes those codes and that scale. Both are dequantised at
+// the one place that uses them, so the invariant above holds as it stands: the bits of a key are the same from either
+// source. The key's scale is applied to its score after the sum (a power of two: the same bits as scaling the 64
+// products, short of underflow, where a score is 0 either way); a value is code * scale before use, exactly.
+template <bool RUN, bool FP8, class KV>
+__device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, KV* __restrict__ kc, KV* __restrict__ vc,
+                                         float* __restrict__ ks, float* __restrict__ vs, float* __restrict__ ws_ml,
+                                         float* __restrict__ ws_acc, int H, int Tcap, int nr_max, int r, size_t stream,
+                                         int pos, int first) {
   const int range = blockIdx.x, h = blockIdx.y;
   if (range * AD_KEYS > pos) return;
   const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
@@ -217,21 +301,47 @@ __device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, bf16* __r
   const size_t base = stream * Tcap * 64 + 8 * dg;
   const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
   bf16x8 kv[4], vv[4];
+  KvRow8 k8[4], v8[4];  // FP8 only
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int key = range * AD_KEYS + kk + 8 * i;
-    kv[i] = zero;
-    vv[i] = zero;
-    if (key < first) {
-      kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
-      vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
-    } else if (RUN ? key <= pos : key == pos) {
-      const bf16* src = RUN ? tok - (ptrdiff_t)(pos - key) * 3 * C : tok;  // the run's row at position key
-      kv[i] = *reinterpret_cast<const bf16x8*>(src + C);
-      vv[i] = *reinterpret_cast<const bf16x8*>(src + 2 * C);
-      if (!RUN || key == pos) {
-        *reinterpret_cast<bf16x8*>(kc + base + (size_t)key * 64) = kv[i];
-        *reinterpret_cast<bf16x8*>(vc + base + (size_t)key * 64) = vv[i];
+    if constexpr (FP8) {
+      k8[i] = v8[i] = KvRow8{uint2{0u, 0u}, 0.f};
+      if (key < first) {
+        k8[i].codes = *reinterpret_cast<const uint2*>(kc + base + (size_t)key * 64);
+        v8[i].codes = *reinterpret_cast<const uint2*>(vc + base + (size_t)key * 64);
+        k8[i].scale = ks[stream * Tcap + key];
+        v8[i].scale = vs[stream * Tcap + key];
+      } else if (RUN ? key <= pos : key == pos) {  // (the 8 lanes of a key agree: kv_quantize8's shuffles stay inside)
+        const bf16* src = RUN ? tok - (ptrdiff_t)(pos - key) * 3 * C : tok;  // the run's row at position key
+        float kf[8], vf[8];
+        unpack8(*reinterpret_cast<const bf16x8*>(src + C), kf);
+        unpack8(*reinterpret_cast<const bf16x8*>(src + 2 * C), vf);
+        k8[i] = kv_quantize8(kf);
+        v8[i] = kv_quantize8(vf);
+        if (!RUN || key == pos) {
+          *reinterpret_cast<uint2*>(kc + base + (size_t)key * 64) = k8[i].codes;
+          *reinterpret_cast<uint2*>(vc + base + (size_t)key * 64) = v8[i].codes;
+          if (dg == 0) {
+            ks[stream * Tcap + key] = k8[i].scale;
+            vs[stream * Tcap + key] = v8[i].scale;
+          }
+        }
+      }
+    } else {
+      kv[i] = zero;
+      vv[i] = zero;
+      if (key < first) {
+        kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
+        vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
+      } else if (RUN ? key <= pos : key == pos) {
+        const bf16* src = RUN ? tok - (ptrdiff_t)(pos - key) * 3 * C : tok;  // the run's row at position key
+        kv[i] = *reinterpret_cast<const bf16x8*>(src + C);
+        vv[i] = *reinterpret_cast<const bf16x8*>(src + 2 * C);
+        if (!RUN || key == pos) {
+          *reinterpret_cast<bf16x8*>(kc + base + (size_t)key * 64) = kv[i];
+          *reinterpret_cast<bf16x8*>(vc + base + (size_t)key * 64) = vv[i];
+        }
       }
     }
   }
@@ -240,12 +350,16 @@ __device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, bf16* __r
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     float kf[8], d = 0.f;
-    unpack8(kv[i], kf);
+    if constexpr (FP8)
+      kv_codes8(k8[i].codes, kf);
+    else
+      unpack8(kv[i], kf);
 #pragma unroll
     for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], kf[j], d);
     d += __shfl_xor(d, 1, 64);
     d += __shfl_xor(d, 2, 64);
     d += __shfl_xor(d, 4, 64);
+    if constexpr (FP8) d *= k8[i].scale;
     s[i] = (range * AD_KEYS + kk + 8 * i <= pos) ? d : -INFINITY;
     mx = fmaxf(mx, s[i]);
   }
@@ -258,7 +372,10 @@ __device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, bf16* __r
   for (int i = 0; i < 4; ++i) {
     const float p = __expf(s[i] - mx);  // 0 for a masked key
     float vf[8];
-    unpack8(vv[i], vf);
+    if constexpr (FP8)
+      kv_dequantize8(v8[i], vf);
+    else
+      unpack8(vv[i], vf);
     l += p;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(p, vf[j], acc[j]);
@@ -289,7 +406,16 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(const bf16* __restrict_
                                                          float* __restrict__ ws_acc, int H, int Tcap, RowPos rows,
                                                          int nr_max) {
   const int b = blockIdx.z, bh = b * H + blockIdx.y;  // (b < 64: int)
-  attn_row<false>(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, nr_max, b, bh, rows.v[b], rows.v[b]);
+  attn_row<false, false>(qkv, kc, vc, nullptr, nullptr, ws_ml, ws_acc, H, Tcap, nr_max, b, bh, rows.v[b], rows.v[b]);
+}
+
+__global__ __launch_bounds__(64) void attn_decode_fp8_kernel(const bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
+                                                             uint8_t* __restrict__ vc, float* __restrict__ ks,
+                                                             float* __restrict__ vs, float* __restrict__ ws_ml,
+                                                             float* __restrict__ ws_acc, int H, int Tcap, RowPos rows,
+                                                             int nr_max) {
+  const int b = blockIdx.z, bh = b * H + blockIdx.y;
+  attn_row<false, true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, b, bh, rows.v[b], rows.v[b]);
 }
 
 // out[b, h*64 + d] = sum_r e^(m_r - m) acc_r[d] / sum_r e^(m_r - m) l_r over the pos[b] / 32 + 1 ranges of row b, in
@@ -326,8 +452,18 @@ __global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict_
                                                          float* __restrict__ ws_acc, int H, int Tcap, RowMap rows,
                                                          int nr_max) {
   const int r = blockIdx.z;
-  attn_row<true>(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, nr_max, r, (size_t)rows.seq[r] * H + blockIdx.y, rows.pos[r],
-                 rows.first[r]);
+  attn_row<true, false>(qkv, kc, vc, nullptr, nullptr, ws_ml, ws_acc, H, Tcap, nr_max, r,
+                        (size_t)rows.seq[r] * H + blockIdx.y, rows.pos[r], rows.first[r]);
+}
+
+__global__ __launch_bounds__(64) void attn_extend_fp8_kernel(const bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
+                                                             uint8_t* __restrict__ vc, float* __restrict__ ks,
+                                                             float* __restrict__ vs, float* __restrict__ ws_ml,
+                                                             float* __restrict__ ws_acc, int H, int Tcap, RowMap rows,
+                                                             int nr_max) {
+  const int r = blockIdx.z;
+  attn_row<true, true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, r, (size_t)rows.seq[r] * H + blockIdx.y,
+                       rows.pos[r], rows.first[r]);
 }
 
 // One row per blockIdx.y, so that the row's position is a scalar load of the argument.
@@ -402,18 +538,54 @@ GPT2MI_EXPORT int gpt2mi_gemm_skinny(int epilogue, int M, int N, int K, const ui
   return gpt2mi::check_launch("gemm_skinny reduce");
 }
 
+namespace {
+// The cache of one layer as an entry received it: the format, the two tensors (bf16, or the fp8 codes) and, with fp8,
+// their scales. The entries and the plan's attention call form one; everything between them passes it on.
+struct KvCache {
+  int format;  // GPT2MI_KV_BF16 / GPT2MI_KV_FP8
+  void *k, *v;
+  float *ks, *vs;
+};
+
+// 22 with a message unless the scales an fp8 cache needs are there (a bf16 cache has none).
+int kv_scales(const char* what, const KvCache& kv) {
+  GPT2MI_REQUIRE(kv.format != GPT2MI_KV_FP8 || (kv.ks && kv.vs), "%s: kscale and vscale of the fp8 cache must not be NULL",
+                 what);
+  return 0;
+}
+
+int kv_store_rows(const char* what, const uint16_t* qkv, const KvCache& kv, int B, int T_src, int n, int t0, int H,
+                  int head_dim, int Tcap, void* stream) {
+  GPT2MI_REQUIRE(head_dim == 64, "%s: head_dim=%d (the decode kernels implement 64)", what, head_dim);
+  GPT2MI_REQUIRE(B >= 1 && H >= 1 && Tcap >= 1, "%s: B=%d, H=%d, Tcap=%d must be positive", what, B, H, Tcap);
+  GPT2MI_REQUIRE(n >= 1 && n <= T_src, "%s: n=%d not in [1, T_src=%d]", what, n, T_src);
+  GPT2MI_REQUIRE(t0 >= 0 && (long long)t0 + n <= Tcap, "%s: t0=%d + n=%d exceeds the cache length Tcap=%d", what, t0, n,
+                 Tcap);
+  if (const int rc = kv_scales(what, kv)) return rc;
+  GPT2MI_REQUIRE(qkv && kv.k && kv.v, "%s: qkv and the caches must not be NULL", what);
+  const size_t total = (size_t)B * n * (2 * H * 64 / 8);
+  const unsigned grid = (unsigned)((total + 255) / 256);
+  if (kv.format == GPT2MI_KV_FP8)
+    kv_store_fp8_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)qkv, (uint8_t*)kv.k, (uint8_t*)kv.v, kv.ks,
+                                                               kv.vs, B, T_src, n, t0, H, Tcap);
+  else
+    kv_store_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)qkv, (bf16*)kv.k, (bf16*)kv.v, B, T_src, n, t0,
+                                                           H, Tcap);
+  return gpt2mi::check_launch(what);
+}
+}  // namespace
+
 GPT2MI_EXPORT int gpt2mi_kv_store(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, int B, int T_src, int n,
                                   int t0, int H, int head_dim, int Tcap, void* stream) {
-  GPT2MI_REQUIRE(head_dim == 64, "kv_store: head_dim=%d (the decode kernels implement 64)", head_dim);
-  GPT2MI_REQUIRE(B >= 1 && H >= 1 && Tcap >= 1, "kv_store: B=%d, H=%d, Tcap=%d must be positive", B, H, Tcap);
-  GPT2MI_REQUIRE(n >= 1 && n <= T_src, "kv_store: n=%d not in [1, T_src=%d]", n, T_src);
-  GPT2MI_REQUIRE(t0 >= 0 && (long long)t0 + n <= Tcap, "kv_store: t0=%d + n=%d exceeds the cache length Tcap=%d", t0, n,
-                 Tcap);
-  GPT2MI_REQUIRE(qkv && kcache && vcache, "kv_store: qkv and the caches must not be NULL");
-  const size_t total = (size_t)B * n * (2 * H * 64 / 8);
-  kv_store_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-      (const bf16*)qkv, (bf16*)kcache, (bf16*)vcache, B, T_src, n, t0, H, Tcap);
-  return gpt2mi::check_launch("kv_store");
+  return kv_store_rows("kv_store", qkv, KvCache{GPT2MI_KV_BF16, kcache, vcache, nullptr, nullptr}, B, T_src, n, t0, H,
+                       head_dim, Tcap, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_kv_store_fp8(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale,
+                                      float* vscale, int B, int T_src, int n, int t0, int H, int head_dim, int Tcap,
+                                      void* stream) {
+  return kv_store_rows("kv_store_fp8", qkv, KvCache{GPT2MI_KV_FP8, kcache, vcache, kscale, vscale}, B, T_src, n, t0, H,
+                       head_dim, Tcap, stream);
 }
 
 GPT2MI_EXPORT size_t gpt2mi_attn_decode_workspace(int B, int H, int Tcap) {
@@ -441,38 +613,44 @@ using gpt2mi::SamePos;
 
 // The tail the two attention entries share, after their own row checks: M rows whose kernel argument is `rows`, at the
 // positions rp (the longest max_pos). The workspace is M * H * nr_max (max, sum) pairs, then as many acc[64].
+// `kernel` and `kernel8` are the entry's kernel over a bf16 and over an fp8 cache.
 template <class Rows>
 int attn_launch(const char* what, void (*kernel)(const bf16*, bf16*, bf16*, float*, float*, int, int, Rows, int),
-                const Rows& rows, const RowPos& rp, int max_pos, const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache,
-                uint16_t* out, float* workspace, size_t workspace_floats, int M, int H, int Tcap, void* stream) {
+                void (*kernel8)(const bf16*, uint8_t*, uint8_t*, float*, float*, float*, float*, int, int, Rows, int),
+                const Rows& rows, const RowPos& rp, int max_pos, const uint16_t* qkv, const KvCache& kv, uint16_t* out,
+                float* workspace, size_t workspace_floats, int M, int H, int Tcap, void* stream) {
   const size_t need = gpt2mi_attn_decode_workspace(M, H, Tcap);
   GPT2MI_REQUIRE(workspace_floats >= need, "%s: workspace too small (%zu floats given, %zu needed)", what,
                  workspace_floats, need);
-  GPT2MI_REQUIRE(qkv && kcache && vcache && out && workspace,
-                 "%s: qkv, the caches, out and workspace must not be NULL", what);
+  if (const int rc = kv_scales(what, kv)) return rc;
+  GPT2MI_REQUIRE(qkv && kv.k && kv.v && out && workspace, "%s: qkv, the caches, out and workspace must not be NULL",
+                 what);
   hipStream_t s = (hipStream_t)stream;
   const int nr_max = attn_ranges(Tcap);
   float* ws_ml = workspace;
   float* ws_acc = workspace + (size_t)M * H * nr_max * 2;
-  kernel<<<dim3(max_pos / AD_KEYS + 1, H, M), 64, 0, s>>>((const bf16*)qkv, (bf16*)kcache, (bf16*)vcache, ws_ml, ws_acc,
-                                                         H, Tcap, rows, nr_max);
+  const dim3 grid(max_pos / AD_KEYS + 1, H, M);
+  if (kv.format == GPT2MI_KV_FP8)
+    kernel8<<<grid, 64, 0, s>>>((const bf16*)qkv, (uint8_t*)kv.k, (uint8_t*)kv.v, kv.ks, kv.vs, ws_ml, ws_acc, H, Tcap,
+                                rows, nr_max);
+  else
+    kernel<<<grid, 64, 0, s>>>((const bf16*)qkv, (bf16*)kv.k, (bf16*)kv.v, ws_ml, ws_acc, H, Tcap, rows, nr_max);
   if (const int rc = gpt2mi::check_launch(what)) return rc;
   attn_combine_kernel<<<dim3(H, M), 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, rp, nr_max);
   return gpt2mi::check_launch(what);
 }
 
 // Each operation below is written once, for one position per row; `what` is the entry's name in its messages.
-int attn_decode_rows(const char* what, const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
-                     float* workspace, size_t workspace_floats, int B, int H, int head_dim, int Tcap, const int* pos,
-                     void* stream) {
+int attn_decode_rows(const char* what, const uint16_t* qkv, const KvCache& kv, uint16_t* out, float* workspace,
+                     size_t workspace_floats, int B, int H, int head_dim, int Tcap, const int* pos, void* stream) {
   GPT2MI_REQUIRE(head_dim == 64, "%s: head_dim=%d (the decode kernels implement 64)", what, head_dim);
   GPT2MI_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && Tcap >= 1, "%s: B=%d, H=%d (<= 65535), Tcap=%d must be positive", what,
                  B, H, Tcap);
   RowPos rp;
   int max_pos;
   if (const int rc = row_positions(what, pos, B, Tcap, &rp, &max_pos)) return rc;
-  return attn_launch(what, attn_decode_kernel, rp, rp, max_pos, qkv, kcache, vcache, out, workspace, workspace_floats,
-                     B, H, Tcap, stream);
+  return attn_launch(what, attn_decode_kernel, attn_decode_fp8_kernel, rp, rp, max_pos, qkv, kv, out, workspace,
+                     workspace_floats, B, H, Tcap, stream);
 }
 
 int embed_decode_rows(const char* what, const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C,
@@ -490,16 +668,24 @@ int embed_decode_rows(const char* what, const int64_t* tok, const float* wte, co
 GPT2MI_EXPORT int gpt2mi_attn_decode_ragged(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
                                             float* workspace, size_t workspace_floats, int B, int H, int head_dim,
                                             int Tcap, const int* pos, void* stream) {
-  return attn_decode_rows("attn_decode_ragged", qkv, kcache, vcache, out, workspace, workspace_floats, B, H, head_dim,
-                          Tcap, pos, stream);
+  return attn_decode_rows("attn_decode_ragged", qkv, KvCache{GPT2MI_KV_BF16, kcache, vcache, nullptr, nullptr}, out,
+                          workspace, workspace_floats, B, H, head_dim, Tcap, pos, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_decode_fp8_ragged(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale,
+                                                float* vscale, uint16_t* out, float* workspace,
+                                                size_t workspace_floats, int B, int H, int head_dim, int Tcap,
+                                                const int* pos, void* stream) {
+  return attn_decode_rows("attn_decode_fp8_ragged", qkv, KvCache{GPT2MI_KV_FP8, kcache, vcache, kscale, vscale}, out,
+                          workspace, workspace_floats, B, H, head_dim, Tcap, pos, stream);
 }
 
 GPT2MI_EXPORT int gpt2mi_attn_decode(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
                                      float* workspace, size_t workspace_floats, int B, int H, int head_dim, int Tcap,
                                      int pos, void* stream) {
   GPT2MI_REQUIRE(pos >= 0 && pos < Tcap, "attn_decode: pos=%d not in [0, Tcap=%d)", pos, Tcap);
-  return attn_decode_rows("attn_decode", qkv, kcache, vcache, out, workspace, workspace_floats, B, H, head_dim, Tcap,
-                          SamePos(pos).v, stream);
+  return attn_decode_rows("attn_decode", qkv, KvCache{GPT2MI_KV_BF16, kcache, vcache, nullptr, nullptr}, out, workspace,
+                          workspace_floats, B, H, head_dim, Tcap, SamePos(pos).v, stream);
 }
 
 GPT2MI_EXPORT int gpt2mi_embed_decode_ragged(const int64_t* tok, const float* wte, const float* wpe, float* x, int B,
@@ -541,9 +727,9 @@ int row_map(const char* what, const int* seq, const int* pos, int R, int B, int 
   return 0;
 }
 
-int attn_extend_rows(const char* what, const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
-                     float* workspace, size_t workspace_floats, int R, int B, int H, int head_dim, int Tcap,
-                     const int* seq, const int* pos, void* stream) {
+int attn_extend_rows(const char* what, const uint16_t* qkv, const KvCache& kv, uint16_t* out, float* workspace,
+                     size_t workspace_floats, int R, int B, int H, int head_dim, int Tcap, const int* seq,
+                     const int* pos, void* stream) {
   GPT2MI_REQUIRE(head_dim == 64, "%s: head_dim=%d (the decode kernels implement 64)", what, head_dim);
   GPT2MI_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && Tcap >= 1, "%s: B=%d, H=%d (<= 65535), Tcap=%d must be positive", what,
                  B, H, Tcap);
@@ -552,8 +738,8 @@ int attn_extend_rows(const char* what, const uint16_t* qkv, uint16_t* kcache, ui
   if (const int rc = row_map(what, seq, pos, R, B, Tcap, &rm, &max_pos)) return rc;
   RowPos rp{};  // the combine is per row: row r merges its own pos[r] / 32 + 1 ranges
   std::copy_n(rm.pos, R, rp.v);
-  return attn_launch(what, attn_extend_kernel, rm, rp, max_pos, qkv, kcache, vcache, out, workspace, workspace_floats,
-                     R, H, Tcap, stream);
+  return attn_launch(what, attn_extend_kernel, attn_extend_fp8_kernel, rm, rp, max_pos, qkv, kv, out, workspace,
+                     workspace_floats, R, H, Tcap, stream);
 }
 
 // The launch list of a step over M rows at pos[m], shared by the step and the extend: they differ in the attention
@@ -596,7 +782,21 @@ int plan_shape(const char* what, const gpt2mi_decode_plan* P) {
   GPT2MI_REQUIRE(P->H >= 1 && P->C == 64 * P->H, "%s: head_dim = C/H must be 64 (C=%d, H=%d)", what, P->C, P->H);
   GPT2MI_REQUIRE(P->L >= 1 && P->Vp >= 64 && P->Vp % 64 == 0, "%s: L=%d, Vp=%d (a multiple of 64) invalid", what, P->L,
                  P->Vp);
+  // the cache format: here and in layer_cache, nowhere else
+  GPT2MI_REQUIRE(P->kv_format == GPT2MI_KV_BF16 || P->kv_format == GPT2MI_KV_FP8,
+                 "%s: kv_format=%d is neither 0 (bf16) nor 1 (fp8 e4m3)", what, P->kv_format);
+  if (P->kv_format == GPT2MI_KV_FP8) {
+    GPT2MI_REQUIRE(P->layers != nullptr, "%s: layers is NULL", what);
+    for (int l = 0; l < P->L; ++l)
+      GPT2MI_REQUIRE(P->layers[l].kscale && P->layers[l].vscale,
+                     "%s: kv_format=1 (fp8) needs layers[%d].kscale and .vscale: one is NULL", what, l);
+  }
   return 0;
+}
+
+// The cache of layer Y in the plan's format, for the attention call.
+KvCache layer_cache(const gpt2mi_decode_plan* P, const gpt2mi_decode_layer& Y) {
+  return KvCache{P->kv_format, Y.kcache, Y.vcache, Y.kscale, Y.vscale};
 }
 
 int plan_buffers(const char* what, const gpt2mi_decode_plan* P, int M, const int64_t* tok) {
@@ -621,7 +821,7 @@ int decode_step_rows(const char* what, const gpt2mi_decode_plan* P, const int64_
   if (const int rc = row_positions(what, pos, B, P->Tcap, &rp, &max_pos)) return rc;
   if (const int rc = plan_buffers(what, P, B, tok)) return rc;
   return decode_launches(what, P, B, tok, pos, stream, [&](const gpt2mi_decode_layer& Y) {
-    return attn_decode_rows(what, P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap,
+    return attn_decode_rows(what, P->qkv, layer_cache(P, Y), P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap,
                             pos, stream);
   });
 }
@@ -641,8 +841,16 @@ GPT2MI_EXPORT int gpt2mi_decode_step(const gpt2mi_decode_plan* P, const int64_t*
 GPT2MI_EXPORT int gpt2mi_attn_extend(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
                                      float* workspace, size_t workspace_floats, int R, int B, int H, int head_dim,
                                      int Tcap, const int* seq, const int* pos, void* stream) {
-  return attn_extend_rows("attn_extend", qkv, kcache, vcache, out, workspace, workspace_floats, R, B, H, head_dim, Tcap,
-                          seq, pos, stream);
+  return attn_extend_rows("attn_extend", qkv, KvCache{GPT2MI_KV_BF16, kcache, vcache, nullptr, nullptr}, out, workspace,
+                          workspace_floats, R, B, H, head_dim, Tcap, seq, pos, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_extend_fp8(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale,
+                                         float* vscale, uint16_t* out, float* workspace, size_t workspace_floats, int R,
+                                         int B, int H, int head_dim, int Tcap, const int* seq, const int* pos,
+                                         void* stream) {
+  return attn_extend_rows("attn_extend_fp8", qkv, KvCache{GPT2MI_KV_FP8, kcache, vcache, kscale, vscale}, out, workspace,
+                          workspace_floats, R, B, H, head_dim, Tcap, seq, pos, stream);
 }
 
 GPT2MI_EXPORT int gpt2mi_decode_extend(const gpt2mi_decode_plan* P, int R, const int64_t* tok, const int* seq,
@@ -657,7 +865,7 @@ GPT2MI_EXPORT int gpt2mi_decode_extend(const gpt2mi_decode_plan* P, int R, const
   GPT2MI_REQUIRE(R <= cap, "%s: R=%d exceeds the plan's row capacity %d (plan->rows, 0: B)", what, R, cap);
   if (const int rc = plan_buffers(what, P, R, tok)) return rc;
   return decode_launches(what, P, R, tok, pos, stream, [&](const gpt2mi_decode_layer& Y) {
-    return attn_extend_rows(what, P->qkv, Y.kcache, Y.vcache, P->ao, P->attn_ws, P->attn_ws_floats, R, B, H, 64,
+    return attn_extend_rows(what, P->qkv, layer_cache(P, Y), P->ao, P->attn_ws, P->attn_ws_floats, R, B, H, 64,
                             P->Tcap, seq, pos, stream);
   });
 }
@@ -693,6 +901,7 @@ int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, f
                    "%s: max pos0=%d + n=%d - 1 above the history cap %d", what, max_pos, n, GPT2MI_PENALTY_MAX_HISTORY);
   }
   GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr, "%s: tok and plan->logits must not be NULL", what);
+  if (const int rc = plan_shape(what, P)) return rc;  // (before the first draw, not only before the first step)
   for (int i = 0; i < n; ++i) {
     for (int b = 0; b < P->B; ++b) rp.v[b] = pos0[b] + i;
     int rc = gpt2mi_sample_penalized(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos, done,

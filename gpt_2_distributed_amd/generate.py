@@ -1,6 +1,6 @@
 """Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
 --prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B
---draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F]``.
+--draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F --kv_dtype {bf16,fp8}]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -50,6 +50,9 @@ def parse_args(argv=None):
                    help="subtracted from the logit of every token generated so far (OpenAI / vLLM); 0: off")
     p.add_argument("--frequency_penalty", type=float, default=0.0,
                    help="times the number of times a token was generated so far, subtracted from its logit; 0: off")
+    p.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"],
+                   help="the key/value cache: bf16, or fp8 (e4m3 codes with a power-of-two scale per 64-wide row, "
+                        "0.53 x the bytes)")
     return p.parse_args(argv)
 
 
@@ -83,7 +86,7 @@ def main(argv=None) -> int:
         raise SystemExit("an empty prompt (--prompt_ids / --prompts_file)")
     model = load_model(a.checkpoint, a.model)
     pen = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
-               frequency_penalty=a.frequency_penalty)
+               frequency_penalty=a.frequency_penalty, kv_dtype=a.kv_dtype)
     if len(prompts) > 1:
         if a.sampler != "device" and a.temperature != 0:
             raise SystemExit("several prompts are served by generate_many, which draws on the device: --sampler device")

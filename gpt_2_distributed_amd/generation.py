@@ -194,6 +194,50 @@ def apply_penalties(logits: torch.Tensor, history: torch.Tensor, lens, gen_start
     return x
 
 
+# ---- the fp8 key/value cache: the rule gpt2mi_kv_store_fp8 and the fp8 attention kernels quantise by, executable -------
+KV_DTYPES = ("bf16", "fp8")
+KV_MIN_EXP = -100  # the smallest scale exponent (an all-zero row has it)
+
+
+def check_kv_dtype(kv_dtype) -> int:
+    """gpt2mi_decode_plan.kv_format of a ``kv_dtype`` string (0 bf16, 1 fp8 e4m3), or a ValueError naming the choices."""
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f'kv_dtype must be "bf16" or "fp8" (got {kv_dtype!r})')
+    return KV_DTYPES.index(kv_dtype)
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """fp32 2^e for integer e in [-126, 127], from the exponent bits."""
+    return ((e.to(torch.int32) + 127) << 23).view(F32)
+
+
+def kv_quantize(x: torch.Tensor):
+    """``(codes uint8 [..., 64], scale fp32 [...])`` of key or value rows x [..., 64] (pure torch, any device): what
+    gpt2mi_kv_store_fp8 and the fp8 attention kernels store, bit for bit.
+
+    One scale per 64-wide row, a power of two: with amax = max |x| over the row (the values widened to fp32) written
+    m * 2^k, m in [1, 2), the exponent is e = k - 8 + (m > 1.75), the smallest with amax <= 448 * 2^e, clamped to
+    e >= -100 (amax == 0: e = -100). ``codes`` are OCP e4m3 (``torch.float8_e4m3fn``) bytes of x * 2^-e rounded to
+    nearest even, ``scale`` = 2^e. Scaling by a power of two is exact and |x * 2^-e| <= 448, so the cast never saturates
+    and never gives NaN: a row's codes and scale are a pure function of its 64 values. NaN / Inf inputs are outside
+    the contract."""
+    if x.size(-1) != 64:
+        raise ValueError(f"kv_quantize takes rows of 64 values [..., 64] (got {tuple(x.shape)})")
+    xf = x.float()
+    amax = xf.abs().amax(dim=-1)
+    f, ex = torch.frexp(amax)  # amax = f * 2^ex with f in [0.5, 1): m = 2 f, k = ex - 1
+    e = ex.to(torch.int32) - 9 + (f > 0.875).to(torch.int32)
+    e = torch.where(amax == 0, torch.full_like(e, KV_MIN_EXP), e).clamp_min(KV_MIN_EXP)
+    codes = (xf * _pow2(-e)[..., None]).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes, _pow2(e)
+
+
+def kv_dequantize(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """fp32 [..., 64]: ``code * scale``, the value every fp8 kernel uses for a cached key or value (exact: an e4m3 value
+    times a power of two is an fp32, and a bf16, number)."""
+    return codes.view(torch.float8_e4m3fn).float() * scale[..., None]
+
+
 def _penalty_keywords(penalties, gen_start) -> dict:
     """``DecodeSession.generate`` / ``speculate``'s penalty keywords from ``_check_penalties``' tuple (``{}`` when the
     values are neutral), the rows' generated parts starting at ``gen_start``."""
@@ -243,13 +287,21 @@ class DecodeSession:
     """The key/value cache of ``batch_size`` sequences of up to ``max_len`` tokens, and the step that extends them.
 
     Cache: per layer ``kcache`` and ``vcache``, bf16 ``[B][H][Tcap][64]`` (a (b, h) stream is contiguous 128-byte rows).
+    With ``kv_dtype="fp8"`` they are the uint8 e4m3 codes of ``kv_quantize`` (64-byte rows) and ``kscale`` / ``vscale``,
+    fp32 ``[B][H][Tcap]``, hold a scale per row: 68 bytes per (head, position) and tensor where bf16 takes 128
+    (``cache_bytes``). ``prefill`` and ``refill`` then quantise what they store, and every step attends over quantised
+    keys and values, its own token's included (csrc/decode.hip attn_row), so a cached row has the bits ``kv_quantize``
+    gives the bf16 row whichever call wrote it. The prompt's own attention runs in the bf16 trunk, unquantised: only
+    what later steps read is quantised, and the logits ``prefill`` returns are those of the bf16 session.
     ``prefill(idx)`` starts the sequences from a prompt, ``step(tokens)`` appends one token to each; both return the fp32
     logits ``[B, V]`` of the newest position. ``lens`` (a host list of B ints) is the number of cached tokens of each
     row; ``pos`` is their common value (None while the rows disagree: ``prefill`` with ``lens``, ``refill``). Every call
     goes through the per-row C entries (``gpt2mi_*_ragged``) with ``lens``, whether the rows agree or not: a row's bits
     depend on its own position only."""
 
-    def __init__(self, model, batch_size: int, max_len: Optional[int] = None):
+    def __init__(self, model, batch_size: int, max_len: Optional[int] = None, kv_dtype: str = "bf16"):
+        self.kv_format = check_kv_dtype(kv_dtype)
+        self.kv_dtype = kv_dtype
         eng = _check_model(model)
         cfg = model.config
         Tcap = cfg.n_positions if max_len is None else int(max_len)
@@ -263,8 +315,12 @@ class DecodeSession:
         B, C, H, L, Vp = self.B, cfg.n_embd, cfg.n_head, cfg.n_layer, model.vpad
         dev = eng.device
         e = lambda *s, dt=BF16: torch.empty(*s, dtype=dt, device=dev)  # noqa: E731
-        self.kcache = e(L, B, H, Tcap, 64)
-        self.vcache = e(L, B, H, Tcap, 64)
+        if self.kv_format == K.KV_FP8:
+            self.kcache, self.vcache = e(L, B, H, Tcap, 64, dt=torch.uint8), e(L, B, H, Tcap, 64, dt=torch.uint8)
+            self.kscale, self.vscale = e(L, B, H, Tcap, dt=F32), e(L, B, H, Tcap, dt=F32)
+        else:
+            self.kcache, self.vcache = e(L, B, H, Tcap, 64), e(L, B, H, Tcap, 64)
+            self.kscale = self.vscale = None
         for name, t in self._scratch(B).items():  # x, xmid, ln, qkv, ao, h, mean, rstd, attn_ws, gemm_ws, logits
             setattr(self, name, t)
         self._tok = e(B, dt=torch.int64)  # the device loop's newest tokens (DecodeSession.generate)
@@ -302,6 +358,23 @@ class DecodeSession:
     def device(self):
         return self.logits.device
 
+    @property
+    def cache_bytes(self) -> int:
+        """The bytes of the key/value cache: the two tensors of every layer and, with fp8, their scales."""
+        return sum(t.numel() * t.element_size() for t in (self.kcache, self.vcache, self.kscale, self.vscale)
+                   if t is not None)
+
+    def _store(self, l: int, qkv, row: Optional[int], B: int, Tp: int, P: int) -> None:
+        """The K / V columns of the first P rows of each of qkv's B sequences of Tp rows into layer l's cache from
+        position 0: every sequence of the session, or with ``row`` that one (B = 1)."""
+        at = (l,) if row is None else (l, row)
+        H = self.cfg.n_head
+        if self.kv_format == K.KV_FP8:
+            K.kv_store_fp8(qkv, self.kcache[at], self.vcache[at], self.kscale[at], self.vscale[at], B, Tp, P, 0, H, 64,
+                           self.Tcap)
+        else:
+            K.kv_store(qkv, self.kcache[at], self.vcache[at], B, Tp, P, 0, H, 64, self.Tcap)
+
     def _build_plan(self, scratch: dict, rows: int) -> K.DecodePlan:
         """The plan over the session's weights and caches with ``scratch`` as its buffers, holding ``rows`` rows (0: B)."""
         eng, cfg = self.engine, self.cfg
@@ -317,6 +390,8 @@ class DecodeSession:
             Y.qkv_b, Y.proj_b, Y.fc1_b, Y.fc2_b = (p(pre + s) for s in ("attn.qkv.bias", "attn.proj.bias",
                                                                          "mlp.fc1.bias", "mlp.fc2.bias"))
             Y.kcache, Y.vcache = self.kcache[l].data_ptr(), self.vcache[l].data_ptr()
+            if self.kv_format == K.KV_FP8:
+                Y.kscale, Y.vscale = self.kscale[l].data_ptr(), self.vscale[l].data_ptr()
         P = K.DecodePlan()
         P.B, P.C, P.H, P.L, P.Vp, P.Tcap = self.B, cfg.n_embd, cfg.n_head, cfg.n_layer, self.model.vpad, self.Tcap
         P.eps = cfg.layer_norm_eps
@@ -328,6 +403,7 @@ class DecodeSession:
             setattr(P, n, scratch[n].data_ptr())
         P.attn_ws_floats, P.gemm_ws_floats = scratch["attn_ws"].numel(), scratch["gemm_ws"].numel()
         P.rows = rows
+        P.kv_format = self.kv_format
         return P
 
     def _ready(self, sync: bool):
@@ -369,12 +445,12 @@ class DecodeSession:
         eng.gemm_sched = eng.base_sched
         idx_p, _, _ = eng._pad(idx, None)
         B, Tp = idx_p.shape
-        C, H, Vp = cfg.n_embd, cfg.n_head, self.model.vpad
+        C, Vp = cfg.n_embd, self.model.vpad
         ws = eng.workspace(B, Tp, BF16)
         # p = 0: no dropout site reads its seed, so the step's dropout stream is not advanced
         eng._trunk_fwd(ws, idx_p, B, Tp, P, BF16, 0.0, 0.0, eng._seeds(0))
         for l in range(cfg.n_layer):
-            K.kv_store(ws.blocks[l].qkv, self.kcache[l], self.vcache[l], B, Tp, P, 0, H, 64, self.Tcap)
+            self._store(l, ws.blocks[l].qkv, None, B, Tp, P)
         if lens is None:
             last = ws.lnf.view(B, Tp, C)[:, P - 1]  # rows b*Tp + P-1: row stride Tp*C
             K.gemm_skinny(K.EPI_F32, B, Vp, C, last, Tp * C, eng.w16("transformer.wte.weight"), C, self.logits, Vp,
@@ -421,11 +497,11 @@ class DecodeSession:
         row, P = int(row), prompt.numel()
         idx_p, _, _ = eng._pad(prompt.view(1, P), None)
         Tp = idx_p.size(1)
-        C, H, Vp = cfg.n_embd, cfg.n_head, self.model.vpad
+        C, Vp = cfg.n_embd, self.model.vpad
         ws = self._one_sequence_workspace(Tp)
         eng._trunk_fwd(ws, idx_p, 1, Tp, P, BF16, 0.0, 0.0, eng._seeds(0))
         for l in range(cfg.n_layer):
-            K.kv_store(ws.blocks[l].qkv, self.kcache[l, row], self.vcache[l, row], 1, Tp, P, 0, H, 64, self.Tcap)
+            self._store(l, ws.blocks[l].qkv, row, 1, Tp, P)
         K.gemm_skinny(K.EPI_F32, 1, Vp, C, ws.lnf[P - 1], Tp * C, eng.w16("transformer.wte.weight"), C, self.logits[row],
                       Vp, workspace=self.gemm_ws)
         self.lens[row] = P
@@ -796,8 +872,9 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
              top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens: Optional[Sequence[int]] = None,
              pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None, draft_fn=None,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-             frequency_penalty: float = 0.0) -> torch.Tensor:
+             frequency_penalty: float = 0.0, kv_dtype: str = "bf16") -> torch.Tensor:
     """``GPT2.generate``: see there."""
+    check_kv_dtype(kv_dtype)
     penalties = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
     pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
     if isinstance(idx, (list, tuple)):
@@ -836,11 +913,11 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
     if prompt_lens is None and n == 0:
         return idx.clone()
     return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad,
-                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties)
+                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype)
 
 
 def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad, draft=None,
-              penalties=(1.0, 0.0, 0.0, False)):
+              penalties=(1.0, 0.0, 0.0, False), kv_dtype="bf16"):
     """The token loop of ``generate``: [B, P + m], row b = its prompt, its m new tokens from column lens[b] on, then
     ``pad`` (``lens`` None: every row holds P tokens and nothing is padded). m = n, or with eos the number of tokens by
     which every row has emitted it. Host sampler: new tokens are collected per step and scattered into the buffer that
@@ -859,7 +936,7 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     if n == 0:
         return seq
     idx = torch.where(cols[:, :P] < lens_t[:, None], idx, torch.zeros_like(idx))  # (a valid token id as padding)
-    sess = DecodeSession(model, B, P + n)
+    sess = DecodeSession(model, B, P + n, kv_dtype)
     logits = sess.prefill(idx, lens)
     rp, pp, fp, on = penalties
     pen = _penalty_keywords(penalties, lens_t.tolist())
@@ -920,8 +997,9 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
                   top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
                   eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                  frequency_penalty: float = 0.0) -> List[torch.Tensor]:
+                  frequency_penalty: float = 0.0, kv_dtype: str = "bf16") -> List[torch.Tensor]:
     """``GPT2.generate_many``: see there."""
+    check_kv_dtype(kv_dtype)
     penalties = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
     if generator is not None:
         raise ValueError("generate_many draws on the device from (seed, prompt index, position): a torch.Generator is "
@@ -946,7 +1024,8 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
         return [p.long().clone() for p in prompts]
     _check_model(model)
     # (at least a chunk and two positions, so that a dummy row of one token need not start over within a chunk)
-    sess = DecodeSession(model, int(batch_size), min(model.config.n_positions, max(longest + n, EOS_CHUNK + 2)))
+    sess = DecodeSession(model, int(batch_size), min(model.config.n_positions, max(longest + n, EOS_CHUNK + 2)),
+                         kv_dtype)
     return serve_prompts(sess, [p.long() for p in prompts], n, temperature, top_k, top_p, seed, eos_token_id, penalties)
 
 

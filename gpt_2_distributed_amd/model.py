@@ -335,18 +335,20 @@ class GPT2(nn.Module):
         return {"loss": loss, "ppl": math.exp(loss) if loss < 700 else float("inf"), "tokens": int(c)}
 
     # ---- generation (nanoGPT's surface; the reference has none) ----------------------------------------
-    def decoder(self, batch_size: int, max_len: Optional[int] = None):
+    def decoder(self, batch_size: int, max_len: Optional[int] = None, kv_dtype: str = "bf16"):
         """A ``generation.DecodeSession``: the per-layer key/value cache (L x 2 x bf16 ``[B][H][Tcap][64]``,
-        ``Tcap = max_len or n_positions``) of ``batch_size`` sequences with ``prefill(idx)`` / ``step(tokens)``."""
+        ``Tcap = max_len or n_positions``) of ``batch_size`` sequences with ``prefill(idx)`` / ``step(tokens)``.
+        ``kv_dtype="fp8"``: the cache as e4m3 codes with one power-of-two scale per 64-wide row, 0.53 x the bytes
+        (``generation.kv_quantize``)."""
         from .generation import DecodeSession
-        return DecodeSession(self, batch_size, max_len)
+        return DecodeSession(self, batch_size, max_len, kv_dtype)
 
     def generate(self, idx, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
                  top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens=None,
                  pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None,
                  draft_fn=None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0) -> torch.Tensor:
+                 frequency_penalty: float = 0.0, kv_dtype: str = "bf16") -> torch.Tensor:
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
         filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
@@ -381,6 +383,13 @@ class GPT2(nn.Module):
         convention: the prompt does not count; 0 off). They move the logits in front of the greedy argmax, temperature,
         ``top_k`` and ``top_p``. A value that is not finite, or ``repetition_penalty <= 0``, raises ``ValueError``.
 
+        ``kv_dtype="fp8"`` keeps the key/value cache as OCP e4m3 codes with one power-of-two scale per (layer, K or V,
+        sequence, head, position): 68 bytes where bf16 takes 128 (``generation.kv_quantize`` is the rule). Every key and
+        value a step attends over is the quantised one, the new token's own included, so everything stated above holds
+        as it does with the default ``"bf16"`` (a row's tokens do not depend on its batch, ``draft_tokens`` is exact);
+        the prompt's own attention runs unquantised in the trunk. The logits move by about the error of e4m3's 3
+        mantissa bits (DESIGN.md "FP8 key/value cache"). Any other string raises ``ValueError``.
+
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
         the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
         ``NotImplementedError``. It does not advance the dropout stream or touch what a later backward needs, so a
@@ -391,12 +400,12 @@ class GPT2(nn.Module):
         from .generation import generate
         return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed,
                         prompt_lens, pad_token_id, draft_tokens, draft_fn, repetition_penalty, presence_penalty,
-                        frequency_penalty)
+                        frequency_penalty, kv_dtype)
 
     def generate_many(self, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                       top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
                       eos_token_id: Optional[int] = None, generator=None, repetition_penalty: float = 1.0,
-                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
+                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0, kv_dtype: str = "bf16"):
         """Continue any number of 1-D ``prompts`` of any lengths by up to ``max_new_tokens`` tokens each; returns a list
         in input order, each entry the prompt plus its new tokens, cut after the first ``eos_token_id``.
 
@@ -411,10 +420,11 @@ class GPT2(nn.Module):
         shapes depend on its prompt alone). Device sampler only: ``generator=`` raises ``ValueError``.
         ``max(len) + max_new_tokens > n_positions`` raises ``ValueError``. Training is left untouched as by
         ``generate``. ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` as for ``generate``: a row's
-        history is its own prompt and new tokens, so the guarantee holds with them."""
+        history is its own prompt and new tokens, so the guarantee holds with them. ``kv_dtype`` as for ``generate``: a
+        row of the fp8 cache is a function of that row's values alone, so the guarantee holds with it too."""
         from .generation import generate_many
         return generate_many(self, prompts, max_new_tokens, batch_size, temperature, top_k, top_p, seed, eos_token_id,
-                             generator, repetition_penalty, presence_penalty, frequency_penalty)
+                             generator, repetition_penalty, presence_penalty, frequency_penalty, kv_dtype)
 
     # ---- optimizer (nanoGPT-style name the north star uses) -----------------------------------------
     def configure_optimizers(self, weight_decay: float = 0.1, learning_rate: float = 1e-4,

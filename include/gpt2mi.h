@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 22
+#define GPT2MI_ABI_VERSION 23
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -285,7 +285,10 @@ typedef struct gpt2mi_decode_layer {
   const float *ln1_w, *ln1_b, *ln2_w, *ln2_b;             /* fp32 [C] */
   const uint16_t *qkv_w, *proj_w, *fc1_w, *fc2_w;         /* bf16 [3C][C], [C][C], [4C][C], [C][4C] */
   const float *qkv_b, *proj_b, *fc1_b, *fc2_b;            /* fp32 */
-  uint16_t *kcache, *vcache;                              /* bf16 [B][H][Tcap][64] */
+  uint16_t *kcache, *vcache;                              /* bf16 [B][H][Tcap][64]; with plan->kv_format = 1 the
+                                                             fp8 codes, uint8 [B][H][Tcap][64], behind a cast */
+  float *kscale, *vscale;                                 /* v23, appended: fp32 [B][H][Tcap], the scales of an fp8
+                                                             cache; not read (may be NULL) with kv_format = 0 */
 } gpt2mi_decode_layer;
 typedef struct gpt2mi_decode_plan {
   int B, C, H, L, Vp, Tcap;                               /* batch, n_embd, heads, layers, padded vocab, cache length */
@@ -304,6 +307,10 @@ typedef struct gpt2mi_decode_plan {
   int rows;                                               /* v21, appended (no earlier offset moved): the rows the
                                                              scratch buffers above (x .. logits, the workspaces) hold;
                                                              0 means B. Read by gpt2mi_decode_extend only. */
+  int kv_format;                                          /* v23, appended: GPT2MI_KV_BF16 (0, what a zeroed field
+                                                             meant before) or GPT2MI_KV_FP8 (1): see the v23 block.
+                                                             On LP64 it fills the former tail padding behind `rows`:
+                                                             sizeof(gpt2mi_decode_plan) did not change */
 } gpt2mi_decode_plan;
 /* embed -> per layer (LN1, qkv, attention at pos, proj + resid, LN2, fc1 + GELU, fc2 + resid) -> ln_f -> lm_head into
  * plan->logits, for the B tokens `tok` (device int64 [B]) at position pos (model.py:295-351 at one position). A
@@ -490,6 +497,35 @@ int gpt2mi_decode_generate_penalized(const gpt2mi_decode_plan* plan, int V, floa
                                      uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
                                      int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream,
                                      float repetition, float presence, float frequency, const int* gen_start);
+
+/* ---- v23: an fp8 key/value cache (csrc/decode.hip). The bf16 cache is 128 bytes per (head, position) and tensor; this
+ * one is 64 OCP e4m3 codes and one fp32 scale, 68 bytes. The executable specification of the format is
+ * gpt_2_distributed_amd/generation.py kv_quantize / kv_dequantize.
+ * One scale per 64-wide row, a power of two 2^e: with amax = max |x| over the row's bf16 values = m 2^k, m in [1, 2),
+ * e = max(k - 8 + (m > 1.75), -100), the smallest e with amax <= 448 2^e (amax = 0: e = -100). code = RNE_e4m3fn(x 2^-e)
+ * and the value every kernel uses is code 2^e. Scaling is exact and |x 2^-e| <= 448, so no conversion saturates or gives
+ * NaN and a row's codes and scale are a pure function of its 64 values. NaN / Inf inputs are outside the contract.
+ * Layout per layer: kcache, vcache uint8 [B][H][Tcap][64]; kscale, vscale fp32 [B][H][Tcap].
+ * Each entry below is its bf16 sibling with the codes in place of the bf16 tensors and the two scale pointers behind
+ * them: the same indexing, the same checks with the same refusals (22 and a message, before any launch), and a NULL
+ * scale pointer refused as well. A key of the call itself is quantised and dequantised in registers before use, by the
+ * function that gpt2mi_kv_store_fp8 quantises with, so a key has the same bits whether it is read from the cache or
+ * from the qkv row: gpt2mi_attn_extend_fp8 has the bits of one gpt2mi_attn_decode_fp8_ragged call per position, and a
+ * row's bits depend on its own inputs and position only. Nothing at or above a row's position is read, nothing but the
+ * row's own position is written, in the codes or in the scales; no atomics.
+ * In a plan, kv_format selects the format for gpt2mi_decode_step*, gpt2mi_decode_extend and gpt2mi_decode_generate*:
+ * any other value than the two below is refused with 22 and a message naming it, and so is kv_format = 1 with a NULL
+ * layers[l].kscale / .vscale. ---- */
+#define GPT2MI_KV_BF16 0
+#define GPT2MI_KV_FP8 1
+int gpt2mi_kv_store_fp8(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale, int B,
+                        int T_src, int n, int t0, int H, int head_dim, int Tcap, void* stream);
+int gpt2mi_attn_decode_fp8_ragged(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
+                                  uint16_t* out, float* workspace, size_t workspace_floats, int B, int H, int head_dim,
+                                  int Tcap, const int* pos, void* stream);
+int gpt2mi_attn_extend_fp8(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
+                           uint16_t* out, float* workspace, size_t workspace_floats, int R, int B, int H, int head_dim,
+                           int Tcap, const int* seq, const int* pos, void* stream);
 
 #ifdef __cplusplus
 }
