@@ -30,36 +30,7 @@ namespace {
 constexpr int D = 64;
 constexpr int BQ = 128;  // queries per workgroup in fwd / dQ (32 per wave = two 16-query MFMA groups)
 constexpr int BKV = 64;  // keys per K/V tile in fwd / dQ
-#ifndef ATTN_FWD_OCC
-#define ATTN_FWD_OCC 3  // forward waves per SIMD the register budget is cut for (launch bounds)
-#endif
-#ifndef ATTN_FWD_LMAX
-#define ATTN_FWD_LMAX 1  // forward rescale test on each lane's own scores (0: cross-lane max every tile, A/B builds)
-#endif
-GPT2MI_PRODUCT_KNOB(ATTN_FWD_OCC, 3);
-GPT2MI_PRODUCT_KNOB(ATTN_FWD_LMAX, 1);
 constexpr int BKB = 128;  // keys per workgroup in dK/dV (4 waves of 32)
-#ifndef ATTN_DKDV_PIPE
-#define ATTN_DKDV_PIPE 0  // dK/dV tile body: 0 phases in separate blocks; 1-3 one block per DIAG variant (A/B builds)
-#endif
-#ifndef ATTN_DKDV_FILL
-#define ATTN_DKDV_FILL 10  // ATTN_DKDV_PIPE 3: VALU instructions placed after each MFMA
-#endif
-GPT2MI_PRODUCT_KNOB(ATTN_DKDV_PIPE, 0);
-#ifndef ATTN_HASH_ANCHOR
-#define ATTN_HASH_ANCHOR 0  // dK/dV dropout hash: 1 = the opaque anchor on the counter sum (no v_mov per hash; A/B)
-#endif
-GPT2MI_PRODUCT_KNOB(ATTN_HASH_ANCHOR, 0);
-#ifndef ATTN_DQ_SGB
-#define ATTN_DQ_SGB 0  // dQ tile: 1 = sched_group_barrier interleave of each half's MFMAs with the other half's VALU (A/B)
-#endif
-#ifndef ATTN_DQ_FA
-#define ATTN_DQ_FA 6  // ATTN_DQ_SGB: VALU instructions after each S / dP MFMA of the second half
-#endif
-#ifndef ATTN_DQ_FB
-#define ATTN_DQ_FB 12  // ATTN_DQ_SGB: VALU instructions after each dQ MFMA of the first half
-#endif
-GPT2MI_PRODUCT_KNOB(ATTN_DQ_SGB, 0);
 constexpr int kThreads = 256;
 constexpr float kLog2e = 1.4426950408889634f;
 
@@ -196,6 +167,12 @@ __device__ __forceinline__ void tile_dma(char* lds, __amdgpu_buffer_rsrc_t rs, i
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(lds + ins * 1024), 16, loff, soff, 0, 0);
   }
 }
+// one fwd / dQ LDS stage: keys [row0, row0 + BKV) of the head at column hc of its C, the K tile and then the V tile
+__device__ __forceinline__ void kv_tile_dma(char* stage, __amdgpu_buffer_rsrc_t rs, int row0, int C, int hc, int ld,
+                                            uint32_t loff, int w) {
+  tile_dma(stage, rs, row0, C + hc, ld, loff, w);
+  tile_dma(stage + BKV * 128, rs, row0, 2 * C + hc, ld, loff, w);
+}
 
 // Block -> (head, query/key block) map: globally heaviest first. Block L takes head L % BH and block L / BH, so
 // every head's heaviest block (the last query block in fwd / dQ, the first key block in dK/dV: its causal work is
@@ -212,12 +189,9 @@ __device__ __forceinline__ void attn_block(int& bh, int& blk) {
   blk = L / BH;
 }
 
-// Dropout of attention probability (q, key) of head bh: 16-bit half (q >> 4) & 1 of
-// drop_hash(seed, (bh*T + (q & ~16))*T + key) — queries q and q^16 of one key share a hash.
-
 // ---------------------------------------------------------------------------------------------
 template <bool DROP>
-__global__ __launch_bounds__(kThreads, ATTN_FWD_OCC) void attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
+__global__ __launch_bounds__(kThreads, 3) void attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
                                                                float* __restrict__ lse, int T, int H, float scale,
                                                                uint64_t seed, uint32_t thr, float inv_keep) {
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * BKV * 128];  // 2 stages x (K, V)
@@ -256,8 +230,7 @@ __global__ __launch_bounds__(kThreads, ATTN_FWD_OCC) void attn_fwd_kernel(const 
   const uint32_t loff = tile_dma_off(ld, lane);
   const int wu = __builtin_amdgcn_readfirstlane(w);
   const __amdgpu_buffer_rsrc_t rs = qkv_rsrc(base);
-  tile_dma(smem, rs, 0, C + h * D, (int)ld, loff, wu);
-  tile_dma(smem + BKV * 128, rs, 0, 2 * C + h * D, (int)ld, loff, wu);
+  kv_tile_dma(smem, rs, 0, C, h * D, (int)ld, loff, wu);
   __syncthreads();  // waits for this wave's DMAs (vmcnt(0)), then for every wave's
 
   for (int j = 0; j < nkv; ++j) {
@@ -282,11 +255,7 @@ __global__ __launch_bounds__(kThreads, ATTN_FWD_OCC) void attn_fwd_kernel(const 
     }
     // next K/V tile straight into the other LDS stage (read last in tile j-1, released by its barrier),
     // issued behind S = K Q^T; it lands while this tile's softmax and P.V run
-    if (j + 1 < nkv) {
-      char* nxt = smem + (cur ^ 1) * 2 * BKV * 128;
-      tile_dma(nxt, rs, (j + 1) * BKV, C + h * D, (int)ld, loff, wu);
-      tile_dma(nxt + BKV * 128, rs, (j + 1) * BKV, 2 * C + h * D, (int)ld, loff, wu);
-    }
+    if (j + 1 < nkv) kv_tile_dma(smem + (cur ^ 1) * 2 * BKV * 128, rs, (j + 1) * BKV, C, h * D, (int)ld, loff, wu);
     if (active) {
       const bool diag = k_lo + BKV - 1 > q_lo;
       if (diag) {  // causal mask only on the diagonal tiles (wave-uniform branch)
@@ -303,22 +272,12 @@ __global__ __launch_bounds__(kThreads, ATTN_FWD_OCC) void attn_fwd_kernel(const 
         // thresholded rescale (defer-max): keep the running max unless some row of the wave grew by
         // more than kRescaleThr (log2 units); P then stays below 2^kRescaleThr. Wave-uniform decision,
         // taken before this tile is exponentiated, so O, l and P all see the same max.
-#if ATTN_FWD_LMAX
         // The test needs no max across the 4 lanes of a query: they share m, and x -> x * sl2 is monotonic, so
         // "every lane's own 16 keys pass" is the same decision as "every query's 64 keys pass". The cross-lane
-        // max is formed only when a rescale is taken (same cand, same bits as the all-lanes form).
+        // max is formed only when a rescale is taken (the cand, bit for bit, of a max over all 64 keys).
         const float lmax = max16(s[qg]);
         if (!__all(lmax * sl2 <= m[qg] + kRescaleThr)) {
           const float cand = xor_max(lmax) * sl2;
-#else
-        float tmax = -INFINITY;  // max of the raw scores (scale > 0)
-#pragma unroll
-        for (int fi = 0; fi < 4; ++fi)
-          tmax = fmaxf(tmax, fmaxf(fmaxf(s[qg][fi][0], s[qg][fi][1]), fmaxf(s[qg][fi][2], s[qg][fi][3])));
-        tmax = xor_max(tmax);
-        const float cand = tmax * sl2;
-        if (!__all(cand <= m[qg] + kRescaleThr)) {
-#endif
           const float mn = fmaxf(m[qg], cand);  // finite: tile 0 holds key 0, visible to every query
           const float corr = __builtin_amdgcn_exp2f(m[qg] - mn);
 #pragma unroll
@@ -340,6 +299,8 @@ __global__ __launch_bounds__(kThreads, ATTN_FWD_OCC) void attn_fwd_kernel(const 
       // P packed to bf16 once per 32-key half (kk): the row sums (before dropout: the normaliser is the undropped
       // softmax denominator) and P.V read the same fragments. Dropout on the packed P (its 1/(1-p) goes into the
       // final scale): one hash per (q, q^16) pair of a key, both decisions from one packed int16 subtract.
+      // In all three kernels the decision of probability (q, key) of head bh is the 16-bit half (q >> 4) & 1 of
+      // drop_hash(seed, (bh*T + (q & ~16))*T + key); drop_pre forms the counter's part common to the tile.
       [[maybe_unused]] uint32_t pre = 0, tk2 = 0;
       if constexpr (DROP) {
         pre = drop_pre(seed32(seed), ((uint32_t)bh * T + q_lo + (lane & 15)) * (uint32_t)T + k_lo + 4 * g);
@@ -448,18 +409,14 @@ __global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(const bf16* __
   const uint32_t loff = tile_dma_off(ld, lane);
   const int wu = __builtin_amdgcn_readfirstlane(w);
   const __amdgpu_buffer_rsrc_t rs = qkv_rsrc(base);
-  tile_dma(smem, rs, 0, C + h * D, (int)ld, loff, wu);
-  tile_dma(smem + BKV * 128, rs, 0, 2 * C + h * D, (int)ld, loff, wu);
+  kv_tile_dma(smem, rs, 0, C, h * D, (int)ld, loff, wu);
   __syncthreads();
   for (int j = 0; j < nkv; ++j) {
     const int cur = j & 1;
     const char* Ks = smem + cur * 2 * BKV * 128;
     const char* Vs = Ks + BKV * 128;
-    if (j + 1 < nkv) {  // next K/V tile by LDS-DMA into the stage released by tile j-1's barrier
-      char* nxt = smem + (cur ^ 1) * 2 * BKV * 128;
-      tile_dma(nxt, rs, (j + 1) * BKV, C + h * D, (int)ld, loff, wu);
-      tile_dma(nxt + BKV * 128, rs, (j + 1) * BKV, 2 * C + h * D, (int)ld, loff, wu);
-    }
+    // next K/V tile by LDS-DMA into the stage released by tile j-1's barrier
+    if (j + 1 < nkv) kv_tile_dma(smem + (cur ^ 1) * 2 * BKV * 128, rs, (j + 1) * BKV, C, h * D, (int)ld, loff, wu);
     const int k_lo = j * BKV;
     if (wave_valid && k_lo <= q_lo + 31) {
       const bool diag = k_lo + BKV - 1 > q_lo;
@@ -531,36 +488,12 @@ __global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(const bf16* __
         f32x4 sa[2][2], dpa[2][2], sb[2][2], dpb[2][2];
         bf16x8 pa[2], pb[2];
         sdp(0, sa, dpa);
-#if ATTN_DQ_SGB
-        // A/B: the second half's S / dP MFMAs placed one by one among the first half's dS chain, then the first half's
-        // dQ MFMAs among the second half's chain (fragment reads first in each region)
-        __builtin_amdgcn_sched_barrier(0);
-        elem(diag_c, 0, sa, dpa, pa);
-        sdp(1, sb, dpb);
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, ATTN_DQ_FA, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        dqm(0, pa);
-        elem(diag_c, 1, sb, dpb, pb);
-        __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, ATTN_DQ_FB, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#else
         elem(diag_c, 0, sa, dpa, pa);
         sdp(1, sb, dpb);
         __builtin_amdgcn_sched_barrier(0);
         dqm(0, pa);
         elem(diag_c, 1, sb, dpb, pb);
         __builtin_amdgcn_sched_barrier(0);
-#endif
         dqm(1, pb);
       };
       if (diag) tile(std::true_type{});
@@ -610,11 +543,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
   const int C = H * D;
   const size_t ld = 3 * (size_t)C;
   const bf16* base = qkv + (size_t)b * T * ld;
-#if ATTN_DKDV_PIPE == 0
   const int k_lo = kb * 128 + 32 * w;
-#else
-  const int k_lo = kb * 128 + 32 * __builtin_amdgcn_readfirstlane(w);  // wave-uniform: scalar branches on it
-#endif
   const bool wave_valid = k_lo < T;
   // K and V rows kb*128 .. +128 (clamped to T - 1 past the end: only invalid waves read those) into LDS, swizzled as
   // every tile (t_off); 4 chunks of 16 B per thread and array
@@ -666,7 +595,6 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
   __syncthreads();
   const char* Kw = Kl + 32 * w * 128;  // this wave's 32 keys
   const char* Vw = Vl + 32 * w * 128;
-#if ATTN_DKDV_PIPE == 0
   for (int i = i0; i < nqt; ++i) {
     const int cur = (i - i0) & 1;
     const char* Qs = stg + cur * kStage;
@@ -725,19 +653,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
           for (int r = 0; r < 4; ++r) {
             uint32_t km[2] = {~0u, ~0u};
             if constexpr (DROP) {
-#if ATTN_HASH_ANCHOR
-              // the counter of this (r, kg) formed, then made opaque: hashed here, not hoisted ahead of the tile (its
-              // masks would not fit), and the add writes a fresh register (no copy of pre_t per hash)
-              const uint32_t off = __builtin_amdgcn_readfirstlane(((uint32_t)r * (uint32_t)T + 16u * kg) * kDropC1);
-              uint32_t pv;
-              asm volatile("v_add_u32 %0, %1, %2" : "=v"(pv) : "s"(off), "v"(pre_t));
-              drop_keep_masks(tk2, drop_fin(pv, seed_kx(seed)), km[0], km[1]);
-#else
               uint32_t pv = pre_t;
               asm volatile("" : "+v"(pv));  // hashed here, not hoisted ahead of the tile (its masks would not fit)
               drop_keep_masks(tk2, drop_fin(pv + ((uint32_t)r * (uint32_t)T + 16u * kg) * kDropC1, seed_kx(seed)),
                               km[0], km[1]);
-#endif
             }
 #pragma unroll
             for (int fl = 0; fl < 2; ++fl) {
@@ -771,238 +690,6 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
     if (i + 1 < nqt) sstore(stg + (cur ^ 1) * kStage);
     __syncthreads();
   }
-#else
-  // one query tile: Q / dO / lse / delta of tile i are in stage (i - i0) & 1; the next tile is staged under it
-  auto step = [&](int i, auto work) {
-    const int cur = (i - i0) & 1;
-    const char* Qs = stg + cur * kStage;
-    const char* Ds = Qs + kTile;
-    const float* Ls = reinterpret_cast<const float*>(Qs + 2 * kTile);
-    const float* Dl = Ls + BQ3;
-    if (i + 1 < nqt) gload(i + 1, stg + (cur ^ 1) * kStage);
-    work(i * BQ3, Qs, Ds, Ls, Dl);
-    if (i + 1 < nqt) sstore(stg + (cur ^ 1) * kStage);
-    __syncthreads();
-  };
-  // the general tile: a wave may be inactive (its keys after the tile's queries) or on the causal diagonal
-  auto general = [&](const int q0, const char* Qs, const char* Ds, const float* Ls, const float* Dl) {
-      if (wave_valid && q0 + BQ3 - 1 >= k_lo) {
-        const bool diag = q0 < k_lo + 31;
-        const uint32_t pre_t = DROP ? drop_pre(seed32(seed), ((uint32_t)bh * T + q0 + 4 * g) * (uint32_t)T + k_lo + (lane & 15)) : 0u;
-        f32x4 s[2][2], dp[2][2];  // [kg][fl]: S[q = q0 + 16fl + 4g + r][key = k_lo + 16kg + (l&15)]
-        f32x4 nl4[2], nd4[2];  // -lse * log2(e), -delta of the tile's queries
-#pragma unroll
-        for (int fl = 0; fl < 2; ++fl) {
-          nl4[fl] = *reinterpret_cast<const f32x4*>(Ls + 16 * fl + 4 * g);
-          nd4[fl] = *reinterpret_cast<const f32x4*>(Dl + 16 * fl + 4 * g);
-          s[0][fl] = s[1][fl] = f32x4{0.f, 0.f, 0.f, 0.f};
-          dp[0][fl] = dp[1][fl] = nd4[fl];
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          bf16x8 kfr[2], vfr[2];
-#pragma unroll
-          for (int kg = 0; kg < 2; ++kg) {
-            kfr[kg] = row_frag(Kw, 16 * kg, kk, lane);
-            vfr[kg] = row_frag(Vw, 16 * kg, kk, lane);
-          }
-#pragma unroll
-          for (int fl = 0; fl < 2; ++fl) {
-            const bf16x8 qa = row_frag(Qs, 16 * fl, kk, lane);
-            const bf16x8 da = row_frag(Ds, 16 * fl, kk, lane);
-#pragma unroll
-            for (int kg = 0; kg < 2; ++kg) {
-              s[kg][fl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kfr[kg], s[kg][fl], 0, 0, 0);
-              dp[kg][fl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vfr[kg], dp[kg][fl], 0, 0, 0);
-            }
-          }
-        }
-        auto elementwise = [&](auto diag_c) {
-          constexpr bool DIAG = decltype(diag_c)::value;
-#pragma unroll
-          for (int kg = 0; kg < 2; ++kg) {
-            const int key = k_lo + 16 * kg + (lane & 15);
-            // the scores' affine part in place, as packed FMA pairs (v_pk_fma_f32; no register beyond s): x = s * sl2 - lse
-#pragma unroll
-            for (int fl = 0; fl < 2; ++fl)
-#pragma unroll
-              for (int r = 0; r < 4; r += 2) {
-                const f32x2 t = __builtin_elementwise_fma(f32x2{s[kg][fl][r], s[kg][fl][r + 1]}, f32x2{sl2, sl2},
-                                                          f32x2{nl4[fl][r], nl4[fl][r + 1]});
-                s[kg][fl][r] = t[0];
-                s[kg][fl][r + 1] = t[1];
-              }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              uint32_t km[2] = {~0u, ~0u};
-              if constexpr (DROP) {
-                uint32_t pv = pre_t;
-                asm volatile("" : "+v"(pv));  // hashed here, not hoisted ahead of the tile (its masks would not fit)
-                drop_keep_masks(tk2, drop_fin(pv + ((uint32_t)r * (uint32_t)T + 16u * kg) * kDropC1, seed_kx(seed)),
-                                km[0], km[1]);
-              }
-#pragma unroll
-              for (int fl = 0; fl < 2; ++fl) {
-                float p = __builtin_amdgcn_exp2f(s[kg][fl][r]);
-                if constexpr (DIAG) p = (q0 + 16 * fl + 4 * g + r < key) ? 0.f : p;
-                float pdv = p, d = dp[kg][fl][r];
-                if constexpr (DROP) {
-                  pdv = __uint_as_float(km[fl] & __float_as_uint(p));
-                  d = sel_mask(km[fl], d, nd4[fl][r]);
-                }
-                dp[kg][fl][r] = pdv;
-                s[kg][fl][r] = p * d;
-              }
-            }
-          }
-        };
-        if (diag) elementwise(std::true_type{});
-        else elementwise(std::false_type{});
-        const bf16x8 p0 = pack_perm(dp[0], 0), p1 = pack_perm(dp[1], 0);
-        const bf16x8 s0 = pack_perm(s[0], 0), s1 = pack_perm(s[1], 0);
-#pragma unroll
-        for (int fd = 0; fd < 4; ++fd) {
-          const bf16x8 dot = tr_frag(Ds, 0, 16 * fd, lane);
-          const bf16x8 qt = tr_frag(Qs, 0, 16 * fd, lane);
-          dv[0][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot, p0, dv[0][fd], 0, 0, 0);
-          dv[1][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot, p1, dv[1][fd], 0, 0, 0);
-          dk[0][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt, s0, dk[0][fd], 0, 0, 0);
-          dk[1][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt, s1, dk[1][fd], 0, 0, 0);
-        }
-      }
-  };
-  // Tiles i0 .. i0 + 3 hold every wave's diagonal tile (wave w: i0 + w) and the inactive waves; from i0 + 4 on every
-  // wave of the workgroup is active and off the diagonal, and the tile is ONE basic block: the S / dP MFMAs, the
-  // elementwise chain and the dV / dK MFMAs scheduled together (key group kg = 0 finished first, its dS formed while
-  // kg = 1's S / dP MFMAs run, its dV / dK MFMAs issued beside kg = 1's elementwise). The Q / dO row fragments are
-  // read per key group (re-read for kg = 1: 8 more ds_read_b128 per tile) instead of held for both (32 VGPRs past
-  // the 3-waves / SIMD budget).
-  for (int i = i0; i < min(i0 + 4, nqt); ++i) step(i, general);
-  auto steady = [&](const int q0, const char* Qs, const char* Ds, const float* Ls, const float* Dl) {
-    const uint32_t pre_t = DROP ? drop_pre(seed32(seed), ((uint32_t)bh * T + q0 + 4 * g) * (uint32_t)T + k_lo + (lane & 15)) : 0u;
-    auto tile = [&]() {
-      constexpr bool DIAG = false;
-      f32x4 s[2][2], dp[2][2];  // [kg][fl]: S[q = q0 + 16fl + 4g + r][key = k_lo + 16kg + (l&15)]
-      f32x4 nl4[2], nd4[2];  // -lse * log2(e), -delta of the tile's queries
-#pragma unroll
-      for (int fl = 0; fl < 2; ++fl) {
-        nl4[fl] = *reinterpret_cast<const f32x4*>(Ls + 16 * fl + 4 * g);
-        nd4[fl] = *reinterpret_cast<const f32x4*>(Dl + 16 * fl + 4 * g);
-      }
-      auto sdp = [&](int kg) {
-#pragma unroll
-        for (int fl = 0; fl < 2; ++fl) {
-          s[kg][fl] = f32x4{0.f, 0.f, 0.f, 0.f};
-          dp[kg][fl] = nd4[fl];
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const bf16x8 kf = row_frag(Kw, 16 * kg, kk, lane), vf = row_frag(Vw, 16 * kg, kk, lane);
-#pragma unroll
-          for (int fl = 0; fl < 2; ++fl) {
-            const bf16x8 qa = row_frag(Qs, 16 * fl, kk, lane);
-            const bf16x8 da = row_frag(Ds, 16 * fl, kk, lane);
-            s[kg][fl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kf, s[kg][fl], 0, 0, 0);
-            dp[kg][fl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(da, vf, dp[kg][fl], 0, 0, 0);
-          }
-        }
-      };
-      auto elem = [&](int kg) {
-        const int key = k_lo + 16 * kg + (lane & 15);
-#pragma unroll
-        for (int fl = 0; fl < 2; ++fl)
-#pragma unroll
-          for (int r = 0; r < 4; r += 2) {
-            const f32x2 t = __builtin_elementwise_fma(f32x2{s[kg][fl][r], s[kg][fl][r + 1]}, f32x2{sl2, sl2},
-                                                      f32x2{nl4[fl][r], nl4[fl][r + 1]});
-            s[kg][fl][r] = t[0];
-            s[kg][fl][r + 1] = t[1];
-          }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          uint32_t km[2] = {~0u, ~0u};
-          if constexpr (DROP) {
-            uint32_t pv = pre_t;
-            asm volatile("" : "+v"(pv));  // hashed here, not hoisted ahead of the tile (its masks would not fit)
-            drop_keep_masks(tk2, drop_fin(pv + ((uint32_t)r * (uint32_t)T + 16u * kg) * kDropC1, seed_kx(seed)),
-                            km[0], km[1]);
-          }
-#pragma unroll
-          for (int fl = 0; fl < 2; ++fl) {
-            float p = __builtin_amdgcn_exp2f(s[kg][fl][r]);
-            if constexpr (DIAG) p = (q0 + 16 * fl + 4 * g + r < key) ? 0.f : p;
-            float pdv = p, d = dp[kg][fl][r];
-            if constexpr (DROP) {
-              pdv = __uint_as_float(km[fl] & __float_as_uint(p));
-              d = sel_mask(km[fl], d, nd4[fl][r]);
-            }
-            dp[kg][fl][r] = pdv;
-            s[kg][fl][r] = p * d;
-          }
-        }
-      };
-      auto dvdk = [&](int kg) {
-        const bf16x8 pp = pack_perm(dp[kg], 0), ss = pack_perm(s[kg], 0);
-#pragma unroll
-        for (int fd = 0; fd < 4; ++fd) {
-          const bf16x8 dot = tr_frag(Ds, 0, 16 * fd, lane);
-          const bf16x8 qt = tr_frag(Qs, 0, 16 * fd, lane);
-          dv[kg][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot, pp, dv[kg][fd], 0, 0, 0);
-          dk[kg][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt, ss, dk[kg][fd], 0, 0, 0);
-        }
-      };
-#if ATTN_DKDV_PIPE == 1  // program order by phase, the scheduler free within the block
-      sdp(0);
-      sdp(1);
-      elem(0);
-      elem(1);
-      dvdk(0);
-      dvdk(1);
-#elif ATTN_DKDV_PIPE == 2  // program order by key group
-      sdp(0);
-      sdp(1);
-      elem(0);
-      dvdk(0);
-      elem(1);
-      dvdk(1);
-#elif ATTN_DKDV_PIPE == 4  // phases fenced (register-pressure check)
-      sdp(0);
-      __builtin_amdgcn_sched_barrier(0);
-      sdp(1);
-      __builtin_amdgcn_sched_barrier(0);
-      elem(0);
-      __builtin_amdgcn_sched_barrier(0);
-      dvdk(0);
-      __builtin_amdgcn_sched_barrier(0);
-      elem(1);
-      __builtin_amdgcn_sched_barrier(0);
-      dvdk(1);
-#else  // 3: key-group pipeline with the MFMAs of one group spread through the other group's elementwise
-      sdp(0);
-      __builtin_amdgcn_sched_barrier(0);
-      sdp(1);
-      elem(0);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, ATTN_DKDV_FILL, 0);  // VALU
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      dvdk(0);
-      elem(1);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-        __builtin_amdgcn_sched_group_barrier(0x002, ATTN_DKDV_FILL, 1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      dvdk(1);
-#endif
-    };
-    tile();
-  };
-  for (int i = i0 + 4; i < nqt; ++i) step(i, steady);
-#endif
   if (!wave_valid) return;
 #pragma unroll
   for (int kg = 0; kg < 2; ++kg) {
@@ -1022,58 +709,61 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
   }
 }
 
+// The argument checks the forward and backward entries share; `what` is the entry's name in the message.
+static int attn_check(const char* what, int B, int T, int H, int head_dim, float p_drop) {
+  GPT2MI_REQUIRE(head_dim == D, "%s: head_dim=%d (only 64 is built)", what, head_dim);
+  GPT2MI_REQUIRE(p_drop <= 0.f || (size_t)B * H * T * T < (1ull << 32),
+                 "%s: B*H*T*T exceeds the 32-bit dropout hash index", what);
+  GPT2MI_REQUIRE(T % 64 == 0 && T > 0, "%s: T=%d must be a multiple of 64", what, T);
+  GPT2MI_REQUIRE((size_t)T * 3 * H * D * sizeof(bf16) < (1ull << 31),
+                 "%s: T*3C too large for the 32-bit buffer offsets of one batch row (T=%d)", what, T);
+  return 0;
+}
+
+// launch(std::bool_constant<DROP>): the kernel instance with dropout compiled in only when some probability is dropped
+template <class Launch>
+static void launch_by_drop(uint32_t thr, Launch&& launch) {
+  if (thr) launch(std::true_type{});
+  else launch(std::false_type{});
+}
+
 }  // namespace
 
 GPT2MI_EXPORT int gpt2mi_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int head_dim,
                                   float p_drop, uint64_t seed, void* stream) {
-  GPT2MI_REQUIRE(head_dim == D, "attn_fwd: head_dim=%d (only 64 is built)", head_dim);
-  GPT2MI_REQUIRE(p_drop <= 0.f || (size_t)B * H * T * T < (1ull << 32),
-                 "attn_fwd: B*H*T*T exceeds the 32-bit dropout hash index");
-  GPT2MI_REQUIRE(T % 64 == 0 && T > 0, "attn_fwd: T=%d must be a multiple of 64", T);
-  GPT2MI_REQUIRE((size_t)T * 3 * H * D * sizeof(bf16) < (1ull << 31),
-                 "attn_fwd: T*3C too large for the 32-bit buffer offsets of one batch row (T=%d)", T);
+  if (const int rc = attn_check("attn_fwd", B, T, H, head_dim, p_drop)) return rc;
   const float scale = 1.f / sqrtf((float)head_dim);
   dim3 grid((T + BQ - 1) / BQ, B * H);
   const uint32_t thr = drop_threshold(p_drop);
   const float ik = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
-  if (thr)
-    attn_fwd_kernel<true><<<grid, kThreads, 0, (hipStream_t)stream>>>((const bf16*)qkv, (bf16*)out, lse, T, H, scale,
-                                                                      seed, thr, ik);
-  else
-    attn_fwd_kernel<false><<<grid, kThreads, 0, (hipStream_t)stream>>>((const bf16*)qkv, (bf16*)out, lse, T, H, scale,
-                                                                       seed, thr, ik);
+  launch_by_drop(thr, [&](auto drop) {
+    attn_fwd_kernel<decltype(drop)::value><<<grid, kThreads, 0, (hipStream_t)stream>>>(
+        (const bf16*)qkv, (bf16*)out, lse, T, H, scale, seed, thr, ik);
+  });
   return gpt2mi::check_launch("attn_fwd");
 }
 
 GPT2MI_EXPORT int gpt2mi_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
                                   float* delta, uint16_t* dqkv, float* dqkv_colsum, int B, int T, int H,
                                   int head_dim, float p_drop, uint64_t seed, void* stream) {
-  GPT2MI_REQUIRE(head_dim == D, "attn_bwd: head_dim=%d (only 64 is built)", head_dim);
-  GPT2MI_REQUIRE(p_drop <= 0.f || (size_t)B * H * T * T < (1ull << 32),
-                 "attn_bwd: B*H*T*T exceeds the 32-bit dropout hash index");
-  GPT2MI_REQUIRE(T % 64 == 0 && T > 0, "attn_bwd: T=%d must be a multiple of 64", T);
-  GPT2MI_REQUIRE((size_t)T * 3 * H * D * sizeof(bf16) < (1ull << 31),
-                 "attn_bwd: T*3C too large for the 32-bit buffer offsets of one batch row (T=%d)", T);
+  if (const int rc = attn_check("attn_bwd", B, T, H, head_dim, p_drop)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const float scale = 1.f / sqrtf((float)head_dim);
   const uint32_t thr = drop_threshold(p_drop);
   const float ik = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
   // dQ first: it forms delta (dO . O per query) for the dK/dV kernel
   const dim3 gq((T + BQ - 1) / BQ, B * H);
-  if (thr)
-    attn_bwd_dq_kernel<true><<<gq, kThreads, 0, s>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta,
-                                                     (bf16*)dqkv, dqkv_colsum, T, H, scale, seed, thr, ik);
-  else
-    attn_bwd_dq_kernel<false><<<gq, kThreads, 0, s>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse,
-                                                      delta, (bf16*)dqkv, dqkv_colsum, T, H, scale, seed, thr, ik);
+  launch_by_drop(thr, [&](auto drop) {
+    attn_bwd_dq_kernel<decltype(drop)::value><<<gq, kThreads, 0, s>>>(
+        (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, dqkv_colsum, T, H, scale, seed,
+        thr, ik);
+  });
   int rc = gpt2mi::check_launch("attn_bwd_dq");
   if (rc) return rc;
   const dim3 gkv((T + BKB - 1) / BKB, B * H);
-  if (thr)
-    attn_bwd_dkdv_kernel<true><<<gkv, 256, 0, s>>>((const bf16*)qkv, (const bf16*)dout, lse, delta, (bf16*)dqkv,
-                                                    dqkv_colsum, T, H, scale, seed, thr, ik);
-  else
-    attn_bwd_dkdv_kernel<false><<<gkv, 256, 0, s>>>((const bf16*)qkv, (const bf16*)dout, lse, delta, (bf16*)dqkv,
-                                                     dqkv_colsum, T, H, scale, seed, thr, ik);
+  launch_by_drop(thr, [&](auto drop) {
+    attn_bwd_dkdv_kernel<decltype(drop)::value><<<gkv, 256, 0, s>>>(
+        (const bf16*)qkv, (const bf16*)dout, lse, delta, (bf16*)dqkv, dqkv_colsum, T, H, scale, seed, thr, ik);
+  });
   return gpt2mi::check_launch("attn_bwd_dkdv");
 }

@@ -58,6 +58,25 @@ def test_refuses_shapes_that_overflow_the_dropout_index():
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libgpt2mi.so not built (run __graft_entry__.build())")
+@pytest.mark.parametrize("B, T, H, head_dim, p_drop, words", [
+    (1, 128, 1, 32, 0.0, b"head_dim=32"),
+    (1, 96, 1, 64, 0.0, b"T=96"),
+    (64, 2048, 16, 64, 0.1, b"dropout hash"),            # B*H*T*T = 2^32 exactly
+    (1, 87424, 64, 64, 0.0, b"32-bit buffer offsets"),   # T*3*H*64*2 B = 2,148,532,224 > 2^31
+], ids=["head_dim", "seq_len", "dropout_hash", "buffer_offsets"])
+def test_attention_entries_share_their_argument_checks(B, T, H, head_dim, p_drop, words):
+    """gpt2mi_attn_fwd and gpt2mi_attn_bwd refuse the same arguments with the same words, each under its own name,
+    before anything is launched (NULL pointers, no GPU needed). No accepted call is made here: it would launch."""
+    from gpt_2_distributed_amd import _lib
+    lib = _lib.load()
+    shape = (B, T, H, head_dim, p_drop, 1, None)
+    for name, call in (("attn_fwd", lambda: lib.gpt2mi_attn_fwd(None, None, None, *shape)),
+                       ("attn_bwd", lambda: lib.gpt2mi_attn_bwd(None, None, None, None, None, None, None, *shape))):
+        rc, msg = call(), lib.gpt2mi_last_error()
+        assert rc == 22 and name.encode() in msg and words in msg, (name, rc, msg)
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libgpt2mi.so not built (run __graft_entry__.build())")
 def test_gemm_schedule_is_a_per_call_argument():
     """ABI v8: the GEMM schedule is passed with every call (no process-global switch is exported); an unknown
     schedule value is refused before any launch."""

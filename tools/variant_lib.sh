@@ -1,6 +1,6 @@
 #!/bin/bash
-# Builds an A/B library variant into tools/ab/lib_<name>.so: the tree's objects with ONE source file recompiled
-# with extra flags (e.g. -DSOME_EXPERIMENT), for tools/lib_ab.py.
+# Builds an A/B library variant into tools/ab/lib_<name>.so: the tree's objects (the Makefile's SRCS, so every entry of
+# the product library) with ONE source file recompiled with extra flags (e.g. -DSOME_EXPERIMENT), for tools/lib_ab.py.
 #   bash tools/variant_lib.sh <name> <source.hip> [flags...]
 set -e
 NAME=$1; SRC=$2; shift 2
@@ -8,7 +8,7 @@ cd "$(dirname "$0")/../gpt_2_distributed_amd/csrc"
 make -s -j8
 mkdir -p ../../tools/ab
 OBJS=""
-for f in runtime.cpp norm_embed.hip xent_adamw.hip gemm_api.hip gemm.hip gemm256.hip gemm_pp.hip splitk_reduce.hip attention.hip fp32.hip transpose.hip aux_ops.hip decode.hip; do
+for f in $(make -s print-srcs); do
   [ "$f" = "$SRC" ] || OBJS="$OBJS build/$f.o"
 done
 EXTRA=""; [ "$SRC" = attention.hip ] && EXTRA="-fno-honor-nans -fno-slp-vectorize"
