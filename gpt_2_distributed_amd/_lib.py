@@ -6,6 +6,7 @@ launches go on torch's current HIP stream.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 from typing import Optional
@@ -18,7 +19,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -121,6 +122,11 @@ _SIGS = {
     "gpt2mi_attn_decode_fp8_ragged": [_p, _p, _p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _p, _p],
     "gpt2mi_attn_extend_fp8": [_p, _p, _p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p,
                                _p],
+    # v24 shared prompt cache: attn_decode_ragged's / attn_decode_fp8_ragged's lists with (share_group, share_len), HOST
+    # arrays of B ints (both may be NULL), behind pos
+    "gpt2mi_attn_decode_shared": [_p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    "gpt2mi_attn_decode_shared_fp8": [_p, _p, _p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _p, _p, _p,
+                                      _p],
 }
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size}
@@ -142,6 +148,12 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise KernelError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`"
                           " (or make -C gpt_2_distributed_amd/csrc)")
+    _lib = open_library(path)
+    return _lib
+
+
+def open_library(path: str) -> ctypes.CDLL:
+    """A build of the library at ``path``, typed and refused unless its C ABI is the bindings'."""
     lib = ctypes.CDLL(path)
     for name, args in _SIGS.items():
         fn = getattr(lib, name)
@@ -149,8 +161,20 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         fn.restype = _RESTYPES.get(name, ctypes.c_int)
     if lib.gpt2mi_abi_version() != ABI_VERSION:
         raise KernelError(f"{path} has C ABI v{lib.gpt2mi_abi_version()}, the bindings expect v{ABI_VERSION}: rebuild it")
-    _lib = lib
     return lib
+
+
+@contextlib.contextmanager
+def using(lib: ctypes.CDLL):
+    """Within the block every binding calls ``lib`` (from ``open_library``) instead of the product library: how an A/B
+    tool runs the package's own call paths over another build in one process."""
+    global _lib
+    product = load()
+    _lib = lib
+    try:
+        yield lib
+    finally:
+        _lib = product
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -442,8 +466,57 @@ class DecodePlan(ctypes.Structure):
         _c_int.from_address(ctypes.addressof(self) + self.KV_FORMAT_OFFSET).value = value
 
 
+    # v24 appends `const int* share_group, *share_len` behind kv_format: the C struct grows by two pointers. The field
+    # list still stays v21's, so an instance is laid over a zeroed buffer of the C struct's size (``__new__``) and the
+    # two pointers are properties over its tail, like kv_format: a plan that never sets them shares nothing.
+    #
+    # THE TRAP: ctypes.sizeof(DecodePlan) is therefore 16 bytes SHORT of sizeof(gpt2mi_decode_plan) (PLAN_BYTES), and
+    # only ``DecodePlan()`` makes an object the library may read. An element of ``(DecodePlan * n)()``, a
+    # ``from_buffer_copy`` or a ``from_address`` has no tail, and the C side would read past its end; a memmove of sizeof
+    # bytes leaves the tail behind. Every binding below passes a plan through ``ref()``, which refuses an object that
+    # ``DecodePlan()`` did not make (tests/test_share_cabi.py). The way out of this, when
+    # the pin on the field list may move, is to put kv_format, share_group and share_len into ``_fields_`` and delete
+    # ``__new__``, the properties and ``ref()``'s check.
+    def __new__(cls, *args, **kw):
+        buf = (ctypes.c_char * cls.PLAN_BYTES)()
+        self = cls.from_buffer(buf)  # (keeps buf alive)
+        self._whole = True
+        return self
+
+    def ref(self):
+        """``ctypes.byref(self)`` for a C entry, refused unless the object is PLAN_BYTES long (made by DecodePlan())."""
+        if not getattr(self, "_whole", False):
+            raise KernelError(f"this DecodePlan was not made by DecodePlan(): it is {ctypes.sizeof(DecodePlan)} bytes "
+                              f"and gpt2mi_decode_plan is {self.PLAN_BYTES} (array element, copy or from_buffer_copy?)")
+        return ctypes.byref(self)
+
+    def _tail_ptr(self, offset: int):
+        self.ref()  # (an object without the tail has nothing at this offset)
+        return _p.from_address(ctypes.addressof(self) + offset)
+
+    def set_share(self, share_group, share_len) -> None:
+        """Point the plan at the share map: two ctypes int arrays of B entries the owner keeps alive and may update in
+        place, or (None, None) for no sharing."""
+        if (share_group is None) != (share_len is None):
+            raise KernelError("share_group and share_len go together")
+        self._share = (share_group, share_len)  # the plan keeps what it points at alive
+        self._tail_ptr(self.SHARE_GROUP_OFFSET).value = None if share_group is None else ctypes.addressof(share_group)
+        self._tail_ptr(self.SHARE_LEN_OFFSET).value = None if share_len is None else ctypes.addressof(share_len)
+
+    @property
+    def share_group(self):
+        return self._tail_ptr(self.SHARE_GROUP_OFFSET).value
+
+    @property
+    def share_len(self):
+        return self._tail_ptr(self.SHARE_LEN_OFFSET).value
+
+
 DecodePlan.KV_FORMAT_OFFSET = DecodePlan.rows.offset + ctypes.sizeof(_c_int)
 assert DecodePlan.KV_FORMAT_OFFSET + ctypes.sizeof(_c_int) <= ctypes.sizeof(DecodePlan)
+DecodePlan.SHARE_GROUP_OFFSET = ctypes.sizeof(DecodePlan)  # (pointer-aligned: the struct holds pointers)
+DecodePlan.SHARE_LEN_OFFSET = DecodePlan.SHARE_GROUP_OFFSET + ctypes.sizeof(_p)
+DecodePlan.PLAN_BYTES = DecodePlan.SHARE_LEN_OFFSET + ctypes.sizeof(_p)  # sizeof(gpt2mi_decode_plan) since v24
 
 
 def gemm_skinny_workspace(M, N, K) -> int:
@@ -481,7 +554,7 @@ def embed_decode(tok, wte, wpe, x, B, C, pos):
 def decode_step(plan: DecodePlan, tok, pos):
     """One token step of the whole network (gpt2mi_decode_step) into plan.logits: decode_step_ragged with every row at
     pos. The package steps through decode_step_ragged; this binding serves the test that holds the two equal."""
-    _call("gpt2mi_decode_step", ctypes.byref(plan), _ptr(tok), pos, _stream())
+    _call("gpt2mi_decode_step", plan.ref(), _ptr(tok), pos, _stream())
 
 
 # ---- v17: device-side sampling (csrc/sample.hip) --------------------------------------------------
@@ -506,7 +579,7 @@ def decode_generate(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, 
     """gpt2mi_decode_generate: n sample-then-step rounds from plan.logits without leaving C: decode_generate_ragged with
     every row starting at pos0 (as decode_step, kept for the test of that)."""
     t, k, p, s, e = _sampler_args(temperature, top_k, top_p, seed, eos)
-    _call("gpt2mi_decode_generate", ctypes.byref(plan), V, t, k, p, s, e, pos0, n, _ptr(tok), _ptr(seq),
+    _call("gpt2mi_decode_generate", plan.ref(), V, t, k, p, s, e, pos0, n, _ptr(tok), _ptr(seq),
           0 if seq is None else seq.stride(0), _ptr(done), _stream())
 
 
@@ -566,7 +639,7 @@ def embed_decode_ragged(tok, wte, wpe, x, B, C, pos):
 
 def decode_step_ragged(plan: DecodePlan, tok, pos):
     """gpt2mi_decode_step_ragged: one token step with row b at pos[b], into plan.logits."""
-    _call("gpt2mi_decode_step_ragged", ctypes.byref(plan), _ptr(tok), _positions(pos, plan.B), _stream())
+    _call("gpt2mi_decode_step_ragged", plan.ref(), _ptr(tok), _positions(pos, plan.B), _stream())
 
 
 def _sample_call(name, logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out, *tail):
@@ -578,7 +651,7 @@ def _sample_call(name, logits, V, scalars, pos, tok_out, row_id, done, seq_out, 
 
 def _generate_call(name, plan, V, scalars, pos0, n, tok, row_id, seq, done, *tail):
     """The argument list of the per-row generate loops; `tail` goes behind the stream."""
-    _call(name, ctypes.byref(plan), V, *scalars, _positions(pos0, plan.B), _row_ids(row_id, plan.B), n, _ptr(tok),
+    _call(name, plan.ref(), V, *scalars, _positions(pos0, plan.B), _row_ids(row_id, plan.B), n, _ptr(tok),
           _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(done), _stream(), *tail)
 
 
@@ -606,7 +679,7 @@ def attn_extend(qkv, kcache, vcache, out, workspace, R, B, H, D, Tcap, seq, pos)
 def decode_extend(plan: DecodePlan, tok, seq, pos):
     """gpt2mi_decode_extend: the step's launch list on len(pos) rows of the row map (seq, pos), into plan.logits."""
     R = len(pos)
-    _call("gpt2mi_decode_extend", ctypes.byref(plan), R, _ptr(tok), _positions(seq, R), _positions(pos, R), _stream())
+    _call("gpt2mi_decode_extend", plan.ref(), R, _ptr(tok), _positions(seq, R), _positions(pos, R), _stream())
 
 
 # ---- v23: the fp8 key/value cache (csrc/decode.hip) ----------------------------------------------------
@@ -668,3 +741,19 @@ def decode_generate_penalized(plan: DecodePlan, V, temperature, top_k, top_p, se
         raise KernelError(f"gen_start has {len(gen_start)} entries for B={plan.B} rows")
     _generate_call("gpt2mi_decode_generate_penalized", plan, V, scalars, pos0, n, tok, row_id, seq, done,
                    float(repetition), float(presence), float(frequency), _host_ints(gen_start))
+
+
+# ---- v24: rows that share a prompt cache (csrc/decode.hip) -------------------------------------------
+def attn_decode_shared(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos, share_group=None, share_len=None,
+                       kscale=None, vscale=None):
+    """gpt2mi_attn_decode_shared (with kscale / vscale: gpt2mi_attn_decode_shared_fp8): attn_decode_ragged with the share
+    map (share_group, share_len), host sequences of B ints or both None. The bits of attn_decode_ragged."""
+    sg, sl = _host_ints(share_group), _host_ints(share_len)
+    if any(a is not None and len(a) != B for a in (sg, sl)):
+        raise KernelError(f"share_group / share_len must have B={B} entries")
+    if kscale is None:
+        _call("gpt2mi_attn_decode_shared", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(workspace),
+              workspace.numel(), B, H, D, Tcap, _positions(pos, B), sg, sl, _stream())
+    else:
+        _call("gpt2mi_attn_decode_shared_fp8", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale),
+              _ptr(out), _ptr(workspace), workspace.numel(), B, H, D, Tcap, _positions(pos, B), sg, sl, _stream())

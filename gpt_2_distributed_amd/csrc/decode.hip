@@ -11,6 +11,8 @@
 // same registers, no scratch, occupancy 8; what differs is listed in DESIGN.md "Multi-token decode step".
 // The cache is bf16 or, since v23, fp8 (e4m3 codes and a power-of-two scale per 64-wide row): attn_row is templated on
 // the format and kv_store has a second kernel; the bf16 instantiations are instruction for instruction what they were.
+// Since v24 rows that hold the same prompt can share its keys and values: attn_row's arithmetic is attn_range, which a
+// second kind of wave (attn_shared) runs for several rows over one load; same bits (DESIGN.md "Shared prompt cache").
 #include <limits.h>
 
 #include <algorithm>
@@ -262,6 +264,65 @@ struct RowPos {
   int v[GPT2MI_DECODE_MAX_B];
 };
 
+// The arithmetic of one (row, range) once its 32 keys and values are in registers, written once for attn_row and for
+// attn_shared below: q is the row's scaled query, the lane's key i is kv[i] / vv[i] (bf16) or k8[i] / v8[i] (fp8), and
+// the partial (max, sum, acc[64]) goes to workspace slot `slot`. Same operations in the same order whoever loaded the
+// keys: that is what makes a shared load bit-identical to the row's own.
+template <bool FP8>
+__device__ __forceinline__ void attn_range(const float* q, const bf16x8* kv, const bf16x8* vv, const KvRow8* k8,
+                                           const KvRow8* v8, float* __restrict__ ws_ml, float* __restrict__ ws_acc,
+                                           int range, int pos, size_t slot, int kk, int dg) {
+  float s[4], mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    float kf[8], d = 0.f;
+    if constexpr (FP8)
+      kv_codes8(k8[i].codes, kf);
+    else
+      unpack8(kv[i], kf);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], kf[j], d);
+    d += __shfl_xor(d, 1, 64);
+    d += __shfl_xor(d, 2, 64);
+    d += __shfl_xor(d, 4, 64);
+    if constexpr (FP8) d *= k8[i].scale;
+    s[i] = (range * AD_KEYS + kk + 8 * i <= pos) ? d : -INFINITY;
+    mx = fmaxf(mx, s[i]);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 8, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // finite: the range's first key is <= pos
+
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, l = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float p = __expf(s[i] - mx);  // 0 for a masked key
+    float vf[8];
+    if constexpr (FP8)
+      kv_dequantize8(v8[i], vf);
+    else
+      unpack8(vv[i], vf);
+    l += p;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(p, vf[j], acc[j]);
+  }
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) {
+    l += __shfl_xor(l, o, 64);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], o, 64);
+  }
+  if (kk == 0) {
+    float* a = ws_acc + slot * 64 + 8 * dg;
+    *reinterpret_cast<f32x4*>(a) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+    *reinterpret_cast<f32x4*>(a + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    if (dg == 0) {
+      ws_ml[2 * slot] = mx;
+      ws_ml[2 * slot + 1] = l;
+    }
+  }
+}
+
 // The work of one wave, written once for both entries: row r of the launch at position pos, keys range * 32 .. + 31 of
 // the cache stream `stream` = seq * H + h (formed by the entry, in the width its seq needs). The keys of a row come
 // from two places: a key below `first` from the cache (written by an earlier call), a key in first..pos from the qkv
@@ -346,56 +407,7 @@ __device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, KV* __res
     }
   }
 
-  float s[4], mx = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float kf[8], d = 0.f;
-    if constexpr (FP8)
-      kv_codes8(k8[i].codes, kf);
-    else
-      unpack8(kv[i], kf);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], kf[j], d);
-    d += __shfl_xor(d, 1, 64);
-    d += __shfl_xor(d, 2, 64);
-    d += __shfl_xor(d, 4, 64);
-    if constexpr (FP8) d *= k8[i].scale;
-    s[i] = (range * AD_KEYS + kk + 8 * i <= pos) ? d : -INFINITY;
-    mx = fmaxf(mx, s[i]);
-  }
-  mx = fmaxf(mx, __shfl_xor(mx, 8, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));  // finite: the range's first key is <= pos
-
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, l = 0.f;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float p = __expf(s[i] - mx);  // 0 for a masked key
-    float vf[8];
-    if constexpr (FP8)
-      kv_dequantize8(v8[i], vf);
-    else
-      unpack8(vv[i], vf);
-    l += p;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(p, vf[j], acc[j]);
-  }
-#pragma unroll
-  for (int o = 8; o < 64; o <<= 1) {
-    l += __shfl_xor(l, o, 64);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] += __shfl_xor(acc[j], o, 64);
-  }
-  const size_t slot = (size_t)(r * H + h) * nr_max + range;
-  if (kk == 0) {
-    float* a = ws_acc + slot * 64 + 8 * dg;
-    *reinterpret_cast<f32x4*>(a) = f32x4{acc[0], acc[1], acc[2], acc[3]};
-    *reinterpret_cast<f32x4*>(a + 4) = f32x4{acc[4], acc[5], acc[6], acc[7]};
-    if (dg == 0) {
-      ws_ml[2 * slot] = mx;
-      ws_ml[2 * slot + 1] = l;
-    }
-  }
+  attn_range<FP8>(q, kv, vv, k8, v8, ws_ml, ws_acc, range, pos, (size_t)(r * H + h) * nr_max + range, kk, dg);
 }
 
 // Grid (ranges, H, B): row b at rows.v[b] of its own cache stream; the x extent is that of the longest row. b is a grid
@@ -416,6 +428,114 @@ __global__ __launch_bounds__(64) void attn_decode_fp8_kernel(const bf16* __restr
                                                              int nr_max) {
   const int b = blockIdx.z, bh = b * H + blockIdx.y;
   attn_row<false, true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, b, bh, rows.v[b], rows.v[b]);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Rows that share a prefix (v24). A share group is a set of rows whose streams hold identical bits at positions
+// [0, shared_len); a range of 32 keys is shared when it lies wholly below shared_len. The map is built and checked on
+// the host (share_map) and travels by value, indexed by blockIdx and by a wave-uniform loop counter only.
+// One grid holds both kinds of wave, so sharing adds no launch: z < B is row z, which runs attn_row for its ranges
+// from own0[z] upward (the range that straddles shared_len and the key at pos included) and returns at once below;
+// z >= B is chunk z - B, up to AD_SHARE_CHUNK members of one group: its wave loads a shared range's keys and values
+// once, from the group's lowest row, and runs attn_range for each member with that member's q, into the member's own
+// slot. Every slot therefore holds the bits attn_row would have put there and attn_combine_kernel is unchanged. The
+// tile's bytes are read once per chunk instead of once per member. The members of a chunk run one after the other, so a
+// wave's time grows with the chunk: measured, the smallest chunk is the fastest (half the bytes, twice the work per wave).
+#ifndef GPT2MI_SHARE_CHUNK
+#define GPT2MI_SHARE_CHUNK 2  // members per wave: DESIGN.md "Shared prompt cache" has the measurements of 2 .. 64
+#endif
+constexpr int AD_SHARE_CHUNK = GPT2MI_SHARE_CHUNK;
+// A step (the plan entries) takes the shared form only when the rows of its sharing groups (two members and a full shared
+// range) number at least this: a chunk's members run one after the other in one wave, and below it that wave outlasts
+// the whole unshared launch, which is a single round of waves there (measurements: DESIGN.md). A launch choice: bits
+// do not depend on it. Read from the map alone. The standalone entries share whatever the map lets them.
+#ifndef GPT2MI_SHARE_MIN_ROWS
+#define GPT2MI_SHARE_MIN_ROWS 16
+#endif
+constexpr int AD_SHARE_MIN_ROWS = GPT2MI_SHARE_MIN_ROWS;
+constexpr int AD_MAX_CHUNKS = GPT2MI_DECODE_MAX_B;  // a group of n >= 2 rows has ceil(n / chunk) <= n - 1 chunks
+static_assert(AD_SHARE_CHUNK >= 2, "a chunk of one member shares nothing");
+
+
+struct ShareMap {
+  int B, chunks;
+  int pos[GPT2MI_DECODE_MAX_B];     // RowPos
+  int own0[GPT2MI_DECODE_MAX_B];    // the first range row b computes from its own stream
+  int member[GPT2MI_DECODE_MAX_B];  // the rows of the chunks, chunk after chunk
+  int c_src[AD_MAX_CHUNKS], c_start[AD_MAX_CHUNKS], c_count[AD_MAX_CHUNKS], c_ranges[AD_MAX_CHUNKS];
+};
+
+// The wave of chunk c: ranges below c_ranges[c] (all 32 keys below shared_len <= every member's pos: no key of this call,
+// no mask). The load is attn_row's `key < first` branch on the source row's stream.
+template <bool FP8, class KV>
+__device__ __forceinline__ void attn_shared(const bf16* __restrict__ qkv, const KV* __restrict__ kc,
+                                            const KV* __restrict__ vc, const float* __restrict__ ks,
+                                            const float* __restrict__ vs, float* __restrict__ ws_ml,
+                                            float* __restrict__ ws_acc, int H, int Tcap, int nr_max, const ShareMap& m,
+                                            int c) {
+  const int range = blockIdx.x, h = blockIdx.y;
+  if (range >= m.c_ranges[c]) return;
+  const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
+  const int C = H * 64;
+  const size_t stream = (size_t)(m.c_src[c] * H + h);
+  const size_t base = stream * Tcap * 64 + 8 * dg;
+  bf16x8 kv[4], vv[4];
+  KvRow8 k8[4], v8[4];  // FP8 only
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int key = range * AD_KEYS + kk + 8 * i;
+    if constexpr (FP8) {
+      k8[i].codes = *reinterpret_cast<const uint2*>(kc + base + (size_t)key * 64);
+      v8[i].codes = *reinterpret_cast<const uint2*>(vc + base + (size_t)key * 64);
+      k8[i].scale = ks[stream * Tcap + key];
+      v8[i].scale = vs[stream * Tcap + key];
+    } else {
+      kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
+      vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
+    }
+  }
+  // The members run one after the other, so a member's q is loaded while the one before it computes: the wave's time is
+  // what a chunk costs, and a load's latency per member would be most of it.
+  const int start = m.c_start[c], count = m.c_count[c];
+  const bf16* q0 = qkv + h * 64 + 8 * dg;
+  int r_next = m.member[start];
+  bf16x8 q_next = *reinterpret_cast<const bf16x8*>(q0 + (size_t)r_next * 3 * C);
+  for (int j = 0; j < count; ++j) {
+    const int r = r_next;
+    float q[8];
+    unpack8(q_next, q);
+    if (j + 1 < count) {
+      r_next = m.member[start + j + 1];
+      q_next = *reinterpret_cast<const bf16x8*>(q0 + (size_t)r_next * 3 * C);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) q[e] *= 0.125f;
+    attn_range<FP8>(q, kv, vv, k8, v8, ws_ml, ws_acc, range, m.pos[r], (size_t)(r * H + h) * nr_max + range, kk, dg);
+  }
+}
+
+// Grid (ranges, H, B + chunks).
+__global__ __launch_bounds__(64) void attn_decode_shared_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
+                                                                bf16* __restrict__ vc, float* __restrict__ ws_ml,
+                                                                float* __restrict__ ws_acc, int H, int Tcap,
+                                                                ShareMap m, int nr_max) {
+  const int z = blockIdx.z;
+  if (z >= m.B) return attn_shared<false>(qkv, kc, vc, nullptr, nullptr, ws_ml, ws_acc, H, Tcap, nr_max, m, z - m.B);
+  if ((int)blockIdx.x < m.own0[z]) return;
+  attn_row<false, false>(qkv, kc, vc, nullptr, nullptr, ws_ml, ws_acc, H, Tcap, nr_max, z, z * H + blockIdx.y, m.pos[z],
+                         m.pos[z]);
+}
+
+__global__ __launch_bounds__(64) void attn_decode_shared_fp8_kernel(const bf16* __restrict__ qkv,
+                                                                    uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
+                                                                    float* __restrict__ ks, float* __restrict__ vs,
+                                                                    float* __restrict__ ws_ml,
+                                                                    float* __restrict__ ws_acc, int H, int Tcap,
+                                                                    ShareMap m, int nr_max) {
+  const int z = blockIdx.z;
+  if (z >= m.B) return attn_shared<true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, m, z - m.B);
+  if ((int)blockIdx.x < m.own0[z]) return;
+  attn_row<false, true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, z, z * H + blockIdx.y, m.pos[z], m.pos[z]);
 }
 
 // out[b, h*64 + d] = sum_r e^(m_r - m) acc_r[d] / sum_r e^(m_r - m) l_r over the pos[b] / 32 + 1 ranges of row b, in
@@ -609,6 +729,58 @@ int row_positions(const char* what, const int* pos, int B, int limit, RowPos* ou
   return 0;
 }
 
+// The share map of an entry (v24), checked next to its positions and in their message format: share_group and share_len
+// are HOST arrays of B ints, both NULL for no sharing. share_group[b] is the lowest row of b's group (b itself when
+// alone), share_len[b] the group's shared length (0 when alone). 22 with a message naming `what` and the index
+// otherwise. On success *out is the kernel's map at the positions rp: out->chunks == 0 when no group has two members and
+// a full shared range, or when fewer than min_rows rows are in such groups, and the caller then launches the unshared
+// kernels. What is shared is read from the map alone.
+int share_map(const char* what, const int* share_group, const int* share_len, int B, const RowPos& rp, ShareMap* out,
+              int min_rows = 2) {
+  GPT2MI_REQUIRE((share_group == nullptr) == (share_len == nullptr),
+                 "%s: share_group and share_len (host, B ints) go together: %s is NULL", what,
+                 share_group ? "share_len" : "share_group");
+  *out = ShareMap{};
+  out->B = B;
+  std::copy_n(rp.v, GPT2MI_DECODE_MAX_B, out->pos);
+  if (!share_group) return 0;
+  int members[GPT2MI_DECODE_MAX_B] = {};
+  for (int b = 0; b < B; ++b) {
+    const int g = share_group[b];
+    GPT2MI_REQUIRE(g >= 0 && g <= b, "%s: share_group[%d]=%d not in [0, %d]", what, b, g, b);
+    GPT2MI_REQUIRE(share_group[g] == g, "%s: share_group[%d]=%d is not its group's lowest row (share_group[%d]=%d)", what,
+                   b, g, g, share_group[g]);
+    GPT2MI_REQUIRE(share_len[b] >= 0, "%s: share_len[%d]=%d is negative", what, b, share_len[b]);
+    GPT2MI_REQUIRE(share_len[b] <= rp.v[b], "%s: share_len[%d]=%d exceeds pos[%d]=%d", what, b, share_len[b], b, rp.v[b]);
+    GPT2MI_REQUIRE(share_len[b] == share_len[g], "%s: share_len[%d]=%d differs from its group's share_len[%d]=%d", what, b,
+                   share_len[b], g, share_len[g]);
+    ++members[g];
+  }
+  for (int b = 0; b < B; ++b)
+    GPT2MI_REQUIRE(members[share_group[b]] > 1 || share_len[b] == 0,
+                   "%s: share_len[%d]=%d for a row alone in its group (must be 0)", what, b, share_len[b]);
+  int at = 0;
+  for (int g = 0; g < B; ++g) {
+    const int ranges = share_len[g] / AD_KEYS;
+    if (share_group[g] != g || members[g] < 2 || ranges < 1) continue;
+    for (int b = g, n = 0; b < B; ++b) {
+      if (share_group[b] != g) continue;
+      if (n % AD_SHARE_CHUNK == 0) {
+        const int c = out->chunks++;
+        out->c_src[c] = g, out->c_start[c] = at, out->c_count[c] = 0, out->c_ranges[c] = ranges;
+      }
+      ++out->c_count[out->chunks - 1], ++n;
+      out->member[at++] = b;
+      out->own0[b] = ranges;
+    }
+  }
+  if (at < min_rows) {  // too few rows share for the shared form to pay: every row reads its own stream
+    out->chunks = 0;
+    std::fill_n(out->own0, GPT2MI_DECODE_MAX_B, 0);
+  }
+  return 0;
+}
+
 using gpt2mi::SamePos;
 
 // The tail the two attention entries share, after their own row checks: M rows whose kernel argument is `rows`, at the
@@ -618,7 +790,7 @@ template <class Rows>
 int attn_launch(const char* what, void (*kernel)(const bf16*, bf16*, bf16*, float*, float*, int, int, Rows, int),
                 void (*kernel8)(const bf16*, uint8_t*, uint8_t*, float*, float*, float*, float*, int, int, Rows, int),
                 const Rows& rows, const RowPos& rp, int max_pos, const uint16_t* qkv, const KvCache& kv, uint16_t* out,
-                float* workspace, size_t workspace_floats, int M, int H, int Tcap, void* stream) {
+                float* workspace, size_t workspace_floats, int M, int H, int Tcap, void* stream, int extra_z = 0) {
   const size_t need = gpt2mi_attn_decode_workspace(M, H, Tcap);
   GPT2MI_REQUIRE(workspace_floats >= need, "%s: workspace too small (%zu floats given, %zu needed)", what,
                  workspace_floats, need);
@@ -629,7 +801,7 @@ int attn_launch(const char* what, void (*kernel)(const bf16*, bf16*, bf16*, floa
   const int nr_max = attn_ranges(Tcap);
   float* ws_ml = workspace;
   float* ws_acc = workspace + (size_t)M * H * nr_max * 2;
-  const dim3 grid(max_pos / AD_KEYS + 1, H, M);
+  const dim3 grid(max_pos / AD_KEYS + 1, H, M + extra_z);  // (extra_z: the chunks of a shared launch)
   if (kv.format == GPT2MI_KV_FP8)
     kernel8<<<grid, 64, 0, s>>>((const bf16*)qkv, (uint8_t*)kv.k, (uint8_t*)kv.v, kv.ks, kv.vs, ws_ml, ws_acc, H, Tcap,
                                 rows, nr_max);
@@ -640,17 +812,31 @@ int attn_launch(const char* what, void (*kernel)(const bf16*, bf16*, bf16*, floa
   return gpt2mi::check_launch(what);
 }
 
-// Each operation below is written once, for one position per row; `what` is the entry's name in its messages.
+// One position per row, at checked positions rp and under a checked map sm (sm.pos is rp): the launch the map asks for.
+int attn_decode_mapped(const char* what, const uint16_t* qkv, const KvCache& kv, uint16_t* out, float* workspace,
+                       size_t workspace_floats, int B, int H, int Tcap, const RowPos& rp, int max_pos,
+                       const ShareMap& sm, void* stream) {
+  if (sm.chunks)  // some range is shared: the one launch that holds both kinds of wave
+    return attn_launch(what, attn_decode_shared_kernel, attn_decode_shared_fp8_kernel, sm, rp, max_pos, qkv, kv, out,
+                       workspace, workspace_floats, B, H, Tcap, stream, sm.chunks);
+  return attn_launch(what, attn_decode_kernel, attn_decode_fp8_kernel, rp, rp, max_pos, qkv, kv, out, workspace,
+                     workspace_floats, B, H, Tcap, stream);
+}
+
+// Each operation below is written once, for one position per row; `what` is the entry's name in its messages. The
+// standalone attention entries: they share whatever the map lets them (share_map's min_rows = 2).
 int attn_decode_rows(const char* what, const uint16_t* qkv, const KvCache& kv, uint16_t* out, float* workspace,
-                     size_t workspace_floats, int B, int H, int head_dim, int Tcap, const int* pos, void* stream) {
+                     size_t workspace_floats, int B, int H, int head_dim, int Tcap, const int* pos, void* stream,
+                     const int* share_group = nullptr, const int* share_len = nullptr) {
   GPT2MI_REQUIRE(head_dim == 64, "%s: head_dim=%d (the decode kernels implement 64)", what, head_dim);
   GPT2MI_REQUIRE(B >= 1 && H >= 1 && H <= 65535 && Tcap >= 1, "%s: B=%d, H=%d (<= 65535), Tcap=%d must be positive", what,
                  B, H, Tcap);
   RowPos rp;
   int max_pos;
   if (const int rc = row_positions(what, pos, B, Tcap, &rp, &max_pos)) return rc;
-  return attn_launch(what, attn_decode_kernel, attn_decode_fp8_kernel, rp, rp, max_pos, qkv, kv, out, workspace,
-                     workspace_floats, B, H, Tcap, stream);
+  ShareMap sm;
+  if (const int rc = share_map(what, share_group, share_len, B, rp, &sm)) return rc;
+  return attn_decode_mapped(what, qkv, kv, out, workspace, workspace_floats, B, H, Tcap, rp, max_pos, sm, stream);
 }
 
 int embed_decode_rows(const char* what, const int64_t* tok, const float* wte, const float* wpe, float* x, int B, int C,
@@ -678,6 +864,23 @@ GPT2MI_EXPORT int gpt2mi_attn_decode_fp8_ragged(const uint16_t* qkv, uint8_t* kc
                                                 const int* pos, void* stream) {
   return attn_decode_rows("attn_decode_fp8_ragged", qkv, KvCache{GPT2MI_KV_FP8, kcache, vcache, kscale, vscale}, out,
                           workspace, workspace_floats, B, H, head_dim, Tcap, pos, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_decode_shared(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
+                                            float* workspace, size_t workspace_floats, int B, int H, int head_dim,
+                                            int Tcap, const int* pos, const int* share_group, const int* share_len,
+                                            void* stream) {
+  return attn_decode_rows("attn_decode_shared", qkv, KvCache{GPT2MI_KV_BF16, kcache, vcache, nullptr, nullptr}, out,
+                          workspace, workspace_floats, B, H, head_dim, Tcap, pos, stream, share_group, share_len);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_decode_shared_fp8(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale,
+                                                float* vscale, uint16_t* out, float* workspace,
+                                                size_t workspace_floats, int B, int H, int head_dim, int Tcap,
+                                                const int* pos, const int* share_group, const int* share_len,
+                                                void* stream) {
+  return attn_decode_rows("attn_decode_shared_fp8", qkv, KvCache{GPT2MI_KV_FP8, kcache, vcache, kscale, vscale}, out,
+                          workspace, workspace_floats, B, H, head_dim, Tcap, pos, stream, share_group, share_len);
 }
 
 GPT2MI_EXPORT int gpt2mi_attn_decode(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out,
@@ -819,10 +1022,13 @@ int decode_step_rows(const char* what, const gpt2mi_decode_plan* P, const int64_
   RowPos rp;
   int max_pos;
   if (const int rc = row_positions(what, pos, B, P->Tcap, &rp, &max_pos)) return rc;
+  GPT2MI_REQUIRE(H <= 65535, "%s: B=%d, H=%d (<= 65535), Tcap=%d must be positive", what, B, H, P->Tcap);
+  ShareMap sm;  // refused here, before the first launch; every layer's attention call then launches from this one map
+  if (const int rc = share_map(what, P->share_group, P->share_len, B, rp, &sm, AD_SHARE_MIN_ROWS)) return rc;
   if (const int rc = plan_buffers(what, P, B, tok)) return rc;
   return decode_launches(what, P, B, tok, pos, stream, [&](const gpt2mi_decode_layer& Y) {
-    return attn_decode_rows(what, P->qkv, layer_cache(P, Y), P->ao, P->attn_ws, P->attn_ws_floats, B, H, 64, P->Tcap,
-                            pos, stream);
+    return attn_decode_mapped(what, P->qkv, layer_cache(P, Y), P->ao, P->attn_ws, P->attn_ws_floats, B, H, P->Tcap, rp,
+                              max_pos, sm, stream);
   });
 }
 }  // namespace
@@ -885,6 +1091,8 @@ int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, f
   if (const int rc = row_positions(what, pos0, P->B, P->Tcap, &rp, &max_pos)) return rc;
   for (int b = 0; b < P->B; ++b)
     GPT2MI_REQUIRE(pos0[b] >= 1, "%s: pos0[%d]=%d must be >= 1 (after a prefill)", what, b, pos0[b]);
+  ShareMap sm;  // at pos0: the positions only grow from there, so a map that passes here passes at every step
+  if (const int rc = share_map(what, P->share_group, P->share_len, P->B, rp, &sm)) return rc;
   GPT2MI_REQUIRE((long long)max_pos + n <= P->Tcap, "%s: max pos0=%d + n=%d exceeds the cache length Tcap=%d", what,
                  max_pos, n, P->Tcap);
   GPT2MI_REQUIRE(!seq || (long long)max_pos + n <= ld_seq, "%s: max pos0=%d + n=%d exceeds ld_seq=%d", what, max_pos, n,

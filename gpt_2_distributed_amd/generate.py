@@ -1,6 +1,7 @@
 """Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
 --prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B
---draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F --kv_dtype {bf16,fp8}]``.
+--draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F --kv_dtype {bf16,fp8}
+--num_samples S]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -8,7 +9,12 @@ included). No tokenizer is shipped: prompts and outputs are GPT-2 BPE ids (50256
 
 Several prompts: repeat ``--prompt_ids`` or give ``--prompts_file`` (one comma-separated prompt per line). They go
 through ``GPT2.generate_many`` (continuous batching on the device sampler, ``--batch`` rows at a time; prompt i draws from
-(``--seed``, i, position)) and one JSON list per prompt is printed, in input order."""
+(``--seed``, i, position)) and one JSON list per prompt is printed, in input order.
+
+``--num_samples S`` (S > 1) draws S continuations of every prompt through ``GPT2.generate(num_samples=S)``: each prompt
+is run once and its rows share its cache. One JSON object per sample is printed, prompt-major:
+``{"prompt": b, "sample": j, "tokens": [...]}`` (the prompt's own padding, if the prompts differ in length, removed).
+``--batch`` is not used then; prompts x S <= 64."""
 from __future__ import annotations
 
 import argparse
@@ -53,6 +59,9 @@ def parse_args(argv=None):
     p.add_argument("--kv_dtype", default="bf16", choices=["bf16", "fp8"],
                    help="the key/value cache: bf16, or fp8 (e4m3 codes with a power-of-two scale per 64-wide row, "
                         "0.53 x the bytes)")
+    p.add_argument("--num_samples", type=int, default=1,
+                   help="continuations per prompt (> 1: one prefill per prompt, its rows share the prompt's cache; "
+                        "prompts x num_samples <= 64)")
     return p.parse_args(argv)
 
 
@@ -87,6 +96,19 @@ def main(argv=None) -> int:
     model = load_model(a.checkpoint, a.model)
     pen = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
                frequency_penalty=a.frequency_penalty, kv_dtype=a.kv_dtype)
+    if a.num_samples > 1:
+        if a.draft_tokens is not None and a.sampler != "device":
+            raise SystemExit("--draft_tokens compares drafts with the device sampler's draws: --sampler device")
+        how = (dict(seed=a.seed, draft_tokens=a.draft_tokens) if a.sampler == "device"
+               else dict(generator=torch.Generator(device="cuda:0").manual_seed(a.seed)))
+        out = model.generate([torch.tensor(q, dtype=torch.int64, device="cuda:0") for q in prompts], a.max_new_tokens,
+                             temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, eos_token_id=a.eos_token_id,
+                             num_samples=a.num_samples, **how, **pen)
+        made = out.size(1) - max(len(q) for q in prompts)
+        for r, row in enumerate(out.tolist()):
+            b, j = divmod(r, a.num_samples)
+            print(json.dumps({"prompt": b, "sample": j, "tokens": row[:len(prompts[b]) + made]}))
+        return 0
     if len(prompts) > 1:
         if a.sampler != "device" and a.temperature != 0:
             raise SystemExit("several prompts are served by generate_many, which draws on the device: --sampler device")

@@ -283,6 +283,55 @@ def _check_model(model):
     return eng
 
 
+class ShareGroups:
+    """Which rows of a session share a prompt: the bookkeeping of ``DecodeSession.fork``, pure host logic.
+
+    A share group is a set of rows and a length ``shared_len``: every member's cache holds identical bits at positions
+    ``[0, shared_len)`` (with fp8 the codes and the scales). A row is in at most one group. ``group[b]`` is the lowest
+    member of b's group, or b when b is alone; ``length[b]`` is the group's shared length, or 0 when b is alone: the
+    two host arrays gpt2mi_decode_plan.share_group / share_len point at (include/gpt2mi.h, v24)."""
+
+    def __init__(self, B: int):
+        self.B = int(B)
+        self.clear()
+
+    def clear(self) -> None:
+        """Dissolve every group (``prefill``, ``reset``)."""
+        self.group, self.length = list(range(self.B)), [0] * self.B
+
+    def members(self, b: int) -> List[int]:
+        return [m for m in range(self.B) if self.group[m] == self.group[b]]
+
+    @property
+    def any(self) -> bool:
+        return any(self.length)
+
+    def leave(self, b: int) -> None:
+        """Take row b out of its group (``refill``, a ``fork`` destination): if b was the lowest member the next lowest
+        becomes the source, and a group left with one member dissolves."""
+        rest = [m for m in self.members(b) if m != b]
+        self.group[b], self.length[b] = b, 0
+        if len(rest) == 1:
+            self.group[rest[0]], self.length[rest[0]] = rest[0], 0
+        else:
+            for m in rest:
+                self.group[m] = rest[0]
+
+    def fork(self, src: int, dst_rows: Sequence[int], src_len: int, share: bool = True) -> None:
+        """``dst_rows`` have become copies of ``src``'s first ``src_len`` positions. Each first leaves its group; with
+        ``share`` they then join src's group at its length, or, src being alone, form a new group with it at
+        ``src_len``."""
+        for d in dst_rows:
+            self.leave(d)
+        if not share:
+            return
+        old = self.members(src)
+        n = self.length[src] if len(old) > 1 else src_len
+        rows = sorted(set(old) | set(dst_rows))
+        for m in rows if len(rows) > 1 else ():  # (no destinations: src stays as it is)
+            self.group[m], self.length[m] = rows[0], n
+
+
 class DecodeSession:
     """The key/value cache of ``batch_size`` sequences of up to ``max_len`` tokens, and the step that extends them.
 
@@ -297,7 +346,13 @@ class DecodeSession:
     logits ``[B, V]`` of the newest position. ``lens`` (a host list of B ints) is the number of cached tokens of each
     row; ``pos`` is their common value (None while the rows disagree: ``prefill`` with ``lens``, ``refill``). Every call
     goes through the per-row C entries (``gpt2mi_*_ragged``) with ``lens``, whether the rows agree or not: a row's bits
-    depend on its own position only."""
+    depend on its own position only.
+
+    ``fork(src, dst_rows)`` makes rows copies of another (several samples of one prompt). Every row still has a complete
+    cache of its own, so every method works on forked rows as on any other; what the session remembers (``share``, a
+    ``ShareGroups``) is which rows hold identical bits below which length, and ``step`` / ``generate`` hand that to the
+    attention kernel, which then reads those keys and values once per group (csrc/decode.hip attn_shared): the same
+    bits, fewer bytes. ``share_group`` / ``share_len`` are the two host arrays."""
 
     def __init__(self, model, batch_size: int, max_len: Optional[int] = None, kv_dtype: str = "bf16"):
         self.kv_format = check_kv_dtype(kv_dtype)
@@ -328,6 +383,8 @@ class DecodeSession:
         self._refill_ws = None            # (Tp, engine.Workspace) of the last refill's one-sequence prefill
         self._plan = self._build_plan({n: getattr(self, n) for n in SCRATCH}, 0)
         self._rows = None                 # (scratch of MAX_BATCH rows, its plan): extend / speculate, on first use
+        self.share = ShareGroups(self.B)
+        self._share_arrays = ((ctypes.c_int * self.B)(), (ctypes.c_int * self.B)())  # what the plan points at
 
     def _scratch(self, M: int) -> dict:
         """The buffers a step over M rows writes (gpt2mi_decode_plan's x .. logits)."""
@@ -416,6 +473,58 @@ class DecodeSession:
     def reset(self) -> None:
         """Rewind to an empty cache (the next call is ``prefill``)."""
         self.pos, self._drawn = 0, False
+        self.share.clear()
+        self._sync_share()
+
+    # ---- rows that share a prompt (gpt2mi_decode_plan.share_group / share_len) ----------------------------------------
+    @property
+    def share_group(self) -> List[int]:
+        return list(self.share.group)
+
+    @property
+    def share_len(self) -> List[int]:
+        return list(self.share.length)
+
+    def _sync_share(self) -> None:
+        """The step plan's view of ``share``: the two host arrays, or NULL while no row shares (v23's launches)."""
+        sg, sl = self._share_arrays
+        sg[:], sl[:] = self.share.group, self.share.length
+        self._plan.set_share(*((sg, sl) if self.share.any else (None, None)))
+
+    @torch.no_grad()
+    def fork(self, src: int, dst_rows: Sequence[int], share: bool = True) -> None:
+        """Make every row of ``dst_rows`` a copy of row ``src``: its cache below ``lens[src]`` (with fp8 codes and
+        scales), its logits and its length. Several samples of one prompt then cost one prefill (``refill(src)``, then
+        one ``fork``), and with ``share`` the rows form a share group, whose shared keys and values every later ``step``
+        / ``generate`` reads once per group. A token ``generate`` drew and has not stepped is stepped first (``flush``).
+
+        ``src`` alone: ``src`` and ``dst_rows`` form a new group with ``shared_len = lens[src]``; ``src`` already in a
+        group: ``dst_rows`` join it at that group's length (a copy of ``src`` agrees with every member below it). A
+        destination first leaves the group it was in. ``share=False`` copies and leaves the destinations alone (the
+        baseline of tools/share_bench.py and of the equality tests). The copies are torch indexing on the cache tensors:
+        once per prompt, not a hot path. ``ValueError``: ``src`` in ``dst_rows``, a row outside [0, B), duplicates in
+        ``dst_rows``, ``lens[src] == 0``."""
+        src, dst = int(src), [int(d) for d in dst_rows]
+        if not all(0 <= r < self.B for r in [src] + dst):
+            raise ValueError(f"fork rows src={src}, dst_rows={dst} not all in [0, B={self.B})")
+        if src in dst:
+            raise ValueError(f"fork: src={src} is among dst_rows={dst}")
+        if len(set(dst)) != len(dst):
+            raise ValueError(f"fork: duplicates in dst_rows={dst}")
+        if self.lens[src] == 0:
+            raise ValueError(f"fork: row src={src} is empty (lens[src] == 0): prefill or refill it first")
+        self.flush()
+        n = self.lens[src]
+        if dst:
+            at = torch.tensor(dst, device=self.device)
+            for t in (self.kcache, self.vcache, self.kscale, self.vscale):
+                if t is not None:  # [L][B][H][Tcap](...): the rows `at` of dim 1, positions below n
+                    t[:, at, :, :n] = t[:, src:src + 1, :, :n]
+            self.logits[at] = self.logits[src].clone()  # (torch refuses a source inside the written tensor)
+            for d in dst:
+                self.lens[d] = n
+        self.share.fork(src, dst, n, share)
+        self._sync_share()
 
     @torch.no_grad()
     def prefill(self, idx: torch.Tensor, lens: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -442,6 +551,8 @@ class DecodeSession:
         if not idx.is_cuda:
             raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
         self._ready(True)
+        self.share.clear()
+        self._sync_share()
         eng.gemm_sched = eng.base_sched
         idx_p, _, _ = eng._pad(idx, None)
         B, Tp = idx_p.shape
@@ -493,6 +604,8 @@ class DecodeSession:
             raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
         self.flush()
         self._ready(True)
+        self.share.leave(int(row))  # (after the flush: that step still reads the row as a member)
+        self._sync_share()
         eng.gemm_sched = eng.base_sched
         row, P = int(row), prompt.numel()
         idx_p, _, _ = eng._pad(prompt.view(1, P), None)
@@ -872,9 +985,12 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
              top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens: Optional[Sequence[int]] = None,
              pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None, draft_fn=None,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-             frequency_penalty: float = 0.0, kv_dtype: str = "bf16") -> torch.Tensor:
+             frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1) -> torch.Tensor:
     """``GPT2.generate``: see there."""
     check_kv_dtype(kv_dtype)
+    s = int(num_samples)
+    if s < 1:
+        raise ValueError(f"num_samples must be >= 1 (got {num_samples})")
     penalties = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
     pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
     if isinstance(idx, (list, tuple)):
@@ -884,6 +1000,15 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
     if idx.dim() != 2:
         raise ValueError(f"generate takes idx [B, P] (got {tuple(idx.shape)})")
     B, P = idx.shape
+    if s > 1:  # row b * s + j is sample j of prompt b; from here on B is the number of rows
+        if B * s > MAX_BATCH:
+            raise ValueError(f"{B} prompts x num_samples={s} = {B * s} rows exceed the {MAX_BATCH} rows of a decode "
+                             f"session (MAX_BATCH)")
+        idx = idx.repeat_interleave(s, dim=0)
+        if prompt_lens is not None:
+            prompt_lens = [int(m) for m in (prompt_lens.tolist() if isinstance(prompt_lens, torch.Tensor)
+                                            else prompt_lens) for _ in range(s)]
+        B *= s
     n = int(max_new_tokens)
     if n < 0:
         raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
@@ -913,11 +1038,11 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
     if prompt_lens is None and n == 0:
         return idx.clone()
     return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad,
-                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype)
+                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype, s)
 
 
 def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad, draft=None,
-              penalties=(1.0, 0.0, 0.0, False), kv_dtype="bf16"):
+              penalties=(1.0, 0.0, 0.0, False), kv_dtype="bf16", samples=1):
     """The token loop of ``generate``: [B, P + m], row b = its prompt, its m new tokens from column lens[b] on, then
     ``pad`` (``lens`` None: every row holds P tokens and nothing is padded). m = n, or with eos the number of tokens by
     which every row has emitted it. Host sampler: new tokens are collected per step and scattered into the buffer that
@@ -937,7 +1062,13 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
         return seq
     idx = torch.where(cols[:, :P] < lens_t[:, None], idx, torch.zeros_like(idx))  # (a valid token id as padding)
     sess = DecodeSession(model, B, P + n, kv_dtype)
-    logits = sess.prefill(idx, lens)
+    if samples == 1:
+        logits = sess.prefill(idx, lens)
+    else:  # each distinct prompt once, by the prefill of one sequence generate_many uses, then copied to its samples
+        for b in range(0, B, samples):
+            sess.refill(b, idx[b, :P if lens is None else lens[b]])
+            sess.fork(b, range(b + 1, b + samples))
+        logits = sess.logits[:, :model.config.vocab_size].clone()
     rp, pp, fp, on = penalties
     pen = _penalty_keywords(penalties, lens_t.tolist())
     if seed is not None:

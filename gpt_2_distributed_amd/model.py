@@ -348,7 +348,7 @@ class GPT2(nn.Module):
                  top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens=None,
                  pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None,
                  draft_fn=None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0, kv_dtype: str = "bf16") -> torch.Tensor:
+                 frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1) -> torch.Tensor:
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
         filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
@@ -390,6 +390,15 @@ class GPT2(nn.Module):
         the prompt's own attention runs unquantised in the trunk. The logits move by about the error of e4m3's 3
         mantissa bits (DESIGN.md "FP8 key/value cache"). Any other string raises ``ValueError``.
 
+        ``num_samples=s`` draws s continuations of every prompt (best-of-n, self-consistency): the result is
+        ``[B * s, P + n]``, prompt-major (row ``b * s + j`` is sample j of prompt b), and a row's draw key is its output
+        row number. Each distinct prompt is run once (``DecodeSession.refill`` into row ``b * s``) and copied to its
+        other rows (``DecodeSession.fork``); the rows of a prompt then form a share group, whose prompt keys and values
+        every step reads once for the group (DESIGN.md "Shared prompt cache"). Everything above works with it
+        (``draft_tokens`` verifies unshared). Without eos the result equals the continuations ``generate_many`` returns
+        for the list in which each prompt appears s times in a row, at ``batch_size = B * s`` with the same ``seed``.
+        ``B * s > 64`` raises ``ValueError``; ``num_samples=1`` is the call without it, on the same code path.
+
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
         the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
         ``NotImplementedError``. It does not advance the dropout stream or touch what a later backward needs, so a
@@ -400,7 +409,7 @@ class GPT2(nn.Module):
         from .generation import generate
         return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed,
                         prompt_lens, pad_token_id, draft_tokens, draft_fn, repetition_penalty, presence_penalty,
-                        frequency_penalty, kv_dtype)
+                        frequency_penalty, kv_dtype, num_samples)
 
     def generate_many(self, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                       top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define GPT2MI_ABI_VERSION 23
+#define GPT2MI_ABI_VERSION 24
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -311,6 +311,14 @@ typedef struct gpt2mi_decode_plan {
                                                              meant before) or GPT2MI_KV_FP8 (1): see the v23 block.
                                                              On LP64 it fills the former tail padding behind `rows`:
                                                              sizeof(gpt2mi_decode_plan) did not change */
+  const int* share_group;                                 /* v24, appended (no earlier offset moved; the struct grows
+                                                             by the two pointers): with share_len the share map of the
+                                                             v24 block, HOST arrays of B ints read during the call
+                                                             only. Both NULL (what a zeroed field means) is v23's
+                                                             behaviour, launch for launch. Read by gpt2mi_decode_step*
+                                                             and gpt2mi_decode_generate_ragged / _penalized; ignored by
+                                                             gpt2mi_decode_extend */
+  const int* share_len;
 } gpt2mi_decode_plan;
 /* embed -> per layer (LN1, qkv, attention at pos, proj + resid, LN2, fc1 + GELU, fc2 + resid) -> ln_f -> lm_head into
  * plan->logits, for the B tokens `tok` (device int64 [B]) at position pos (model.py:295-351 at one position). A
@@ -526,6 +534,32 @@ int gpt2mi_attn_decode_fp8_ragged(const uint16_t* qkv, uint8_t* kcache, uint8_t*
 int gpt2mi_attn_extend_fp8(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
                            uint16_t* out, float* workspace, size_t workspace_floats, int R, int B, int H, int head_dim,
                            int Tcap, const int* seq, const int* pos, void* stream);
+
+/* ---- v24: rows that share a prompt (csrc/decode.hip). Several continuations of one prompt sit in rows whose caches
+ * hold identical bits over the prompt (generation.py DecodeSession.fork); the step then reads those keys and values once
+ * per group of rows, not once per row.
+ * The share map is two HOST arrays of B ints beside the position array, checked with it before any launch:
+ * share_group[b] is the lowest row of b's group (b itself for a row alone) and share_len[b] the group's shared length (0
+ * for a row alone). The caller guarantees that every member's cache holds the bits of row share_group[b]'s at positions
+ * [0, share_len[b]), codes and scales with fp8. Both arrays NULL: no sharing, gpt2mi_attn_decode_ragged's launches.
+ * A range of 32 keys is shared when it lies wholly below share_len. One wave loads a shared range from the lowest row's
+ * stream once and computes, for each member of a chunk of the group in turn, that member's partial (max, sum, acc) with the
+ * operations and the order gpt2mi_attn_decode_ragged uses, into the member's own workspace slot; every row computes its
+ * ranges from share_len / 32 upward from its own stream as before, in the same launch; the combine is unchanged. out and
+ * the caches therefore have the bits of gpt2mi_attn_decode_ragged on the same inputs, and positions below
+ * 32 * (share_len / 32) of a member other than the lowest are not read. When no group has two members and a full shared
+ * range, the launches are gpt2mi_attn_decode_ragged's; so are those of a plan entry (not of the two entries below)
+ * while fewer than 16 rows are in such groups, where the shared form measured no faster: a launch choice, the same bits.
+ * Refused with 22 and a message naming the entry and the index, before any launch, beside gpt2mi_attn_decode_ragged's
+ * checks: exactly one of the two arrays NULL; share_group[b] outside [0, b]; share_group[share_group[b]] !=
+ * share_group[b]; share_len[b] < 0; share_len[b] > pos[b]; share_len[b] != share_len[share_group[b]]; share_len[b] != 0
+ * for a row alone in its group. The generate loops check the map against pos0. ---- */
+int gpt2mi_attn_decode_shared(const uint16_t* qkv, uint16_t* kcache, uint16_t* vcache, uint16_t* out, float* workspace,
+                              size_t workspace_floats, int B, int H, int head_dim, int Tcap, const int* pos,
+                              const int* share_group, const int* share_len, void* stream);
+int gpt2mi_attn_decode_shared_fp8(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
+                                  uint16_t* out, float* workspace, size_t workspace_floats, int B, int H, int head_dim,
+                                  int Tcap, const int* pos, const int* share_group, const int* share_len, void* stream);
 
 #ifdef __cplusplus
 }
