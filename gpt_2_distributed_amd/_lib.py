@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # the ABI these bindings are written against (include/gpt2mi.h GPT2MI_ABI_VERSION): a stale or foreign
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
+# additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
+ABI_MINOR = 1
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -27,6 +29,7 @@ _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_s
 _SIGS = {
     "gpt2mi_last_error": [],
     "gpt2mi_abi_version": [],
+    "gpt2mi_abi_minor": [],
     "gpt2mi_embed_fwd": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
     "gpt2mi_embed_bwd": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
     "gpt2mi_layernorm_fwd": [_p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_float, _p],
@@ -127,7 +130,15 @@ _SIGS = {
     "gpt2mi_attn_decode_shared": [_p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
     "gpt2mi_attn_decode_shared_fp8": [_p, _p, _p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _p, _p, _p,
                                       _p],
+    # v24.1 log-probabilities: gpt2mi_sample_penalized's list with (const gpt2mi_logprobs* lp) before the stream;
+    # gpt2mi_decode_generate_penalized's list with it at the end
+    "gpt2mi_sample_logprobs": [_p, _c_int, _c_int, _c_int, _c_float, _c_int, _c_float, _c_u64, _p, _p, ctypes.c_int64,
+                               _p, _p, _p, _c_int, _p, _p, _p, _p, _p],
+    "gpt2mi_decode_generate_logprobs": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _p, _p, _c_int,
+                                        _p, _p, _c_int, _p, _p, _c_float, _c_float, _c_float, _p, _p],
 }
+# the entries a library of minor m lacks: what came with a minor above m
+_SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size}
 
@@ -152,15 +163,21 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     return _lib
 
 
-def open_library(path: str) -> ctypes.CDLL:
-    """A build of the library at ``path``, typed and refused unless its C ABI is the bindings'."""
+def open_library(path: str, min_minor: int = ABI_MINOR) -> ctypes.CDLL:
+    """A build of the library at ``path``, typed and refused unless its C ABI is the bindings': the version equal, the
+    minor at least ``min_minor`` (a library from before the minor number existed has minor 0). An A/B tool that loads
+    an older build of the same version passes the minor it can do with; the entries that build lacks stay untyped."""
     lib = ctypes.CDLL(path)
+    minor = lib.gpt2mi_abi_minor() if hasattr(lib, "gpt2mi_abi_minor") else 0
+    if lib.gpt2mi_abi_version() != ABI_VERSION or minor < min_minor:
+        raise KernelError(f"{path} has C ABI v{lib.gpt2mi_abi_version()}.{minor}, the bindings expect v{ABI_VERSION}."
+                          f"{min_minor} or a later minor: rebuild it")
     for name, args in _SIGS.items():
+        if _SINCE_MINOR.get(name, 0) > minor:
+            continue
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = _RESTYPES.get(name, ctypes.c_int)
-    if lib.gpt2mi_abi_version() != ABI_VERSION:
-        raise KernelError(f"{path} has C ABI v{lib.gpt2mi_abi_version()}, the bindings expect v{ABI_VERSION}: rebuild it")
     return lib
 
 
@@ -757,3 +774,70 @@ def attn_decode_shared(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos, 
     else:
         _call("gpt2mi_attn_decode_shared_fp8", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale),
               _ptr(out), _ptr(workspace), workspace.numel(), B, H, D, Tcap, _positions(pos, B), sg, sl, _stream())
+
+
+# ---- v24.1: per-token log-probabilities from the sampler (csrc/sample.hip, csrc/decode.hip) ------------------
+LOGPROBS_MAX_TOP = 20  # gpt2mi.h GPT2MI_LOGPROBS_MAX_TOP
+
+
+class Logprobs(ctypes.Structure):
+    """gpt2mi_logprobs"""
+    _fields_ = [("logprob", _p), ("ld", _c_int), ("top_n", _c_int), ("top_id", _p), ("top_logprob", _p), ("col", _p)]
+
+
+def _logprobs_arg(logprob, top_ids, top_logprobs, col, B):
+    """(the gpt2mi_logprobs of the tensors, what must outlive the call); (None, None) for logprob None: lp = NULL.
+    logprob is fp32 [B, ld] (or [B]: ld 1), top_ids int32 / top_logprobs fp32 [B, ld, top_n], all contiguous."""
+    if logprob is None:
+        if top_ids is not None or top_logprobs is not None or col is not None:
+            raise KernelError("top_ids / top_logprobs / col go with logprob")
+        return None, None
+    ld = logprob.size(1) if logprob.dim() == 2 else 1
+    if logprob.dtype != torch.float32 or not logprob.is_contiguous() or logprob.numel() != B * ld:
+        raise KernelError(f"logprob must be a contiguous fp32 [B={B}, ld] (or [B]) tensor")
+    if (top_ids is None) != (top_logprobs is None):
+        raise KernelError("top_ids and top_logprobs go together")
+    n = 0 if top_ids is None else top_ids.size(-1)
+    if n and (top_ids.dtype != torch.int32 or top_logprobs.dtype != torch.float32 or not top_ids.is_contiguous()
+              or not top_logprobs.is_contiguous() or top_ids.numel() != B * ld * n or top_logprobs.numel() != B * ld * n):
+        raise KernelError(f"top_ids (int32) and top_logprobs (fp32) must be contiguous [B={B}, ld={ld}, top_n]")
+    cols = _host_ints(col)
+    if cols is not None and len(cols) != B:
+        raise KernelError(f"col has {len(cols)} entries for B={B} rows")
+    lp = Logprobs(_ptr(logprob), ld, n, _ptr(top_ids) if n else None, _ptr(top_logprobs) if n else None,
+                  ctypes.cast(cols, _p) if cols is not None else None)
+    return ctypes.byref(lp), (lp, cols)
+
+
+def sample_logprobs(logits, V, temperature, top_k, top_p, seed, pos, tok_out, logprob=None, top_ids=None,
+                    top_logprobs=None, col=None, row_id=None, eos=None, done=None, seq_out=None, probs_out=None,
+                    repetition=1.0, presence=0.0, frequency=0.0, hist=None, hist_row=None, gen_start=None,
+                    logits_out=None):
+    """gpt2mi_sample_logprobs: `sample_penalized`, and row b's raw log-probability of the token it draws into
+    logprob[b, col[b]] (col None: pos[b]), its top_n alternatives into top_ids / top_logprobs[b, col[b]]
+    (generation.token_logprobs). logprob None: lp = NULL, gpt2mi_sample_penalized itself under this entry's name."""
+    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
+    B = logits.size(0)
+    rows, starts = _host_ints(hist_row), _host_ints(gen_start)  # (kept alive to the end of the call)
+    if any(a is not None and len(a) != B for a in (rows, starts)):
+        raise KernelError(f"hist_row / gen_start must have B={B} entries")
+    pen = Penalties(float(repetition), float(presence), float(frequency), _ptr(hist),
+                    0 if hist is None else hist.stride(0), 0 if hist is None else hist.size(0),
+                    ctypes.cast(rows, _p) if rows is not None else None,
+                    ctypes.cast(starts, _p) if starts is not None else None)
+    lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, col, B)
+    _sample_call("gpt2mi_sample_logprobs", logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out,
+                 ctypes.byref(pen), _ptr(logits_out), lp)
+
+
+def decode_generate_logprobs(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, logprob=None,
+                             top_ids=None, top_logprobs=None, row_id=None, eos=None, seq=None, done=None, repetition=1.0,
+                             presence=0.0, frequency=0.0, gen_start=None):
+    """gpt2mi_decode_generate_logprobs: `decode_generate_penalized`, step i writing column pos0[b] + i of logprob /
+    top_ids / top_logprobs as it does of seq."""
+    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
+    if gen_start is not None and len(gen_start) != plan.B:
+        raise KernelError(f"gen_start has {len(gen_start)} entries for B={plan.B} rows")
+    lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, None, plan.B)
+    _generate_call("gpt2mi_decode_generate_logprobs", plan, V, scalars, pos0, n, tok, row_id, seq, done,
+                   float(repetition), float(presence), float(frequency), _host_ints(gen_start), lp)

@@ -34,6 +34,16 @@ void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 // the sampler's penalty values (gpt2mi.h v22), checked; *on = whether any of them is non-neutral (csrc/sample.hip)
 int check_penalty_values(const char* what, float repetition, float presence, float frequency, bool* on);
+// what of a gpt2mi_logprobs (gpt2mi.h v24.1) does not depend on the rows: top_n and the three pointers (csrc/sample.hip)
+int check_logprobs(const char* what, const gpt2mi_logprobs* lp, int V);
+// The launch of the LP sampling kernels (csrc/sample_lp.hip) for sample_rows of csrc/sample.hip, which has checked
+// everything: pos, row_id and col are B values each; pen is NULL when the penalties are neutral, else hist_row and
+// gen_start are B values too.
+int launch_sample_lp(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k,
+                     float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
+                     int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, const gpt2mi_penalties* pen,
+                     const int* hist_row, const int* gen_start, float* logits_out, const gpt2mi_logprobs* lp,
+                     const int* col, void* stream);
 
 // What a scalar-position entry hands to the per-row implementation: every row at `pos`. All GPT2MI_DECODE_MAX_B
 // entries are filled, so B is checked where the array is read and nowhere else.

@@ -1078,11 +1078,14 @@ GPT2MI_EXPORT int gpt2mi_decode_extend(const gpt2mi_decode_plan* P, int R, const
 
 namespace {
 // The token loop with row b starting at pos0[b]: sample, then (but for the last token) step, n times. With non-neutral
-// penalty values (gpt2mi_decode_generate_penalized) seq is the history the sampler reads, row b's own row of it.
+// penalty values (gpt2mi_decode_generate_penalized) seq is the history the sampler reads, row b's own row of it. With
+// `lp` (gpt2mi_decode_generate_logprobs; may be NULL) step i writes column pos0[b] + i of it: its col is NULL, the
+// sampler's "col[b] = pos[b]".
 int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
                          float top_p, uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
                          int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream, float repetition = 1.f,
-                         float presence = 0.f, float frequency = 0.f, const int* gen_start = nullptr) {
+                         float presence = 0.f, float frequency = 0.f, const int* gen_start = nullptr,
+                         const gpt2mi_logprobs* lp = nullptr) {
   GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
   GPT2MI_REQUIRE(V >= 1 && V <= P->Vp, "%s: V=%d not in [1, Vp=%d]", what, V, P->Vp);
   GPT2MI_REQUIRE(n >= 0, "%s: n=%d must be >= 0", what, n);
@@ -1108,12 +1111,21 @@ int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, f
     GPT2MI_REQUIRE((long long)max_pos + n - 1 <= GPT2MI_PENALTY_MAX_HISTORY,
                    "%s: max pos0=%d + n=%d - 1 above the history cap %d", what, max_pos, n, GPT2MI_PENALTY_MAX_HISTORY);
   }
+  if (lp) {
+    if (const int rc = gpt2mi::check_logprobs(what, lp, V)) return rc;
+    GPT2MI_REQUIRE(lp->col == nullptr, "%s: logprobs col must be NULL in the loop (step i writes column pos0[b] + i)",
+                   what);
+    GPT2MI_REQUIRE((long long)max_pos + n <= lp->ld, "%s: max pos0=%d + n=%d exceeds the logprobs ld=%d", what, max_pos,
+                   n, lp->ld);
+  }
   GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr, "%s: tok and plan->logits must not be NULL", what);
   if (const int rc = plan_shape(what, P)) return rc;  // (before the first draw, not only before the first step)
   for (int i = 0; i < n; ++i) {
     for (int b = 0; b < P->B; ++b) rp.v[b] = pos0[b] + i;
-    int rc = gpt2mi_sample_penalized(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos, done,
-                                     tok, seq, ld_seq, nullptr, on ? &pen : nullptr, nullptr, stream);
+    int rc = lp ? gpt2mi_sample_logprobs(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
+                                         done, tok, seq, ld_seq, nullptr, on ? &pen : nullptr, nullptr, lp, stream)
+                : gpt2mi_sample_penalized(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
+                                          done, tok, seq, ld_seq, nullptr, on ? &pen : nullptr, nullptr, stream);
     if (rc) return rc;
     if (i + 1 < n) {
       rc = decode_step_rows(what, P, tok, rp.v, stream);
@@ -1139,6 +1151,15 @@ GPT2MI_EXPORT int gpt2mi_decode_generate_penalized(const gpt2mi_decode_plan* P, 
                                                    float presence, float frequency, const int* gen_start) {
   return decode_generate_rows("decode_generate_penalized", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n,
                               tok, seq, ld_seq, done, stream, repetition, presence, frequency, gen_start);
+}
+
+GPT2MI_EXPORT int gpt2mi_decode_generate_logprobs(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
+                                                  float top_p, uint64_t seed, int64_t eos, const int* pos0,
+                                                  const uint32_t* row_id, int n, int64_t* tok, int64_t* seq, int ld_seq,
+                                                  uint8_t* done, void* stream, float repetition, float presence,
+                                                  float frequency, const int* gen_start, const gpt2mi_logprobs* lp) {
+  return decode_generate_rows("decode_generate_logprobs", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n,
+                              tok, seq, ld_seq, done, stream, repetition, presence, frequency, gen_start, lp);
 }
 
 GPT2MI_EXPORT int gpt2mi_decode_generate(const gpt2mi_decode_plan* P, int V, float temperature, int top_k, float top_p,

@@ -30,3 +30,4 @@ int check_launch(const char* what) {
 GPT2MI_EXPORT const char* gpt2mi_last_error(void) { return gpt2mi::g_err; }
 
 GPT2MI_EXPORT int gpt2mi_abi_version(void) { return GPT2MI_ABI_VERSION; }
+GPT2MI_EXPORT int gpt2mi_abi_minor(void) { return GPT2MI_ABI_MINOR; }

@@ -1,7 +1,7 @@
 """Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
 --prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B
 --draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F --kv_dtype {bf16,fp8}
---num_samples S]``.
+--num_samples S --logprobs [N]]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -14,7 +14,12 @@ through ``GPT2.generate_many`` (continuous batching on the device sampler, ``--b
 ``--num_samples S`` (S > 1) draws S continuations of every prompt through ``GPT2.generate(num_samples=S)``: each prompt
 is run once and its rows share its cache. One JSON object per sample is printed, prompt-major:
 ``{"prompt": b, "sample": j, "tokens": [...]}`` (the prompt's own padding, if the prompts differ in length, removed).
-``--batch`` is not used then; prompts x S <= 64."""
+``--batch`` is not used then; prompts x S <= 64.
+
+``--logprobs [N]`` makes every line a JSON object (``"tokens"`` as above) with ``"logprobs"``, the log-probability of each
+new token under the model's own distribution (before penalties, temperature and filters), and ``"cum_logprob"``, their
+sum; with N > 0 also ``"top_logprobs"``, per new token the N most likely ``[id, logprob]`` pairs. Without the flag the
+lines are what they were."""
 from __future__ import annotations
 
 import argparse
@@ -62,7 +67,22 @@ def parse_args(argv=None):
     p.add_argument("--num_samples", type=int, default=1,
                    help="continuations per prompt (> 1: one prefill per prompt, its rows share the prompt's cache; "
                         "prompts x num_samples <= 64)")
+    p.add_argument("--logprobs", type=int, nargs="?", const=0, default=None, metavar="N",
+                   help="print each new token's log-probability and their sum; N > 0 (<= 20): the N most likely tokens "
+                        "of each step as well")
     return p.parse_args(argv)
+
+
+def with_logprobs(line, out, row: int, first: int, last: int, top_n: int):
+    """``line`` (a dict, or a token list, which becomes ``{"tokens": ...}``) with the values of columns [first, last) of
+    row ``row`` of a ``generate(..., logprobs=)`` result."""
+    line = dict(line) if isinstance(line, dict) else {"tokens": line}
+    line["logprobs"] = out.logprobs[row, first:last].tolist()
+    line["cum_logprob"] = sum(line["logprobs"])
+    if top_n > 0:
+        line["top_logprobs"] = [[[i, v] for i, v in zip(ids, vals)] for ids, vals in
+                                zip(out.top_ids[row, first:last].tolist(), out.top_logprobs[row, first:last].tolist())]
+    return line
 
 
 def load_model(ckpt_dir: str, size: str) -> GPT2:
@@ -96,6 +116,8 @@ def main(argv=None) -> int:
     model = load_model(a.checkpoint, a.model)
     pen = dict(repetition_penalty=a.repetition_penalty, presence_penalty=a.presence_penalty,
                frequency_penalty=a.frequency_penalty, kv_dtype=a.kv_dtype)
+    if a.logprobs is not None:
+        pen["logprobs"] = a.logprobs
     if a.num_samples > 1:
         if a.draft_tokens is not None and a.sampler != "device":
             raise SystemExit("--draft_tokens compares drafts with the device sampler's draws: --sampler device")
@@ -104,10 +126,14 @@ def main(argv=None) -> int:
         out = model.generate([torch.tensor(q, dtype=torch.int64, device="cuda:0") for q in prompts], a.max_new_tokens,
                              temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, eos_token_id=a.eos_token_id,
                              num_samples=a.num_samples, **how, **pen)
+        res, out = out, (out if a.logprobs is None else out.tokens)
         made = out.size(1) - max(len(q) for q in prompts)
         for r, row in enumerate(out.tolist()):
             b, j = divmod(r, a.num_samples)
-            print(json.dumps({"prompt": b, "sample": j, "tokens": row[:len(prompts[b]) + made]}))
+            line = {"prompt": b, "sample": j, "tokens": row[:len(prompts[b]) + made]}
+            if a.logprobs is not None:
+                line = with_logprobs(line, res, r, len(prompts[b]), len(prompts[b]) + made, a.logprobs)
+            print(json.dumps(line))
         return 0
     if len(prompts) > 1:
         if a.sampler != "device" and a.temperature != 0:
@@ -115,8 +141,12 @@ def main(argv=None) -> int:
         outs = model.generate_many([torch.tensor(q, dtype=torch.int64, device="cuda:0") for q in prompts],
                                    a.max_new_tokens, batch_size=a.batch, temperature=a.temperature, top_k=a.top_k,
                                    top_p=a.top_p, seed=a.seed, eos_token_id=a.eos_token_id, **pen)
-        for row in outs:
-            print(json.dumps(row.tolist()))
+        for q, row in zip(prompts, outs):
+            if a.logprobs is None:
+                print(json.dumps(row.tolist()))
+            else:  # (a tuple of 1-D results: one row)
+                one = type(row)(*(t[None] for t in row))
+                print(json.dumps(with_logprobs(row.tokens.tolist(), one, 0, len(q), row.tokens.numel(), a.logprobs)))
         return 0
     prompt = prompts[0]
     idx = torch.tensor([prompt] * a.batch, dtype=torch.int64, device="cuda:0")
@@ -126,6 +156,10 @@ def main(argv=None) -> int:
            else dict(generator=torch.Generator(device="cuda:0").manual_seed(a.seed)))
     out = model.generate(idx, a.max_new_tokens, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
                          eos_token_id=a.eos_token_id, **how, **pen)
+    if a.logprobs is not None:
+        for r, row in enumerate(out.tokens.tolist()):
+            print(json.dumps(with_logprobs(row, out, r, len(prompt), len(row), a.logprobs)))
+        return 0
     for row in out.tolist():
         print(json.dumps(row))
     return 0

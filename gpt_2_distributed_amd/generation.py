@@ -19,6 +19,10 @@ A step appends one token per row. ``DecodeSession.extend`` appends several to a 
 steps; ``DecodeSession.speculate`` uses it to verify drafted tokens (``ngram_draft``, or any callable) and returns
 exactly the tokens of the device loop (DESIGN.md "Multi-token decode step").
 
+With ``logprobs=`` the device sampler also returns, from the launch that draws a token, the token's log-probability
+under the model's own distribution and the most likely alternatives (``gpt2mi_sample_logprobs``; ``token_logprobs`` is
+the rule, ``LogprobBuffer`` where a session puts them; DESIGN.md "Token log-probabilities").
+
 Numerics are the autocast path's whatever the autocast state: bf16 GEMM operands from the engine's weight shadow, fp32
 accumulation, fp32 residual stream / LayerNorm / softmax, dropout off (p = 0 whatever ``model.training`` is, and
 ``.training`` is not touched). Logits are fp32. ``model.precision == "fp32"`` has no decode kernels and raises.
@@ -31,7 +35,7 @@ forward re-allocates, and (b) it must not be called between a forward and its ba
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -192,6 +196,90 @@ def apply_penalties(logits: torch.Tensor, history: torch.Tensor, lens, gen_start
     if pp != 0.0:
         x = torch.where(count > 0, x - f32(pp), x)
     return x
+
+
+# ---- log-probabilities: the rule gpt2mi_sample_logprobs states beside the token it draws, executable -------------------
+def token_logprobs(logits: torch.Tensor, tokens: Optional[torch.Tensor] = None, top_n: int = 0):
+    """The raw model distribution's log-probabilities, in float64 (pure torch, any device): ``(logprob, top_ids,
+    top_logprobs)`` from logits [..., V]; what csrc/sample.hip computes beside a draw, and what the host sampler path
+    returns.
+
+    Per row of fp32 logits l: M = max l, S = sum exp(l_i - M), lse = M + log(S), logprob(i) = l_i - lse. The row is
+    the model's own: no penalty, temperature or top-k / top-p filter enters, so the value depends on the row and V only.
+    ``logprob`` [...] is that of ``tokens`` [...] (None without tokens). ``top_ids`` (int64) / ``top_logprobs``
+    [..., top_n] are the ``top_n`` largest l_i in descending order, equal values by ascending index; the order compares
+    the fp32 values and is exact, -inf entries come after every finite one, by index. NaN logits are outside the
+    contract, as in the sampler."""
+    V = logits.size(-1)
+    top_n = int(top_n)
+    if not 0 <= top_n <= V:
+        raise ValueError(f"top_n must lie in [0, V={V}] (got {top_n})")
+    l32 = logits.float()
+    l = l32.double()
+    M = l.max(-1, keepdim=True).values
+    lse = M + torch.log(torch.exp(l - M).sum(-1, keepdim=True))
+    logprob = None
+    if tokens is not None:
+        if tokens.shape != logits.shape[:-1]:
+            raise ValueError(f"tokens {tuple(tokens.shape)} must be one per row of logits {tuple(logits.shape)}")
+        logprob = (l.gather(-1, tokens.to(l.device).long()[..., None]) - lse)[..., 0]
+    # (a stable sort keeps equal values, -0 and +0 among them, in index order)
+    top_ids = torch.sort(l32, dim=-1, descending=True, stable=True).indices[..., :top_n]
+    return logprob, top_ids, l.gather(-1, top_ids) - lse
+
+
+class LogprobBuffer:
+    """Where ``DecodeSession.generate`` / ``speculate`` put log-probabilities, column-aligned with ``seq``: the value of
+    the token in ``seq[b, c]`` is ``logprob[b, c]`` (fp32 [B, T]) and its alternatives ``top_ids`` (int32) /
+    ``top_logprobs`` (fp32) ``[b, c, :top_n]``. Columns nothing wrote hold 0."""
+
+    def __init__(self, B: int, T: int, top_n: int = 0, device="cuda"):
+        top_n = int(top_n)
+        if not 0 <= top_n <= K.LOGPROBS_MAX_TOP:
+            raise ValueError(f"top_n must lie in [0, {K.LOGPROBS_MAX_TOP}] (GPT2MI_LOGPROBS_MAX_TOP; got {top_n})")
+        self.B, self.T, self.top_n = B, T, top_n
+        self.logprob = torch.zeros(B, T, dtype=F32, device=device)
+        self.top_ids = torch.zeros(B, T, top_n, dtype=torch.int32, device=device)
+        self.top_logprobs = torch.zeros(B, T, top_n, dtype=F32, device=device)
+
+    def tensors(self) -> dict:
+        """The sampler bindings' keywords."""
+        return dict(logprob=self.logprob, top_ids=self.top_ids if self.top_n else None,
+                    top_logprobs=self.top_logprobs if self.top_n else None)
+
+    def put(self, rows: Sequence[int], cols: Sequence[int], values, src: Sequence[int]) -> None:
+        """``[rows[i], cols[i]]`` = row ``src[i]`` of ``values`` = (logprob [R], top_ids [R, n], top_logprobs [R, n]):
+        index writes, nothing read back."""
+        dev = self.logprob.device
+        r, c, j = (torch.tensor(list(v), dtype=torch.int64, device=dev) for v in (rows, cols, src))
+        self.logprob[r, c] = values[0].to(dev)[j].float()
+        if self.top_n:
+            self.top_ids[r, c] = values[1].to(dev)[j].to(torch.int32)
+            self.top_logprobs[r, c] = values[2].to(dev)[j].float()
+
+    def clear(self, row: Optional[int] = None) -> None:
+        for t in (self.logprob, self.top_ids, self.top_logprobs):
+            (t if row is None else t[row]).zero_()
+
+
+class GenerateOutput(NamedTuple):
+    """``generate(..., logprobs=)``: the tokens it returns without, and per column the raw log-probability of a generated
+    token (0 in prompt and pad columns and after a row's eos) and its alternatives."""
+    tokens: torch.Tensor
+    logprobs: torch.Tensor
+    top_ids: torch.Tensor
+    top_logprobs: torch.Tensor
+
+
+def _check_logprobs(logprobs) -> Optional[int]:
+    """``logprobs=None | True | int`` of generate / generate_many as top_n (None: off)."""
+    if logprobs is None or logprobs is False:
+        return None
+    n = 0 if logprobs is True else int(logprobs)
+    if not 0 <= n <= K.LOGPROBS_MAX_TOP:
+        raise ValueError(f"logprobs must be None, True or an int in [0, {K.LOGPROBS_MAX_TOP}] alternatives per token "
+                         f"(got {logprobs!r})")
+    return n
 
 
 # ---- the fp8 key/value cache: the rule gpt2mi_kv_store_fp8 and the fp8 attention kernels quantise by, executable -------
@@ -683,22 +771,31 @@ class DecodeSession:
             raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
         return dict(repetition=rp, presence=pp, frequency=fp, gen_start=start)
 
-    def _draw(self, logits, pos, out, temperature, top_k, top_p, seed, pen: dict, hist=None, **kw) -> None:
+    def _draw(self, logits, pos, out, temperature, top_k, top_p, seed, pen: dict, hist=None, lp: Optional[dict] = None,
+              **kw) -> None:
         """One token per row of ``logits`` at ``pos`` into ``out``: gpt2mi_sample_ragged, or with ``pen`` (``_penalties``'
-        keywords, not empty) gpt2mi_sample_penalized over the history ``hist``. ``kw``: row_id, eos, done."""
-        if pen:
+        keywords, not empty) gpt2mi_sample_penalized over the history ``hist``. ``kw``: row_id, eos, done. With ``lp``
+        (logprob, top_ids, top_logprobs and optionally col) gpt2mi_sample_logprobs: the same draw and its values."""
+        if lp is not None:
+            K.sample_logprobs(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **lp, **kw,
+                              **({"hist": hist, **pen} if pen else {}))
+        elif pen:
             K.sample_penalized(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **kw,
                                **{"hist": hist, **pen})
         else:
             K.sample_ragged(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **kw)
 
-    def _loop(self, n: int, temperature, top_k, top_p, seed, pen: dict, **kw) -> None:
+    def _loop(self, n: int, temperature, top_k, top_p, seed, pen: dict, lp: Optional[dict] = None, **kw) -> None:
         """``n`` sample-then-step rounds from ``lens`` into ``_tok``: gpt2mi_decode_generate_ragged, or with ``pen``
-        gpt2mi_decode_generate_penalized. ``kw``: row_id, eos, seq, done."""
-        loop = K.decode_generate_penalized if pen else K.decode_generate_ragged
+        gpt2mi_decode_generate_penalized, or with ``lp`` (a LogprobBuffer's tensors) gpt2mi_decode_generate_logprobs.
+        ``kw``: row_id, eos, seq, done."""
+        if lp is not None:
+            kw = {**kw, **lp}
+        loop = K.decode_generate_logprobs if lp is not None else (K.decode_generate_penalized if pen
+                                                                  else K.decode_generate_ragged)
         loop(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n, self._tok, **kw, **pen)
 
-    def _check_run(self, n: int, row_id, eos_token_id, seq, done, penalties, gen_start):
+    def _check_run(self, n: int, row_id, eos_token_id, seq, done, penalties, gen_start, logprobs=None):
         """The argument checks ``generate`` and ``speculate`` share, then ``flush``; (row_id, done, pen) as checked:
         ``done`` is None without eos, ``pen`` is ``_penalties``' keywords over ``seq``."""
         row_id = _check_row_id(row_id, self.B)
@@ -709,6 +806,10 @@ class DecodeSession:
         if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
             raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
         pen = self._penalties(*penalties, gen_start, seq, "seq", max(self.lens) + int(self._drawn) + n - 1)
+        if logprobs is not None and (not isinstance(logprobs, LogprobBuffer) or logprobs.B != self.B
+                                     or logprobs.T < max(self.lens) + int(self._drawn) + n):
+            raise ValueError(f"logprobs must be a LogprobBuffer of B={self.B} rows and at least "
+                             f"{max(self.lens) + int(self._drawn) + n} columns")
         self.flush()  # the token the previous call ended on
         return row_id, done if eos_token_id is not None else None, pen
 
@@ -716,7 +817,7 @@ class DecodeSession:
     def sample(self, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                seed: int = 0, row_id: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
                presence_penalty: float = 0.0, frequency_penalty: float = 0.0, gen_start: Optional[Sequence[int]] = None,
-               history: Optional[torch.Tensor] = None) -> torch.Tensor:
+               history: Optional[torch.Tensor] = None, logprobs: Optional[int] = None):
         """Tokens [B] (int64, device) for position ``lens[b]`` from the logits of the last ``prefill`` / ``step``: one
         launch, no host synchronisation. Row b's token is a function of (its logits, the parameters, seed, its draw key,
         its position): ``sample_reference`` with ``uniform_at(seed, row_id[b], lens[b])``; ``row_id`` (B ints, default
@@ -724,23 +825,32 @@ class DecodeSession:
 
         With a non-neutral ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` the logits are first
         moved by ``apply_penalties`` over ``history[b, :lens[b]]`` (device int64 [B, T], required then: ``ValueError``
-        without), the generated part from ``gen_start[b]`` (default 0); ``logits`` itself is not modified."""
+        without), the generated part from ``gen_start[b]`` (default 0); ``logits`` itself is not modified.
+
+        ``logprobs=n`` (0 <= n <= 20) returns ``(tokens, logprob [B], top_ids [B, n], top_logprobs [B, n])``: the raw
+        distribution's values of ``token_logprobs``, from the same launch (gpt2mi_sample_logprobs); the tokens are those
+        of the call without."""
         self._check_sampler(temperature, top_p, seed)
         if self._drawn:
             raise RuntimeError("the logits are those generate() drew its last token from: step() that token first")
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, history, "history",
                               max(self.lens))
         out = torch.empty(self.B, dtype=torch.int64, device=self.logits.device)
+        if logprobs is None:
+            self._draw(self.logits, self.lens, out, temperature, top_k, top_p, seed, pen, history,
+                       row_id=_check_row_id(row_id, self.B))
+            return out
+        buf = LogprobBuffer(self.B, 1, logprobs, self.logits.device)
         self._draw(self.logits, self.lens, out, temperature, top_k, top_p, seed, pen, history,
-                   row_id=_check_row_id(row_id, self.B))
-        return out
+                   dict(buf.tensors(), col=[0] * self.B), row_id=_check_row_id(row_id, self.B))
+        return out, buf.logprob[:, 0], buf.top_ids[:, 0], buf.top_logprobs[:, 0]
 
     @torch.no_grad()
     def generate(self, n: int, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                  seed: int = 0, eos_token_id: Optional[int] = None, seq: Optional[torch.Tensor] = None,
                  done: Optional[torch.Tensor] = None, row_id: Optional[Sequence[int]] = None,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                 gen_start: Optional[Sequence[int]] = None) -> torch.Tensor:
+                 gen_start: Optional[Sequence[int]] = None, logprobs: Optional["LogprobBuffer"] = None) -> torch.Tensor:
         """Draw row b's tokens of positions ``lens[b] .. lens[b] + n - 1`` in one C call (gpt2mi_decode_generate_ragged:
         sample, step, sample, ... on the stream, no Python and no synchronisation in between). The tokens go to column
         ``lens[b] + i`` of ``seq`` (int64 [B, >= max(lens) + n], optional); with ``eos_token_id``, ``done`` (uint8 [B])
@@ -750,14 +860,20 @@ class DecodeSession:
 
         With non-neutral penalties (as for ``sample``) ``seq`` is the history and is required (``ValueError`` without):
         row b holds its tokens at ``seq[b, :lens[b]]`` on entry, prompt included, and the loop reads what it appends
-        (gpt2mi_decode_generate_penalized); ``gen_start[b]`` (default 0) is where the row's generated part begins."""
+        (gpt2mi_decode_generate_penalized); ``gen_start[b]`` (default 0) is where the row's generated part begins.
+
+        ``logprobs`` (a ``LogprobBuffer`` of B rows and as many columns as the call reaches) receives, in the column each
+        token goes to in ``seq``, the token's raw log-probability and alternatives (gpt2mi_decode_generate_logprobs: the
+        same launches with the sampling kernel's LP form, nothing more read back); a finished row's eos has 0."""
         self._check_sampler(temperature, top_p, seed)
         n = int(n)
         if n < 1:
             raise ValueError(f"generate takes n >= 1 (got {n})")
         row_id, done, pen = self._check_run(n, row_id, eos_token_id, seq, done,
-                                            (repetition_penalty, presence_penalty, frequency_penalty), gen_start)
-        self._loop(n, temperature, top_k, top_p, seed, pen, row_id=row_id, eos=eos_token_id, seq=seq, done=done)
+                                            (repetition_penalty, presence_penalty, frequency_penalty), gen_start,
+                                            logprobs)
+        self._loop(n, temperature, top_k, top_p, seed, pen, None if logprobs is None else logprobs.tensors(),
+                   row_id=row_id, eos=eos_token_id, seq=seq, done=done)
         self.lens = [m + n - 1 for m in self.lens]
         self._drawn = True
         return self._tok
@@ -821,12 +937,15 @@ class DecodeSession:
         self.logits.index_copy_(0, torch.tensor(dst, device=self.device),
                                 rows.index_select(0, torch.tensor(src, device=self.device)))
 
-    def _verify(self, toks: List[int], seqs: List[int], poss: List[int], keys: List[int], sampler) -> List[int]:
+    def _verify(self, toks: List[int], seqs: List[int], poss: List[int], keys: List[int], sampler,
+                logprobs: Optional[int] = None):
         """One ``gpt2mi_decode_extend`` over the rows (token, sequence, position) and one ``gpt2mi_sample_ragged`` over
         their logits, row r at position ``poss[r] + 1`` with draw key ``keys[r]``; the R tokens, read back.
 
         ``sampler`` is (temperature, top_k, top_p, seed) or, penalised, those and (the penalty keywords, seq): see
-        ``verify_history``."""
+        ``verify_history``. With ``logprobs=n`` the draw is gpt2mi_sample_logprobs into buffers of R rows and one
+        column (col 0, ld 1) and the result is (the tokens, (logprob [R], top_ids [R, n], top_logprobs [R, n])), the
+        values left on the device."""
         V = self.cfg.vocab_size
         if not all(0 <= t < V for t in toks):
             raise ValueError(f"draft tokens must lie in [0, vocab_size={V}) (got {toks})")
@@ -836,9 +955,14 @@ class DecodeSession:
         K.decode_extend(plan, tok_t, seqs, poss)
         out = torch.empty(R, dtype=torch.int64, device=self.device)
         temperature, top_k, top_p, seed = sampler[:4]
+        if logprobs is None:
+            self._draw(scratch["logits"][:R], [p + 1 for p in poss], out, temperature, top_k, top_p, seed,
+                       verify_history(sampler, tok_t, seqs, poss), row_id=keys)
+            return out.tolist()
+        buf = LogprobBuffer(R, 1, logprobs, self.device)
         self._draw(scratch["logits"][:R], [p + 1 for p in poss], out, temperature, top_k, top_p, seed,
-                   verify_history(sampler, tok_t, seqs, poss), row_id=keys)
-        return out.tolist()
+                   verify_history(sampler, tok_t, seqs, poss), lp=dict(buf.tensors(), col=[0] * R), row_id=keys)
+        return out.tolist(), (buf.logprob[:, 0], buf.top_ids[:, 0], buf.top_logprobs[:, 0])
 
     @torch.no_grad()
     def speculate(self, n: int, k: int, draft_fn=None, temperature: float = 1.0, top_k: Optional[int] = None,
@@ -846,7 +970,7 @@ class DecodeSession:
                   seq: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
                   row_id: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
                   presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                  gen_start: Optional[Sequence[int]] = None) -> dict:
+                  gen_start: Optional[Sequence[int]] = None, logprobs: Optional["LogprobBuffer"] = None) -> dict:
         """``generate(n, ...)`` with up to ``k`` drafted tokens of every row verified per pass over the weights: the same
         tokens in ``seq``, the same ``done`` flags and, with the last token drawn and not stepped, the same ``_tok``,
         ``lens`` and ``logits``, in fewer passes when the drafts are right. ``B * (k + 1) <= 64``.
@@ -869,7 +993,11 @@ class DecodeSession:
 
         Penalties as for ``generate`` (``seq`` required), and as exact: the verify call's row r draws at ``poss[r] + 1``
         from the history of its sequence up to and including the row's token (``_verify``), which is the history the
-        one-token loop has there."""
+        one-token loop has there.
+
+        ``logprobs`` as for ``generate``, with the same bits: the first draw and every verify call run the sampler's LP
+        form, an accepted row's value goes to its token's column and a rejected draft's is dropped with its token; the
+        columns after a row's eos hold 0."""
         n, k = int(n), int(k)
         if n < 1 or k < 0:
             raise ValueError(f"speculate takes n >= 1 and k >= 0 (got n={n}, k={k})")
@@ -877,15 +1005,22 @@ class DecodeSession:
             raise ValueError(f"B={self.B} rows of {k} drafts + 1 exceed the {MAX_BATCH} rows of a call")
         self._check_sampler(temperature, top_p, seed)
         row_id, done, pen = self._check_run(n, row_id, eos_token_id, seq, done,
-                                            (repetition_penalty, presence_penalty, frequency_penalty), gen_start)
+                                            (repetition_penalty, presence_penalty, frequency_penalty), gen_start,
+                                            logprobs)
         lens0 = list(self.lens)
-        self._draw(self.logits, self.lens, self._tok, temperature, top_k, top_p, seed, pen, seq, row_id=row_id,
-                   eos=eos_token_id, done=done)
+        if logprobs is not None:  # the call's columns: what no accepted row writes (after a row's eos) is 0
+            at = torch.arange(logprobs.T, device=self.device)[None] - torch.tensor(lens0, device=self.device)[:, None]
+            keep = (at < 0) | (at >= n)
+            for t in (logprobs.logprob, logprobs.top_ids, logprobs.top_logprobs):
+                t.masked_fill_(~keep if t.dim() == 2 else ~keep[..., None], 0)
+        self._draw(self.logits, self.lens, self._tok, temperature, top_k, top_p, seed, pen, seq,
+                   None if logprobs is None else logprobs.tensors(), row_id=row_id, eos=eos_token_id, done=done)
         first = self._tok.tolist()
         history = [[] for _ in range(self.B)] if seq is None else [r[:m] for r, m in zip(seq.tolist(), lens0)]
         keys = list(range(self.B)) if row_id is None else row_id
         new, stats = speculate_loop(self, n, k, draft_fn or ngram_draft, eos_token_id, history, first, keys,
-                                    (temperature, top_k, top_p, seed) + (((pen, seq),) if pen else ()))
+                                    (temperature, top_k, top_p, seed) + (((pen, seq),) if pen else ()),
+                                    **({} if logprobs is None else {"logprobs": logprobs}))
         self._tok.copy_(torch.tensor([t[-1] for t in new], dtype=torch.int64))
         self._drawn = True
         if eos_token_id is not None:
@@ -928,11 +1063,15 @@ def ngram_draft(history: List[int], k: int, max_ngram: int = 3) -> List[int]:
     return []
 
 
-def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first, keys, sampler):
+def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first, keys, sampler, logprobs=None):
     """The bookkeeping of ``DecodeSession.speculate`` over a session (anything with ``B``, ``lens``, ``_verify`` and
     ``_accept``): ``first[b]`` is row b's first token, drawn and not stepped. Returns (the tokens of each row: n of
     them, or fewer ending in eos; the stats). A draft counts as accepted iff it equals the token drawn before it and
-    that token is not eos; the row then advances by accepted + 1 and takes the logits row of its last accepted draft."""
+    that token is not eos; the row then advances by accepted + 1 and takes the logits row of its last accepted draft.
+
+    With ``logprobs`` (a ``LogprobBuffer``; the first tokens' values are in it already) ``_verify`` is asked for the
+    values too (``logprobs=top_n``, returning (tokens, values)); the value of the token drawn from row r belongs to
+    column ``poss[r] + 1`` of its sequence and is put there iff the token is taken."""
     B = sess.B
     new = [[int(first[b])] for b in range(B)]
     stats = dict(calls=0, drafted=0, accepted=0, tokens=0)
@@ -948,8 +1087,11 @@ def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first,
             spans.append((b, len(toks), drafts))
             for i, t in enumerate([new[b][-1]] + drafts):
                 toks.append(t), seqs.append(b), poss.append(sess.lens[b] + i), ks.append(keys[b])
-        drawn = sess._verify(toks, seqs, poss, ks, sampler)
-        src, dst = [], []
+        if logprobs is None:
+            drawn = sess._verify(toks, seqs, poss, ks, sampler)
+        else:
+            drawn, values = sess._verify(toks, seqs, poss, ks, sampler, logprobs=logprobs.top_n)
+        src, dst, taken = [], [], []
         for b, r0, drafts in spans:
             a = 0
             while a < len(drafts) and drafts[a] == drawn[r0 + a] != eos_token_id:
@@ -957,9 +1099,12 @@ def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first,
             new[b] += [int(t) for t in drawn[r0:r0 + a + 1]]
             sess.lens[b] += a + 1
             src.append(r0 + a), dst.append(b)
+            taken += range(r0, r0 + a + 1)
             stats["drafted"] += len(drafts)
             stats["accepted"] += a
         sess._accept(src, dst)
+        if logprobs is not None:
+            logprobs.put([seqs[r] for r in taken], [poss[r] + 1 for r in taken], values, taken)
         stats["calls"] += 1
     stats["tokens"] = sum(len(t) for t in new)
     return new, stats
@@ -985,9 +1130,10 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
              top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens: Optional[Sequence[int]] = None,
              pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None, draft_fn=None,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-             frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1) -> torch.Tensor:
+             frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1, logprobs=None):
     """``GPT2.generate``: see there."""
     check_kv_dtype(kv_dtype)
+    top_n = _check_logprobs(logprobs)
     s = int(num_samples)
     if s < 1:
         raise ValueError(f"num_samples must be >= 1 (got {num_samples})")
@@ -1036,20 +1182,32 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
     _check_model(model)
     idx = idx.long()
     if prompt_lens is None and n == 0:
-        return idx.clone()
+        return idx.clone() if top_n is None else _no_logprobs(idx.clone(), top_n)
     return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad,
-                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype, s)
+                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype, s, top_n)
+
+
+def _no_logprobs(tokens: torch.Tensor, top_n: int) -> GenerateOutput:
+    """``tokens`` with the values of columns nothing was generated in."""
+    shape, dev = tuple(tokens.shape), tokens.device
+    return GenerateOutput(tokens, torch.zeros(shape, dtype=F32, device=dev),
+                          torch.zeros(shape + (top_n,), dtype=torch.int32, device=dev),
+                          torch.zeros(shape + (top_n,), dtype=F32, device=dev))
 
 
 def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad, draft=None,
-              penalties=(1.0, 0.0, 0.0, False), kv_dtype="bf16", samples=1):
+              penalties=(1.0, 0.0, 0.0, False), kv_dtype="bf16", samples=1, top_n=None):
     """The token loop of ``generate``: [B, P + m], row b = its prompt, its m new tokens from column lens[b] on, then
     ``pad`` (``lens`` None: every row holds P tokens and nothing is padded). m = n, or with eos the number of tokens by
     which every row has emitted it. Host sampler: new tokens are collected per step and scattered into the buffer that
     holds the prompts; device sampler: gpt2mi_sample_ragged writes row b's token of step i to column lens[b] + i of it.
     ``penalties`` = (repetition, presence, frequency, any non-neutral): that buffer is then the history too, with the
     generated part starting at lens[b]; the host sampler writes each step's tokens into it as it goes and passes its
-    logits through apply_penalties."""
+    logits through apply_penalties.
+    ``top_n`` (None: off) returns a ``GenerateOutput``: the device sampler writes each token's log-probability and
+    ``top_n`` alternatives to the token's column of a ``LogprobBuffer``, the host sampler takes them from
+    ``token_logprobs`` of the step's logits, before the penalties; columns that hold no generated token (prompt, pad,
+    after a row's eos) are 0."""
     B, P = idx.shape
     dev = idx.device
     if eos_token_id is not None and seed is not None and not 0 <= eos_token_id < model.config.vocab_size:
@@ -1059,7 +1217,9 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     seq = torch.full((B, P + n), pad, dtype=torch.int64, device=dev)
     seq[:, :P] = torch.where(cols[:, :P] < lens_t[:, None], idx, seq[:, :P])  # the callers' padding may be anything
     if n == 0:
-        return seq
+        return seq if top_n is None else _no_logprobs(seq, top_n)
+    buf = None if top_n is None else LogprobBuffer(B, P + n, top_n, dev)
+    lp = {} if buf is None else {"logprobs": buf}
     idx = torch.where(cols[:, :P] < lens_t[:, None], idx, torch.zeros_like(idx))  # (a valid token id as padding)
     sess = DecodeSession(model, B, P + n, kv_dtype)
     if samples == 1:
@@ -1074,22 +1234,27 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     if seed is not None:
         done = None if eos_token_id is None else torch.zeros(B, dtype=torch.uint8, device=dev)
         if draft is None:
-            made = _device_loop(sess, n, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen)
+            made = _device_loop(sess, n, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen, **lp)
         else:  # (draft = (k, draft_fn): the same tokens, up to k + 1 of a row per pass over the weights)
-            sess.speculate(n, draft[0], draft[1], temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen)
+            sess.speculate(n, draft[0], draft[1], temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen, **lp)
             made = n
         if eos_token_id is None:
-            return seq
+            return seq if buf is None else GenerateOutput(seq, buf.logprob, buf.top_ids, buf.top_logprobs)
         new = seq.gather(1, lens_t[:, None] + torch.arange(made, device=dev)[None])
     else:
         toks = []
         done = torch.zeros(B, dtype=torch.bool, device=dev)
         for i in range(n):
+            raw = logits  # (the model's own row: what the log-probabilities are taken from)
             if on:
                 logits = apply_penalties(logits, seq, lens_t + i, lens_t, rp, pp, fp)
             nxt = sample_next(logits, temperature, top_k, generator, top_p)
             if eos_token_id is not None:
                 nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)  # a finished row keeps emitting eos
+            if buf is not None:  # (a row finished before this step: 0, as the device sampler writes)
+                live = list(range(B)) if eos_token_id is None else (~done).nonzero()[:, 0].tolist()
+                buf.put(live, [int(m) + i for m in lens_t[live].tolist()], token_logprobs(raw, nxt, top_n), live)
+            if eos_token_id is not None:
                 done = done | (nxt == eos_token_id)
             toks.append(nxt)
             if on:  # the next step's history
@@ -1106,13 +1271,22 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
         if bool(finished.any()):
             made = int(finished.int().argmax()) + 1
     keep = cols[:, :P + made] < (lens_t + made)[:, None]
-    return torch.where(keep, seq[:, :P + made], torch.full_like(seq[:, :P + made], pad))
+    tokens = torch.where(keep, seq[:, :P + made], torch.full_like(seq[:, :P + made], pad))
+    if buf is None:
+        return tokens
+    if eos_token_id is not None:  # a finished row's further columns: 0 in the alternatives as in the value
+        gen = cols[:, :P + made] >= lens_t[:, None]
+        keep = keep & ~(((tokens == eos_token_id) & gen).cumsum(1) - ((tokens == eos_token_id) & gen).long() > 0)
+    return GenerateOutput(tokens, *(torch.where(keep if t.dim() == 2 else keep[..., None], t[:, :P + made],
+                                                torch.zeros_like(t[:, :P + made]))
+                                    for t in (buf.logprob, buf.top_ids, buf.top_logprobs)))
 
 
 def _device_loop(sess: DecodeSession, n, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen) -> int:
     """``n`` tokens per row with the sampler on the device, into ``seq``; the number issued. Without eos one C call and
     nothing read back; with eos EOS_CHUNK tokens at a time, the done flags read once per chunk, until every row has
-    emitted it (the caller cuts the result after the column by which they all have)."""
+    emitted it (the caller cuts the result after the column by which they all have). ``pen``: the penalty keywords
+    and, with log-probabilities, ``logprobs``."""
     made = 0
     while made < n:
         m = n - made if eos_token_id is None else min(EOS_CHUNK, n - made)
@@ -1128,9 +1302,11 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
                   top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
                   eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                  frequency_penalty: float = 0.0, kv_dtype: str = "bf16") -> List[torch.Tensor]:
+                  frequency_penalty: float = 0.0, kv_dtype: str = "bf16", logprobs=None) -> list:
     """``GPT2.generate_many``: see there."""
     check_kv_dtype(kv_dtype)
+    top_n = _check_logprobs(logprobs)
+    lp = {} if top_n is None else {"logprobs": top_n}
     penalties = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
     if generator is not None:
         raise ValueError("generate_many draws on the device from (seed, prompt index, position): a torch.Generator is "
@@ -1152,16 +1328,17 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
     if eos_token_id is not None and not 0 <= eos_token_id < model.config.vocab_size:
         raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={model.config.vocab_size})")
     if not prompts or n == 0:
-        return [p.long().clone() for p in prompts]
+        return [p.long().clone() if top_n is None else _no_logprobs(p.long().clone(), top_n) for p in prompts]
     _check_model(model)
     # (at least a chunk and two positions, so that a dummy row of one token need not start over within a chunk)
     sess = DecodeSession(model, int(batch_size), min(model.config.n_positions, max(longest + n, EOS_CHUNK + 2)),
                          kv_dtype)
-    return serve_prompts(sess, [p.long() for p in prompts], n, temperature, top_k, top_p, seed, eos_token_id, penalties)
+    return serve_prompts(sess, [p.long() for p in prompts], n, temperature, top_k, top_p, seed, eos_token_id, penalties,
+                         **lp)
 
 
 def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, eos_token_id,
-                  penalties=(1.0, 0.0, 0.0, False)) -> List[torch.Tensor]:
+                  penalties=(1.0, 0.0, 0.0, False), logprobs: Optional[int] = None) -> list:
     """The loop of ``generate_many`` over a session (anything with DecodeSession's ``B``, ``Tcap``, ``lens``,
     ``device``, ``refill``, ``generate`` and ``flush``). Rows are slots: a slot holds prompt ``owner[row]`` (None: a
     dummy of one token whose output is dropped) and draws with ``row_id = owner[row]``. The device loop runs in chunks
@@ -1172,7 +1349,11 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
     ``penalties`` = (repetition, presence, frequency, any non-neutral). With them ``seq`` is the history the sampler
     reads: a slot's prompt is written to ``seq[row, :len]`` when it is filled (otherwise seq holds generated tokens only)
     and the generated part starts at the prompt's length. A row reads its own row below its own position only, so a
-    prompt's continuation still does not depend on what it is batched with."""
+    prompt's continuation still does not depend on what it is batched with.
+
+    ``logprobs=top_n`` (None: off) gives ``generate`` a ``LogprobBuffer`` beside ``seq``; a harvested prompt is then a
+    ``GenerateOutput`` cut where its tokens are cut (0 in the prompt's columns), and a slot's row of the buffer is
+    cleared when the slot is filled."""
     B, dev = sess.B, sess.device
     on = penalties[3]
     out: List[Optional[torch.Tensor]] = [None] * len(prompts)
@@ -1183,6 +1364,8 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
     done = torch.zeros(B, dtype=torch.uint8, device=dev)
     dummy = torch.zeros(1, dtype=torch.int64, device=dev)
     DUMMY_ID = 0xFFFFFFFF
+    buf = None if logprobs is None else LogprobBuffer(B, sess.Tcap, logprobs, dev)
+    lp = {} if buf is None else {"logprobs": buf}
 
     def fill(row):
         owner[row] = pending.pop() if pending else None
@@ -1192,6 +1375,8 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
         done[row] = 0
         if on:
             seq[row, :prompt.numel()] = prompt
+        if buf is not None:
+            buf.clear(row)
 
     for row in range(B):
         fill(row)
@@ -1201,7 +1386,7 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
             if owner[r] is None and sess.lens[r] + m + 1 > sess.Tcap:
                 fill(r)
         sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done,
-                      row_id=[DUMMY_ID if o is None else o for o in owner], **_penalty_keywords(penalties, start))
+                      row_id=[DUMMY_ID if o is None else o for o in owner], **_penalty_keywords(penalties, start), **lp)
         sess.flush()  # every row's logits are now those of its next position: a refilled row joins on equal terms
         host = torch.cat([done.to(torch.int64)[:, None], seq], dim=1).cpu()  # the one read of the chunk
         for r in range(B):
@@ -1214,5 +1399,10 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
                 if hits.numel():
                     new = new[:int(hits[0]) + 1]
             out[owner[r]] = torch.cat([prompts[owner[r]].to(dev), new.to(dev)])
+            if buf is not None:  # (device slices: nothing more is read back)
+                end = start[r] + new.numel()
+                out[owner[r]] = GenerateOutput(out[owner[r]], *(
+                    torch.cat([torch.zeros_like(t[r, :start[r]]), t[r, start[r]:end]])
+                    for t in (buf.logprob, buf.top_ids, buf.top_logprobs)))
             fill(r)
     return out

@@ -348,7 +348,7 @@ class GPT2(nn.Module):
                  top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens=None,
                  pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None,
                  draft_fn=None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1) -> torch.Tensor:
+                 frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1, logprobs=None):
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
         filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
@@ -399,6 +399,18 @@ class GPT2(nn.Module):
         for the list in which each prompt appears s times in a row, at ``batch_size = B * s`` with the same ``seed``.
         ``B * s > 64`` raises ``ValueError``; ``num_samples=1`` is the call without it, on the same code path.
 
+        ``logprobs=True`` or an int n in [0, 20] returns the named tuple ``(tokens, logprobs, top_ids, top_logprobs)``
+        in place of the tensor (``None``, the default: the tensor, as before). ``tokens`` is that tensor;
+        ``logprobs`` (fp32, its shape) holds each generated token's log-probability under the model's own
+        distribution, ``log_softmax`` of the logits row before penalties, temperature and filters (the OpenAI
+        convention; ``generation.token_logprobs`` is the rule), and 0 in prompt columns, pad columns and after a row's
+        eos, so ``out.logprobs.sum(1)`` is the continuation's log-likelihood and
+        ``out.logprobs.sum(1).view(B, s).argmax(1)`` the best of ``num_samples=s``. ``top_ids`` (int32) and
+        ``top_logprobs`` ``[rows, P + m, n]`` are the n most likely tokens of each such row, descending, equal values
+        by index. With ``seed`` the values come out of the sampling kernel, from the row it drew from: a function of
+        that logits row alone, so everything above holds for them bit for bit (batch independence, ``draft_tokens``,
+        ``num_samples``, ``kv_dtype``); the host sampler takes them from the same rule in float64.
+
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
         the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
         ``NotImplementedError``. It does not advance the dropout stream or touch what a later backward needs, so a
@@ -409,12 +421,13 @@ class GPT2(nn.Module):
         from .generation import generate
         return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed,
                         prompt_lens, pad_token_id, draft_tokens, draft_fn, repetition_penalty, presence_penalty,
-                        frequency_penalty, kv_dtype, num_samples)
+                        frequency_penalty, kv_dtype, num_samples, logprobs)
 
     def generate_many(self, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                       top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
                       eos_token_id: Optional[int] = None, generator=None, repetition_penalty: float = 1.0,
-                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0, kv_dtype: str = "bf16"):
+                      presence_penalty: float = 0.0, frequency_penalty: float = 0.0, kv_dtype: str = "bf16",
+                      logprobs=None):
         """Continue any number of 1-D ``prompts`` of any lengths by up to ``max_new_tokens`` tokens each; returns a list
         in input order, each entry the prompt plus its new tokens, cut after the first ``eos_token_id``.
 
@@ -430,10 +443,12 @@ class GPT2(nn.Module):
         ``max(len) + max_new_tokens > n_positions`` raises ``ValueError``. Training is left untouched as by
         ``generate``. ``repetition_penalty`` / ``presence_penalty`` / ``frequency_penalty`` as for ``generate``: a row's
         history is its own prompt and new tokens, so the guarantee holds with them. ``kv_dtype`` as for ``generate``: a
-        row of the fp8 cache is a function of that row's values alone, so the guarantee holds with it too."""
+        row of the fp8 cache is a function of that row's values alone, so the guarantee holds with it too.
+        ``logprobs`` as for ``generate``: each entry is then such a tuple for its prompt, cut where its tokens are cut;
+        the values are functions of the row's logits, so the guarantee covers them."""
         from .generation import generate_many
         return generate_many(self, prompts, max_new_tokens, batch_size, temperature, top_k, top_p, seed, eos_token_id,
-                             generator, repetition_penalty, presence_penalty, frequency_penalty, kv_dtype)
+                             generator, repetition_penalty, presence_penalty, frequency_penalty, kv_dtype, logprobs)
 
     # ---- optimizer (nanoGPT-style name the north star uses) -----------------------------------------
     def configure_optimizers(self, weight_decay: float = 0.1, learning_rate: float = 1e-4,

@@ -27,9 +27,12 @@ extern "C" {
 #endif
 
 #define GPT2MI_ABI_VERSION 24
+/* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
+#define GPT2MI_ABI_MINOR 1
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
+int gpt2mi_abi_minor(void);   /* returns GPT2MI_ABI_MINOR of the built library (v24.1; absent before) */
 
 /* K1: x[b,t,:] = drop(wte[idx[b,t],:] + wpe[t,:])  — model.py:295-304 (embedding, add, dropout).
  * Rows with t >= T_valid are sequence padding (T rounded up to the attention tile by the engine): x = 0
@@ -560,6 +563,45 @@ int gpt2mi_attn_decode_shared(const uint16_t* qkv, uint16_t* kcache, uint16_t* v
 int gpt2mi_attn_decode_shared_fp8(const uint16_t* qkv, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
                                   uint16_t* out, float* workspace, size_t workspace_floats, int B, int H, int head_dim,
                                   int Tcap, const int* pos, const int* share_group, const int* share_len, void* stream);
+
+/* ---- v24.1: per-token log-probabilities from the sampling kernel (csrc/sample_lp.hip, csrc/decode.hip). The executable
+ * specification is gpt_2_distributed_amd/generation.py token_logprobs.
+ * Per row of fp32 logits l[0 .. V): M = max l, S = sum exp(l_i - M), lse = M + log(S), logprob(i) = l_i - lse: the RAW
+ * model distribution, before penalties, the temperature division and top-k / top-p (the OpenAI convention, vLLM's
+ * default). lse is a function of the row's bits and V only (not of the sampler's values, the seed, the position, B or the
+ * kernel form): S is summed in a fixed order (per thread over its 50 registers, an xor butterfly, the 16 waves in order),
+ * no atomics, so two calls give the same bits. The top_n alternatives are the top_n largest l_i in descending order,
+ * equal values by ascending index (-0 and +0 are equal; -inf entries come last, by index); the order compares fp32
+ * values and is exact. NaN logits are outside the contract.
+ * The kernels are instantiations of the sampling kernel of their own (the others are compiled as before): lse and the
+ * alternatives are formed from the registers right after the load, the drawn token's raw logit is one load from the
+ * logits buffer at the end. A row whose done flag was set on entry gets eos and logprob 0; its alternatives are written
+ * like any row's. ---- */
+#define GPT2MI_LOGPROBS_MAX_TOP 20
+typedef struct gpt2mi_logprobs {
+  float* logprob;     /* device fp32 [B][ld]: row b's value goes to logprob[b*ld + col[b]] */
+  int ld;
+  int top_n;          /* 0 .. GPT2MI_LOGPROBS_MAX_TOP and <= V; 0: the two arrays below are not read */
+  int32_t* top_id;    /* device [B][ld][top_n] */
+  float* top_logprob; /* device [B][ld][top_n] */
+  const int* col;     /* HOST [B], may be NULL: col[b] = pos[b] */
+} gpt2mi_logprobs;
+/* gpt2mi_sample_penalized with the log-probabilities of what it draws. lp == NULL is gpt2mi_sample_penalized exactly
+ * (launches, bits, refusals); otherwise tok_out, seq_out, done, probs_out and logits_out have the bits of that call.
+ * col travels to the kernel by value. Refused with 22 and a message, before any launch, beside the forwarded checks:
+ * top_n outside [0, GPT2MI_LOGPROBS_MAX_TOP] or > V, a NULL logprob, top_n > 0 with a NULL top array, col[b] (pos[b]
+ * without col) outside [0, ld). */
+int gpt2mi_sample_logprobs(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
+                           uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
+                           int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out,
+                           const gpt2mi_penalties* pen, float* logits_out, const gpt2mi_logprobs* lp, void* stream);
+/* gpt2mi_decode_generate_penalized likewise (lp == NULL: that entry exactly). Step i writes column pos0[b] + i of row b,
+ * as it does in seq, so lp->col must be NULL; refused as well: max pos0 + n > lp->ld. */
+int gpt2mi_decode_generate_logprobs(const gpt2mi_decode_plan* plan, int V, float temperature, int top_k, float top_p,
+                                    uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
+                                    int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream,
+                                    float repetition, float presence, float frequency, const int* gen_start,
+                                    const gpt2mi_logprobs* lp);
 
 #ifdef __cplusplus
 }
