@@ -548,9 +548,26 @@ def gemm_skinny(epilogue, M, N, K, A, lda, W, ldw, C, ldc, bias=None, resid=None
           _ptr(workspace), ws_n, _stream())
 
 
-def kv_store(qkv, kcache, vcache, B, T_src, n, t0, H, D, Tcap):
-    """Copy the K / V columns of the first n rows of each sequence of qkv [B*T_src, 3C] to cache positions t0.."""
-    _call("gpt2mi_kv_store", _ptr(qkv), _ptr(kcache), _ptr(vcache), B, T_src, n, t0, H, D, Tcap, _stream())
+# The entries that take a key/value cache, and their forms over an fp8 cache (v23): the same list with
+# (kscale, vscale) behind (kcache, vcache).
+_FP8_ENTRY = {"gpt2mi_kv_store": "gpt2mi_kv_store_fp8", "gpt2mi_attn_decode_ragged": "gpt2mi_attn_decode_fp8_ragged",
+              "gpt2mi_attn_extend": "gpt2mi_attn_extend_fp8", "gpt2mi_attn_decode_shared": "gpt2mi_attn_decode_shared_fp8"}
+
+
+def _kv_call(name, qkv, kcache, vcache, kscale, vscale, *tail, fp8=None):
+    """Entry `name` on (qkv, the cache, *tail, the stream): over a bf16 cache, or with `fp8` (None: when either scale is
+    given, so half a pair is the C entry's NULL refusal and never a bf16 read of codes) its fp8 form over uint8 codes
+    [B][H][Tcap][64] and fp32 scales [B][H][Tcap] (generation.kv_quantize)."""
+    if fp8 is None:
+        fp8 = kscale is not None or vscale is not None
+    scales = (_ptr(kscale), _ptr(vscale)) if fp8 else ()
+    _call(_FP8_ENTRY[name] if fp8 else name, _ptr(qkv), _ptr(kcache), _ptr(vcache), *scales, *tail, _stream())
+
+
+def kv_store(qkv, kcache, vcache, B, T_src, n, t0, H, D, Tcap, kscale=None, vscale=None):
+    """Copy the K / V columns of the first n rows of each sequence of qkv [B*T_src, 3C] to cache positions t0.. (with
+    kscale / vscale: quantised, gpt2mi_kv_store_fp8)."""
+    _kv_call("gpt2mi_kv_store", qkv, kcache, vcache, kscale, vscale, B, T_src, n, t0, H, D, Tcap)
 
 
 def attn_decode_workspace(B, H, Tcap) -> int:
@@ -644,10 +661,10 @@ def _positions(pos, B):
     return _host_ints(pos)
 
 
-def attn_decode_ragged(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos):
-    """attn_decode with row b at pos[b] (a host sequence of B ints)."""
-    _call("gpt2mi_attn_decode_ragged", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(workspace),
-          workspace.numel(), B, H, D, Tcap, _positions(pos, B), _stream())
+def attn_decode_ragged(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos, kscale=None, vscale=None):
+    """attn_decode with row b at pos[b] (a host sequence of B ints); with kscale / vscale over an fp8 cache."""
+    _kv_call("gpt2mi_attn_decode_ragged", qkv, kcache, vcache, kscale, vscale, _ptr(out), _ptr(workspace),
+             workspace.numel(), B, H, D, Tcap, _positions(pos, B))
 
 
 def embed_decode_ragged(tok, wte, wpe, x, B, C, pos):
@@ -687,10 +704,11 @@ def decode_generate_ragged(plan: DecodePlan, V, temperature, top_k, top_p, seed,
 
 
 # ---- v21: several rows of a launch in one sequence (csrc/decode.hip) -----------------------------------
-def attn_extend(qkv, kcache, vcache, out, workspace, R, B, H, D, Tcap, seq, pos):
-    """gpt2mi_attn_extend: attention of R rows, row r at position pos[r] of sequence seq[r] (host sequences of R ints)."""
-    _call("gpt2mi_attn_extend", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(workspace), workspace.numel(),
-          R, B, H, D, Tcap, _positions(seq, R), _positions(pos, R), _stream())
+def attn_extend(qkv, kcache, vcache, out, workspace, R, B, H, D, Tcap, seq, pos, kscale=None, vscale=None):
+    """gpt2mi_attn_extend: attention of R rows, row r at position pos[r] of sequence seq[r] (host sequences of R ints);
+    with kscale / vscale over an fp8 cache."""
+    _kv_call("gpt2mi_attn_extend", qkv, kcache, vcache, kscale, vscale, _ptr(out), _ptr(workspace), workspace.numel(),
+             R, B, H, D, Tcap, _positions(seq, R), _positions(pos, R))
 
 
 def decode_extend(plan: DecodePlan, tok, seq, pos):
@@ -703,22 +721,22 @@ def decode_extend(plan: DecodePlan, tok, seq, pos):
 KV_BF16, KV_FP8 = 0, 1  # gpt2mi.h GPT2MI_KV_*: gpt2mi_decode_plan.kv_format
 
 
+# The fp8 names forward to _kv_call's fp8 form whatever the scales are, so a missing scale is the C entry's refusal.
 def kv_store_fp8(qkv, kcache, vcache, kscale, vscale, B, T_src, n, t0, H, D, Tcap):
     """kv_store into an fp8 cache: uint8 codes [B][H][Tcap][64] and fp32 scales [B][H][Tcap] (generation.kv_quantize)."""
-    _call("gpt2mi_kv_store_fp8", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale), B, T_src, n, t0, H,
-          D, Tcap, _stream())
+    _kv_call("gpt2mi_kv_store", qkv, kcache, vcache, kscale, vscale, B, T_src, n, t0, H, D, Tcap, fp8=True)
 
 
 def attn_decode_fp8_ragged(qkv, kcache, vcache, kscale, vscale, out, workspace, B, H, D, Tcap, pos):
     """attn_decode_ragged over an fp8 cache."""
-    _call("gpt2mi_attn_decode_fp8_ragged", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale), _ptr(out),
-          _ptr(workspace), workspace.numel(), B, H, D, Tcap, _positions(pos, B), _stream())
+    _kv_call("gpt2mi_attn_decode_ragged", qkv, kcache, vcache, kscale, vscale, _ptr(out), _ptr(workspace),
+             workspace.numel(), B, H, D, Tcap, _positions(pos, B), fp8=True)
 
 
 def attn_extend_fp8(qkv, kcache, vcache, kscale, vscale, out, workspace, R, B, H, D, Tcap, seq, pos):
     """attn_extend over an fp8 cache."""
-    _call("gpt2mi_attn_extend_fp8", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale), _ptr(out),
-          _ptr(workspace), workspace.numel(), R, B, H, D, Tcap, _positions(seq, R), _positions(pos, R), _stream())
+    _kv_call("gpt2mi_attn_extend", qkv, kcache, vcache, kscale, vscale, _ptr(out), _ptr(workspace), workspace.numel(),
+             R, B, H, D, Tcap, _positions(seq, R), _positions(pos, R), fp8=True)
 
 
 # ---- v22: penalties in the sampler (csrc/sample.hip, csrc/decode.hip) -----------------------------------
@@ -768,12 +786,8 @@ def attn_decode_shared(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos, 
     sg, sl = _host_ints(share_group), _host_ints(share_len)
     if any(a is not None and len(a) != B for a in (sg, sl)):
         raise KernelError(f"share_group / share_len must have B={B} entries")
-    if kscale is None:
-        _call("gpt2mi_attn_decode_shared", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(out), _ptr(workspace),
-              workspace.numel(), B, H, D, Tcap, _positions(pos, B), sg, sl, _stream())
-    else:
-        _call("gpt2mi_attn_decode_shared_fp8", _ptr(qkv), _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale),
-              _ptr(out), _ptr(workspace), workspace.numel(), B, H, D, Tcap, _positions(pos, B), sg, sl, _stream())
+    _kv_call("gpt2mi_attn_decode_shared", qkv, kcache, vcache, kscale, vscale, _ptr(out), _ptr(workspace),
+             workspace.numel(), B, H, D, Tcap, _positions(pos, B), sg, sl)
 
 
 # ---- v24.1: per-token log-probabilities from the sampler (csrc/sample.hip, csrc/decode.hip) ------------------

@@ -9,8 +9,9 @@
 // The attention of the step and of the multi-row extend are two __global__ entries over one body (attn_row). Their
 // gfx950 disassemblies (the Makefile's flags, -S) were compared with those of the two separate kernels they replace:
 // same registers, no scratch, occupancy 8; what differs is listed in DESIGN.md "Multi-token decode step".
-// The cache is bf16 or, since v23, fp8 (e4m3 codes and a power-of-two scale per 64-wide row): attn_row is templated on
-// the format and kv_store has a second kernel; the bf16 instantiations are instruction for instruction what they were.
+// The cache is bf16 or, since v23, fp8 (e4m3 codes and a power-of-two scale per 64-wide row). What differs between the
+// two is in one type per format (KvBf16, KvFp8: what a lane holds of a row and how it is loaded, formed, stored and
+// expanded); the store kernel, the attention bodies and their kernels are written once over that type.
 // Since v24 rows that hold the same prompt can share its keys and values: attn_row's arithmetic is attn_range, which a
 // second kind of wave (attn_shared) runs for several rows over one load; same bits (DESIGN.md "Shared prompt cache").
 #include <limits.h>
@@ -154,32 +155,6 @@ SkinnySplit skinny_split(int N, int K) {
   return s;
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Cache fill of the prefill: one thread per 16 bytes of the K and V columns of the n valid rows of each sequence.
-__global__ __launch_bounds__(256) void kv_store_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                       bf16* __restrict__ vc, int B, int T_src, int n, int t0, int H,
-                                                       int Tcap) {
-  const int C = H * 64, per_row = 2 * C / 8;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (size_t)B * n * per_row) return;
-  const int j = (int)(i % per_row);
-  const size_t row = i / per_row;
-  const int t = (int)(row % n), b = (int)(row / n);
-  const int col = 8 * j;  // in [0, 2C): K then V
-  const int which = col / C, c = col % C, h = c / 64, d = c % 64;
-  const bf16x8 v = *reinterpret_cast<const bf16x8*>(qkv + ((size_t)b * T_src + t) * 3 * C + C + col);
-  bf16* dst = (which ? vc : kc) + (((size_t)b * H + h) * Tcap + t0 + t) * 64 + d;
-  *reinterpret_cast<bf16x8*>(dst) = v;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Single-query attention. One wave per (range of 32 keys, b, h): lane (kk = lane / 8, dg = lane % 8) holds dims
-// 8 dg .. 8 dg + 7 of keys k0 + kk + 8 i, i < 4 (the 8 lanes of a key read its 128-byte row), so a K or V load of the
-// wave is 8 whole rows. The key at pos is the new token's: its lanes take k and v from qkv and write them to the
-// cache (no lane reads what another wrote). Scores in fp32, one softmax over the range, partial (max, sum, acc[64])
-// to the workspace; attn_combine_kernel merges the ranges in order.
-constexpr int AD_KEYS = 32;
-
 __device__ __forceinline__ void unpack8(bf16x8 v, float* f) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) f[j] = bf2f(v[j]);
@@ -190,7 +165,8 @@ __device__ __forceinline__ void unpack8(bf16x8 v, float* f) {
 // row of K or V is 64 OCP e4m3 codes and one fp32 scale 2^e, e the smallest exponent with amax <= 448 * 2^e and
 // >= -100. Scaling by a power of two is exact and |x * 2^-e| <= 448, so the conversion never saturates: the codes are
 // a pure function of the row's 64 bf16 values. This pair is the one quantiser and the one dequantiser of the file:
-// kv_store_fp8_kernel and attn_row both call it, so the two writers of a cache position cannot disagree.
+// KvFp8 below calls it for kv_store_kernel and for attn_row alike, so the two writers of a cache position cannot
+// disagree.
 struct KvRow8 {
   uint2 codes;  // this lane's 8 codes, dim 8 dg + j in byte j
   float scale;  // 2^e of the whole row
@@ -233,13 +209,78 @@ __device__ __forceinline__ void kv_dequantize8(const KvRow8& r, float* f) {
   for (int j = 0; j < 8; ++j) f[j] *= r.scale;
 }
 
-// kv_store_kernel's indexing with the rows quantised: the 8 threads of a (b, t, K or V, h) row are 8 adjacent lanes
-// (a row is 8 consecutive values of i and blocks start at multiples of 8). Threads beyond the last row take part in
-// the shuffles on row 0's values and store nothing.
-__global__ __launch_bounds__(256) void kv_store_fp8_kernel(const bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
-                                                           uint8_t* __restrict__ vc, float* __restrict__ ks,
-                                                           float* __restrict__ vs, int B, int T_src, int n, int t0,
-                                                           int H, int Tcap) {
+// ---------------------------------------------------------------------------------------------------------------
+// A cache tensor, the keys or the values of a layer as [stream][Tcap] rows of 64, in one of the two formats. Each type
+// says what lane dg of the 8 lanes of a row holds of it (dims 8 dg .. 8 dg + 7) and is the only code that knows how
+// such a row is zeroed, loaded from (stream, key), formed from the same dims of a qkv row, stored and expanded to fp32.
+// A row is stored in two steps: every lane `store`s its dims, and the dg == 0 lane alone calls `store_once` for what
+// the row holds once (the fp8 scale; nothing in bf16). The caller owns that branch so that a key and its value share
+// it: with a branch inside each store the compiler lays the stores of the second row out twice.
+// The store kernel and the attention below are written once over KV = KvBf16 or KvFp8; a kernel takes the keys and the
+// values as two of them, by value.
+
+// Lane dg's place in a stream, formed once per thread: its 8 dims of row `key` are elements at + 64 key .. + 7 of the
+// tensor, the row's scale (fp8) is element row0 + key of the scales.
+struct KvLane {
+  size_t at, row0;
+  __device__ __forceinline__ KvLane(size_t stream, int Tcap, int dg) : at(stream * Tcap * 64 + 8 * dg), row0(stream * Tcap) {}
+};
+
+struct KvBf16 {
+  using Row = bf16x8;
+  bf16* rows;  // [stream][Tcap][64]
+
+  static __device__ __forceinline__ Row zero() { return Row{0, 0, 0, 0, 0, 0, 0, 0}; }
+  static __device__ __forceinline__ Row from_qkv(bf16x8 x) { return x; }
+  __device__ __forceinline__ Row load(const KvLane& w, int key) const {
+    return *reinterpret_cast<const Row*>(rows + w.at + (size_t)key * 64);
+  }
+  __device__ __forceinline__ void store(const KvLane& w, int key, const Row& r) const {
+    *reinterpret_cast<Row*>(rows + w.at + (size_t)key * 64) = r;
+  }
+  __device__ __forceinline__ void store_once(const KvLane&, int, const Row&) const {}
+  // A key as 8 floats and the factor its score takes after the 8-lane sum; a value as 8 floats.
+  static __device__ __forceinline__ void key8(const Row& r, float* f) { unpack8(r, f); }
+  static __device__ __forceinline__ float score_scale(const Row&) { return 1.f; }
+  static __device__ __forceinline__ void value8(const Row& r, float* f) { unpack8(r, f); }
+};
+
+// A key or value is held as (8 codes, scale) whichever source it has: loaded that way, or quantised in registers by
+// kv_quantize8 (whose shuffles stay inside the 8 lanes of the row, which take a branch together), and stored as those
+// codes and that scale. Both are dequantised at the one place that uses them. A key's scale is
+// applied to its score after the sum (a power of two: the same bits as scaling the 64 products, short of underflow,
+// where a score is 0 either way); a value is code * scale before use, exactly.
+struct KvFp8 {
+  using Row = KvRow8;
+  uint8_t* codes;  // [stream][Tcap][64]
+  float* scales;   // [stream][Tcap]
+
+  static __device__ __forceinline__ Row zero() { return Row{uint2{0u, 0u}, 0.f}; }
+  static __device__ __forceinline__ Row from_qkv(bf16x8 x) {
+    float f[8];
+    unpack8(x, f);
+    return kv_quantize8(f);
+  }
+  __device__ __forceinline__ Row load(const KvLane& w, int key) const {
+    return Row{*reinterpret_cast<const uint2*>(codes + w.at + (size_t)key * 64), scales[w.row0 + key]};
+  }
+  __device__ __forceinline__ void store(const KvLane& w, int key, const Row& r) const {
+    *reinterpret_cast<uint2*>(codes + w.at + (size_t)key * 64) = r.codes;
+  }
+  __device__ __forceinline__ void store_once(const KvLane& w, int key, const Row& r) const {
+    scales[w.row0 + key] = r.scale;
+  }
+  static __device__ __forceinline__ void key8(const Row& r, float* f) { kv_codes8(r.codes, f); }
+  static __device__ __forceinline__ float score_scale(const Row& r) { return r.scale; }
+  static __device__ __forceinline__ void value8(const Row& r, float* f) { kv_dequantize8(r, f); }
+};
+
+// Cache fill of the prefill: one thread per 8 values of the K and V columns of the n valid rows of each sequence. The 8
+// threads of a (b, t, K or V, h) row are 8 adjacent lanes (a row is 8 consecutive values of i and blocks start at
+// multiples of 8), as from_qkv needs. Threads beyond the last row form row 0's values with them and store nothing.
+template <class KV>
+__global__ __launch_bounds__(256) void kv_store_kernel(const bf16* __restrict__ qkv, KV kc, KV vc, int B, int T_src,
+                                                       int n, int t0, int H, int Tcap) {
   const int C = H * 64, per_row = 2 * C / 8;
   const size_t at = (size_t)blockIdx.x * 256 + threadIdx.x;
   const bool live = at < (size_t)B * n * per_row;
@@ -249,14 +290,22 @@ __global__ __launch_bounds__(256) void kv_store_fp8_kernel(const bf16* __restric
   const int t = (int)(row % n), b = (int)(row / n);
   const int col = 8 * j;  // in [0, 2C): K then V
   const int which = col / C, c = col % C, h = c / 64, d = c % 64;
-  float f[8];
-  unpack8(*reinterpret_cast<const bf16x8*>(qkv + ((size_t)b * T_src + t) * 3 * C + C + col), f);
-  const KvRow8 q = kv_quantize8(f);
+  const typename KV::Row r =
+      KV::from_qkv(*reinterpret_cast<const bf16x8*>(qkv + ((size_t)b * T_src + t) * 3 * C + C + col));
   if (!live) return;
-  const size_t pos = ((size_t)b * H + h) * Tcap + t0 + t;
-  *reinterpret_cast<uint2*>((which ? vc : kc) + pos * 64 + d) = q.codes;
-  if (d == 0) (which ? vs : ks)[pos] = q.scale;
+  const KV& dst = which ? vc : kc;
+  const KvLane w((size_t)b * H + h, Tcap, d / 8);
+  dst.store(w, t0 + t, r);
+  if (d == 0) dst.store_once(w, t0 + t, r);
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Single-query attention. One wave per (range of 32 keys, b, h): lane (kk = lane / 8, dg = lane % 8) holds dims
+// 8 dg .. 8 dg + 7 of keys k0 + kk + 8 i, i < 4 (the 8 lanes of a key read its 128-byte row), so a K or V load of the
+// wave is 8 whole rows. The key at pos is the new token's: its lanes take k and v from qkv and write them to the
+// cache (no lane reads what another wrote). Scores in fp32, one softmax over the range, partial (max, sum, acc[64])
+// to the workspace; attn_combine_kernel merges the ranges in order.
+constexpr int AD_KEYS = 32;
 
 // A position per row: the host array of the C entry, validated there and passed by value as a kernel argument, so a
 // kernel never indexes memory with a position nobody checked. Indexed by blockIdx: scalar loads.
@@ -265,27 +314,24 @@ struct RowPos {
 };
 
 // The arithmetic of one (row, range) once its 32 keys and values are in registers, written once for attn_row and for
-// attn_shared below: q is the row's scaled query, the lane's key i is kv[i] / vv[i] (bf16) or k8[i] / v8[i] (fp8), and
-// the partial (max, sum, acc[64]) goes to workspace slot `slot`. Same operations in the same order whoever loaded the
-// keys: that is what makes a shared load bit-identical to the row's own.
-template <bool FP8>
-__device__ __forceinline__ void attn_range(const float* q, const bf16x8* kv, const bf16x8* vv, const KvRow8* k8,
-                                           const KvRow8* v8, float* __restrict__ ws_ml, float* __restrict__ ws_acc,
-                                           int range, int pos, size_t slot, int kk, int dg) {
+// attn_shared below: q is the row's scaled query, the lane's key i is kr[i] and its value vr[i], and the partial
+// (max, sum, acc[64]) goes to workspace slot `slot`. Same operations in the same order whoever loaded the keys: that is
+// what makes a shared load bit-identical to the row's own.
+template <class KV>
+__device__ __forceinline__ void attn_range(const float* q, const typename KV::Row* kr, const typename KV::Row* vr,
+                                           float* __restrict__ ws_ml, float* __restrict__ ws_acc, int range, int pos,
+                                           size_t slot, int kk, int dg) {
   float s[4], mx = -INFINITY;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     float kf[8], d = 0.f;
-    if constexpr (FP8)
-      kv_codes8(k8[i].codes, kf);
-    else
-      unpack8(kv[i], kf);
+    KV::key8(kr[i], kf);
 #pragma unroll
     for (int j = 0; j < 8; ++j) d = __builtin_fmaf(q[j], kf[j], d);
     d += __shfl_xor(d, 1, 64);
     d += __shfl_xor(d, 2, 64);
     d += __shfl_xor(d, 4, 64);
-    if constexpr (FP8) d *= k8[i].scale;
+    d *= KV::score_scale(kr[i]);
     s[i] = (range * AD_KEYS + kk + 8 * i <= pos) ? d : -INFINITY;
     mx = fmaxf(mx, s[i]);
   }
@@ -298,10 +344,7 @@ __device__ __forceinline__ void attn_range(const float* q, const bf16x8* kv, con
   for (int i = 0; i < 4; ++i) {
     const float p = __expf(s[i] - mx);  // 0 for a masked key
     float vf[8];
-    if constexpr (FP8)
-      kv_dequantize8(v8[i], vf);
-    else
-      unpack8(vv[i], vf);
+    KV::value8(vr[i], vf);
     l += p;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = __builtin_fmaf(p, vf[j], acc[j]);
@@ -330,25 +373,17 @@ __device__ __forceinline__ void attn_range(const float* q, const bf16x8* kv, con
 // consecutive positions and `first` is the position of the run's first row. The keys of this call are never read from
 // the cache: other waves of this launch are writing them. The row at position t alone writes k / v to position t of
 // its stream, so every position has one writer, and nothing above pos is read. The bits of a key are the same from
-// either source (the cache holds what the qkv row held), so a row gets the same bits whether its run is fed in one
-// call or one row per call. RUN = false is the run of one (first == pos, the only qkv row read is the row's own) as a
-// compile-time choice: from first == pos alone the compiler does not drop the row offset (pos - key) * 3C.
+// either source (the cache holds what KV::from_qkv makes of the qkv row, and a key of the call is held as exactly that),
+// so a row gets the same bits whether its run is fed in one call or one row per call. RUN = false is the run of one
+// (first == pos, the only qkv row read is the row's own) as a compile-time choice: from first == pos alone the compiler
+// does not drop the row offset (pos - key) * 3C.
 // A wave whose range starts beyond pos leaves before any load or store (wave-uniform: one wave per block, range and
 // row from blockIdx; the body has no barrier), so its workspace slot stays unwritten and attn_combine_kernel does not
 // read it. The workspace slot is that of row r, not of the sequence.
-//
-// FP8 = true is the body over the fp8 cache (kc / vc are the code bytes, ks / vs the scales [stream][Tcap]; FP8 = false
-// does not touch ks / vs and is the bf16 body unchanged). A key is then held as (8 codes, scale) whichever source it
-// has: a key below `first` is loaded that way, a key of the call is quantised in registers by kv_quantize8, the
-// quantiser of the store kernel, and the row at position t writes those codes and that scale. Both are dequantised at
-// the one place that uses them, so the invariant above holds as it stands: the bits of a key are the same from either
-// source. The key's scale is applied to its score after the sum (a power of two: the same bits as scaling the 64
-// products, short of underflow, where a score is 0 either way); a value is code * scale before use, exactly.
-template <bool RUN, bool FP8, class KV>
-__device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, KV* __restrict__ kc, KV* __restrict__ vc,
-                                         float* __restrict__ ks, float* __restrict__ vs, float* __restrict__ ws_ml,
-                                         float* __restrict__ ws_acc, int H, int Tcap, int nr_max, int r, size_t stream,
-                                         int pos, int first) {
+template <bool RUN, class KV>
+__device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, const KV& kc, const KV& vc,
+                                         float* __restrict__ ws_ml, float* __restrict__ ws_acc, int H, int Tcap,
+                                         int nr_max, int r, size_t stream, int pos, int first) {
   const int range = blockIdx.x, h = blockIdx.y;
   if (range * AD_KEYS > pos) return;
   const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
@@ -359,75 +394,42 @@ __device__ __forceinline__ void attn_row(const bf16* __restrict__ qkv, KV* __res
 #pragma unroll
   for (int j = 0; j < 8; ++j) q[j] *= 0.125f;  // 1/sqrt(64), exact
 
-  const size_t base = stream * Tcap * 64 + 8 * dg;
-  const bf16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
-  bf16x8 kv[4], vv[4];
-  KvRow8 k8[4], v8[4];  // FP8 only
+  const KvLane w(stream, Tcap, dg);
+  typename KV::Row kr[4], vr[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int key = range * AD_KEYS + kk + 8 * i;
-    if constexpr (FP8) {
-      k8[i] = v8[i] = KvRow8{uint2{0u, 0u}, 0.f};
-      if (key < first) {
-        k8[i].codes = *reinterpret_cast<const uint2*>(kc + base + (size_t)key * 64);
-        v8[i].codes = *reinterpret_cast<const uint2*>(vc + base + (size_t)key * 64);
-        k8[i].scale = ks[stream * Tcap + key];
-        v8[i].scale = vs[stream * Tcap + key];
-      } else if (RUN ? key <= pos : key == pos) {  // (the 8 lanes of a key agree: kv_quantize8's shuffles stay inside)
-        const bf16* src = RUN ? tok - (ptrdiff_t)(pos - key) * 3 * C : tok;  // the run's row at position key
-        float kf[8], vf[8];
-        unpack8(*reinterpret_cast<const bf16x8*>(src + C), kf);
-        unpack8(*reinterpret_cast<const bf16x8*>(src + 2 * C), vf);
-        k8[i] = kv_quantize8(kf);
-        v8[i] = kv_quantize8(vf);
-        if (!RUN || key == pos) {
-          *reinterpret_cast<uint2*>(kc + base + (size_t)key * 64) = k8[i].codes;
-          *reinterpret_cast<uint2*>(vc + base + (size_t)key * 64) = v8[i].codes;
-          if (dg == 0) {
-            ks[stream * Tcap + key] = k8[i].scale;
-            vs[stream * Tcap + key] = v8[i].scale;
-          }
-        }
-      }
-    } else {
-      kv[i] = zero;
-      vv[i] = zero;
-      if (key < first) {
-        kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
-        vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
-      } else if (RUN ? key <= pos : key == pos) {
-        const bf16* src = RUN ? tok - (ptrdiff_t)(pos - key) * 3 * C : tok;  // the run's row at position key
-        kv[i] = *reinterpret_cast<const bf16x8*>(src + C);
-        vv[i] = *reinterpret_cast<const bf16x8*>(src + 2 * C);
-        if (!RUN || key == pos) {
-          *reinterpret_cast<bf16x8*>(kc + base + (size_t)key * 64) = kv[i];
-          *reinterpret_cast<bf16x8*>(vc + base + (size_t)key * 64) = vv[i];
+    kr[i] = vr[i] = KV::zero();
+    if (key < first) {
+      kr[i] = kc.load(w, key);
+      vr[i] = vc.load(w, key);
+    } else if (RUN ? key <= pos : key == pos) {  // (the 8 lanes of a key agree)
+      const bf16* src = RUN ? tok - (ptrdiff_t)(pos - key) * 3 * C : tok;  // the run's row at position key
+      kr[i] = KV::from_qkv(*reinterpret_cast<const bf16x8*>(src + C));
+      vr[i] = KV::from_qkv(*reinterpret_cast<const bf16x8*>(src + 2 * C));
+      if (!RUN || key == pos) {
+        kc.store(w, key, kr[i]);
+        vc.store(w, key, vr[i]);
+        if (dg == 0) {
+          kc.store_once(w, key, kr[i]);
+          vc.store_once(w, key, vr[i]);
         }
       }
     }
   }
 
-  attn_range<FP8>(q, kv, vv, k8, v8, ws_ml, ws_acc, range, pos, (size_t)(r * H + h) * nr_max + range, kk, dg);
+  attn_range<KV>(q, kr, vr, ws_ml, ws_acc, range, pos, (size_t)(r * H + h) * nr_max + range, kk, dg);
 }
 
 // Grid (ranges, H, B): row b at rows.v[b] of its own cache stream; the x extent is that of the longest row. b is a grid
 // index of its own so that the position is one scalar load from the start of the wave: behind a division of a
 // (b, h) index by H every cache load waited for it.
-__global__ __launch_bounds__(64) void attn_decode_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
-                                                         float* __restrict__ ws_acc, int H, int Tcap, RowPos rows,
-                                                         int nr_max) {
+template <class KV>
+__global__ __launch_bounds__(64) void attn_decode_kernel(const bf16* __restrict__ qkv, KV kc, KV vc,
+                                                         float* __restrict__ ws_ml, float* __restrict__ ws_acc, int H,
+                                                         int Tcap, RowPos rows, int nr_max) {
   const int b = blockIdx.z, bh = b * H + blockIdx.y;  // (b < 64: int)
-  attn_row<false, false>(qkv, kc, vc, nullptr, nullptr, ws_ml, ws_acc, H, Tcap, nr_max, b, bh, rows.v[b], rows.v[b]);
-}
-
-__global__ __launch_bounds__(64) void attn_decode_fp8_kernel(const bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
-                                                             uint8_t* __restrict__ vc, float* __restrict__ ks,
-                                                             float* __restrict__ vs, float* __restrict__ ws_ml,
-                                                             float* __restrict__ ws_acc, int H, int Tcap, RowPos rows,
-                                                             int nr_max) {
-  const int b = blockIdx.z, bh = b * H + blockIdx.y;
-  attn_row<false, true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, b, bh, rows.v[b], rows.v[b]);
+  attn_row<false>(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, nr_max, b, bh, rows.v[b], rows.v[b]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -467,32 +469,21 @@ struct ShareMap {
 
 // The wave of chunk c: ranges below c_ranges[c] (all 32 keys below shared_len <= every member's pos: no key of this call,
 // no mask). The load is attn_row's `key < first` branch on the source row's stream.
-template <bool FP8, class KV>
-__device__ __forceinline__ void attn_shared(const bf16* __restrict__ qkv, const KV* __restrict__ kc,
-                                            const KV* __restrict__ vc, const float* __restrict__ ks,
-                                            const float* __restrict__ vs, float* __restrict__ ws_ml,
-                                            float* __restrict__ ws_acc, int H, int Tcap, int nr_max, const ShareMap& m,
-                                            int c) {
+template <class KV>
+__device__ __forceinline__ void attn_shared(const bf16* __restrict__ qkv, const KV& kc, const KV& vc,
+                                            float* __restrict__ ws_ml, float* __restrict__ ws_acc, int H, int Tcap,
+                                            int nr_max, const ShareMap& m, int c) {
   const int range = blockIdx.x, h = blockIdx.y;
   if (range >= m.c_ranges[c]) return;
   const int lane = threadIdx.x, kk = lane >> 3, dg = lane & 7;
   const int C = H * 64;
-  const size_t stream = (size_t)(m.c_src[c] * H + h);
-  const size_t base = stream * Tcap * 64 + 8 * dg;
-  bf16x8 kv[4], vv[4];
-  KvRow8 k8[4], v8[4];  // FP8 only
+  const KvLane w((size_t)(m.c_src[c] * H + h), Tcap, dg);
+  typename KV::Row kr[4], vr[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int key = range * AD_KEYS + kk + 8 * i;
-    if constexpr (FP8) {
-      k8[i].codes = *reinterpret_cast<const uint2*>(kc + base + (size_t)key * 64);
-      v8[i].codes = *reinterpret_cast<const uint2*>(vc + base + (size_t)key * 64);
-      k8[i].scale = ks[stream * Tcap + key];
-      v8[i].scale = vs[stream * Tcap + key];
-    } else {
-      kv[i] = *reinterpret_cast<const bf16x8*>(kc + base + (size_t)key * 64);
-      vv[i] = *reinterpret_cast<const bf16x8*>(vc + base + (size_t)key * 64);
-    }
+    kr[i] = kc.load(w, key);
+    vr[i] = vc.load(w, key);
   }
   // The members run one after the other, so a member's q is loaded while the one before it computes: the wave's time is
   // what a chunk costs, and a load's latency per member would be most of it.
@@ -510,32 +501,19 @@ __device__ __forceinline__ void attn_shared(const bf16* __restrict__ qkv, const 
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) q[e] *= 0.125f;
-    attn_range<FP8>(q, kv, vv, k8, v8, ws_ml, ws_acc, range, m.pos[r], (size_t)(r * H + h) * nr_max + range, kk, dg);
+    attn_range<KV>(q, kr, vr, ws_ml, ws_acc, range, m.pos[r], (size_t)(r * H + h) * nr_max + range, kk, dg);
   }
 }
 
 // Grid (ranges, H, B + chunks).
-__global__ __launch_bounds__(64) void attn_decode_shared_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                                bf16* __restrict__ vc, float* __restrict__ ws_ml,
-                                                                float* __restrict__ ws_acc, int H, int Tcap,
-                                                                ShareMap m, int nr_max) {
+template <class KV>
+__global__ __launch_bounds__(64) void attn_decode_shared_kernel(const bf16* __restrict__ qkv, KV kc, KV vc,
+                                                                float* __restrict__ ws_ml, float* __restrict__ ws_acc,
+                                                                int H, int Tcap, ShareMap m, int nr_max) {
   const int z = blockIdx.z;
-  if (z >= m.B) return attn_shared<false>(qkv, kc, vc, nullptr, nullptr, ws_ml, ws_acc, H, Tcap, nr_max, m, z - m.B);
+  if (z >= m.B) return attn_shared(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, nr_max, m, z - m.B);
   if ((int)blockIdx.x < m.own0[z]) return;
-  attn_row<false, false>(qkv, kc, vc, nullptr, nullptr, ws_ml, ws_acc, H, Tcap, nr_max, z, z * H + blockIdx.y, m.pos[z],
-                         m.pos[z]);
-}
-
-__global__ __launch_bounds__(64) void attn_decode_shared_fp8_kernel(const bf16* __restrict__ qkv,
-                                                                    uint8_t* __restrict__ kc, uint8_t* __restrict__ vc,
-                                                                    float* __restrict__ ks, float* __restrict__ vs,
-                                                                    float* __restrict__ ws_ml,
-                                                                    float* __restrict__ ws_acc, int H, int Tcap,
-                                                                    ShareMap m, int nr_max) {
-  const int z = blockIdx.z;
-  if (z >= m.B) return attn_shared<true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, m, z - m.B);
-  if ((int)blockIdx.x < m.own0[z]) return;
-  attn_row<false, true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, z, z * H + blockIdx.y, m.pos[z], m.pos[z]);
+  attn_row<false>(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, nr_max, z, z * H + blockIdx.y, m.pos[z], m.pos[z]);
 }
 
 // out[b, h*64 + d] = sum_r e^(m_r - m) acc_r[d] / sum_r e^(m_r - m) l_r over the pos[b] / 32 + 1 ranges of row b, in
@@ -567,23 +545,13 @@ struct RowMap {
 
 // Grid (ranges, H, R): several rows of one launch in the same sequence; the combine is attn_combine_kernel over R rows
 // at pos[r].
-__global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ kc,
-                                                         bf16* __restrict__ vc, float* __restrict__ ws_ml,
-                                                         float* __restrict__ ws_acc, int H, int Tcap, RowMap rows,
-                                                         int nr_max) {
+template <class KV>
+__global__ __launch_bounds__(64) void attn_extend_kernel(const bf16* __restrict__ qkv, KV kc, KV vc,
+                                                         float* __restrict__ ws_ml, float* __restrict__ ws_acc, int H,
+                                                         int Tcap, RowMap rows, int nr_max) {
   const int r = blockIdx.z;
-  attn_row<true, false>(qkv, kc, vc, nullptr, nullptr, ws_ml, ws_acc, H, Tcap, nr_max, r,
-                        (size_t)rows.seq[r] * H + blockIdx.y, rows.pos[r], rows.first[r]);
-}
-
-__global__ __launch_bounds__(64) void attn_extend_fp8_kernel(const bf16* __restrict__ qkv, uint8_t* __restrict__ kc,
-                                                             uint8_t* __restrict__ vc, float* __restrict__ ks,
-                                                             float* __restrict__ vs, float* __restrict__ ws_ml,
-                                                             float* __restrict__ ws_acc, int H, int Tcap, RowMap rows,
-                                                             int nr_max) {
-  const int r = blockIdx.z;
-  attn_row<true, true>(qkv, kc, vc, ks, vs, ws_ml, ws_acc, H, Tcap, nr_max, r, (size_t)rows.seq[r] * H + blockIdx.y,
-                       rows.pos[r], rows.first[r]);
+  attn_row<true>(qkv, kc, vc, ws_ml, ws_acc, H, Tcap, nr_max, r, (size_t)rows.seq[r] * H + blockIdx.y, rows.pos[r],
+                 rows.first[r]);
 }
 
 // One row per blockIdx.y, so that the row's position is a scalar load of the argument.
@@ -674,6 +642,15 @@ int kv_scales(const char* what, const KvCache& kv) {
   return 0;
 }
 
+// The one place that turns the format into the kernels' cache type: f(keys, values), as KvBf16 or as KvFp8.
+template <class F>
+void kv_typed(const KvCache& kv, F f) {
+  if (kv.format == GPT2MI_KV_FP8)
+    f(KvFp8{(uint8_t*)kv.k, kv.ks}, KvFp8{(uint8_t*)kv.v, kv.vs});
+  else
+    f(KvBf16{(bf16*)kv.k}, KvBf16{(bf16*)kv.v});
+}
+
 int kv_store_rows(const char* what, const uint16_t* qkv, const KvCache& kv, int B, int T_src, int n, int t0, int H,
                   int head_dim, int Tcap, void* stream) {
   GPT2MI_REQUIRE(head_dim == 64, "%s: head_dim=%d (the decode kernels implement 64)", what, head_dim);
@@ -685,12 +662,9 @@ int kv_store_rows(const char* what, const uint16_t* qkv, const KvCache& kv, int 
   GPT2MI_REQUIRE(qkv && kv.k && kv.v, "%s: qkv and the caches must not be NULL", what);
   const size_t total = (size_t)B * n * (2 * H * 64 / 8);
   const unsigned grid = (unsigned)((total + 255) / 256);
-  if (kv.format == GPT2MI_KV_FP8)
-    kv_store_fp8_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)qkv, (uint8_t*)kv.k, (uint8_t*)kv.v, kv.ks,
-                                                               kv.vs, B, T_src, n, t0, H, Tcap);
-  else
-    kv_store_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)qkv, (bf16*)kv.k, (bf16*)kv.v, B, T_src, n, t0,
-                                                           H, Tcap);
+  kv_typed(kv, [&](auto kc, auto vc) {
+    kv_store_kernel<<<grid, 256, 0, (hipStream_t)stream>>>((const bf16*)qkv, kc, vc, B, T_src, n, t0, H, Tcap);
+  });
   return gpt2mi::check_launch(what);
 }
 }  // namespace
@@ -785,12 +759,12 @@ using gpt2mi::SamePos;
 
 // The tail the two attention entries share, after their own row checks: M rows whose kernel argument is `rows`, at the
 // positions rp (the longest max_pos). The workspace is M * H * nr_max (max, sum) pairs, then as many acc[64].
-// `kernel` and `kernel8` are the entry's kernel over a bf16 and over an fp8 cache.
-template <class Rows>
-int attn_launch(const char* what, void (*kernel)(const bf16*, bf16*, bf16*, float*, float*, int, int, Rows, int),
-                void (*kernel8)(const bf16*, uint8_t*, uint8_t*, float*, float*, float*, float*, int, int, Rows, int),
-                const Rows& rows, const RowPos& rp, int max_pos, const uint16_t* qkv, const KvCache& kv, uint16_t* out,
-                float* workspace, size_t workspace_floats, int M, int H, int Tcap, void* stream, int extra_z = 0) {
+// `kernel` names the entry's kernel template: KV_KERNEL(name) gives name<KV> for the cache type it is shown.
+#define KV_KERNEL(name) [](auto kc) { return name<decltype(kc)>; }
+template <class Rows, class Kernel>
+int attn_launch(const char* what, Kernel kernel, const Rows& rows, const RowPos& rp, int max_pos, const uint16_t* qkv,
+                const KvCache& kv, uint16_t* out, float* workspace, size_t workspace_floats, int M, int H, int Tcap,
+                void* stream, int extra_z = 0) {
   const size_t need = gpt2mi_attn_decode_workspace(M, H, Tcap);
   GPT2MI_REQUIRE(workspace_floats >= need, "%s: workspace too small (%zu floats given, %zu needed)", what,
                  workspace_floats, need);
@@ -802,11 +776,9 @@ int attn_launch(const char* what, void (*kernel)(const bf16*, bf16*, bf16*, floa
   float* ws_ml = workspace;
   float* ws_acc = workspace + (size_t)M * H * nr_max * 2;
   const dim3 grid(max_pos / AD_KEYS + 1, H, M + extra_z);  // (extra_z: the chunks of a shared launch)
-  if (kv.format == GPT2MI_KV_FP8)
-    kernel8<<<grid, 64, 0, s>>>((const bf16*)qkv, (uint8_t*)kv.k, (uint8_t*)kv.v, kv.ks, kv.vs, ws_ml, ws_acc, H, Tcap,
-                                rows, nr_max);
-  else
-    kernel<<<grid, 64, 0, s>>>((const bf16*)qkv, (bf16*)kv.k, (bf16*)kv.v, ws_ml, ws_acc, H, Tcap, rows, nr_max);
+  kv_typed(kv, [&](auto kc, auto vc) {
+    kernel(kc)<<<grid, 64, 0, s>>>((const bf16*)qkv, kc, vc, ws_ml, ws_acc, H, Tcap, rows, nr_max);
+  });
   if (const int rc = gpt2mi::check_launch(what)) return rc;
   attn_combine_kernel<<<dim3(H, M), 64, 0, s>>>(ws_ml, ws_acc, (bf16*)out, H, rp, nr_max);
   return gpt2mi::check_launch(what);
@@ -817,10 +789,10 @@ int attn_decode_mapped(const char* what, const uint16_t* qkv, const KvCache& kv,
                        size_t workspace_floats, int B, int H, int Tcap, const RowPos& rp, int max_pos,
                        const ShareMap& sm, void* stream) {
   if (sm.chunks)  // some range is shared: the one launch that holds both kinds of wave
-    return attn_launch(what, attn_decode_shared_kernel, attn_decode_shared_fp8_kernel, sm, rp, max_pos, qkv, kv, out,
-                       workspace, workspace_floats, B, H, Tcap, stream, sm.chunks);
-  return attn_launch(what, attn_decode_kernel, attn_decode_fp8_kernel, rp, rp, max_pos, qkv, kv, out, workspace,
-                     workspace_floats, B, H, Tcap, stream);
+    return attn_launch(what, KV_KERNEL(attn_decode_shared_kernel), sm, rp, max_pos, qkv, kv, out, workspace,
+                       workspace_floats, B, H, Tcap, stream, sm.chunks);
+  return attn_launch(what, KV_KERNEL(attn_decode_kernel), rp, rp, max_pos, qkv, kv, out, workspace, workspace_floats, B,
+                     H, Tcap, stream);
 }
 
 // Each operation below is written once, for one position per row; `what` is the entry's name in its messages. The
@@ -941,9 +913,10 @@ int attn_extend_rows(const char* what, const uint16_t* qkv, const KvCache& kv, u
   if (const int rc = row_map(what, seq, pos, R, B, Tcap, &rm, &max_pos)) return rc;
   RowPos rp{};  // the combine is per row: row r merges its own pos[r] / 32 + 1 ranges
   std::copy_n(rm.pos, R, rp.v);
-  return attn_launch(what, attn_extend_kernel, attn_extend_fp8_kernel, rm, rp, max_pos, qkv, kv, out, workspace,
-                     workspace_floats, R, H, Tcap, stream);
+  return attn_launch(what, KV_KERNEL(attn_extend_kernel), rm, rp, max_pos, qkv, kv, out, workspace, workspace_floats, R,
+                     H, Tcap, stream);
 }
+#undef KV_KERNEL  // its three users are above
 
 // The launch list of a step over M rows at pos[m], shared by the step and the extend: they differ in the attention
 // (`attn`, called once per layer between the qkv and the proj GEMM) and in what they checked before.

@@ -513,12 +513,8 @@ class DecodeSession:
         """The K / V columns of the first P rows of each of qkv's B sequences of Tp rows into layer l's cache from
         position 0: every sequence of the session, or with ``row`` that one (B = 1)."""
         at = (l,) if row is None else (l, row)
-        H = self.cfg.n_head
-        if self.kv_format == K.KV_FP8:
-            K.kv_store_fp8(qkv, self.kcache[at], self.vcache[at], self.kscale[at], self.vscale[at], B, Tp, P, 0, H, 64,
-                           self.Tcap)
-        else:
-            K.kv_store(qkv, self.kcache[at], self.vcache[at], B, Tp, P, 0, H, 64, self.Tcap)
+        kc, vc, ks, vs = (t if t is None else t[at] for t in (self.kcache, self.vcache, self.kscale, self.vscale))
+        K.kv_store(qkv, kc, vc, B, Tp, P, 0, self.cfg.n_head, 64, self.Tcap, kscale=ks, vscale=vs)
 
     def _build_plan(self, scratch: dict, rows: int) -> K.DecodePlan:
         """The plan over the session's weights and caches with ``scratch`` as its buffers, holding ``rows`` rows (0: B)."""

@@ -13,7 +13,7 @@ import torch
 from gpt_2_distributed_amd import generation
 from gpt_2_distributed_amd.generation import ngram_draft, speculate_loop
 from tests.conftest import REPO
-from tests.test_kernel_resources import HIPCC, _resources
+from tests.test_kernel_resources import HIPCC, _instantiation, _resources
 
 LIB = os.path.join(REPO, "gpt_2_distributed_amd", "libgpt2mi.so")
 needs_lib = pytest.mark.skipif(not os.path.exists(LIB), reason="libgpt2mi.so not built (run __graft_entry__.build())")
@@ -313,8 +313,6 @@ def test_cli_takes_draft_tokens():
 @pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")
 def test_attn_extend_kernel_has_no_scratch_and_no_spills():
     """The row map arrives as a kernel argument and is indexed by blockIdx: scalar loads, not a private array."""
-    found = {k: v for k, v in _resources("decode.hip").items() if "attn_extend_kernel" in k}
-    assert len(found) == 1, sorted(found)
-    for k, v in found.items():
-        assert v["ScratchSize [bytes/lane]"] == 0, f"{k}: scratch {v}"
-        assert v["VGPRs Spill"] == 0, f"{k}: spills {v}"
+    k, v = _instantiation(_resources("decode.hip"), "attn_extend_kernel", "KvBf16")
+    assert v["ScratchSize [bytes/lane]"] == 0, f"{k}: scratch {v}"
+    assert v["VGPRs Spill"] == 0, f"{k}: spills {v}"

@@ -8,7 +8,7 @@ import torch
 
 from gpt_2_distributed_amd.generation import sample_next
 from tests.conftest import REPO
-from tests.test_kernel_resources import HIPCC, _resources
+from tests.test_kernel_resources import HIPCC, _instantiation, _resources
 
 LIB = os.path.join(REPO, "gpt_2_distributed_amd", "libgpt2mi.so")
 needs_lib = pytest.mark.skipif(not os.path.exists(LIB), reason="libgpt2mi.so not built (run __graft_entry__.build())")
@@ -167,9 +167,10 @@ def test_abi_is_v14_or_later_and_binds_the_decode_entries(lib):
 def test_decode_kernels_have_no_scratch_and_no_spills():
     """The streaming kernels keep their operands in registers: any scratch use is an HBM round trip per element."""
     kernels = _resources("decode.hip")
-    for sub in ("skinny_gemm_kernel", "skinny_reduce_kernel", "kv_store_kernel", "attn_decode_kernel",
-                "attn_combine_kernel", "embed_decode_kernel"):
+    for sub in ("skinny_gemm_kernel", "skinny_reduce_kernel", "attn_combine_kernel", "embed_decode_kernel"):
         assert any(sub in k for k in kernels), f"{sub} not found in decode.hip"
+    for family in ("kv_store_kernel", "attn_decode_kernel"):  # (templates over the cache type: the bf16 cache's)
+        _instantiation(kernels, family, "KvBf16")
     for k, v in kernels.items():
         assert v["ScratchSize [bytes/lane]"] == 0, f"{k}: scratch {v}"
         assert v["VGPRs Spill"] == 0, f"{k}: spills {v}"

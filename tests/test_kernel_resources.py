@@ -41,6 +41,14 @@ def _resources(src, extra=()):
     return kernels
 
 
+def _instantiation(kernels, family, fmt):
+    """The one instantiation of decode.hip's kernel template `family` over the cache type `fmt` (KvBf16 / KvFp8), as
+    (name, resources): the compiler's name of it holds both names."""
+    found = {k: v for k, v in kernels.items() if family in k and fmt in k}
+    assert len(found) == 1, f"{family}<{fmt}>: expected one kernel, found {sorted(found)}"
+    return next(iter(found.items()))
+
+
 @pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")
 @pytest.mark.parametrize("src", sorted(EXPECT))
 def test_no_scratch_and_occupancy(src):

@@ -12,7 +12,7 @@ import torch
 
 from gpt_2_distributed_amd.generation import check_kv_dtype, kv_dequantize, kv_quantize
 from tests.conftest import REPO
-from tests.test_kernel_resources import HIPCC, _resources
+from tests.test_kernel_resources import HIPCC, _instantiation, _resources
 
 LIB = os.path.join(REPO, "gpt_2_distributed_amd", "libgpt2mi.so")
 needs_lib = pytest.mark.skipif(not os.path.exists(LIB), reason="libgpt2mi.so not built (run __graft_entry__.build())")
@@ -304,9 +304,7 @@ def test_generate_entries_check_kv_format_before_the_first_draw(lib):
 @pytest.mark.skipif(not shutil.which(HIPCC) and not os.path.exists(HIPCC), reason="hipcc not available")
 def test_fp8_kernels_have_no_scratch_and_no_spills():
     kernels = _resources("decode.hip")
-    for sub in ("kv_store_fp8_kernel", "attn_decode_fp8_kernel", "attn_extend_fp8_kernel"):
-        found = {k: v for k, v in kernels.items() if sub in k}
-        assert found, f"{sub} not found in decode.hip"
-        for k, v in found.items():
-            assert v["ScratchSize [bytes/lane]"] == 0, f"{k}: scratch {v}"
-            assert v["VGPRs Spill"] == 0, f"{k}: spills {v}"
+    for family in ("kv_store_kernel", "attn_decode_kernel", "attn_extend_kernel"):
+        k, v = _instantiation(kernels, family, "KvFp8")
+        assert v["ScratchSize [bytes/lane]"] == 0, f"{k}: scratch {v}"
+        assert v["VGPRs Spill"] == 0, f"{k}: spills {v}"

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 from gpt_2_distributed_amd.generation import ShareGroups
-from tests.test_kernel_resources import HIPCC, _resources
+from tests.test_kernel_resources import HIPCC, _instantiation, _resources
 
 
 def state(g):
@@ -120,10 +120,8 @@ def test_shared_kernels_have_no_scratch_and_no_spills():
     """And at least 4 waves per SIMD (up to 128 VGPRs): a wave keeps a range's keys and values across its members beside
     attn_range's state and the next member's q, so it may have half of attn_decode_kernel's 8, and no less."""
     kernels = _resources("decode.hip")
-    for sub in ("attn_decode_shared_kernel", "attn_decode_shared_fp8_kernel"):
-        found = {k: v for k, v in kernels.items() if sub in k}
-        assert found, f"{sub} not found in decode.hip"
-        for k, v in found.items():
-            assert v["ScratchSize [bytes/lane]"] == 0, f"{k}: scratch {v}"
-            assert v["VGPRs Spill"] == 0, f"{k}: spills {v}"
-            assert v["Occupancy [waves/SIMD]"] >= 4, f"{k}: occupancy {v}"
+    for fmt in ("KvBf16", "KvFp8"):
+        k, v = _instantiation(kernels, "attn_decode_shared_kernel", fmt)
+        assert v["ScratchSize [bytes/lane]"] == 0, f"{k}: scratch {v}"
+        assert v["VGPRs Spill"] == 0, f"{k}: spills {v}"
+        assert v["Occupancy [waves/SIMD]"] >= 4, f"{k}: occupancy {v}"

@@ -13,6 +13,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gpt_2_distributed_amd import _lib as K  # noqa: E402
+from gpt_2_distributed_amd.generation import kv_quantize  # noqa: E402
 
 dev = "cuda"
 
@@ -311,10 +312,13 @@ def decode_mode(libs, st):
     """LIB_AB_OP=decode: the decode entries with a scalar position (gpt2mi_attn_decode, gpt2mi_embed_decode,
     gpt2mi_sample greedy and at temperature 0.8 / top_k 50 / top_p 0.95, gpt2mi_decode_step on a random-weight plan) and
     their _ragged forms at equal and at mixed positions; gpt2mi_attn_extend and gpt2mi_decode_extend over row maps, and
-    gpt2mi_sample_penalized with neutral and non-neutral values.
-    Small shapes (B = 4, H = 2, Tcap = 70, positions 0 / 31 / 32 / 69,
+    gpt2mi_sample_penalized with neutral and non-neutral values. The cache entries over both formats: gpt2mi_kv_store
+    and gpt2mi_kv_store_fp8, gpt2mi_attn_decode_fp8_ragged, gpt2mi_attn_extend_fp8, and gpt2mi_attn_decode_shared[_fp8]
+    over share maps.
+    Small shapes (B = 4 or 5, H = 2, Tcap = 70, positions 0 / 31 / 32 / 69,
     V = 509 and 50257) and GPT-2 124M's widths at B = 1, 8, 64 with pos = 575 in a 1024-position cache. Every library
-    gets clones of the same seeded inputs; every output (out, both caches, x, tok, seq, probs_out, logits) is compared
+    gets clones of the same seeded inputs; every output (out, the whole workspace, both caches and their scales, x, tok,
+    seq, probs_out, logits) is compared
     bitwise against the first library's; each row is timed in interleaved rounds (HIP events around back-to-back
     launches, the median round). A row whose symbol a library lacks is skipped for that library, and says so."""
     g = torch.Generator(device=dev).manual_seed(0)
@@ -361,34 +365,76 @@ def decode_mode(libs, st):
             out += [(f"pos={p}", p, [p] * B), (f"ragged pos={p}", None, [p] * B)]
         return out + [("ragged mixed", None, mixed)]
 
-    def attn(B, H, Tcap, vs):
-        C = 64 * H
-        qkv, kc0, vc0 = rn(B, 3 * C, dt=bf), rn(B, H, Tcap, 64, dt=bf), rn(B, H, Tcap, 64, dt=bf)
-        ws_n = libs[0].gpt2mi_attn_decode_workspace(B, H, Tcap)
-        make = lambda: dict(out=torch.zeros(B, C, dtype=bf, device=dev), kcache=kc0.clone(), vcache=vc0.clone(),  # noqa
-                            ws=torch.zeros(ws_n, device=dev))
-        for name, p, plist in vs:
-            sym = "gpt2mi_attn_decode" + ("" if p is not None else "_ragged")
-            arg = p if p is not None else ints(plist)
-            row(f"attn_decode B={B} H={H} Tcap={Tcap} {name}", sym, make,
-                lambda lib, s, sym=sym, arg=arg: getattr(lib, sym)(
-                    qkv.data_ptr(), s["kcache"].data_ptr(), s["vcache"].data_ptr(), s["out"].data_ptr(),
-                    s["ws"].data_ptr(), ws_n, B, H, 64, Tcap, arg, st))
+    def cache(B, H, Tcap, fp8, shares=()):
+        """A random cache of B streams as a function that clones it: kcache / vcache [B][H][Tcap][64] in bf16, or with fp8
+        their codes and kscale / vscale [B][H][Tcap] (generation.kv_quantize of random rows). `shares`: (rows, length)
+        groups whose rows hold a copy of the lowest one's first `length` positions."""
+        src = dict(kcache=rn(B, H, Tcap, 64, dt=bf), vcache=rn(B, H, Tcap, 64, dt=bf))
+        if fp8:
+            (kc, ks), (vc, vs) = (kv_quantize(t) for t in src.values())
+            src = dict(kcache=kc, vcache=vc, kscale=ks, vscale=vs)
+        for rows, n in shares:
+            for t in src.values():
+                t[rows, :, :n] = t[rows[0], :, :n]
+        return lambda: {k: v.clone() for k, v in src.items()}
 
-    def attn_extend(B, H, Tcap, maps):
-        """gpt2mi_attn_extend over each row map (label, seq, pos): R rows of B sequences."""
+    # the cache of a state as an entry takes it: kcache, vcache and, over fp8, kscale, vscale
+    cache_args = lambda s: [s[k].data_ptr() for k in ("kcache", "vcache", "kscale", "vscale") if k in s]  # noqa: E731
+    fp8_tag = lambda fp8: "_fp8" if fp8 else ""  # noqa: E731
+
+    def kv_store(B, H, Tcap, T_src, n, t0):
+        """gpt2mi_kv_store and gpt2mi_kv_store_fp8 of the first n of T_src rows per sequence to positions t0..: one thread
+        per 8 values, B n 16 H of them. The label says how many and how many of them the last block of 256 holds: at H = 12
+        the count is a multiple of 256 whenever B n is one of 4, so the small row and B = 1 are the partial last blocks."""
+        qkv = rn(B * T_src, 3 * 64 * H, dt=bf)
+        threads = B * n * 16 * H
+        for fp8 in (False, True):
+            row(f"kv_store{fp8_tag(fp8)} B={B} H={H} Tcap={Tcap} n={n} t0={t0} threads={threads} "
+                f"(last block {threads % 256 or 256})",
+                "gpt2mi_kv_store" + fp8_tag(fp8), cache(B, H, Tcap, fp8),
+                lambda lib, s, fp8=fp8: getattr(lib, "gpt2mi_kv_store" + fp8_tag(fp8))(
+                    qkv.data_ptr(), *cache_args(s), B, T_src, n, t0, H, 64, Tcap, st))
+
+    def attn(B, H, Tcap, vs, fp8=False, shared=()):
+        """The variants `vs` of gpt2mi_attn_decode[_ragged] (fp8: gpt2mi_attn_decode_fp8_ragged, which has no scalar form),
+        then gpt2mi_attn_decode_shared[_fp8] over each case of `shared`: (label, pos, share_group, share_len)."""
         C = 64 * H
+        qkv = rn(B, 3 * C, dt=bf)
+        ws_n = libs[0].gpt2mi_attn_decode_workspace(B, H, Tcap)
+        state = lambda c: dict(out=torch.zeros(B, C, dtype=bf, device=dev), ws=torch.zeros(ws_n, device=dev), **c())  # noqa
+        own = cache(B, H, Tcap, fp8)
+        for name, p, plist in vs:
+            if fp8 and p is not None:
+                continue
+            sym = "gpt2mi_attn_decode" + fp8_tag(fp8) + ("" if p is not None else "_ragged")
+            arg = p if p is not None else ints(plist)
+            row(f"attn_decode{fp8_tag(fp8)} B={B} H={H} Tcap={Tcap} {name}", sym, lambda: state(own),
+                lambda lib, s, sym=sym, arg=arg: getattr(lib, sym)(
+                    qkv.data_ptr(), *cache_args(s), s["out"].data_ptr(), s["ws"].data_ptr(), ws_n, B, H, 64, Tcap, arg,
+                    st))
+        for name, pos, group, length in shared:
+            sym = "gpt2mi_attn_decode_shared" + fp8_tag(fp8)
+            groups = [([b for b in range(B) if group[b] == g], length[g]) for g in sorted(set(group)) if length[g]]
+            row(f"attn_decode_shared{fp8_tag(fp8)} B={B} H={H} Tcap={Tcap} {name}", sym,
+                lambda c=cache(B, H, Tcap, fp8, groups): state(c),
+                lambda lib, s, sym=sym, pa=ints(pos), ga=ints(group), la=ints(length): getattr(lib, sym)(
+                    qkv.data_ptr(), *cache_args(s), s["out"].data_ptr(), s["ws"].data_ptr(), ws_n, B, H, 64, Tcap, pa,
+                    ga, la, st))
+
+    def attn_extend(B, H, Tcap, maps, fp8=False):
+        """gpt2mi_attn_extend (fp8: gpt2mi_attn_extend_fp8) over each row map (label, seq, pos): R rows of B sequences."""
+        C = 64 * H
+        sym = "gpt2mi_attn_extend" + fp8_tag(fp8)
         for name, seq, pos in maps:
             R = len(seq)
-            qkv, kc0, vc0 = rn(R, 3 * C, dt=bf), rn(B, H, Tcap, 64, dt=bf), rn(B, H, Tcap, 64, dt=bf)
+            qkv = rn(R, 3 * C, dt=bf)
             ws_n = libs[0].gpt2mi_attn_decode_workspace(R, H, Tcap)
-            make = lambda R=R, kc0=kc0, vc0=vc0, ws_n=ws_n: dict(  # noqa: E731
-                out=torch.zeros(R, C, dtype=bf, device=dev), kcache=kc0.clone(), vcache=vc0.clone(),
-                ws=torch.zeros(ws_n, device=dev))
-            row(f"attn_extend B={B} H={H} Tcap={Tcap} {name}", "gpt2mi_attn_extend", make,
-                lambda lib, s, R=R, qkv=qkv, ws_n=ws_n, sa=ints(seq), pa=ints(pos): lib.gpt2mi_attn_extend(
-                    qkv.data_ptr(), s["kcache"].data_ptr(), s["vcache"].data_ptr(), s["out"].data_ptr(),
-                    s["ws"].data_ptr(), ws_n, R, B, H, 64, Tcap, sa, pa, st))
+            make = lambda R=R, ws_n=ws_n, c=cache(B, H, Tcap, fp8): dict(  # noqa: E731
+                out=torch.zeros(R, C, dtype=bf, device=dev), ws=torch.zeros(ws_n, device=dev), **c())
+            row(f"attn_extend{fp8_tag(fp8)} B={B} H={H} Tcap={Tcap} {name}", sym, make,
+                lambda lib, s, R=R, qkv=qkv, ws_n=ws_n, sa=ints(seq), pa=ints(pos): getattr(lib, sym)(
+                    qkv.data_ptr(), *cache_args(s), s["out"].data_ptr(), s["ws"].data_ptr(), ws_n, R, B, H, 64, Tcap, sa,
+                    pa, st))
 
     def embed(B, C, V, Tcap, vs):
         tok = torch.randint(0, V, (B,), device=dev, generator=g)
@@ -500,17 +546,29 @@ def decode_mode(libs, st):
             ("one-absent", [0, 0, 0, 0, 2, 2, 2, 2], [30, 31, 32, 33, 66, 67, 68, 69])]
     one_run = lambda R: (f"R={R} one run to pos=575", [0] * R, list(range(576 - R, 576)))  # noqa: E731
     small = variants(4, (0, 31, 32, 69), [0, 31, 32, 69])
-    attn(4, 2, 70, small)
-    attn_extend(3, 2, 70, maps)
+    # a group of three among five rows at a shared length of one and of two whole ranges (tests/test_share_kernels_gpu.py)
+    share5 = [(f"3 of 5 share {n}", pos, [0, 1, 0, 3, 0], [n, 0, n, 0, n])
+              for n, pos in ((32, [32, 31, 45, 0, 69]), (64, [64, 31, 66, 0, 69]))]
+    kv_store(5, 2, 70, 7, 3, 30)
+    for fp8 in (False, True):
+        attn(4, 2, 70, small, fp8)
+        attn(5, 2, 70, (), fp8, share5)
+        attn_extend(3, 2, 70, maps, fp8)
     embed(4, 128, 509, 70, small)
     for V, ldl in ((509, 512), (50257, 50432)):
         sample(4, V, ldl, 70, small)
         sample_penalized(4, V, ldl, 70)
     step(4, 128, 2, 2, 509, 512, 70, small, reps=5, extends=maps)
-    attn_extend(1, 12, 1024, [one_run(8)])
+    for fp8 in (False, True):
+        attn_extend(1, 12, 1024, [one_run(8)], fp8)
     for B in (1, 8, 64):
         big = variants(B, (575,), [575 - (37 * b) % 576 for b in range(B)])
-        attn(B, 12, 1024, big)
+        # groups of four rows over a prompt of 512 (a row alone at B = 1), each row somewhere in the 64 positions behind it
+        n = 512 if B >= 4 else 0
+        share = [(f"groups of 4 share {n}", [575 - (37 * b) % 64 for b in range(B)], [b - b % 4 for b in range(B)], [n] * B)]
+        kv_store(B, 12, 1024, 64, 37, 5)
+        for fp8 in (False, True):
+            attn(B, 12, 1024, big, fp8, share)
         embed(B, 768, 50257, 1024, big)
         sample(B, 50257, 50432, 1024, big)
         step(B, 768, 12, 12, 50257, 50432, 1024, big, reps=5,
