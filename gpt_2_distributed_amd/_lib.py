@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
 # additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
-ABI_MINOR = 1
+ABI_MINOR = 2
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -136,11 +136,25 @@ _SIGS = {
                                _p, _p, _p, _c_int, _p, _p, _p, _p, _p],
     "gpt2mi_decode_generate_logprobs": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _p, _p, _c_int,
                                         _p, _p, _c_int, _p, _p, _c_float, _c_float, _c_float, _p, _p],
+    # v24.2 beam search: top_id, top_logprob, cum, done, G, W, eos, tok_out, parent_out, cum_out, done_out, stream
+    "gpt2mi_beam_select": [_p, _p, _p, _p, _c_int, _c_int, ctypes.c_int64, _p, _p, _p, _p, _p],
+    # kv_format, L, H, R, window
+    "gpt2mi_beam_reorder_workspace": [_c_int, _c_int, _c_int, _c_int, _c_int],
+    # kcache, vcache, kscale, vscale, kv_format, L, layer_rows, B, H, Tcap, seq, ld_seq, parent (device), G, W, lo, hi (HOST
+    # arrays of G W ints), workspace, workspace_bytes, stream
+    "gpt2mi_beam_reorder": [_p, _p, _p, _p, _c_int, _c_int, _c_size, _c_int, _c_int, _c_int, _p, _c_int, _p, _c_int, _c_int,
+                            _p, _p, _p, _c_size, _p],
+    # plan, V, W, eos, pos0, lo (HOST arrays), n, tok, seq, ld_seq, cum, done, parents, workspace, workspace_bytes, stream
+    "gpt2mi_decode_beam_search": [_p, _c_int, _c_int, ctypes.c_int64, _p, _p, _c_int, _p, _p, _c_int, _p, _p, _p, _p,
+                                  _c_size, _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
-_SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1}
+_SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
+                "gpt2mi_beam_select": 2, "gpt2mi_beam_reorder_workspace": 2, "gpt2mi_beam_reorder": 2,
+                "gpt2mi_decode_beam_search": 2}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
-             "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size}
+             "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
+             "gpt2mi_beam_reorder_workspace": _c_size}
 
 EXPORTED = tuple(_SIGS)
 
@@ -855,3 +869,54 @@ def decode_generate_logprobs(plan: DecodePlan, V, temperature, top_k, top_p, see
     lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, None, plan.B)
     _generate_call("gpt2mi_decode_generate_logprobs", plan, V, scalars, pos0, n, tok, row_id, seq, done,
                    float(repetition), float(presence), float(frequency), _host_ints(gen_start), lp)
+
+
+# ---- v24.2: beam search on the device (csrc/beam.hip) ---------------------------------------------------------
+BEAM_LOOP_BYTES = DECODE_MAX_B * (8 * LOGPROBS_MAX_TOP + 4)  # gpt2mi.h GPT2MI_BEAM_LOOP_BYTES
+
+
+def beam_select(top_ids, top_logprobs, cum, done, G, W, eos, tok_out, parent_out, cum_out, done_out):
+    """gpt2mi_beam_select (generation.beam_select is the rule): top_ids int32 / top_logprobs fp32 [G W, W], cum fp32 and
+    done uint8 [G W]; the new beams' tok_out int64, parent_out int32 (absolute rows), cum_out, done_out [G W]."""
+    for name, t, dt in (("top_ids", top_ids, torch.int32), ("top_logprobs", top_logprobs, torch.float32),
+                        ("cum", cum, torch.float32), ("done", done, torch.uint8), ("tok_out", tok_out, torch.int64),
+                        ("parent_out", parent_out, torch.int32), ("cum_out", cum_out, torch.float32),
+                        ("done_out", done_out, torch.uint8)):
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < G * W * (W if name.startswith("top_") else 1):
+            raise KernelError(f"beam_select: {name} must be a contiguous {dt} tensor of G W{' W' * name.startswith('top_')} "
+                              f"elements")
+    _call("gpt2mi_beam_select", _ptr(top_ids), _ptr(top_logprobs), _ptr(cum), _ptr(done), G, W,
+          -1 if eos is None else int(eos), _ptr(tok_out), _ptr(parent_out), _ptr(cum_out), _ptr(done_out), _stream())
+
+
+def beam_reorder_workspace(kv_format, L, H, R, window) -> int:
+    """Bytes of staging gpt2mi_beam_reorder needs for R rows and windows of up to `window` positions."""
+    return load().gpt2mi_beam_reorder_workspace(kv_format, L, H, R, window)
+
+
+def beam_reorder(kcache, vcache, parent, G, W, lo, hi, workspace, seq=None, kscale=None, vscale=None):
+    """gpt2mi_beam_reorder on cache tensors [L, B, H, Tcap, 64] (bf16, or uint8 codes with kscale / vscale fp32
+    [L, B, H, Tcap]): rows r < G W with parent[r] != r (device int32) take positions [lo[r], hi[r]) of row parent[r], in
+    the caches and in seq (int64 [>= G W, ld]); lo / hi are host sequences of G W ints."""
+    fp8 = kscale is not None or vscale is not None
+    tensors = [kcache, vcache] + ([kscale, vscale] if fp8 else [])
+    if kcache.dim() != 5 or any(t is None or not t.is_contiguous() for t in tensors) or vcache.shape != kcache.shape:
+        raise KernelError("beam_reorder takes contiguous cache tensors [L, B, H, Tcap, 64] (and scales [L, B, H, Tcap])")
+    if parent.dtype != torch.int32 or not parent.is_contiguous() or parent.numel() < G * W:
+        raise KernelError("beam_reorder: parent must be a contiguous int32 tensor of G W rows")
+    if seq is not None and (seq.dtype != torch.int64 or seq.dim() != 2 or seq.stride(1) != 1 or seq.size(0) < G * W):
+        raise KernelError("beam_reorder: seq must be int64 [>= G W, ld] with contiguous rows")
+    L, B, H, Tcap = kcache.shape[:4]
+    _call("gpt2mi_beam_reorder", _ptr(kcache), _ptr(vcache), _ptr(kscale), _ptr(vscale), KV_FP8 if fp8 else KV_BF16, L,
+          B * H * Tcap, B, H, Tcap, _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(parent), G, W,
+          _positions(lo, G * W), _positions(hi, G * W), _ptr(workspace),
+          0 if workspace is None else workspace.numel() * workspace.element_size(), _stream())
+
+
+def decode_beam_search(plan: DecodePlan, V, W, pos0, lo, n, tok, seq, cum, done, workspace, eos=None, parents=None):
+    """gpt2mi_decode_beam_search: n rounds of (top W, select, reorder, step) over the plan's rows, groups of W; cum fp32 /
+    done uint8 [B] carry the state, parents (int32 [n, B], optional) receives every step's parent rows."""
+    _call("gpt2mi_decode_beam_search", plan.ref(), V, W, -1 if eos is None else int(eos), _positions(pos0, plan.B),
+          _positions(lo, plan.B), n, _ptr(tok), _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(cum), _ptr(done),
+          _ptr(parents), _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(),
+          _stream())

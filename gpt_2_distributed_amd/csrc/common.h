@@ -45,6 +45,11 @@ int launch_sample_lp(const char* what, const float* logits, int ldl, int B, int 
                      const int* hist_row, const int* gen_start, float* logits_out, const gpt2mi_logprobs* lp,
                      const int* col, void* stream);
 
+// The step of csrc/decode.hip for a token loop in another unit (csrc/beam.hip), under that loop's name in messages:
+// every check of gpt2mi_decode_step_ragged at pos without a launch, and the step itself.
+int decode_step_check(const char* what, const gpt2mi_decode_plan* plan, const int64_t* tok, const int* pos);
+int decode_step_as(const char* what, const gpt2mi_decode_plan* plan, const int64_t* tok, const int* pos, void* stream);
+
 // What a scalar-position entry hands to the per-row implementation: every row at `pos`. All GPT2MI_DECODE_MAX_B
 // entries are filled, so B is checked where the array is read and nowhere else.
 struct SamePos {

@@ -36,6 +36,27 @@ __device__ __forceinline__ int tid_pinned() {
   return t;
 }
 
+// The row of a 1024-thread workgroup: thread t's x[i] is logit i * 1024 + t of `row`, NaN for an index >= V (no
+// comparison is true for it, fmaxf drops it; the padding columns of the buffer are not read). The one load of
+// sample_row and of the beam search's top-W kernel (csrc/beam.hip), so that they hold the same registers.
+// Chunk i of the row is read through a raw buffer over its own valid part, [i * 1024, min(V, (i + 1) * 1024)): the
+// hardware drops the lanes past it (they get 0; a chunk with nothing valid reads nothing), the descriptor is scalar
+// work and the 50 loads share one offset register, so they are all in flight together (50 clamped 64-bit addresses
+// would take 100 registers).
+__device__ __forceinline__ void load_row(float (&x)[SM_NE], const float* row, int V) {
+  const uint32_t voff = 4u * threadIdx.x;
+  auto chunk_rsrc = [&](int i) {
+    const int n = min(max(V - i * SM_THREADS, 0), SM_THREADS);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(row + min(i * SM_THREADS, V - 1)), 0, 4 * n, 0x00020000);
+  };
+#pragma unroll
+  for (int i = 0; i < SM_NE; ++i)
+    x[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(chunk_rsrc(i), voff, 0, 0));
+  const int t = tid_pinned();
+#pragma unroll
+  for (int i = 0; i < SM_NE; ++i) x[i] = i * SM_THREADS + t < V ? x[i] : __builtin_nanf("");
+}
+
 // The LP prologue, shared by the four LP kernels: the raw row's lse, and its top_n alternatives straight to global memory
 // (top_id / top_lp: the row's top_n slots). x is read only; `red` / `par` are sample_row's reduction rows and their
 // parity, used by its protocol (one barrier a reduction, the two rows alternately).
@@ -186,25 +207,8 @@ __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int
   };
 
   // the row. Indices >= V hold NaN: no comparison below is true for them, so they are never counted, kept or chosen
-  // (fmaxf drops them); the padding columns of the buffer are not read.
   float x[SM_NE];
-  // Chunk i of the row is read through a raw buffer over its own valid part, [i * 1024, min(V, (i + 1) * 1024)): the
-  // hardware drops the lanes past it (they get 0; a chunk with nothing valid reads nothing), the descriptor is scalar
-  // work and the 50 loads share one offset register, so they are all in flight together (50 clamped 64-bit addresses
-  // would take 100 registers).
-  const uint32_t voff = 4u * tid;
-  auto chunk_rsrc = [&](const float* row, int i) {
-    const int n = min(max(V - i * SM_THREADS, 0), SM_THREADS);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(row + min(i * SM_THREADS, V - 1)), 0, 4 * n, 0x00020000);
-  };
-#pragma unroll
-  for (int i = 0; i < SM_NE; ++i)
-    x[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(chunk_rsrc(lp, i), voff, 0, 0));
-  {
-    const int t = tid_here();
-#pragma unroll
-    for (int i = 0; i < SM_NE; ++i) x[i] = i * SM_THREADS + t < V ? x[i] : __builtin_nanf("");
-  }
+  load_row(x, lp, V);
   float lse = 0.f;
   if constexpr (LP) lse = logprob_prologue(x, V, red, par, top_n, top_id, top_lp);
   if constexpr (PEN) {

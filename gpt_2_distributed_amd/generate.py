@@ -1,7 +1,7 @@
 """Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
 --prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B
 --draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F --kv_dtype {bf16,fp8}
---num_samples S --logprobs [N]]``.
+--num_samples S --logprobs [N] --num_beams W --length_penalty A --num_return_sequences R]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -19,7 +19,14 @@ is run once and its rows share its cache. One JSON object per sample is printed,
 ``--logprobs [N]`` makes every line a JSON object (``"tokens"`` as above) with ``"logprobs"``, the log-probability of each
 new token under the model's own distribution (before penalties, temperature and filters), and ``"cum_logprob"``, their
 sum; with N > 0 also ``"top_logprobs"``, per new token the N most likely ``[id, logprob]`` pairs. Without the flag the
-lines are what they were."""
+lines are what they were.
+
+``--num_beams W`` searches instead of drawing (``GPT2.generate(num_beams=W)``: beam search on the device over the prompt's
+shared cache) and prints, prompt-major, one JSON object per returned beam, best first:
+``{"prompt": b, "beam": j, "tokens": [...], "score": s, "cum_logprob": c}`` (``tokens``: the prompt and the beam up to and
+including its first eos). ``--length_penalty`` enters the final ranking only and ``--num_return_sequences`` (default 1,
+at most W) says how many beams of each prompt are printed. The sampler's flags (``--sampler device`` among them) do not
+go with it; prompts x W <= 64."""
 from __future__ import annotations
 
 import argparse
@@ -32,7 +39,7 @@ import torch
 from .model import GPT2, GPT2Config, MODEL_SIZES
 
 
-def parse_args(argv=None):
+def make_parser():
     p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--checkpoint", required=True, help="a step_XXXXXXX directory written by save_checkpoint")
     p.add_argument("--model", default="124M", choices=sorted(MODEL_SIZES) + ["auto"],
@@ -70,7 +77,27 @@ def parse_args(argv=None):
     p.add_argument("--logprobs", type=int, nargs="?", const=0, default=None, metavar="N",
                    help="print each new token's log-probability and their sum; N > 0 (<= 20): the N most likely tokens "
                         "of each step as well")
-    return p.parse_args(argv)
+    p.add_argument("--num_beams", type=int, default=None,
+                   help="beam search with this many beams per prompt (1..20; prompts x num_beams <= 64) instead of "
+                        "sampling: the sampler's flags do not go with it")
+    p.add_argument("--length_penalty", type=float, default=1.0,
+                   help="--num_beams: the final score is cum_logprob / length ** this (1: the mean log-probability)")
+    p.add_argument("--num_return_sequences", type=int, default=1, help="--num_beams: beams printed per prompt, best first")
+    return p
+
+
+def parse_args(argv=None):
+    return make_parser().parse_args(argv)
+
+
+def beam_lines(out, prompt_lens):
+    """The JSON objects of a ``generate(num_beams=)`` result, prompt-major, a beam cut after its last token."""
+    lines = []
+    for b, n in enumerate(prompt_lens):
+        for j in range(out.tokens.size(1)):
+            lines.append({"prompt": b, "beam": j, "tokens": out.tokens[b, j, :n + int(out.lengths[b, j])].tolist(),
+                          "score": float(out.scores[b, j]), "cum_logprob": float(out.cum_logprob[b, j])})
+    return lines
 
 
 def with_logprobs(line, out, row: int, first: int, last: int, top_n: int):
@@ -106,6 +133,8 @@ def load_model(ckpt_dir: str, size: str) -> GPT2:
 
 def main(argv=None) -> int:
     a = parse_args(argv)
+    if a.num_beams is not None and a.sampler == "device":
+        raise SystemExit("--sampler device draws tokens: it does not go with --num_beams, which searches")
     lines = list(a.prompt_ids or [])
     if a.prompts_file:
         with open(a.prompts_file) as f:
@@ -118,6 +147,18 @@ def main(argv=None) -> int:
                frequency_penalty=a.frequency_penalty, kv_dtype=a.kv_dtype)
     if a.logprobs is not None:
         pen["logprobs"] = a.logprobs
+    if a.num_beams is not None:
+        # (only what the user set travels on: generate refuses the sampler's keywords beside num_beams by name)
+        default = make_parser().get_default
+        given = {k: v for k, v in dict(temperature=a.temperature, top_k=a.top_k, top_p=a.top_p,
+                                       draft_tokens=a.draft_tokens, num_samples=a.num_samples, **pen).items()
+                 if v != default(k)}
+        out = model.generate([torch.tensor(q, dtype=torch.int64, device="cuda:0") for q in prompts] * a.batch,
+                             a.max_new_tokens, eos_token_id=a.eos_token_id, num_beams=a.num_beams,
+                             length_penalty=a.length_penalty, num_return_sequences=a.num_return_sequences, **given)
+        for line in beam_lines(out, [len(q) for q in prompts] * a.batch):
+            print(json.dumps(line))
+        return 0
     if a.num_samples > 1:
         if a.draft_tokens is not None and a.sampler != "device":
             raise SystemExit("--draft_tokens compares drafts with the device sampler's draws: --sampler device")

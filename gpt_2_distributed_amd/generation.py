@@ -23,6 +23,12 @@ With ``logprobs=`` the device sampler also returns, from the launch that draws a
 under the model's own distribution and the most likely alternatives (``gpt2mi_sample_logprobs``; ``token_logprobs`` is
 the rule, ``LogprobBuffer`` where a session puts them; DESIGN.md "Token log-probabilities").
 
+With ``num_beams=`` ``generate`` searches: the W beams of a prompt are W rows forked from one prefill, and each token
+is chosen by ``gpt2mi_decode_beam_search`` on the device (the rows' top-W log-probabilities, the selection, the move of
+the generated suffix of the cache rows to their new parents, the step), nothing read back in between. ``beam_select``
+is the selection rule, ``beam_rank`` the final ranking and ``beam_pick`` what is returned of it (DESIGN.md "Beam
+search").
+
 Numerics are the autocast path's whatever the autocast state: bf16 GEMM operands from the engine's weight shadow, fp32
 accumulation, fp32 residual stream / LayerNorm / softmax, dropout off (p = 0 whatever ``model.training`` is, and
 ``.training`` is not touched). Logits are fp32. ``model.precision == "fp32"`` has no decode kernels and raises.
@@ -282,6 +288,120 @@ def _check_logprobs(logprobs) -> Optional[int]:
     return n
 
 
+# ---- beam search: the rule gpt2mi_beam_select applies, executable, and the final ranking ---------------------------------
+def _host_array(v, dtype):
+    import numpy as np
+    return np.ascontiguousarray((v.detach().cpu() if isinstance(v, torch.Tensor) else torch.as_tensor(v)).numpy()).astype(
+        dtype, copy=False)
+
+
+def beam_select(cum, done, top_ids, top_logprobs, eos, W: int):
+    """One step of beam search over groups of ``W`` rows, in numpy float32: what gpt2mi_beam_select computes bit for bit.
+    ``(tok int64 [R], parent int32 [R], cum float32 [R], done uint8 [R])`` from ``cum`` [R], ``done`` [R] and the rows'
+    ``top_ids`` / ``top_logprobs`` [R, W] (``token_logprobs(row, top_n=W)``'s order: value descending, equal values by
+    ascending index); R = G W, group g in rows g W .. g W + W - 1. ``eos`` -1 (or None): no eos, nothing is finished.
+
+    Candidates of a group: a live beam j offers its W tokens, rank r at score ``cum[j] + top_logprobs[j][r]`` (one fp32
+    add); a finished beam offers ``eos`` at score ``cum[j]``, rank 0. They are ordered by (score descending, beam j
+    ascending, rank r ascending), comparing fp32 values (-0 == +0; -inf scores come last, by (j, r)); NaN is outside the
+    contract. The tie-break is the rank within the beam and not the token id: ``fl(cum + lp)`` can map two distinct
+    log-probabilities to one score, and a rule stated over token ids of the whole vocabulary would then disagree with
+    one that sees each beam's W best. The W first candidates become the new beams, best first: ``tok``, ``parent`` (an
+    absolute row), the score as the new ``cum`` and ``done = parent's done or tok == eos``.
+
+    At the first step the state is ``cum = [0, -inf, ..., -inf]`` per group: the rows are forks of one prefill, so only
+    beam 0 may expand. A finished beam stays in the set, emitting eos, and competes on its raw ``cum``: no length
+    penalty enters here (see ``beam_rank``)."""
+    import numpy as np
+    W = int(W)
+    eos = -1 if eos is None else int(eos)
+    cum, done = _host_array(cum, np.float32).reshape(-1), _host_array(done, np.uint8).reshape(-1)
+    R = cum.size
+    if W < 1 or R % W or done.size != R:
+        raise ValueError(f"beam_select takes R = G * W rows of cum and done (got {R} and {done.size}, W={W})")
+    ids, lps = _host_array(top_ids, np.int64).reshape(R, W), _host_array(top_logprobs, np.float32).reshape(R, W)
+    tok, parent = np.zeros(R, np.int64), np.zeros(R, np.int32)
+    cum_out, done_out = np.zeros(R, np.float32), np.zeros(R, np.uint8)
+    for g0 in range(0, R, W):
+        cands = []  # (score, beam, rank, token, finished)
+        for j in range(W):
+            row = g0 + j
+            if eos >= 0 and done[row]:
+                cands.append((cum[row], j, 0, eos, True))
+            else:
+                cands += [(np.float32(cum[row] + lps[row, r]), j, r, int(ids[row, r]), False) for r in range(W)]
+        cands.sort(key=lambda c: (-float(c[0]), c[1], c[2]))  # (-0.0 == 0.0 as floats; inf, a -inf score, sorts last)
+        for slot, (score, j, _, t, fin) in enumerate(cands[:W]):
+            tok[g0 + slot], parent[g0 + slot], cum_out[g0 + slot] = t, g0 + j, score
+            done_out[g0 + slot] = fin or (eos >= 0 and t == eos)
+    return tok, parent, cum_out, done_out
+
+
+def beam_rank(cum, lengths, length_penalty: float = 1.0):
+    """The final ranking of beam search, on the host in float64: ``(order, score)`` for ``cum`` and ``lengths`` [..., W]
+    (a beam's length: its generated tokens up to and including its first eos). ``score = cum / max(length, 1) **
+    length_penalty``; ``order`` lists each group's beams by score descending, equal scores by beam index.
+
+    The length penalty enters only here. Inside the loop finished and live beams compete on their raw cumulative
+    log-probability and a finished beam stays in the set (``beam_select``): this is not HF's hypothesis heap, which takes
+    a finished hypothesis out of the beams, scores it with the penalty at once and can stop early."""
+    cum = torch.as_tensor(cum).double().cpu()
+    length = torch.as_tensor(lengths).double().cpu().clamp_min(1.0)
+    score = cum / length ** float(length_penalty)
+    return torch.sort(score, dim=-1, descending=True, stable=True).indices, score
+
+
+class BeamOutput(NamedTuple):
+    """``generate(..., num_beams=W)``: per prompt its ``num_return_sequences`` best beams, best first. ``tokens`` int64
+    [B, r, P + m] (a row as ``generate`` lays it out: the prompt, the beam's tokens, pad after its first eos), ``scores``
+    float64 [B, r] (``beam_rank``), ``cum_logprob`` fp32 [B, r] (the sum the loop formed) and ``lengths`` int64 [B, r]."""
+    tokens: torch.Tensor
+    scores: torch.Tensor
+    cum_logprob: torch.Tensor
+    lengths: torch.Tensor
+
+
+def beam_pick(tokens, cum, lengths, W: int, length_penalty: float = 1.0, num_return_sequences: int = 1) -> "BeamOutput":
+    """The result of a search from its final state: ``tokens`` [B W, T], ``cum`` [B W] and ``lengths`` [B W], row
+    ``b W + j`` beam j of prompt b, as the ``BeamOutput`` of each prompt's ``num_return_sequences`` best beams in
+    ``beam_rank``'s order. Pure indexing on whatever device the state is on: entry ``[b, i]`` of every field belongs to the
+    same beam, and the result for r beams is the first r entries of the result for W."""
+    R, W, r = tokens.size(0), int(W), int(num_return_sequences)
+    if W < 1 or R % W or cum.shape != (R,) or lengths.shape != (R,) or not 1 <= r <= W:
+        raise ValueError(f"beam_pick takes B * W rows of tokens, cum and lengths and 1 <= num_return_sequences <= W (got "
+                         f"{R}, {tuple(cum.shape)}, {tuple(lengths.shape)}, W={W}, num_return_sequences={r})")
+    B, dev = R // W, tokens.device
+    order, score = beam_rank(cum.view(B, W), lengths.view(B, W), length_penalty)
+    order = order[:, :r]
+    rows = (torch.arange(B)[:, None] * W + order).reshape(-1).to(dev)
+    return BeamOutput(tokens[rows].view(B, r, -1), score.gather(1, order).to(dev), cum[rows].view(B, r),
+                      lengths[rows].view(B, r))
+
+
+def _check_beams(num_beams, length_penalty, num_return_sequences, B: int, vocab_size: int, others: dict):
+    """``generate``'s beam keywords as (W, length_penalty, num_return_sequences), or the ValueError naming the one that is
+    wrong; ``others``: the sampler's keywords by name, each (value, neutral value)."""
+    W = int(num_beams)
+    if not 1 <= W <= K.LOGPROBS_MAX_TOP:
+        raise ValueError(f"num_beams must lie in [1, {K.LOGPROBS_MAX_TOP}] (got {num_beams})")
+    if W > vocab_size:
+        raise ValueError(f"num_beams={W} exceeds vocab_size={vocab_size}")
+    if B * W > MAX_BATCH:
+        raise ValueError(f"{B} prompts x num_beams={W} = {B * W} rows exceed the {MAX_BATCH} rows of a decode session "
+                         f"(MAX_BATCH)")
+    r = int(num_return_sequences)
+    if not 1 <= r <= W:
+        raise ValueError(f"num_return_sequences must lie in [1, num_beams={W}] (got {num_return_sequences})")
+    lp = float(length_penalty)
+    if not abs(lp) < float("inf"):  # (NaN too)
+        raise ValueError(f"length_penalty must be finite (got {length_penalty})")
+    for name, (value, neutral) in others.items():
+        if value is not None and value != neutral:
+            raise ValueError(f"{name} does not go with num_beams: beam search is deterministic and ranks the model's own "
+                             f"distribution (got {name}={value!r})")
+    return W, lp, r
+
+
 # ---- the fp8 key/value cache: the rule gpt2mi_kv_store_fp8 and the fp8 attention kernels quantise by, executable -------
 KV_DTYPES = ("bf16", "fp8")
 KV_MIN_EXP = -100  # the smallest scale exponent (an all-zero row has it)
@@ -471,6 +591,7 @@ class DecodeSession:
         self._refill_ws = None            # (Tp, engine.Workspace) of the last refill's one-sequence prefill
         self._plan = self._build_plan({n: getattr(self, n) for n in SCRATCH}, 0)
         self._rows = None                 # (scratch of MAX_BATCH rows, its plan): extend / speculate, on first use
+        self._beam_ws = None              # beam_search's workspace (top-W, parents, the reorder's staging), on first use
         self.share = ShareGroups(self.B)
         self._share_arrays = ((ctypes.c_int * self.B)(), (ctypes.c_int * self.B)())  # what the plan points at
 
@@ -874,6 +995,66 @@ class DecodeSession:
         self._drawn = True
         return self._tok
 
+    # ---- beam search (gpt2mi_decode_beam_search) ------------------------------------------------------------------------
+    @torch.no_grad()
+    def beam_search(self, n: int, num_beams: int, eos_token_id: Optional[int], seq: torch.Tensor, cum: torch.Tensor,
+                    done: torch.Tensor, parents: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``n`` tokens of beam search over the session's rows in one C call (gpt2mi_decode_beam_search): rows
+        ``g W .. g W + W - 1`` (W = ``num_beams``) are the beams of prompt g, made by ``refill(g W)`` and
+        ``fork(g W, the others)``, so that they are one share group whose shared length is the prompt's. Per token: the
+        rows' top-W log-probabilities, ``beam_select``, the move of positions [prompt length, lens) of the cache rows
+        and of ``seq`` to the new parents, and the step; nothing is synchronised or read back. ``seq`` (int64 [B, >=
+        max(lens) + n]) holds row b's tokens and receives the new ones at columns ``lens[b] + i``; ``cum`` (fp32 [B])
+        and ``done`` (uint8 [B]) carry the state: ``[0, -inf, ...]`` per group and 0 before the first call. With
+        ``eos_token_id`` finished beams keep emitting it. ``parents`` (int32 [n, B], optional) receives each step's
+        parent rows. As after ``generate`` the last token is not stepped (``flush``); returns the newest tokens [B]."""
+        n, W = int(n), int(num_beams)
+        if n < 1:
+            raise ValueError(f"beam_search takes n >= 1 (got {n})")
+        if not 1 <= W <= K.LOGPROBS_MAX_TOP or self.B % W or W > self.cfg.vocab_size:
+            raise ValueError(f"num_beams={num_beams} must lie in [1, {K.LOGPROBS_MAX_TOP}], divide B={self.B} and not "
+                             f"exceed vocab_size={self.cfg.vocab_size}")
+        if min(self.lens) == 0:
+            raise RuntimeError("beam_search before prefill: there are no logits")
+        if self.cfg.vocab_size > K.SAMPLE_MAX_V:
+            raise NotImplementedError(f"the top-W kernel holds rows of up to {K.SAMPLE_MAX_V} logits "
+                                      f"(vocab_size {self.cfg.vocab_size})")
+        if eos_token_id is not None and not 0 <= int(eos_token_id) < self.cfg.vocab_size:
+            raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={self.cfg.vocab_size})")
+        lo = list(self.lens)  # W = 1: a row is its own parent for ever, nothing moves
+        for g in range(0, self.B if W > 1 else 0, W):
+            rows = list(range(g, g + W))
+            if (any(self.share.group[b] != g or self.share.length[b] < 1 for b in rows)
+                    or len({self.lens[b] for b in rows}) != 1):
+                raise ValueError(f"rows {g}..{g + W - 1} are not the beams of one prompt: refill({g}) and "
+                                 f"fork({g}, the others) first (share_group {self.share.group[g:g + W]}, share_len "
+                                 f"{self.share.length[g:g + W]}, lens {self.lens[g:g + W]})")
+            lo[g:g + W] = self.share.length[g:g + W]
+        if max(self.lens) + int(self._drawn) + n > self.Tcap:
+            raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
+        if (seq is None or seq.dtype != torch.int64 or seq.dim() != 2 or seq.size(0) != self.B or seq.stride(1) != 1
+                or seq.size(1) < max(self.lens) + int(self._drawn) + n):
+            raise ValueError(f"seq must be int64 [B={self.B}, >= {max(self.lens) + int(self._drawn) + n}] with contiguous "
+                             f"rows")
+        if cum is None or cum.dtype != F32 or cum.shape != (self.B,) or not cum.is_contiguous():
+            raise ValueError(f"cum must be fp32 [B={self.B}]")
+        if done is None or done.dtype != torch.uint8 or done.shape != (self.B,) or not done.is_contiguous():
+            raise ValueError(f"done must be uint8 [B={self.B}]")
+        if parents is not None and (parents.dtype != torch.int32 or not parents.is_contiguous()
+                                    or parents.numel() < n * self.B):
+            raise ValueError(f"parents must be a contiguous int32 [n={n}, B={self.B}]")
+        self._ready(False)
+        self.flush()
+        window = max(m + n - 1 - l for m, l in zip(self.lens, lo))
+        need = K.BEAM_LOOP_BYTES + K.beam_reorder_workspace(self.kv_format, self.cfg.n_layer, self.cfg.n_head, self.B, window)
+        if self._beam_ws is None or self._beam_ws.numel() < need:
+            self._beam_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        K.decode_beam_search(self._plan, self.cfg.vocab_size, W, self.lens, lo, n, self._tok, seq, cum, done,
+                             self._beam_ws, eos=eos_token_id, parents=parents)
+        self.lens = [m + n - 1 for m in self.lens]
+        self._drawn = True
+        return self._tok
+
     # ---- several tokens of a sequence per launch (gpt2mi_decode_extend) ----------------------------------------------
     def _rows_plan(self):
         """The plan whose buffers hold MAX_BATCH rows (same weights and caches), allocated on first use."""
@@ -1126,9 +1307,20 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
              top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens: Optional[Sequence[int]] = None,
              pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None, draft_fn=None,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-             frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1, logprobs=None):
+             frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1, logprobs=None,
+             num_beams: Optional[int] = None, length_penalty: float = 1.0, num_return_sequences: int = 1):
     """``GPT2.generate``: see there."""
     check_kv_dtype(kv_dtype)
+    if num_beams is not None:
+        return _generate_beams(model, idx, max_new_tokens, num_beams, length_penalty, num_return_sequences, eos_token_id,
+                               prompt_lens, pad_token_id, kv_dtype,
+                               dict(seed=(seed, None), generator=(generator, None), temperature=(temperature, 1.0),
+                                    top_k=(top_k, None), top_p=(top_p, None), draft_tokens=(draft_tokens, None),
+                                    draft_fn=(draft_fn, None), repetition_penalty=(repetition_penalty, 1.0),
+                                    presence_penalty=(presence_penalty, 0.0), frequency_penalty=(frequency_penalty, 0.0),
+                                    num_samples=(num_samples, 1), logprobs=(logprobs, None)))
+    if length_penalty != 1.0 or num_return_sequences != 1:
+        raise ValueError("length_penalty and num_return_sequences go with num_beams")
     top_n = _check_logprobs(logprobs)
     s = int(num_samples)
     if s < 1:
@@ -1181,6 +1373,69 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
         return idx.clone() if top_n is None else _no_logprobs(idx.clone(), top_n)
     return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad,
                      None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype, s, top_n)
+
+
+def _generate_beams(model, idx, max_new_tokens, num_beams, length_penalty, num_return_sequences, eos_token_id,
+                    prompt_lens, pad_token_id, kv_dtype, others: dict) -> BeamOutput:
+    """``generate(num_beams=W)``: every prompt through ``refill`` once and forked to its W rows (the ``num_samples``
+    path), ``DecodeSession.beam_search`` in one call, or with eos EOS_CHUNK tokens at a time with one read of the done
+    flags per chunk (as ``_device_loop``), then ``beam_rank`` on the host."""
+    pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
+    if isinstance(idx, (list, tuple)):
+        if prompt_lens is not None:
+            raise ValueError("a list of prompts carries its own lengths: prompt_lens goes with a padded idx [B, P]")
+        idx, prompt_lens = _pad_prompts(idx, pad)
+    if idx.dim() != 2:
+        raise ValueError(f"generate takes idx [B, P] (got {tuple(idx.shape)})")
+    B, P = idx.shape
+    V = model.config.vocab_size
+    W, lp, nret = _check_beams(num_beams, length_penalty, num_return_sequences, B, V, others)
+    n = int(max_new_tokens)
+    if n < 0:
+        raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
+    lens = [P] * B
+    if prompt_lens is not None:
+        lens = _check_lens(prompt_lens, B, P)
+        P = max(lens)
+        idx = idx[:, :P]
+    if not 0 <= pad < V:
+        raise ValueError(f"pad_token_id {pad} not in [0, vocab_size={V})")
+    if eos_token_id is not None and not 0 <= int(eos_token_id) < V:
+        raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={V})")
+    if P + n > model.config.n_positions:
+        raise ValueError(f"prompt length {P} + max_new_tokens {n} > n_positions {model.config.n_positions}")
+    _check_model(model)
+    idx, dev, R = idx.long(), idx.device, B * W
+    lens_t = torch.tensor(lens, device=dev).repeat_interleave(W)  # per row
+    cols = torch.arange(P + n, device=dev)[None]
+    seq = torch.full((R, P + n), pad, dtype=torch.int64, device=dev)
+    seq[:, :P] = torch.where(cols[:, :P] < lens_t[:, None], idx.repeat_interleave(W, dim=0), seq[:, :P])
+    cum = torch.full((R,), float("-inf"), dtype=F32, device=dev)
+    cum[::W] = 0.0
+    done = torch.zeros(R, dtype=torch.uint8, device=dev)
+    made = 0
+    if n > 0:
+        sess = DecodeSession(model, R, P + n, kv_dtype)
+        for b in range(B):
+            sess.refill(b * W, idx[b, :lens[b]])
+            sess.fork(b * W, range(b * W + 1, b * W + W))
+        while made < n:
+            m = n - made if eos_token_id is None else min(EOS_CHUNK, n - made)
+            sess.beam_search(m, W, eos_token_id, seq, cum, done)
+            made += m
+            if eos_token_id is not None and bool(done.all()):
+                break
+    else:
+        cum[:] = 0.0  # (nothing generated: every returned beam is the prompt)
+    new = seq.gather(1, lens_t[:, None] + torch.arange(made, device=dev)[None])  # [R, made]
+    length = torch.full((R,), made, dtype=torch.int64, device=dev)
+    if eos_token_id is not None and made:
+        hit = new == eos_token_id
+        length = torch.where(hit.any(1), hit.int().argmax(1) + 1, length)
+        made = int(length.max())  # the column by which every beam has emitted eos (or the last one issued)
+    keep = cols[:, :P + made] < (lens_t + length)[:, None]
+    tokens = torch.where(keep, seq[:, :P + made], torch.full_like(seq[:, :P + made], pad))
+    return beam_pick(tokens, cum, length, W, lp, nret)
 
 
 def _no_logprobs(tokens: torch.Tensor, top_n: int) -> GenerateOutput:

@@ -348,7 +348,8 @@ class GPT2(nn.Module):
                  top_p: Optional[float] = None, seed: Optional[int] = None, prompt_lens=None,
                  pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None,
                  draft_fn=None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1, logprobs=None):
+                 frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1, logprobs=None,
+                 num_beams: Optional[int] = None, length_penalty: float = 1.0, num_return_sequences: int = 1):
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
         filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
@@ -411,6 +412,28 @@ class GPT2(nn.Module):
         that logits row alone, so everything above holds for them bit for bit (batch independence, ``draft_tokens``,
         ``num_samples``, ``kv_dtype``); the host sampler takes them from the same rule in float64.
 
+        ``num_beams=W`` (1 <= W <= 20) searches instead of drawing and returns the named tuple ``BeamOutput(tokens
+        [B, r, P + m], scores [B, r], cum_logprob [B, r], lengths [B, r])``, per prompt its r =
+        ``num_return_sequences`` (default 1, at most W) best beams, best first; a row of ``tokens`` is laid out as
+        above, with pad after the beam's first eos. Each prompt is run once and forked to its W rows (the
+        ``num_samples`` path: the rows share the prompt's cache), and every token is chosen on the device by
+        ``gpt2mi_decode_beam_search``: each row's W most likely tokens under the model's own distribution (the values
+        ``logprobs=`` reports), ``generation.beam_select`` (the W best of the up to W * W candidates by cumulative
+        fp32 log-probability; equal scores by beam, then by rank within the beam), the move of the generated suffix of
+        the cache rows to their new parents, and the step. Nothing is read back in between (with ``eos_token_id`` the
+        done flags once per 32 tokens), a prompt's result does not depend on its batch, and ``kv_dtype="fp8"``,
+        ``prompt_lens`` and a list of prompts work. ``num_beams=1`` gives the greedy tokens. A finished beam stays in
+        the set, emitting eos, and competes on its raw cumulative log-probability; ``length_penalty`` (default 1.0)
+        enters only the final ranking, ``score = cum_logprob / max(length, 1) ** length_penalty`` with ``length`` the
+        beam's tokens up to and including its first eos (``generation.beam_rank``). This is not HF's hypothesis heap:
+        there is no ``early_stopping`` and a finished hypothesis is not scored, with the penalty, at the moment it
+        finishes. ``ValueError``, naming the argument: ``num_beams`` outside [1, 20] or above ``vocab_size``,
+        ``B * num_beams > 64``, ``num_return_sequences`` outside [1, num_beams], a non-finite ``length_penalty``, and
+        any of ``seed``, ``generator``, ``temperature != 1``, ``top_k``, ``top_p``, the penalties, ``draft_tokens``,
+        ``num_samples > 1`` and ``logprobs`` given with ``num_beams``. Not offered: beams in ``generate_many``, the
+        per-token log-probabilities of a beam, sampling and diverse beam search. ``num_beams=None`` (the default) is
+        the call without it, on the same code path.
+
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
         the autocast state, with dropout off whatever ``self.training`` is; ``precision == "fp32"`` raises
         ``NotImplementedError``. It does not advance the dropout stream or touch what a later backward needs, so a
@@ -421,7 +444,8 @@ class GPT2(nn.Module):
         from .generation import generate
         return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed,
                         prompt_lens, pad_token_id, draft_tokens, draft_fn, repetition_penalty, presence_penalty,
-                        frequency_penalty, kv_dtype, num_samples, logprobs)
+                        frequency_penalty, kv_dtype, num_samples, logprobs, num_beams, length_penalty,
+                        num_return_sequences)
 
     def generate_many(self, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                       top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,

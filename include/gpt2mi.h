@@ -28,7 +28,7 @@ extern "C" {
 
 #define GPT2MI_ABI_VERSION 24
 /* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
-#define GPT2MI_ABI_MINOR 1
+#define GPT2MI_ABI_MINOR 2
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -602,6 +602,62 @@ int gpt2mi_decode_generate_logprobs(const gpt2mi_decode_plan* plan, int V, float
                                     int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream,
                                     float repetition, float presence, float frequency, const int* gen_start,
                                     const gpt2mi_logprobs* lp);
+
+/* ---- v24.2: beam search on the device (csrc/beam.hip). The executable specification of the selection rule is
+ * gpt_2_distributed_amd/generation.py beam_select.
+ * The W beams of a prompt are W adjacent rows, group g in rows g W .. g W + W - 1, forks of one prefill: their caches
+ * hold identical bits over the prompt, so re-parenting the beams moves only the generated suffix of the cache rows.
+ * State per row: cum, the fp32 cumulative log-probability, and done. A live beam j offers its W most likely tokens in
+ * gpt2mi_sample_logprobs' order (value descending, equal values by ascending index), rank r at score
+ * cum[j] + top_logprob[j][r], one IEEE fp32 add; a finished beam offers token eos at score cum[j], rank 0. Candidates are
+ * ordered by (score descending, beam ascending, rank ascending), comparing fp32 values (-0 == +0; equal -inf scores tie
+ * like any others); NaN is outside the contract. The W first become the new beams, best first, in the group's rows. ---- */
+/* One launch, one workgroup per group: top_id (int32) / top_logprob device [G W][W]; cum fp32 / done uint8 device [G W].
+ * For new beam row s: tok_out[s] (int64) its token, parent_out[s] (int32) the absolute row it continues, cum_out[s] its
+ * score, done_out[s] = its parent's done or tok == eos. eos = -1: no eos; the done flags are then not read and done_out
+ * is 0. Each candidate counts the candidates ahead of it and the one with count c < W writes slot c: no float atomics, no
+ * order that depends on scheduling. cum_out / done_out may be cum / done or other buffers (a group's inputs are read
+ * before anything is written). Nothing but rows [0, G W) of the four outputs is written.
+ * Refused with 22 and a message before any launch: W outside [1, GPT2MI_LOGPROBS_MAX_TOP], G W outside
+ * [1, GPT2MI_DECODE_MAX_B], eos < -1, a NULL pointer. */
+int gpt2mi_beam_select(const int32_t* top_id, const float* top_logprob, const float* cum, const uint8_t* done, int G,
+                       int W, int64_t eos, int64_t* tok_out, int32_t* parent_out, float* cum_out, uint8_t* done_out,
+                       void* stream);
+/* For every row r < G W with parent[r] != r, positions [lo[r], hi[r]) of row r become those of row parent[r]: in kcache
+ * and vcache (kv_format 0: bf16 [L][B][H][Tcap][64]; 1: uint8 codes, and kscale / vscale fp32 [L][B][H][Tcap], NULL
+ * otherwise), layer l at l * layer_rows rows of 64 behind layer 0 (layer_rows >= B H Tcap; not read for L = 1), and in
+ * seq, int64 [>= G W][ld_seq] (may be NULL), over the same columns. parent is a DEVICE int32 [G W] array (the select's
+ * output): the kernels treat a value outside row r's group [g W, g W + W) as "no move" before they form any address from
+ * it. lo and hi are HOST arrays, checked here and passed by value; the rows of a group must have one window. Two
+ * launches: the windows of the moved rows are gathered into the workspace, then written back, so no launch reads a
+ * position another workgroup of it writes, whatever cycles the permutation has. Nothing outside the windows of moved
+ * rows is written: not position hi, not rows >= G W, not the positions below lo. Every window empty: no launch.
+ * workspace: gpt2mi_beam_reorder_workspace(kv_format, L, H, G W, max_r hi[r] - lo[r]) bytes, 16-byte aligned.
+ * Refused with 22 and a message before any launch: W or G W as above, a kv_format other than 0 / 1, L, H or Tcap < 1,
+ * B < G W, 2 L H + 1 > 65535, layer_rows < B H Tcap with L > 1, a window outside 0 <= lo <= hi <= Tcap (hi > ld_seq with
+ * seq) or differing within a group, a workspace too small or misaligned, a NULL cache, scale (fp8), parent, lo or hi. */
+size_t gpt2mi_beam_reorder_workspace(int kv_format, int L, int H, int R, int window); /* bytes; 0 for invalid arguments */
+int gpt2mi_beam_reorder(void* kcache, void* vcache, float* kscale, float* vscale, int kv_format, int L,
+                        size_t layer_rows, int B, int H, int Tcap, int64_t* seq, int ld_seq, const int32_t* parent, int G,
+                        int W, const int* lo, const int* hi, void* workspace, size_t workspace_bytes, void* stream);
+/* The token loop, on the stream with nothing synchronised or read back: plan->B = G W rows, row b at pos0[b] >= 1 with
+ * its logits in plan->logits, its prompt ending at lo[b] in [1, pos0[b]] (HOST arrays; one value per group each). For
+ * i < n: the per-row top W of plan->logits (gpt2mi_sample_logprobs' alternatives at top_n = W, bit for bit: the same
+ * function on the same registers); gpt2mi_beam_select into tok, cum and done in place, the tokens also to column
+ * pos0[b] + i of seq; gpt2mi_beam_reorder with the windows [lo[b], pos0[b] + i); if i + 1 < n, gpt2mi_decode_step_ragged at
+ * pos0[b] + i. Finished rows keep being stepped with eos. The plan's share map stays valid throughout: positions below
+ * lo are never written. cum (fp32) / done (uint8) device [B] hold the state on entry ({0, -inf, ...} per group and 0 at
+ * the first step) and on return; parents (device int32 [n][B], may be NULL) receives each step's parent rows.
+ * workspace: GPT2MI_BEAM_LOOP_BYTES + gpt2mi_beam_reorder_workspace(plan->kv_format, L, H, B, max_b pos0[b] + n - 1 - lo[b])
+ * bytes, 16-byte aligned. The layers' caches must be equally spaced (one tensor per kind, as the package allocates them).
+ * Refused with 22 and a message before any launch: what gpt2mi_decode_step_ragged refuses at pos0, B not a multiple of
+ * W, W or B as above, W > V, V outside [1, Vp] or above GPT2MI_SAMPLE_MAX_V, eos outside [-1, V), n < 0, pos0[b] or lo[b]
+ * out of range or differing within a group, max pos0 + n > Tcap or > ld_seq, unequally spaced layer caches, a workspace
+ * too small or misaligned, a NULL pointer. */
+#define GPT2MI_BEAM_LOOP_BYTES (GPT2MI_DECODE_MAX_B * (8 * GPT2MI_LOGPROBS_MAX_TOP + 4))
+int gpt2mi_decode_beam_search(const gpt2mi_decode_plan* plan, int V, int W, int64_t eos, const int* pos0, const int* lo,
+                              int n, int64_t* tok, int64_t* seq, int ld_seq, float* cum, uint8_t* done, int32_t* parents,
+                              void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
