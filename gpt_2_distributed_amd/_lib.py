@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
 # additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
-ABI_MINOR = 2
+ABI_MINOR = 3
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -80,6 +80,12 @@ _SIGS = {
     # sched, stream
     "gpt2mi_gemm_wgrad_grouped": [_c_int, _p, _p, _c_int, _p, _p, _p, _p, _p, _c_int, _c_float, _p, _p, _c_size,
                                   _c_int, _c_int, _p],
+    # v24.3: count, M[], N[], K, A[], lda[], B[], ldb[], C[], ldc[] (host arrays), accumulate, alpha, alpha_dev, table
+    # (device scratch), table_bytes, sched, stream
+    "gpt2mi_gemm_wgrad_batch": [_c_int, _p, _p, _c_int, _p, _p, _p, _p, _p, _p, _c_int, _c_float, _p, _p, _c_size,
+                                _c_int, _p],
+    "gpt2mi_gemm_wgrad_batch_scratch": [_c_int],
+    "gpt2mi_gemm_wgrad_batch_max": [],
     # v14 decode: epilogue, M, N, K, A, lda, W, ldw, C, ldc, bias, resid, workspace, workspace_floats, stream
     "gpt2mi_gemm_skinny": [_c_int, _c_int, _c_int, _c_int, _p, _c_int, _p, _c_int, _p, _c_int, _p, _p, _p, _c_size, _p],
     "gpt2mi_gemm_skinny_workspace": [_c_int, _c_int, _c_int],
@@ -151,10 +157,11 @@ _SIGS = {
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
                 "gpt2mi_beam_select": 2, "gpt2mi_beam_reorder_workspace": 2, "gpt2mi_beam_reorder": 2,
-                "gpt2mi_decode_beam_search": 2}
+                "gpt2mi_decode_beam_search": 2, "gpt2mi_gemm_wgrad_batch": 3, "gpt2mi_gemm_wgrad_batch_scratch": 3,
+                "gpt2mi_gemm_wgrad_batch_max": 3}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
-             "gpt2mi_beam_reorder_workspace": _c_size}
+             "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size}
 
 EXPORTED = tuple(_SIGS)
 
@@ -333,6 +340,81 @@ def wgrad_group_splits(shapes, K, cus=256):
         if best_cost is None or cost < best_cost * 0.99:
             best, best_cost = s, cost
     return best
+
+
+GROUP_MAX = 4  # problems of one gemm_wgrad_grouped launch (gemm_plan.h kGroupMax)
+
+
+def gemm_wgrad_batch_max() -> int:
+    return load().gpt2mi_gemm_wgrad_batch_max()
+
+
+def gemm_wgrad_batch_scratch(count: int) -> int:
+    """Bytes of device scratch the problem table of a gemm_wgrad_batch launch of ``count`` problems takes."""
+    return load().gpt2mi_gemm_wgrad_batch_scratch(count)
+
+
+def gemm_wgrad_batch(problems, K, accumulate=True, alpha=1.0, alpha_dev=None, table=None, sched=SCHED_AUTO):
+    """Any number of weight gradients (up to gemm_wgrad_batch_max()) over the same K tokens in ONE launch without
+    split-K: problems = [(M, N, A, lda, B, ldb, C[, ldc])], each C[M][N] (+)= alpha A^T B with the bits of
+    gemm_wgrad(splits=1). table: a device byte tensor of gemm_wgrad_batch_scratch(len(problems)) bytes, which receives
+    the problem table stream-ordered ahead of the launch."""
+    n = len(problems)
+    ints = lambda vals: (_c_int * n)(*vals)  # noqa: E731
+    ptrs = lambda vals: (_p * n)(*vals)  # noqa: E731
+    tb = table.numel() * table.element_size() if table is not None else 0
+    _call("gpt2mi_gemm_wgrad_batch", n, ints([q[0] for q in problems]), ints([q[1] for q in problems]), K,
+          ptrs([_ptr(q[2]) for q in problems]), ints([q[3] for q in problems]), ptrs([_ptr(q[4]) for q in problems]),
+          ints([q[5] for q in problems]), ptrs([_ptr(q[6]) for q in problems]),
+          ints([q[7] if len(q) > 7 else q[1] for q in problems]), int(accumulate), alpha, _ptr(alpha_dev), _ptr(table),
+          tb, int(sched), _stream())
+
+
+def wgrad_batch_plan(shapes, K, cus=256):
+    """How the weight gradients of output shapes [(M, N)] (256-multiples) over the same K tokens run as one deferred
+    family: (body, tail, tail_split), index lists into ``shapes``. The body's whole problems go into one
+    gemm_wgrad_batch launch, one unsplit tile per block, and fill whole rounds of ``cus`` blocks as nearly as whole
+    problems allow: the tail is the set of problems with the fewest tiles that still covers the tiles past the last
+    whole round (fewest problems, then the first listed, among equals); everything when there is no whole round. The
+    tail runs split-K through gemm_wgrad_grouped at the wgrad_group_splits cost model's factor for it (its rounds of
+    ``cus`` blocks x K per split + the slab term; no split below 256 tokens). GPT-2 124M, 12 blocks: 1 296 tiles = a
+    body of 1 278 (4.99 rounds of 256) and two proj problems (18 tiles x 14 splits = 252 blocks, one round)."""
+    tiles = [(m // 256) * (n // 256) for m, n in shapes]
+    total = sum(tiles)
+    need = total if total < cus else total % cus
+    tail = []
+    if need == total:
+        tail = list(range(len(shapes)))
+    elif need > 0:
+        # subset sums up to need + the largest problem: best[s] = the index tuple reaching s (fewest, then first)
+        cap = need + max(tiles)
+        best = {0: ()}
+        for i, t in enumerate(tiles):
+            for s, idx in sorted(best.items(), reverse=True):
+                if s + t <= cap:
+                    cand = idx + (i,)
+                    old = best.get(s + t)
+                    if old is None or (len(cand), cand) < (len(old), old):
+                        best[s + t] = cand
+        tail = list(best[min(s for s in best if s >= need)])
+    chosen = set(tail)
+    body = [i for i in range(len(shapes)) if i not in chosen]
+    split = wgrad_group_splits([shapes[i] for i in tail], K, cus) if tail else 1
+    return body, tail, split
+
+
+def gemm_wgrad_planned(problems, K, plan, accumulate=True, alpha=1.0, alpha_dev=None, table=None, workspace=None,
+                       sched=SCHED_AUTO):
+    """The launches of a wgrad_batch_plan over problems = [(M, N, A, lda, B, ldb, C)] (dense C): the body as one
+    gemm_wgrad_batch launch, the tail as gemm_wgrad_grouped launches of at most GROUP_MAX problems at the plan's
+    split (workspace: split x the largest such group's outputs, in floats)."""
+    body, tail, split = plan
+    if body:
+        gemm_wgrad_batch([problems[i] for i in body], K, accumulate=accumulate, alpha=alpha, alpha_dev=alpha_dev,
+                         table=table, sched=sched)
+    for j in range(0, len(tail), GROUP_MAX):
+        gemm_wgrad_grouped([problems[i] for i in tail[j:j + GROUP_MAX]], K, accumulate=accumulate, alpha=alpha,
+                           alpha_dev=alpha_dev, workspace=workspace, splits=split, sched=sched)
 
 
 def wgrad_splits(M, N, K, cus=256):

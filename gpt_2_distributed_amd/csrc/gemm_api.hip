@@ -3,6 +3,8 @@
 // splitk_reduce.hip).
 //
 //   C[m,n] (op)= epilogue( alpha * sum_k A(m,k) * B(n,k) )
+#include <mutex>
+
 #include "common.h"
 #include "gemm_params.h"
 #include "gpt2mi.h"
@@ -149,6 +151,118 @@ GPT2MI_EXPORT int gpt2mi_gemm_wgrad_grouped(int count, const int* M, const int* 
   const int rc = gpt2mi::gemm_pp_launch_grouped(plan, G, s);
   if (rc) return rc;
   return gpt2mi::splitk_reduce_grouped(slab, out, n, count, plan.splits, accumulate, s);
+}
+
+namespace {
+
+// Pinned staging for the problem tables of gpt2mi_gemm_wgrad_batch: kStageSlots slots per device in rotation, each
+// with the event of its last upload. A slot is rewritten only after that copy has run, a wait only a caller more than
+// kStageSlots batched launches ahead of the GPU ever meets: the upload is an asynchronous copy from pinned memory on the
+// caller's stream, ordered before the launch, and the host waits for nothing the stream has not finished long ago.
+constexpr int kStageSlots = 8, kStageDevices = 16;
+struct TableStage {
+  std::mutex mu;
+  char* host = nullptr;  // kStageSlots x kStageBytes
+  hipEvent_t done[kStageSlots] = {};
+  bool pending[kStageSlots] = {};
+  unsigned next = 0;
+};
+constexpr size_t kStageBytes = (gemm_batch_table_bytes(kBatchMax) + 255) / 256 * 256;
+static_assert(sizeof(GemmParams) % alignof(GemmParams) == 0 && alignof(GemmParams) >= alignof(int), "table layout");
+TableStage g_stage[kStageDevices];
+
+// table (device) <- the `bytes` that fill(host slot) writes, on stream s
+template <typename Fill>
+int upload_table(void* table, size_t bytes, hipStream_t s, Fill fill) {
+  int dev = 0;
+  GPT2MI_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kStageDevices,
+                 "gemm_wgrad_batch: no current device below %d", kStageDevices);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess) {  // (a stream the query does not take is not a capturing one)
+    (void)hipGetLastError();
+    cap = hipStreamCaptureStatusNone;
+  }
+  GPT2MI_REQUIRE(cap == hipStreamCaptureStatusNone,
+                 "gemm_wgrad_batch: the stream is capturing (the table upload waits on events: not capturable)");
+  TableStage& st = g_stage[dev];
+  std::lock_guard<std::mutex> lock(st.mu);
+  if (!st.host) {  // (host is set last: a failed first call is tried again from the event it stopped at)
+    for (int i = 0; i < kStageSlots; ++i)
+      GPT2MI_REQUIRE(st.done[i] != nullptr || hipEventCreateWithFlags(&st.done[i], hipEventDisableTiming) == hipSuccess,
+                     "gemm_wgrad_batch: hipEventCreate failed");
+    void* h = nullptr;
+    GPT2MI_REQUIRE(hipHostMalloc(&h, kStageSlots * kStageBytes, hipHostMallocDefault) == hipSuccess && h != nullptr,
+                   "gemm_wgrad_batch: no pinned staging memory");
+    st.host = (char*)h;
+  }
+  const unsigned slot = st.next++ % kStageSlots;
+  if (st.pending[slot])
+    GPT2MI_REQUIRE(hipEventSynchronize(st.done[slot]) == hipSuccess, "gemm_wgrad_batch: staging slot wait failed");
+  char* h = st.host + slot * kStageBytes;
+  fill(h);
+  GPT2MI_REQUIRE(hipMemcpyAsync(table, h, bytes, hipMemcpyHostToDevice, s) == hipSuccess,
+                 "gemm_wgrad_batch: table upload failed");
+  GPT2MI_REQUIRE(hipEventRecord(st.done[slot], s) == hipSuccess, "gemm_wgrad_batch: hipEventRecord failed");
+  st.pending[slot] = true;
+  return 0;
+}
+
+}  // namespace
+
+GPT2MI_EXPORT int gpt2mi_gemm_wgrad_batch_max(void) { return kBatchMax; }
+GPT2MI_EXPORT size_t gpt2mi_gemm_wgrad_batch_scratch(int count) {
+  return count >= 1 && count <= kBatchMax ? gemm_batch_table_bytes(count) : 0;
+}
+
+// `count` full-tile weight gradients over the same K tokens as ONE launch without split-K: every block owns one 256x256
+// output tile of one problem, accumulates it in registers over all K tokens and writes (or accumulates into) C once. No
+// slabs, no reduction launch: what a step with many same-K weight gradients (every GPT2Block's four, deferred to the end
+// of the trunk backward) needs to fill whole rounds of CUs without splitting tiles. Each C_g holds the bits
+// gpt2mi_gemm_wgrad(M_g, N_g, K, ..., splits = 1) gives it.
+GPT2MI_EXPORT int gpt2mi_gemm_wgrad_batch(int count, const int* M, const int* N, int K, const uint16_t* const* A,
+                                          const int* lda, const uint16_t* const* B, const int* ldb, float* const* C,
+                                          const int* ldc, int accumulate, float alpha, const float* alpha_dev,
+                                          void* table, size_t table_bytes, int sched, void* stream) {
+  GPT2MI_REQUIRE(count >= 1 && count <= kBatchMax, "gemm_wgrad_batch: count=%d (1..%d)", count, kBatchMax);
+  GPT2MI_REQUIRE(K % 128 == 0 && K > 0, "gemm_wgrad_batch: K=%d must be a multiple of 128", K);
+  GPT2MI_REQUIRE((sched & ~(GPT2MI_SCHED_NO_PERSISTENT | GPT2MI_SCHED_SHARED_CUS)) == 0,
+                 "gemm_wgrad_batch: bad sched %#x", sched);
+  long long tiles = 0;
+  for (int g = 0; g < count; ++g) {
+    GPT2MI_REQUIRE(M[g] > 0 && N[g] > 0 && M[g] % 256 == 0 && N[g] % 256 == 0,
+                   "gemm_wgrad_batch: problem %d is %d x %d (multiples of 256 only)", g, M[g], N[g]);
+    GPT2MI_REQUIRE(A[g] && B[g] && C[g] && lda[g] >= M[g] && ldb[g] >= N[g] && ldc[g] >= N[g] && ldc[g] % 4 == 0 &&
+                       lda[g] % 8 == 0 && ldb[g] % 8 == 0,
+                   "gemm_wgrad_batch: problem %d: null operand or bad lda=%d ldb=%d ldc=%d", g, lda[g], ldb[g], ldc[g]);
+    tiles += (long long)(M[g] / 256) * (N[g] / 256);
+  }
+  GPT2MI_REQUIRE(tiles < (1ll << 30), "gemm_wgrad_batch: %lld tiles", tiles);
+  const size_t bytes = gemm_batch_table_bytes(count);
+  GPT2MI_REQUIRE(table != nullptr && table_bytes >= bytes && (uintptr_t)table % 16 == 0,
+                 "gemm_wgrad_batch: table scratch of %zu bytes < %zu (gpt2mi_gemm_wgrad_batch_scratch), or not 16-B aligned",
+                 table_bytes, bytes);
+  const GemmPlan plan = gpt2mi::plan_wgrad_batch(count, M, N, K, sched);
+  GPT2MI_REQUIRE(plan.family != GemmFamily::Refused, "gemm_wgrad_batch: refused by the planner");
+  hipStream_t s = (hipStream_t)stream;
+  GemmBatch G{};
+  G.p = (const GemmParams*)table;
+  G.prefix = (const int*)((const char*)table + (size_t)count * sizeof(GemmParams));
+  G.count = count;
+  G.tiles = plan.grid;
+  const int rc = upload_table(table, bytes, s, [&](char* h) {
+    GemmParams* p = (GemmParams*)h;
+    int* prefix = (int*)(h + (size_t)count * sizeof(GemmParams));
+    prefix[0] = 0;
+    for (int g = 0; g < count; ++g) {
+      p[g] = gemm_params(plan, M[g], N[g], K, A[g], lda[g], B[g], ldb[g], alpha, alpha_dev);
+      p[g].C = C[g];
+      p[g].ldc = ldc[g];
+      p[g].accumulate = accumulate;
+      prefix[g + 1] = prefix[g] + (M[g] / 256) * (N[g] / 256);
+    }
+  });
+  if (rc) return rc;
+  return gpt2mi::gemm_pp_launch_batch(plan, G, s);
 }
 
 // The same weight gradient with the second operand given TRANSPOSED, k-contiguous: Bt stored [N][K] (X^T, e.g. the

@@ -37,6 +37,20 @@ struct GemmGroup {
   int count, tiles;
 };
 
+// Batched weight gradients (gpt2mi_gemm_wgrad_batch; gemm_pp.hip gemm_pp_kernel, BAT): up to kBatchMax unsplit problems
+// in one launch. The table is too large for a kernel argument (kBatchMax x sizeof(GemmParams) against 4 KiB), so it
+// lives in device memory: p[count] and prefix[count + 1] (the output tiles of problems 0 .. g-1) in the caller's
+// scratch, uploaded stream-ordered ahead of the launch.
+using gpt2mi::kBatchMax;
+struct GemmBatch {
+  const GemmParams* p;
+  const int* prefix;
+  int count, tiles;
+};
+constexpr size_t gemm_batch_table_bytes(int count) {
+  return (size_t)count * sizeof(GemmParams) + (size_t)(count + 1) * sizeof(int);
+}
+
 namespace gpt2mi {
 // CUs of the current device rounded down to a multiple of the 8 XCDs (256 when no device answers): plan_gemm's `cus`
 int num_cus();
@@ -49,6 +63,7 @@ inline int no_instance(const char* file, const GemmPlan& plan) {
 }
 int gemm_pp_launch(const GemmPlan& plan, const GemmParams& P, hipStream_t s);          // gemm_pp.hip
 int gemm_pp_launch_grouped(const GemmPlan& plan, const GemmGroup& G, hipStream_t s);   // gemm_pp.hip
+int gemm_pp_launch_batch(const GemmPlan& plan, const GemmBatch& G, hipStream_t s);     // gemm_pp.hip
 int gemm256_launch(const GemmPlan& plan, const GemmParams& P, hipStream_t s);          // gemm256.hip
 int gemm128_launch(const GemmPlan& plan, const GemmParams& P, hipStream_t s);          // gemm.hip
 // Split-K slab sums (splitk_reduce.hip), every one in split order (deterministic):

@@ -243,4 +243,28 @@ constexpr GemmPlan plan_wgrad_grouped(int count, const int* M, const int* N, int
   return p;
 }
 
+// gpt2mi_gemm_wgrad_batch: `count` full-tile weight gradients over the same K tokens as one ping-pong launch, one block
+// per output tile over all K (plan_wgrad's one-split case for every problem: the EPI_F32 epilogue writes or accumulates
+// C itself; no slabs, no reduction). The problem table lives in device memory (gemm_params.h GemmBatch): 4 x 36 problems
+// (a 36-block model's four matrices) and room to spare
+constexpr int kBatchMax = 256;
+constexpr GemmPlan plan_wgrad_batch(int count, const int* M, const int* N, int K, int sched) {
+  GemmPlan p{};
+  if (count < 1 || count > kBatchMax || K <= 0 || K % 128 != 0 || (sched & ~kSchedFlags) != 0) return p;
+  int tiles = 0;
+  for (int g = 0; g < count; ++g) {
+    if (M[g] <= 0 || N[g] <= 0 || M[g] % 256 != 0 || N[g] % 256 != 0) return p;
+    tiles += (M[g] / 256) * (N[g] / 256);
+  }
+  p.family = GemmFamily::PingPong;
+  p.a_t = p.b_t = true;
+  p.epi = EPI_F32;
+  p.map = 3;
+  p.grouped = true;
+  p.grid = tiles;
+  p.splits = 1;
+  p.k_per_split = K;
+  return p;
+}
+
 }  // namespace gpt2mi

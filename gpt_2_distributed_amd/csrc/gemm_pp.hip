@@ -284,11 +284,31 @@ __device__ __forceinline__ void tile_of(int pid, int tiles_m, int tiles_n, int& 
 // kernel argument is the problem table then; P below is a reference into it (for GRP = false, to the one problem), so
 // the single-problem kernels compile exactly as before (a by-value copy or a device-function parameter made the
 // persistent residual kernels spill).
-template <bool GRP>
-using PPArg = typename std::conditional<GRP, GemmGroup, GemmParams>::type;
-template <bool GRP>
-__device__ __forceinline__ const GemmParams& pp_problem(const PPArg<GRP>& a, int& item) {
-  if constexpr (GRP) {
+// BAT (with GRP): a batched weight-gradient launch (gpt2mi_gemm_wgrad_batch): up to kBatchMax unsplit problems, one
+// block per output tile over all K tokens, the EPI_F32 epilogue into C itself. The table is in device memory (GemmBatch);
+// a block finds its problem by a binary search of the tile prefix (wave-uniform: scalar loads) and copies that one entry
+// into registers (wave-uniform again, SGPRs) before anything is stored, so P stays what the single-problem code reads.
+// Items are problem-major in table order (the XCD remap gives each XCD a contiguous item range: the 32 blocks an XCD
+// runs at a time walk the same token rows of one or two problems' panels), GM-grouped inside a problem.
+template <bool GRP, bool BAT>
+using PPArg = typename std::conditional<BAT, GemmBatch, typename std::conditional<GRP, GemmGroup, GemmParams>::type>::type;
+template <bool BAT>
+using PPLocal = typename std::conditional<BAT, GemmParams, char>::type;
+template <bool GRP, bool BAT>
+__device__ __forceinline__ const GemmParams& pp_problem(const PPArg<GRP, BAT>& a, [[maybe_unused]] PPLocal<BAT>& local,
+                                                        int& item) {
+  if constexpr (BAT) {
+    const int t = xcd_remap(blockIdx.x, a.tiles);
+    int lo = 0, hi = a.count - 1;  // the last g with prefix[g] <= t
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (a.prefix[mid] <= t) lo = mid;
+      else hi = mid - 1;
+    }
+    item = t - a.prefix[lo];
+    local = a.p[lo];
+    return local;
+  } else if constexpr (GRP) {
     const int nsplit = (a.p[0].K + a.p[0].k_per_split - 1) / a.p[0].k_per_split;
     const int it = xcd_remap(blockIdx.x, a.tiles * nsplit);
     const int split = it / a.tiles, t = it - split * a.tiles;
@@ -304,10 +324,12 @@ __device__ __forceinline__ const GemmParams& pp_problem(const PPArg<GRP>& a, int
   }
 }
 template <bool A_T, bool B_T, int EPI, int MAP, bool PERSIST = false, bool BND = false, bool DYN = false,
-          bool GRP = false>
-__global__ __launch_bounds__(kThreads, 1) void gemm_pp_kernel(PPArg<GRP> KA) {
+          bool GRP = false, bool BAT = false>
+__global__ __launch_bounds__(kThreads, 1) void gemm_pp_kernel(PPArg<GRP, BAT> KA) {
+  static_assert(!BAT || (GRP && !PERSIST && !BND && EPI == EPI_F32), "BAT: the unsplit full-tile weight gradients");
   int item0;
-  const GemmParams& P = pp_problem<GRP>(KA, item0);
+  [[maybe_unused]] PPLocal<BAT> local;
+  const GemmParams& P = pp_problem<GRP, BAT>(KA, local, item0);
   constexpr bool AIL = MAP & 1, BIL = MAP & 2;  // interleaved half-tile maps (half_map; the transposed operands')
   static_assert(!PERSIST || MAP == 0, "the persistent epilogue assumes the contiguous half-tile map");
   // phase-4 B reads (see ktile): the persistent schedule and the weight gradients (both operands by buffer DMA); the
@@ -1026,6 +1048,11 @@ int num_cus() {
 int gemm_pp_launch_grouped(const GemmPlan& plan, const GemmGroup& G, hipStream_t s) {
   gemm_pp_kernel<true, true, EPI_SLAB, 3, false, false, false, true><<<dim3(plan.grid), kThreads, 0, s>>>(G);
   return check_launch("gemm_pp_grouped");
+}
+
+int gemm_pp_launch_batch(const GemmPlan& plan, const GemmBatch& G, hipStream_t s) {
+  gemm_pp_kernel<true, true, EPI_F32, 3, false, false, false, true, true><<<dim3(plan.grid), kThreads, 0, s>>>(G);
+  return check_launch("gemm_pp_batch");
 }
 
 // wgrad (both operands m-contiguous): this kernel since the LDS-DMA went to inline asm (lm_head wgrad 4046 vs

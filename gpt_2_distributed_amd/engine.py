@@ -29,6 +29,7 @@ HBM layout per (B, T) workspace (M = B*T tokens, C = n_embd, Vp = vocab padded t
              (returned as a [B,T,V] view that stays valid as long as the caller holds it)
   backward scratch: dres fp32 [M,C], dres_bf bf16 [M,C], dln bf16 [M,C], dU bf16 [M,4C],
              dqkv bf16 [M,3C], delta fp32 [B*H,T], dqkv_cs fp32 [M/32,3C]
+  deferred weight gradients (Engine.DEFER_WGRADS): per block its own dres_bf, dproj bf16 [M,C], dU, dqkv
 
 Evaluation (``Engine.score``) is forward-only and has its own, small workspace (``EvalWorkspace``: two residual
 buffers, ONE block's activations, ln_f, the loss rows): no logits tensor (bf16: the lm_head runs fused with the
@@ -45,6 +46,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as K
+from ._lib import wgrad_batch_plan as K_wgrad_batch_plan
 from ._lib import wgrad_group_splits as K_wgrad_group_splits
 from ._lib import wgrad_splits as K_wgrad_splits
 from .dropout_keys import MULTIPLIERS
@@ -186,6 +188,69 @@ class Workspace(Scratch):
         self.lse_ce = e(M, dt=F32)
         self.inv_count = e(1, dt=F32)
         self.dscale = e(1, dt=F32)
+        self._deferred = None
+
+    def deferred(self, cfg):
+        """The deferred weight-gradient mode's buffers (Engine._wgrad_mode), allocated at its first backward: every
+        block's own dU, dqkv and the two branch gradients (fc2's and proj's dY), which the dgrad, attention and
+        LayerNorm-backward kernels write in place of the shared scratch so that all of them are still there after block
+        0; the problem table's scratch; and the tail's slabs where the shared ones are too small."""
+        if self._deferred is None:
+            self._deferred = _Deferred(self, cfg)
+        return self._deferred
+
+
+def deferred_bytes(cfg, M) -> int:
+    """Bytes of the per-block operand buffers the deferred weight-gradient mode adds (bf16: dU [M,4C], dqkv [M,3C] and
+    two [M,C] branch gradients per block)."""
+    return cfg.n_layer * 18 * M * cfg.n_embd
+
+
+# what the deferred mode may add to a workspace (a policy constant): GPT-2 124M at B = 64 takes 10.9 GB, 350M at B = 32
+# 14.5 GB
+DEFER_CAP_BYTES = 16 << 30
+
+
+def wgrad_mode(group: bool, defer: bool, bf16: bool, n_embd: int, M: int, bf16_slabs: bool, hooks: bool,
+               extra_bytes: int, cap: int = DEFER_CAP_BYTES) -> str:
+    """How a whole-trunk backward issues the blocks' weight gradients: "four" (one launch and one reduction per matrix),
+    "pairs" (two grouped launches per block, Engine._wgrad_group) or "deferred" (one batched launch and a split-K tail
+    after block 0, Engine._wgrad_deferred). group / defer: the GROUP_WGRADS / DEFER_WGRADS knobs. Grouping needs bf16
+    autocast with fp32 slabs, widths that are multiples of 256 and whole 128-token K-tile pairs; deferral needs that
+    too, no gradient hooks (a data-parallel wrapper wants each unit's gradients as its backward ends, to overlap their
+    reduction with the rest) and per-block operand buffers (extra_bytes) within the cap."""
+    if not (group and bf16 and n_embd % 256 == 0 and M % 128 == 0 and not bf16_slabs):
+        return "four"
+    if defer and not hooks and extra_bytes <= cap:
+        return "deferred"
+    return "pairs"
+
+
+class _DeferredBlock:
+    """A block's view of the backward scratch in the deferred mode: its own operand buffers, the shared rest."""
+
+    def __init__(self, S, e, M, C):
+        self.dres, self.dln, self.delta, self.dqkv_cs, self.wgrad_ws = S.dres, S.dln, S.delta, S.dqkv_cs, S.wgrad_ws
+        self.dres_bf = e(M, C)  # the fc2 branch gradient (written by the LayerNorm backward of the block above)
+        self.dproj = e(M, C)    # the proj branch gradient
+        self.dU = e(M, 4 * C)
+        self.dqkv = e(M, 3 * C)
+
+
+class _Deferred:
+    def __init__(self, ws, cfg):
+        C, L, M = cfg.n_embd, cfg.n_layer, ws.M
+        dev = ws.dres.device
+        e = lambda *s, dt=BF16: act_empty(*s, dtype=dt, device=dev)  # noqa: E731
+        self.blocks = [_DeferredBlock(ws, e, M, C) for _ in range(L)]
+        # the problems in the order the backward forms their operands: block L-1 first, fc2 / fc1 / proj / qkv in each
+        self.shapes = [(C, 4 * C), (4 * C, C), (C, C), (3 * C, C)] * L
+        self.plan = K_wgrad_batch_plan(self.shapes, M)
+        body, tail, split = self.plan
+        self.table = torch.empty(max(K.gemm_wgrad_batch_scratch(len(body)), 16), dtype=torch.uint8, device=dev)
+        need = max((split * sum(self.shapes[i][0] * self.shapes[i][1] for i in tail[j:j + K.GROUP_MAX])
+                    for j in range(0, len(tail), K.GROUP_MAX)), default=0)
+        self.tail_ws = ws.wgrad_ws if ws.wgrad_ws.numel() >= need else e(need, dt=F32)
 
 
 class _Alternating:
@@ -841,8 +906,27 @@ class Engine:
     GROUP_WGRADS = os.environ.get("GPT2MI_GROUP_WGRADS", "1") != "0"
 
     def _group_ok(self, act, M) -> bool:
-        return self.GROUP_WGRADS and act == BF16 and self.cfg.n_embd % 256 == 0 and M % 128 == 0 and \
-            not self.wgrad_bf16_slabs
+        return self._wgrad_mode(act, M) != "four"
+
+    # All of the trunk's block weight gradients after block 0's backward (gpt2mi_gemm_wgrad_batch): issued one block at
+    # a time, a block's 108 output tiles (GPT-2 124M) fill 256 CUs only when every tile is split 7 ways over the
+    # tokens, which costs fp32 slabs written and read back (2.3 GB a step), 24 reductions and 24 single-round launches.
+    # The 12 blocks' 1 296 tiles together are five whole rounds of unsplit tiles (each accumulated in registers over
+    # all tokens and written once) plus a remainder that one split-K round takes (_lib.wgrad_batch_plan). The operands
+    # must outlive their block for that: every block gets its own dU, dqkv and branch gradients (Workspace.deferred),
+    # written in place by the kernels that form them. Off with gradient hooks installed (_wgrad_mode).
+    # GPT2MI_DEFER_WGRADS=0: the two grouped launches per block.
+    DEFER_WGRADS = os.environ.get("GPT2MI_DEFER_WGRADS", "1") != "0"
+
+    def _wgrad_mode(self, act, M) -> str:
+        hooks = self.grad_sync is not None or self.param_provider is not None or self.store is not None
+        return wgrad_mode(self.GROUP_WGRADS, self.DEFER_WGRADS, act == BF16, self.cfg.n_embd, M, self.wgrad_bf16_slabs,
+                          hooks, deferred_bytes(self.cfg, M))
+
+    def _wgrad_deferred(self, D, M, probs):
+        with self._probe("wgrad"):
+            K.gemm_wgrad_planned(probs, M, D.plan, accumulate=not self._grad_fresh, table=D.table,
+                                 workspace=D.tail_ws, sched=self._sched())
 
     def _wgrad_or_defer(self, S, act, m, n, M, a, lda, b, ldb, out, defer):
         if defer is None:
@@ -855,9 +939,10 @@ class Engine:
             K.gemm_wgrad_grouped(probs, M, accumulate=not self._grad_fresh, workspace=S.wgrad_ws,
                                  splits=K_wgrad_group_splits([(q[0], q[1]) for q in probs], M), sched=self._sched())
 
-    def _mlp_bwd(self, l, A, S, dY, dx_out, M, act, defer=None):
+    def _mlp_bwd(self, l, A, S, dY, dx_out, M, act, defer=None, flush=True):
         """dY = grad of the fc2 output with drop2 applied (its bias grad already taken) -> dx_out = grad of
-        the MLP input (bf16), weight grads of fc1/fc2 (or their problems appended to ``defer``) and the fc1 bias grad."""
+        the MLP input (bf16), weight grads of fc1/fc2 (or their problems appended to ``defer``, launched as a group
+        here when ``flush``) and the fc1 bias grad."""
         C = self.cfg.n_embd
         pre = f"transformer.h.{l}."
         self._dgrad(act, M, S.dU, dY, pre + "mlp.fc2.weight", 4 * C, C, K.EPI_GELU_BWD, aux=A.dgelu, ldaux=4 * C,
@@ -865,7 +950,7 @@ class Engine:
         self._wgrad_or_defer(S, act, C, 4 * C, M, dY, C, A.h, 4 * C, self.g(pre + "mlp.fc2.weight"), defer)
         self._dgrad(act, M, dx_out, S.dU, pre + "mlp.fc1.weight", C, 4 * C)
         self._wgrad_or_defer(S, act, 4 * C, C, M, S.dU, 4 * C, A.ln2, C, self.g(pre + "mlp.fc1.weight"), defer)
-        if defer:  # fc2 + fc1, while their operands are the latest written
+        if defer and flush:  # fc2 + fc1, while their operands are the latest written
             self._wgrad_group(S, M, defer)
             defer.clear()
 
@@ -885,23 +970,31 @@ class Engine:
         else:
             K.colsum_bf16(S.dqkv, self.g(pre + "attn.qkv.bias"), M, 3 * C, 3 * C)
 
-    def _block_bwd(self, l, A, S, x_in, B, T, act, pr, pa, seeds, last):
+    def _block_bwd(self, l, A, S, x_in, B, T, act, pr, pa, seeds, last, D=None, probs=None):
         """S.dres = grad of the block output; S.dres_bf = its fc2 branch grad (drop2 applied) ->
-        S.dres = grad of the block input; unless `last`, S.dres_bf = the fc2 branch grad of block l-1."""
+        S.dres = grad of the block input; unless `last`, S.dres_bf = the fc2 branch grad of block l-1.
+        D (the deferred mode, Workspace.deferred): the block's operands live in D.blocks[l] (its dres_bf the fc2 branch
+        grad, its dproj the proj one; the fc2 branch grad of block l-1 goes to D.blocks[l-1].dres_bf) and its four
+        weight-gradient problems are appended to ``probs`` instead of being launched."""
         C = self.cfg.n_embd
         M = B * T
         pre = f"transformer.h.{l}."
-        grp = [] if self._group_ok(act, M) else None
-        self._mlp_bwd(l, A, S, S.dres_bf, S.dln, M, act, grp)
+        if D is not None:
+            S = D.blocks[l]
+            dproj, dnext, grp = S.dproj, (None if last else D.blocks[l - 1].dres_bf), probs
+        else:
+            dproj = dnext = S.dres_bf
+            grp = [] if self._group_ok(act, M) else None
+        self._mlp_bwd(l, A, S, S.dres_bf, S.dln, M, act, grp, flush=D is None)
         K.layernorm_bwd(A.xmid, self.p(pre + "ln2.weight"), A.m2, A.r2, S.dln, S.dres, self.g(pre + "ln2.weight"),
-                        self.g(pre + "ln2.bias"), S.dres_bf, self.g(pre + "attn.proj.bias"), M, C, pr,
+                        self.g(pre + "ln2.bias"), dproj, self.g(pre + "attn.proj.bias"), M, C, pr,
                         seeds[("proj", l)])
-        self._attn_bwd(l, A, S, S.dres_bf, S.dln, B, T, act, pa, seeds, grp)
-        if grp:  # proj + qkv, before LN1's backward overwrites dres_bf (the proj weight gradient's operand)
+        self._attn_bwd(l, A, S, dproj, S.dln, B, T, act, pa, seeds, grp)
+        if grp and D is None:  # proj + qkv, before LN1's backward overwrites dres_bf (the proj wgrad's operand)
             self._wgrad_group(S, M, grp)
         if not last:
             K.layernorm_bwd(x_in, self.p(pre + "ln1.weight"), A.m1, A.r1, S.dln, S.dres,
-                            self.g(pre + "ln1.weight"), self.g(pre + "ln1.bias"), S.dres_bf,
+                            self.g(pre + "ln1.weight"), self.g(pre + "ln1.bias"), dnext,
                             self.g(f"transformer.h.{l-1}.mlp.fc2.bias"), M, C, pr, seeds[("fc2", l - 1)])
         else:
             K.layernorm_bwd(x_in, self.p(pre + "ln1.weight"), A.m1, A.r1, S.dln, S.dres,
@@ -914,16 +1007,25 @@ class Engine:
         B, T = idx.shape
         M = B * T
         x = ws.x
+        # the blocks' weight gradients: launched block by block, or all of them after block 0 (_wgrad_mode)
+        D = ws.deferred(self.cfg) if self._wgrad_mode(act, M) == "deferred" else None
+        probs = [] if D is not None else None
         # ln_f backward starts the residual gradient; emits the fc2 branch grad of the last block
         self._unit_bwd("head")
         K.layernorm_bwd(x[L], self.p("transformer.ln_f.weight"), ws.mf, ws.rf, ws.dln, ws.dres,
-                        self.g("transformer.ln_f.weight"), self.g("transformer.ln_f.bias"), ws.dres_bf,
+                        self.g("transformer.ln_f.weight"), self.g("transformer.ln_f.bias"),
+                        D.blocks[L - 1].dres_bf if D is not None else ws.dres_bf,
                         self.g(f"transformer.h.{L-1}.mlp.fc2.bias"), M, C, pr, seeds[("fc2", L - 1)], dres_init=True)
         self._ready("head")
         for l in reversed(range(L)):
             self._unit_bwd(f"h.{l}")
-            self._block_bwd(l, ws.blocks[l], ws, x[l], B, T, act, pr, pa, seeds, last=(l == 0))
-            self._ready(f"h.{l}")
+            self._block_bwd(l, ws.blocks[l], ws, x[l], B, T, act, pr, pa, seeds, last=(l == 0), D=D, probs=probs)
+            if D is None:
+                self._ready(f"h.{l}")
+        if D is not None:
+            self._wgrad_deferred(D, M, probs)
+            for l in reversed(range(L)):
+                self._ready(f"h.{l}")
         # embedding backward: atomics into the tied wte grad (the lm_head wgrad already wrote it)
         self._unit_bwd("embed")
         K.embed_bwd(idx, ws.dres, self.g("transformer.wte.weight"), self.g("transformer.wpe.weight"), B, T, C, pr,

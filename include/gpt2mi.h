@@ -28,7 +28,7 @@ extern "C" {
 
 #define GPT2MI_ABI_VERSION 24
 /* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
-#define GPT2MI_ABI_MINOR 2
+#define GPT2MI_ABI_MINOR 3
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -126,6 +126,23 @@ int gpt2mi_gemm_wgrad_grouped(int count, const int* M, const int* N, int K, cons
                               const uint16_t* const* B, const int* ldb, float* const* C, int accumulate, float alpha,
                               const float* alpha_dev, float* workspace, size_t workspace_floats, int splits, int sched,
                               void* stream);
+
+/* Batched weight gradients (v24.3; the same autograd wgrads, for every GPT2Block of the model at once): for g < count
+ * (<= gpt2mi_gemm_wgrad_batch_max(), at least 4 x 36), C[g][M[g]][N[g]] (+)= alpha*(alpha_dev?) * A[g]^T B[g] over the
+ * same K tokens as ONE launch WITHOUT split-K: one block per 256x256 output tile over all K, which writes or accumulates
+ * C itself (no slabs, no reduction launch). Host arrays of count entries; every M[g], N[g] a multiple of 256, K of 128,
+ * lda / ldb multiples of 8, ldc[g] >= N[g] a multiple of 4. Each C[g] gets the bits gpt2mi_gemm_wgrad gives it with
+ * splits = 1. table: device scratch of gpt2mi_gemm_wgrad_batch_scratch(count) bytes, 16-byte aligned, which receives the
+ * problem table by an asynchronous copy on `stream` ahead of the launch (no host synchronisation; not capturable into
+ * a graph); it must stay untouched until the launch has run. The copy's source is pinned host staging the library keeps
+ * for it (8 slots of 34 KB per device, allocated at the first call: the one allocation behind this ABI, host memory
+ * only). sched as gpt2mi_gemm_wgrad_grouped. */
+int gpt2mi_gemm_wgrad_batch(int count, const int* M, const int* N, int K, const uint16_t* const* A, const int* lda,
+                            const uint16_t* const* B, const int* ldb, float* const* C, const int* ldc, int accumulate,
+                            float alpha, const float* alpha_dev, void* table, size_t table_bytes, int sched,
+                            void* stream);
+size_t gpt2mi_gemm_wgrad_batch_scratch(int count); /* 0 for a count outside 1..max */
+int gpt2mi_gemm_wgrad_batch_max(void);
 
 /* K4-K8: causal flash attention, head_dim 64 — model.py:124-155. q/k/v read from qkv [B*T, 3C];
  * out [B*T, C] head-merged; lse [B*H, T] (natural log of the 1/sqrt(D)-scaled scores). */
