@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
 # additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
-ABI_MINOR = 3
+ABI_MINOR = 4
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -153,12 +153,19 @@ _SIGS = {
     # plan, V, W, eos, pos0, lo (HOST arrays), n, tok, seq, ld_seq, cum, done, parents, workspace, workspace_bytes, stream
     "gpt2mi_decode_beam_search": [_p, _c_int, _c_int, ctypes.c_int64, _p, _p, _c_int, _p, _p, _c_int, _p, _p, _p, _p,
                                   _c_size, _p],
+    # v24.4 constraints: gpt2mi_sample_logprobs' list with (const gpt2mi_constraints* con) before the stream;
+    # gpt2mi_decode_generate_logprobs' list with it at the end
+    "gpt2mi_sample_constrained": [_p, _c_int, _c_int, _c_int, _c_float, _c_int, _c_float, _c_u64, _p, _p, ctypes.c_int64,
+                                  _p, _p, _p, _c_int, _p, _p, _p, _p, _p, _p],
+    "gpt2mi_decode_generate_constrained": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _p, _p, _c_int,
+                                           _p, _p, _c_int, _p, _p, _c_float, _c_float, _c_float, _p, _p, _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
                 "gpt2mi_beam_select": 2, "gpt2mi_beam_reorder_workspace": 2, "gpt2mi_beam_reorder": 2,
                 "gpt2mi_decode_beam_search": 2, "gpt2mi_gemm_wgrad_batch": 3, "gpt2mi_gemm_wgrad_batch_scratch": 3,
-                "gpt2mi_gemm_wgrad_batch_max": 3}
+                "gpt2mi_gemm_wgrad_batch_max": 3, "gpt2mi_sample_constrained": 4,
+                "gpt2mi_decode_generate_constrained": 4}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
              "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size}
@@ -845,6 +852,18 @@ class Penalties(ctypes.Structure):
                 ("ld_hist", _c_int), ("hist_rows", _c_int), ("hist_row", _p), ("gen_start", _p)]
 
 
+def _penalties_arg(B, repetition, presence, frequency, hist, hist_row, gen_start):
+    """(the gpt2mi_penalties of the keywords, the host arrays it points at, which must outlive the call)."""
+    rows, starts = _host_ints(hist_row), _host_ints(gen_start)
+    if any(a is not None and len(a) != B for a in (rows, starts)):
+        raise KernelError(f"hist_row / gen_start must have B={B} entries")
+    pen = Penalties(float(repetition), float(presence), float(frequency), _ptr(hist),
+                    0 if hist is None else hist.stride(0), 0 if hist is None else hist.size(0),
+                    ctypes.cast(rows, _p) if rows is not None else None,
+                    ctypes.cast(starts, _p) if starts is not None else None)
+    return pen, (rows, starts)
+
+
 def sample_penalized(logits, V, temperature, top_k, top_p, seed, pos, tok_out, row_id=None, eos=None, done=None,
                      seq_out=None, probs_out=None, repetition=1.0, presence=0.0, frequency=0.0, hist=None,
                      hist_row=None, gen_start=None, logits_out=None):
@@ -853,13 +872,7 @@ def sample_penalized(logits, V, temperature, top_k, top_p, seed, pos, tok_out, r
     the penalised logits."""
     scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
     B = logits.size(0)
-    rows, starts = _host_ints(hist_row), _host_ints(gen_start)  # (kept alive to the end of the call)
-    if any(a is not None and len(a) != B for a in (rows, starts)):
-        raise KernelError(f"hist_row / gen_start must have B={B} entries")
-    pen = Penalties(float(repetition), float(presence), float(frequency), _ptr(hist),
-                    0 if hist is None else hist.stride(0), 0 if hist is None else hist.size(0),
-                    ctypes.cast(rows, _p) if rows is not None else None,
-                    ctypes.cast(starts, _p) if starts is not None else None)
+    pen, _alive_pen = _penalties_arg(B, repetition, presence, frequency, hist, hist_row, gen_start)
     _sample_call("gpt2mi_sample_penalized", logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out,
                  ctypes.byref(pen), _ptr(logits_out))
 
@@ -928,13 +941,7 @@ def sample_logprobs(logits, V, temperature, top_k, top_p, seed, pos, tok_out, lo
     (generation.token_logprobs). logprob None: lp = NULL, gpt2mi_sample_penalized itself under this entry's name."""
     scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
     B = logits.size(0)
-    rows, starts = _host_ints(hist_row), _host_ints(gen_start)  # (kept alive to the end of the call)
-    if any(a is not None and len(a) != B for a in (rows, starts)):
-        raise KernelError(f"hist_row / gen_start must have B={B} entries")
-    pen = Penalties(float(repetition), float(presence), float(frequency), _ptr(hist),
-                    0 if hist is None else hist.stride(0), 0 if hist is None else hist.size(0),
-                    ctypes.cast(rows, _p) if rows is not None else None,
-                    ctypes.cast(starts, _p) if starts is not None else None)
+    pen, _alive_pen = _penalties_arg(B, repetition, presence, frequency, hist, hist_row, gen_start)
     lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, col, B)
     _sample_call("gpt2mi_sample_logprobs", logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out,
                  ctypes.byref(pen), _ptr(logits_out), lp)
@@ -951,6 +958,71 @@ def decode_generate_logprobs(plan: DecodePlan, V, temperature, top_k, top_p, see
     lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, None, plan.B)
     _generate_call("gpt2mi_decode_generate_logprobs", plan, V, scalars, pos0, n, tok, row_id, seq, done,
                    float(repetition), float(presence), float(frequency), _host_ints(gen_start), lp)
+
+
+# ---- v24.4: logit bias, min-p, minimum length and stop sequences in the sampler (csrc/sample_con.hip, csrc/decode.hip) --
+STOP_MAX_SEQS, STOP_MAX_LEN = 8, 16  # gpt2mi.h GPT2MI_STOP_MAX_SEQS / GPT2MI_STOP_MAX_LEN
+
+
+class Constraints(ctypes.Structure):
+    """gpt2mi_constraints"""
+    _fields_ = [("bias", _p), ("ld_bias", _c_int), ("bias_rows", _c_int), ("bias_row", _p), ("min_p", _c_float),
+                ("min_new", _c_int), ("n_stop", _c_int), ("stop", _p), ("stop_len", _p)]
+
+
+def _constraints_arg(logit_bias, bias_row, min_p, min_new_tokens, stop, B):
+    """(the gpt2mi_constraints of the keywords, what must outlive the call). logit_bias is a device fp32 [rows, ld] tensor
+    with contiguous rows (None: no bias), bias_row B ints (-1: none; None: row b reads row b), stop a list of token
+    lists. The values go to the entry as they are: it is the one that refuses them."""
+    if logit_bias is not None and (logit_bias.dtype != torch.float32 or logit_bias.dim() != 2 or logit_bias.stride(1) != 1):
+        raise KernelError("logit_bias must be an fp32 [rows, V] tensor with contiguous rows")
+    rows = _host_ints(bias_row)
+    if rows is not None and len(rows) != B:
+        raise KernelError(f"bias_row has {len(rows)} entries for B={B} rows")
+    stop = [[int(t) for t in s] for s in (stop or [])]
+    lens = _host_ints([len(s) for s in stop]) if stop else None
+    table = None
+    if stop:  # (a length the entry refuses still gets its row: the tokens past STOP_MAX_LEN are not passed on)
+        table = (ctypes.c_int32 * (len(stop) * STOP_MAX_LEN))()
+        for i, s in enumerate(stop):
+            table[i * STOP_MAX_LEN:i * STOP_MAX_LEN + min(len(s), STOP_MAX_LEN)] = s[:STOP_MAX_LEN]
+    con = Constraints(_ptr(logit_bias), 0 if logit_bias is None else logit_bias.stride(0),
+                      0 if logit_bias is None else logit_bias.size(0), ctypes.cast(rows, _p) if rows is not None else None,
+                      float(min_p), int(min_new_tokens), len(stop), ctypes.cast(table, _p) if stop else None,
+                      ctypes.cast(lens, _p) if stop else None)
+    return ctypes.byref(con), (con, rows, lens, table)
+
+
+def sample_constrained(logits, V, temperature, top_k, top_p, seed, pos, tok_out, logprob=None, top_ids=None,
+                       top_logprobs=None, col=None, row_id=None, eos=None, done=None, seq_out=None, probs_out=None,
+                       repetition=1.0, presence=0.0, frequency=0.0, hist=None, hist_row=None, gen_start=None,
+                       logits_out=None, logit_bias=None, bias_row=None, min_p=0.0, min_new_tokens=0, stop=None):
+    """gpt2mi_sample_constrained: `sample_logprobs` under generation.apply_constraints (logit_bias fp32 [rows, V], row b
+    reading row bias_row[b]; min_new_tokens holding eos back while pos[b] - gen_start[b] < it), sample_reference's min_p
+    and generation.stop_match over hist (stop: up to 8 lists of up to 16 tokens; a match sets done[b]). logits_out takes
+    the row after the bias and the eos suppression. Every keyword neutral: sample_logprobs itself under this name."""
+    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
+    B = logits.size(0)
+    pen, _alive_pen = _penalties_arg(B, repetition, presence, frequency, hist, hist_row, gen_start)
+    lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, col, B)
+    con, _alive_con = _constraints_arg(logit_bias, bias_row, min_p, min_new_tokens, stop, B)
+    _sample_call("gpt2mi_sample_constrained", logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out,
+                 ctypes.byref(pen), _ptr(logits_out), lp, con)
+
+
+def decode_generate_constrained(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, logprob=None,
+                                top_ids=None, top_logprobs=None, row_id=None, eos=None, seq=None, done=None,
+                                repetition=1.0, presence=0.0, frequency=0.0, gen_start=None, logit_bias=None,
+                                bias_row=None, min_p=0.0, min_new_tokens=0, stop=None):
+    """gpt2mi_decode_generate_constrained: `decode_generate_logprobs` with sample_constrained's keywords, seq the history
+    the stop sequences are matched in."""
+    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
+    if gen_start is not None and len(gen_start) != plan.B:
+        raise KernelError(f"gen_start has {len(gen_start)} entries for B={plan.B} rows")
+    lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, None, plan.B)
+    con, _alive_con = _constraints_arg(logit_bias, bias_row, min_p, min_new_tokens, stop, plan.B)
+    _generate_call("gpt2mi_decode_generate_constrained", plan, V, scalars, pos0, n, tok, row_id, seq, done,
+                   float(repetition), float(presence), float(frequency), _host_ints(gen_start), lp, con)
 
 
 # ---- v24.2: beam search on the device (csrc/beam.hip) ---------------------------------------------------------

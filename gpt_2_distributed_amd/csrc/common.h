@@ -44,6 +44,19 @@ int launch_sample_lp(const char* what, const float* logits, int ldl, int B, int 
                      int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, const gpt2mi_penalties* pen,
                      const int* hist_row, const int* gen_start, float* logits_out, const gpt2mi_logprobs* lp,
                      const int* col, void* stream);
+// The launch of the constrained sampling kernels (csrc/sample_con.hip), likewise: hist_row, gen_start and bias_row
+// (-1: no bias row) are B values each, col too with lp; pen may be NULL (no history), pen_on says whether its values
+// are non-neutral; lmp = fp32(log(min_p)), -inf for min_p = 0.
+int launch_sample_con(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k,
+                      float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
+                      int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, const gpt2mi_penalties* pen,
+                      bool pen_on, const int* hist_row, const int* gen_start, float* logits_out,
+                      const gpt2mi_logprobs* lp, const int* col, const gpt2mi_constraints* con, const int* bias_row,
+                      float lmp, void* stream);
+// What of a gpt2mi_constraints (gpt2mi.h v24.4) does not depend on the rows' positions: the values, the stop table and
+// the bias rows of B rows into bias_row[] (-1: none); *on = whether anything is non-neutral (csrc/sample.hip)
+int check_constraints(const char* what, const gpt2mi_constraints* con, int B, int V, int64_t eos, const uint8_t* done,
+                      int* bias_row, bool* on);
 
 // The step of csrc/decode.hip for a token loop in another unit (csrc/beam.hip), under that loop's name in messages:
 // every check of gpt2mi_decode_step_ragged at pos without a launch, and the step itself.

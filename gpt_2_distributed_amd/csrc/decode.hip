@@ -948,12 +948,13 @@ namespace {
 // The token loop with row b starting at pos0[b]: sample, then (but for the last token) step, n times. With non-neutral
 // penalty values (gpt2mi_decode_generate_penalized) seq is the history the sampler reads, row b's own row of it. With
 // `lp` (gpt2mi_decode_generate_logprobs; may be NULL) step i writes column pos0[b] + i of it: its col is NULL, the
-// sampler's "col[b] = pos[b]".
+// sampler's "col[b] = pos[b]". With a non-neutral `con` (gpt2mi_decode_generate_constrained; may be NULL) the draws are
+// gpt2mi_sample_constrained's, seq again the history and gen_start where a row's generated part begins.
 int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
                          float top_p, uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
                          int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream, float repetition = 1.f,
                          float presence = 0.f, float frequency = 0.f, const int* gen_start = nullptr,
-                         const gpt2mi_logprobs* lp = nullptr) {
+                         const gpt2mi_logprobs* lp = nullptr, const gpt2mi_constraints* con = nullptr) {
   GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
   GPT2MI_REQUIRE(V >= 1 && V <= P->Vp, "%s: V=%d not in [1, Vp=%d]", what, V, P->Vp);
   GPT2MI_REQUIRE(n >= 0, "%s: n=%d must be >= 0", what, n);
@@ -986,11 +987,23 @@ int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, f
     GPT2MI_REQUIRE((long long)max_pos + n <= lp->ld, "%s: max pos0=%d + n=%d exceeds the logprobs ld=%d", what, max_pos,
                    n, lp->ld);
   }
+  bool con_on = false;
+  if (con) {
+    int bias_row[GPT2MI_DECODE_MAX_B];
+    if (const int rc = gpt2mi::check_constraints(what, con, P->B, V, eos, done, bias_row, &con_on)) return rc;
+    GPT2MI_REQUIRE(con->n_stop == 0 || seq != nullptr, "%s: stop sequences need seq, the history buffer: it is NULL", what);
+    for (int b = 0; b < P->B && gen_start && con_on; ++b)
+      GPT2MI_REQUIRE(gen_start[b] >= 0 && gen_start[b] <= pos0[b], "%s: gen_start[%d]=%d not in [0, pos0=%d]", what, b,
+                     gen_start[b], pos0[b]);
+  }
   GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr, "%s: tok and plan->logits must not be NULL", what);
   if (const int rc = plan_shape(what, P)) return rc;  // (before the first draw, not only before the first step)
   for (int i = 0; i < n; ++i) {
     for (int b = 0; b < P->B; ++b) rp.v[b] = pos0[b] + i;
-    int rc = lp ? gpt2mi_sample_logprobs(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
+    int rc = con_on
+                 ? gpt2mi_sample_constrained(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
+                                             done, tok, seq, ld_seq, nullptr, &pen, nullptr, lp, con, stream)
+             : lp ? gpt2mi_sample_logprobs(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
                                          done, tok, seq, ld_seq, nullptr, on ? &pen : nullptr, nullptr, lp, stream)
                 : gpt2mi_sample_penalized(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
                                           done, tok, seq, ld_seq, nullptr, on ? &pen : nullptr, nullptr, stream);
@@ -1028,6 +1041,16 @@ GPT2MI_EXPORT int gpt2mi_decode_generate_logprobs(const gpt2mi_decode_plan* P, i
                                                   float frequency, const int* gen_start, const gpt2mi_logprobs* lp) {
   return decode_generate_rows("decode_generate_logprobs", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n,
                               tok, seq, ld_seq, done, stream, repetition, presence, frequency, gen_start, lp);
+}
+
+GPT2MI_EXPORT int gpt2mi_decode_generate_constrained(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
+                                                     float top_p, uint64_t seed, int64_t eos, const int* pos0,
+                                                     const uint32_t* row_id, int n, int64_t* tok, int64_t* seq,
+                                                     int ld_seq, uint8_t* done, void* stream, float repetition,
+                                                     float presence, float frequency, const int* gen_start,
+                                                     const gpt2mi_logprobs* lp, const gpt2mi_constraints* con) {
+  return decode_generate_rows("decode_generate_constrained", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n,
+                              tok, seq, ld_seq, done, stream, repetition, presence, frequency, gen_start, lp, con);
 }
 
 GPT2MI_EXPORT int gpt2mi_decode_generate(const gpt2mi_decode_plan* P, int V, float temperature, int top_k, float top_p,

@@ -35,6 +35,11 @@
 // sample_row of sample_row.h): logprob_prologue, between the load and everything that
 // changes the row, forms lse = max + log(sum exp(x - max)) of the raw row and writes the top_n alternatives; at the end
 // thread 0 loads the drawn token's raw logit and writes l_tok - lse (gpt2mi.h v24.1, generation.py token_logprobs).
+//
+// Constraints (CON, v24.4: kernels and a unit of their own once more, sample_con.hip): a bias row added after the
+// penalties, the eos held back below a minimum length, min-p as one more bound on thr, and stop sequences matched by
+// thread 0 against the history and the token it drew (gpt2mi.h v24.4, generation.py apply_constraints / stop_match).
+// sample_rows below checks a gpt2mi_constraints and sends only a non-neutral one there.
 #include "sample_row.h"
 
 namespace {
@@ -66,11 +71,13 @@ __global__ __launch_bounds__(SM_THREADS) void penalized_kernel(const float* __re
 }
 
 // gpt2mi_sample_ragged, and gpt2mi_sample with every pos[b] equal and no row_id; `what` is the entry's name in messages.
-// `pen` (may be NULL) and logits_out: gpt2mi_sample_penalized's; `lpo` (may be NULL): gpt2mi_sample_logprobs'.
+// `pen` (may be NULL) and logits_out: gpt2mi_sample_penalized's; `lpo` (may be NULL): gpt2mi_sample_logprobs'; `con` (may
+// be NULL): gpt2mi_sample_constrained's, and only a non-neutral one leaves the launches below.
 int sample_rows(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
                 uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done, int64_t* tok_out,
                 int64_t* seq_out, int ld_seq, float* probs_out, void* stream, const gpt2mi_penalties* pen = nullptr,
-                float* logits_out = nullptr, const gpt2mi_logprobs* lpo = nullptr) {
+                float* logits_out = nullptr, const gpt2mi_logprobs* lpo = nullptr,
+                const gpt2mi_constraints* con = nullptr) {
   GPT2MI_REQUIRE(B >= 1 && B <= GPT2MI_DECODE_MAX_B && V >= 1, "%s: B=%d not in [1, %d] or V=%d not positive", what, B,
                  GPT2MI_DECODE_MAX_B, V);
   GPT2MI_REQUIRE(V <= GPT2MI_SAMPLE_MAX_V, "%s: V=%d above the kernel's row capacity %d", what, V, GPT2MI_SAMPLE_MAX_V);
@@ -115,7 +122,29 @@ int sample_rows(const char* what, const float* logits, int ldl, int B, int V, fl
       col[b] = c;
     }
   }
+  bool con_on = false;
+  int bias_row[GPT2MI_DECODE_MAX_B] = {};
+  if (con) {
+    if (const int rc = gpt2mi::check_constraints(what, con, B, V, eos, done, bias_row, &con_on)) return rc;
+    const bool reads = con->n_stop > 0;  // the history, whatever the penalty values
+    GPT2MI_REQUIRE(!reads || (pen && pen->hist), "%s: stop sequences need the history buffer: hist is NULL", what);
+    for (int b = 0; b < B && con_on && !on; ++b) {  // (with penalty values on, the rows are checked above)
+      const int hr = pen && pen->hist_row ? pen->hist_row[b] : b, gs = pen && pen->gen_start ? pen->gen_start[b] : 0;
+      GPT2MI_REQUIRE(!reads || pen->ld_hist >= pos[b], "%s: ld_hist=%d < pos[%d]=%d", what, pen->ld_hist, b, pos[b]);
+      GPT2MI_REQUIRE(!reads || (hr >= 0 && hr < pen->hist_rows), "%s: hist_row[%d]=%d not in [0, hist_rows=%d)", what, b,
+                     hr, pen->hist_rows);
+      GPT2MI_REQUIRE(gs >= 0 && gs <= pos[b], "%s: gen_start[%d]=%d not in [0, pos=%d]", what, b, gs, pos[b]);
+      rows.hist_row[b] = reads ? hr : 0;
+      rows.gen_start[b] = gs;
+    }
+  }
   GPT2MI_REQUIRE(logits && tok_out, "%s: logits and tok_out must not be NULL", what);
+  if (con_on) {
+    const float lmp = con->min_p > 0.f ? (float)log((double)con->min_p) : -INFINITY;
+    return gpt2mi::launch_sample_con(what, logits, ldl, B, V, temperature, top_k, top_p, seed, keys.pos, keys.row_id, eos,
+                                     done, tok_out, seq_out, ld_seq, probs_out, pen, on, rows.hist_row, rows.gen_start,
+                                     logits_out, lpo, col, con, bias_row, lmp, stream);
+  }
   if (on) {
     if (lpo)
       return gpt2mi::launch_sample_lp(what, logits, ldl, B, V, temperature, top_k, top_p, seed, keys.pos, keys.row_id,
@@ -168,7 +197,57 @@ int check_logprobs(const char* what, const gpt2mi_logprobs* lp, int V) {
                  "%s: logprobs top_n=%d needs top_id and top_logprob: one is NULL", what, lp->top_n);
   return 0;
 }
+int check_constraints(const char* what, const gpt2mi_constraints* con, int B, int V, int64_t eos, const uint8_t* done,
+                      int* bias_row, bool* on) {
+  GPT2MI_REQUIRE(con->min_p >= 0.f && con->min_p <= 1.f, "%s: constraints min_p=%g not in [0, 1] (0: off)", what,
+                 (double)con->min_p);  // (NaN fails too)
+  GPT2MI_REQUIRE(con->min_new >= 0, "%s: constraints min_new=%d is negative (0: off)", what, con->min_new);
+  GPT2MI_REQUIRE(con->min_new == 0 || eos >= 0, "%s: constraints min_new=%d needs an eos to hold back (eos=%lld)", what,
+                 con->min_new, (long long)eos);
+  GPT2MI_REQUIRE(con->n_stop >= 0 && con->n_stop <= GPT2MI_STOP_MAX_SEQS, "%s: constraints n_stop=%d not in [0, %d]", what,
+                 con->n_stop, GPT2MI_STOP_MAX_SEQS);
+  if (con->n_stop > 0) {
+    GPT2MI_REQUIRE(con->stop && con->stop_len, "%s: constraints n_stop=%d needs stop and stop_len: one is NULL", what,
+                   con->n_stop);
+    for (int s = 0; s < con->n_stop; ++s) {
+      GPT2MI_REQUIRE(con->stop_len[s] >= 1 && con->stop_len[s] <= GPT2MI_STOP_MAX_LEN,
+                     "%s: constraints stop_len[%d]=%d not in [1, %d]", what, s, con->stop_len[s], GPT2MI_STOP_MAX_LEN);
+      for (int j = 0; j < con->stop_len[s]; ++j) {
+        const int32_t t = con->stop[s * GPT2MI_STOP_MAX_LEN + j];
+        GPT2MI_REQUIRE(t >= 0 && t < V, "%s: constraints stop[%d][%d]=%d not in [0, V=%d)", what, s, j, t, V);
+      }
+    }
+    GPT2MI_REQUIRE(eos >= 0, "%s: stop sequences end a row as eos does: eos=%lld is not a token", what, (long long)eos);
+    GPT2MI_REQUIRE(done != nullptr, "%s: stop sequences need the done flags: done is NULL", what);
+  }
+  bool any_bias = false;
+  for (int b = 0; b < B; ++b) bias_row[b] = -1;
+  if (con->bias) {
+    GPT2MI_REQUIRE(con->ld_bias >= V && con->bias_rows >= 1, "%s: constraints bias with ld_bias=%d < V=%d or bias_rows=%d < 1",
+                   what, con->ld_bias, V, con->bias_rows);
+    GPT2MI_REQUIRE(con->bias_row || con->bias_rows >= B, "%s: constraints bias_rows=%d < B=%d without a bias_row", what,
+                   con->bias_rows, B);
+    for (int b = 0; b < B; ++b) {
+      const int r = con->bias_row ? con->bias_row[b] : b;
+      GPT2MI_REQUIRE(r >= -1 && r < con->bias_rows, "%s: constraints bias_row[%d]=%d not in [-1, bias_rows=%d)", what, b, r,
+                     con->bias_rows);
+      bias_row[b] = r;
+      any_bias = any_bias || r >= 0;
+    }
+  }
+  *on = any_bias || con->min_p > 0.f || con->min_new > 0 || con->n_stop > 0;
+  return 0;
+}
 }  // namespace gpt2mi
+
+GPT2MI_EXPORT int gpt2mi_sample_constrained(const float* logits, int ldl, int B, int V, float temperature, int top_k,
+                                            float top_p, uint64_t seed, const int* pos, const uint32_t* row_id,
+                                            int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq,
+                                            float* probs_out, const gpt2mi_penalties* pen, float* logits_out,
+                                            const gpt2mi_logprobs* lp, const gpt2mi_constraints* con, void* stream) {
+  return sample_rows("sample_constrained", logits, ldl, B, V, temperature, top_k, top_p, seed, pos, row_id, eos, done,
+                     tok_out, seq_out, ld_seq, probs_out, stream, pen, logits_out, lp, con);
+}
 
 GPT2MI_EXPORT int gpt2mi_sample_penalized(const float* logits, int ldl, int B, int V, float temperature, int top_k,
                                           float top_p, uint64_t seed, const int* pos, const uint32_t* row_id,

@@ -1,6 +1,7 @@
 // The body of the sampling kernels (csrc/sample.hip has the description) and the by-value structs of their arguments.
-// Two translation units instantiate it: sample.hip the plain and the penalised kernels, sample_lp.hip the LP ones. All
-// of it sits in an unnamed namespace: each unit has its own copy and its own kernels.
+// Three translation units instantiate it: sample.hip the plain and the penalised kernels, sample_lp.hip the LP ones,
+// sample_con.hip the constrained ones. All of it sits in an unnamed namespace: each unit has its own copy and its own
+// kernels.
 #ifndef GPT2MI_SAMPLE_ROW_H
 #define GPT2MI_SAMPLE_ROW_H
 #include <limits.h>
@@ -43,15 +44,17 @@ __device__ __forceinline__ int tid_pinned() {
 // hardware drops the lanes past it (they get 0; a chunk with nothing valid reads nothing), the descriptor is scalar
 // work and the 50 loads share one offset register, so they are all in flight together (50 clamped 64-bit addresses
 // would take 100 registers).
+__device__ __forceinline__ float load_chunk(const float* row, int V, int i, uint32_t voff) {
+  const int n = min(max(V - i * SM_THREADS, 0), SM_THREADS);
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_raw_buffer_load_b32(
+                 __builtin_amdgcn_make_buffer_rsrc((void*)(row + min(i * SM_THREADS, V - 1)), 0, 4 * n, 0x00020000), voff,
+                 0, 0));
+}
 __device__ __forceinline__ void load_row(float (&x)[SM_NE], const float* row, int V) {
   const uint32_t voff = 4u * threadIdx.x;
-  auto chunk_rsrc = [&](int i) {
-    const int n = min(max(V - i * SM_THREADS, 0), SM_THREADS);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(row + min(i * SM_THREADS, V - 1)), 0, 4 * n, 0x00020000);
-  };
 #pragma unroll
-  for (int i = 0; i < SM_NE; ++i)
-    x[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(chunk_rsrc(i), voff, 0, 0));
+  for (int i = 0; i < SM_NE; ++i) x[i] = load_chunk(row, V, i, voff);
   const int t = tid_pinned();
 #pragma unroll
   for (int i = 0; i < SM_NE; ++i) x[i] = i * SM_THREADS + t < V ? x[i] : __builtin_nanf("");
@@ -138,6 +141,18 @@ __device__ __forceinline__ float logprob_prologue(const float (&x)[SM_NE], int V
   return lse;
 }
 
+// The constrained form (CON, gpt2mi.h v24.4): a gpt2mi_constraints as the kernels take it, by value. bias_row[b] < 0:
+// row b has no bias row. lmp = fp32(log(min_p)), -inf: off. The stop table is read by thread 0 only.
+struct ConRows {
+  const float* bias;
+  int ld_bias;
+  float lmp;
+  int min_new, n_stop;
+  int bias_row[GPT2MI_DECODE_MAX_B];
+  int stop_len[GPT2MI_STOP_MAX_SEQS];
+  int32_t stop[GPT2MI_STOP_MAX_SEQS][GPT2MI_STOP_MAX_LEN];
+};
+
 // GREEDY (temperature == 0) is a kernel of its own: as one branch of the sampling kernel it kept the row live to the
 // end of the other branch, beside the exponentials.
 // The kernel's body: row b = blockIdx.x of the buffers, drawn with the key (draw_row, pos) and written to column pos of
@@ -145,7 +160,12 @@ __device__ __forceinline__ float logprob_prologue(const float (&x)[SM_NE], int V
 // PEN: `hist` is the row's history (positions [0, pos) are read, [gen_start, pos) count as generated), rp / pp / fp the
 // repetition, presence and frequency values, logits_out the row-major [B][V] copy of the penalised row (may be NULL).
 // LP: lp_out is where the drawn token's log-probability goes, top_id / top_lp the row's top_n slots (logprob_prologue).
-template <bool GREEDY, bool PEN, bool LP>
+// CON: `con` holds the row's constraints (generation.py apply_constraints, stop_match). After the penalties, in this
+// order: the row's bias row is added, one coalesced load and one fp32 add per element in groups of ten (no second row
+// array); while pos - gen_start < min_new the eos logit becomes -inf; logits_out takes the row as it stands; after the
+// top-p search thr = max(thr, max + lmp) (min-p); thread 0 sets done when the drawn token completes a stop sequence
+// that lies in [gen_start, pos] (hist is read for that also when PEN is off).
+template <bool GREEDY, bool PEN, bool LP, bool CON = false>
 __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int ldl, int V, float temperature,
                                            int top_k, float top_p, uint64_t seed, uint32_t draw_row, int pos,
                                            int64_t eos, uint8_t* __restrict__ done, int64_t* __restrict__ tok_out,
@@ -154,7 +174,7 @@ __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int
                                            float pp = 0.f, float fp = 0.f, float* __restrict__ logits_out = nullptr,
                                            float* __restrict__ lp_out = nullptr, int top_n = 0,
                                            int32_t* __restrict__ top_id = nullptr,
-                                           float* __restrict__ top_lp = nullptr) {
+                                           float* __restrict__ top_lp = nullptr, const ConRows* con = nullptr) {
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const float* lp = logits + (size_t)b * ldl;
   __shared__ uint32_t red[2][SM_WAVES];
@@ -239,6 +259,35 @@ __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int
         x[i] = v;
       }
     }
+    if constexpr (!CON) {
+      if (logits_out) {
+#pragma unroll
+        for (int i = 0; i < SM_NE; ++i) {
+          const int e = i * SM_THREADS + tid_here();
+          if (e < V) logits_out[(size_t)b * V + e] = x[i];
+        }
+      }
+    }
+  }
+  if constexpr (CON) {
+    const int br = con->bias_row[b];
+    if (br >= 0) {  // (block-uniform) load_row's chunk loads over the bias row: a lane past V adds 0 to its NaN
+      const float* brow = con->bias + (size_t)br * con->ld_bias;
+      const uint32_t voff = 4u * threadIdx.x;
+#pragma unroll
+      for (int g = 0; g < SM_NE; g += 10) {
+        float bv[10];
+#pragma unroll
+        for (int j = 0; j < 10; ++j) bv[j] = load_chunk(brow, V, g + j, voff);
+#pragma unroll
+        for (int j = 0; j < 10; ++j) x[g + j] = pinned(x[g + j] + bv[j]);
+      }
+    }
+    if (con->min_new > 0 && pos - gen_start < con->min_new) {  // (block-uniform; the entry checked eos >= 0)
+      const int at = (int)eos - tid_here();
+#pragma unroll
+      for (int i = 0; i < SM_NE; ++i) x[i] = at == i * SM_THREADS ? -INFINITY : x[i];
+    }
     if (logits_out) {
 #pragma unroll
       for (int i = 0; i < SM_NE; ++i) {
@@ -321,6 +370,7 @@ __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int
       }
       thr = keyf(lo);
     }
+    if constexpr (CON) thr = fmaxf(thr, pinned(mx + con->lmp));  // min-p (lmp = -inf: thr as it was)
     // from here the array holds the kept tokens' e = exp(x - max), 0 elsewhere
     float(&ev)[SM_NE] = x;
 #pragma unroll
@@ -439,6 +489,20 @@ __device__ __forceinline__ void sample_row(const float* __restrict__ logits, int
         if constexpr (LP) was_done = true;
       } else if (t64 == eos) {
         done[b] = 1;
+      } else if constexpr (CON) {
+        // stop sequences: the n - 1 history entries before pos and the token in the register against sequence s, when
+        // the match lies in [gen_start, pos] and the row then holds min_new generated tokens; every index formed is in
+        // [gen_start, pos), inside the window the entry checked
+        const int made = pos - gen_start + 1;
+        bool hit = false;
+        for (int s = 0; s < con->n_stop; ++s) {
+          const int n = con->stop_len[s], first = pos - n + 1;
+          if (gen_start < 0 || first < gen_start || made < con->min_new || t64 != con->stop[s][n - 1]) continue;
+          bool same = true;
+          for (int j = 0; j < n - 1; ++j) same = same && hist[first + j] == (int64_t)con->stop[s][j];
+          hit = hit || same;
+        }
+        if (hit) done[b] = 1;
       }
     }
     tok_out[b] = t64;

@@ -1,7 +1,8 @@
 """Sample from a checkpoint: ``python -m gpt_2_distributed_amd.generate --checkpoint out/step_0001000 --model 124M
 --prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B
 --draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F --kv_dtype {bf16,fp8}
---num_samples S --logprobs [N] --num_beams W --length_penalty A --num_return_sequences R]``.
+--num_samples S --logprobs [N] --num_beams W --length_penalty A --num_return_sequences R --logit_bias T:V,T:V
+--min_p M --min_new_tokens N --stop IDS [--stop IDS ...]]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -26,7 +27,12 @@ shared cache) and prints, prompt-major, one JSON object per returned beam, best 
 ``{"prompt": b, "beam": j, "tokens": [...], "score": s, "cum_logprob": c}`` (``tokens``: the prompt and the beam up to and
 including its first eos). ``--length_penalty`` enters the final ranking only and ``--num_return_sequences`` (default 1,
 at most W) says how many beams of each prompt are printed. The sampler's flags (``--sampler device`` among them) do not
-go with it; prompts x W <= 64."""
+go with it; prompts x W <= 64.
+
+``--logit_bias 50256:-100,198:2.5`` adds a value to a token's logit (``-inf`` bans it), ``--min_p 0.05`` drops the tokens
+less than that fraction as likely as the most likely one, ``--min_new_tokens 8`` holds ``--eos_token_id`` back for that
+many tokens and ``--stop 198,198`` (repeatable) ends a sequence at the token that completes the given tokens; the last two
+need ``--eos_token_id``. They go with either ``--sampler`` (``GPT2.generate``'s keywords), not with ``--num_beams``."""
 from __future__ import annotations
 
 import argparse
@@ -83,7 +89,32 @@ def make_parser():
     p.add_argument("--length_penalty", type=float, default=1.0,
                    help="--num_beams: the final score is cum_logprob / length ** this (1: the mean log-probability)")
     p.add_argument("--num_return_sequences", type=int, default=1, help="--num_beams: beams printed per prompt, best first")
+    p.add_argument("--logit_bias", type=parse_logit_bias, default=None, metavar="TOKEN:VALUE,...",
+                   help="added to the logits of the named tokens after the penalties (-inf bans a token)")
+    p.add_argument("--min_p", type=float, default=None,
+                   help="drop every token less than this fraction as likely as the most likely one; 0 or unset: off")
+    p.add_argument("--min_new_tokens", type=int, default=0,
+                   help="--eos_token_id is held back until a sequence has this many new tokens")
+    p.add_argument("--stop", type=parse_stop, action="append", default=None, metavar="IDS",
+                   help="comma-separated token ids: a sequence ends at the token that completes them (needs "
+                        "--eos_token_id); may be given up to 8 times, 16 tokens each")
     return p
+
+
+def parse_logit_bias(text: str) -> dict:
+    """``"50256:-100,198:2.5"`` as ``{50256: -100.0, 198: 2.5}``."""
+    try:
+        return {int(t): float(v) for t, v in (item.split(":") for item in text.split(",") if item.strip())}
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected TOKEN:VALUE[,TOKEN:VALUE...] (got {text!r})")
+
+
+def parse_stop(text: str) -> list:
+    """``"198,198"`` as ``[198, 198]``."""
+    try:
+        return [int(t) for t in text.split(",") if t.strip()]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected comma-separated token ids (got {text!r})")
 
 
 def parse_args(argv=None):
@@ -147,6 +178,8 @@ def main(argv=None) -> int:
                frequency_penalty=a.frequency_penalty, kv_dtype=a.kv_dtype)
     if a.logprobs is not None:
         pen["logprobs"] = a.logprobs
+    pen.update({k: v for k, v in dict(logit_bias=a.logit_bias, min_p=a.min_p, min_new_tokens=a.min_new_tokens,
+                                      stop=a.stop).items() if v})  # (only what was set: as the defaults, nothing)
     if a.num_beams is not None:
         # (only what the user set travels on: generate refuses the sampler's keywords beside num_beams by name)
         default = make_parser().get_default

@@ -23,6 +23,10 @@ With ``logprobs=`` the device sampler also returns, from the launch that draws a
 under the model's own distribution and the most likely alternatives (``gpt2mi_sample_logprobs``; ``token_logprobs`` is
 the rule, ``LogprobBuffer`` where a session puts them; DESIGN.md "Token log-probabilities").
 
+With ``logit_bias=``, ``min_p=``, ``min_new_tokens=`` and ``stop=`` the sampler is constrained, on the device in the same
+launch (``gpt2mi_sample_constrained``; ``apply_constraints``, ``sample_reference``'s ``min_p`` and ``stop_match`` are the
+rule; DESIGN.md "Constraints in the sampler").
+
 With ``num_beams=`` ``generate`` searches: the W beams of a prompt are W rows forked from one prefill, and each token
 is chosen by ``gpt2mi_decode_beam_search`` on the device (the rows' top-W log-probabilities, the selection, the move of
 the generated suffix of the cache rows to their new parents, the step), nothing read back in between. ``beam_select``
@@ -69,13 +73,15 @@ def _nucleus_keep(key: torch.Tensor, probs: torch.Tensor, top_p: float) -> torch
 
 
 def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[int] = None,
-                generator: Optional[torch.Generator] = None, top_p: Optional[float] = None) -> torch.Tensor:
+                generator: Optional[torch.Generator] = None, top_p: Optional[float] = None,
+                min_p: Optional[float] = None) -> torch.Tensor:
     """Next token ids [B] from logits [B, V] (nanoGPT's rule; pure torch, any device).
 
     ``temperature == 0`` is greedy argmax. Otherwise ``logits / temperature``, optionally everything below the
     ``top_k``-th largest logit of a row set to -inf, softmax, optionally (``top_p`` in (0, 1)) every token dropped whose
     strictly more probable tokens already weigh ``top_p`` or more, and one ``torch.multinomial`` draw per row from
-    ``generator``."""
+    ``generator``. ``min_p`` in (0, 1] also drops every token whose value lies below the row maximum +
+    ``log_min_p(min_p)`` (``sample_reference``'s rule: p_i < min_p * p_max); greedy ignores it."""
     if logits.dim() != 2:
         raise ValueError(f"sample_next takes logits [B, V] (got {tuple(logits.shape)})")
     if temperature < 0:
@@ -87,12 +93,15 @@ def sample_next(logits: torch.Tensor, temperature: float = 1.0, top_k: Optional[
     if temperature == 0:
         return logits.argmax(dim=-1)
     logits = logits / temperature
+    floor = None if not min_p else logits.max(-1, keepdim=True).values + log_min_p(min_p)
     if top_k is not None and top_k < logits.size(-1):
         kth = torch.topk(logits, top_k, dim=-1).values[:, -1:]
         logits = logits.masked_fill(logits < kth, float("-inf"))
     probs = torch.softmax(logits, dim=-1)
     if top_p is not None and top_p < 1:
         probs = probs.masked_fill(~_nucleus_keep(probs, probs, top_p), 0.0)  # (multinomial normalises what is left)
+    if floor is not None:
+        probs = probs.masked_fill(logits < floor, 0.0)
     return torch.multinomial(probs, num_samples=1, generator=generator).squeeze(1)
 
 
@@ -117,15 +126,28 @@ def uniform_at(seed: int, b: int, pos: int) -> float:
     return (c >> 40) * 2.0 ** -24
 
 
+def log_min_p(min_p: float) -> float:
+    """``lmp`` of the min-p rule: fp32(log(double(fp32(min_p)))), formed on the host (-inf for 0)."""
+    import math
+    import numpy as np
+    m = float(np.float32(min_p))
+    return float(np.float32(math.log(m))) if m > 0 else float("-inf")
+
+
 def sample_reference(logits: torch.Tensor, temperature: float, top_k: Optional[int], top_p: Optional[float],
-                     u: torch.Tensor):
+                     u: torch.Tensor, min_p: Optional[float] = None):
     """What gpt2mi_sample computes, in float64 (any device): ``(tokens [B], probs [B, V])`` from logits [B, V] and the
     uniforms ``u`` [B] (``uniform_at``'s for the device's draw).
 
     ``temperature == 0``: argmax, the lowest index among equal maxima (probs one-hot). Otherwise x = fp32
     ``logits / temperature``; top-k keeps x >= the k-th largest value; top-p, on the softmax p of what top-k kept, keeps
     token i iff the tokens with a strictly larger value weigh < top_p; the token is the first index, in vocabulary
-    order, whose inclusive cumulative kept probability exceeds u * Z (Z the kept mass). probs = p_i / Z, 0 if filtered."""
+    order, whose inclusive cumulative kept probability exceeds u * Z (Z the kept mass). probs = p_i / Z, 0 if filtered.
+
+    ``min_p`` in (0, 1] (None or 0: off; greedy ignores it): with mx the row maximum of x, token i is also dropped unless
+    ``x_i >= fl32(mx + log_min_p(min_p))``, one fp32 add. The ratio of a token to the maximum does not depend on what
+    else was filtered, so this is HF's and vLLM's "p_i >= min_p * p_max", stated on the values so that it is exact. A
+    row with no finite value gives token 0."""
     B, V = logits.shape
     x = logits.float()
     if temperature == 0:
@@ -140,10 +162,12 @@ def sample_reference(logits: torch.Tensor, temperature: float, top_k: Optional[i
     p = torch.softmax(xd.masked_fill(~keep, float("-inf")), dim=-1)
     if top_p is not None and top_p < 1:
         keep = keep & _nucleus_keep(xd, p, top_p)  # (ties decided by the value, not by the p it rounds to)
+    if min_p:
+        keep = keep & (x >= x.max(-1, keepdim=True).values + torch.full((), log_min_p(min_p), dtype=F32, device=x.device))
     pk = p * keep
     Z = pk.sum(-1, keepdim=True)
     cdf = pk.cumsum(-1)
-    tok = (cdf > u.double().to(x.device)[:, None] * Z).int().argmax(-1)
+    tok = (cdf > u.double().to(x.device)[:, None] * Z).int().argmax(-1)  # (a row of NaN: no crossing, token 0)
     return tok, pk / Z
 
 
@@ -202,6 +226,103 @@ def apply_penalties(logits: torch.Tensor, history: torch.Tensor, lens, gen_start
     if pp != 0.0:
         x = torch.where(count > 0, x - f32(pp), x)
     return x
+
+
+# ---- constraints: the rule gpt2mi_sample_constrained applies between the penalties and the draw, executable -----------
+STOP_MAX_SEQS, STOP_MAX_LEN = K.STOP_MAX_SEQS, K.STOP_MAX_LEN
+
+
+def _check_constraints(logit_bias=None, min_p=None, min_new_tokens=0, stop=None, eos_token_id=None,
+                       vocab_size: Optional[int] = None):
+    """(min_p as a float, 0.0: off; min_new_tokens as an int; stop as a list of int lists), or a ValueError. logit_bias
+    is a tensor [..., V] or a ``{token: value}`` dict (None: none); only its values and tokens are checked here."""
+    mp = 0.0 if min_p is None else float(min_p)
+    if not 0 <= mp <= 1:  # (NaN too)
+        raise ValueError(f"min_p must lie in [0, 1] (got {min_p}); 0 or None turns it off")
+    mn = int(min_new_tokens)
+    if mn < 0:
+        raise ValueError(f"min_new_tokens must be >= 0 (got {min_new_tokens})")
+    stops = [[int(t) for t in s] for s in (stop or [])]
+    if (mn > 0 or stops) and eos_token_id is None:
+        raise ValueError("min_new_tokens and stop need an eos_token_id: the first holds eos back, a row that completes a "
+                         "stop sequence goes on emitting it")
+    if len(stops) > STOP_MAX_SEQS:
+        raise ValueError(f"at most {STOP_MAX_SEQS} stop sequences (got {len(stops)})")
+    for s in stops:
+        if not 1 <= len(s) <= STOP_MAX_LEN:
+            raise ValueError(f"a stop sequence holds 1 to {STOP_MAX_LEN} tokens (got {len(s)})")
+        if vocab_size is not None and not all(0 <= t < vocab_size for t in s):
+            raise ValueError(f"stop tokens must lie in [0, vocab_size={vocab_size}) (got {s})")
+    if isinstance(logit_bias, dict):
+        toks, vals = [int(t) for t in logit_bias], [float(v) for v in logit_bias.values()]
+        if vocab_size is not None and not all(0 <= t < vocab_size for t in toks):
+            raise ValueError(f"logit_bias tokens must lie in [0, vocab_size={vocab_size}) (got {toks})")
+        if any(v != v or v == float("inf") for v in vals):
+            raise ValueError("logit_bias values must be finite or -inf (which bans the token)")
+    elif logit_bias is not None:
+        if vocab_size is not None and logit_bias.size(-1) != vocab_size:
+            raise ValueError(f"logit_bias must be [.., V={vocab_size}] (got {tuple(logit_bias.shape)})")
+        if bool((torch.isnan(logit_bias) | (logit_bias == float("inf"))).any()):
+            raise ValueError("logit_bias values must be finite or -inf (which bans the token)")
+    return mp, mn, stops
+
+
+def apply_constraints(logits: torch.Tensor, pos, gen_start, logit_bias: Optional[torch.Tensor] = None, bias_row=None,
+                      min_new_tokens: int = 0, eos_token_id: Optional[int] = None) -> torch.Tensor:
+    """The row a constrained draw dumps and goes on from: fp32 [B, V] from the (penalised) logits [B, V] (pure torch, any
+    device; what csrc/sample_con.hip computes bit for bit). In this order:
+    bias: ``x = x + logit_bias[bias_row[b]]`` (one fp32 add per element) for a row with ``bias_row[b] >= 0``
+    (``bias_row`` None: row b reads row b; ``logit_bias`` fp32 [rows, V], -inf bans a token); a row without a bias row
+    keeps its bits. Minimum length: ``min_new_tokens > 0`` and ``pos[b] - gen_start[b] < min_new_tokens`` (``pos[b]`` the
+    column being drawn, ``gen_start`` None: 0): ``x[eos_token_id] = -inf``."""
+    if logits.dim() != 2:
+        raise ValueError(f"apply_constraints takes logits [B, V] (got {tuple(logits.shape)})")
+    x = logits.float()
+    B, V = x.shape
+    dev = x.device
+    if logit_bias is not None:
+        _check_constraints(logit_bias, vocab_size=V)
+        rows = torch.arange(B, device=dev) if bias_row is None else torch.as_tensor(bias_row, device=dev).long().reshape(B)
+        if bool((rows < -1).any() | (rows >= logit_bias.size(0)).any()):
+            raise ValueError(f"bias_row must lie in [-1, {logit_bias.size(0)})")
+        bias = logit_bias.to(dev).float()[rows.clamp_min(0)]
+        x = torch.where((rows >= 0)[:, None], x + bias, x)
+    mn = int(min_new_tokens)
+    if mn > 0:
+        if eos_token_id is None or not 0 <= int(eos_token_id) < V:
+            raise ValueError(f"min_new_tokens needs an eos_token_id in [0, V={V}) (got {eos_token_id})")
+        pos_t = torch.as_tensor(pos, device=dev).long().reshape(B)
+        start_t = torch.zeros_like(pos_t) if gen_start is None else torch.as_tensor(gen_start, device=dev).long().reshape(B)
+        held = (pos_t - start_t) < mn
+        x = x.clone()
+        x[:, int(eos_token_id)] = torch.where(held, torch.full_like(x[:, 0], float("-inf")), x[:, int(eos_token_id)])
+    return x
+
+
+def stop_match(history: List[int], gen_start: int, stops, min_new_tokens: int = 0) -> bool:
+    """Whether the last token of ``history`` (the row's tokens so far, the one just drawn at ``pos = len(history) - 1``
+    last) completes a stop sequence: for some s in ``stops`` of length n, ``history[pos - n + 1 .. pos] == s``, the match
+    wholly in the generated part (``pos - n + 1 >= gen_start``), and the row then holds at least ``min_new_tokens``
+    generated tokens (``pos - gen_start + 1 >= min_new_tokens``)."""
+    pos = len(history) - 1
+    if pos < 0 or pos - gen_start + 1 < min_new_tokens:
+        return False
+    for s in stops:
+        n = len(s)
+        if n >= 1 and pos - n + 1 >= gen_start >= 0 and [int(t) for t in history[pos - n + 1:]] == [int(t) for t in s]:
+            return True
+    return False
+
+
+def first_stop(tokens: List[int], gen_start: int, stops, min_new_tokens: int = 0, eos_token_id=None) -> Optional[int]:
+    """The index in ``tokens`` (a row's prompt and new tokens) of the first generated token that completes a stop
+    sequence (``stop_match``) before any eos, or None: where the sampler set the row's done flag for one."""
+    for i in range(gen_start, len(tokens)):
+        if tokens[i] == eos_token_id:
+            return None
+        if stop_match(tokens[:i + 1], gen_start, stops, min_new_tokens):
+            return i
+    return None
 
 
 # ---- log-probabilities: the rule gpt2mi_sample_logprobs states beside the token it draws, executable -------------------
@@ -451,6 +572,49 @@ def _penalty_keywords(penalties, gen_start) -> dict:
     values are neutral), the rows' generated parts starting at ``gen_start``."""
     rp, pp, fp, on = penalties
     return dict(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp, gen_start=list(gen_start)) if on else {}
+
+
+def _constraint_set(logit_bias, allowed_token_ids, min_p, min_new_tokens, stop, eos_token_id, V: int, B: int, dev,
+                    per_row: bool = True) -> Optional[dict]:
+    """``generate`` / ``generate_many``'s constraint keywords as ``DecodeSession.generate``'s (without ``gen_start``), or
+    None when nothing is on. ``logit_bias`` is a ``{token: value}`` dict, a [V] tensor or (``per_row``) a [B, V] tensor;
+    ``allowed_token_ids`` adds -inf everywhere else. A dict, a [V] tensor and the allowed list make one device row every
+    row reads (``bias_row`` all 0); a [B, V] tensor gives row b its own."""
+    mp, mn, stops = _check_constraints(logit_bias, min_p, min_new_tokens, stop, eos_token_id, V)
+    bias = None
+    if isinstance(logit_bias, dict):
+        bias = torch.zeros(1, V, dtype=F32)
+        for t, v in logit_bias.items():
+            bias[0, int(t)] = float(v)
+    elif logit_bias is not None:
+        if logit_bias.dim() not in (1, 2) or (logit_bias.dim() == 2 and (not per_row or logit_bias.size(0) != B)):
+            raise ValueError(f"logit_bias must be a dict, a [V={V}] tensor{f' or a [B={B}, V] tensor' if per_row else ''} "
+                             f"(got {tuple(logit_bias.shape)})")
+        bias = logit_bias.detach().float().reshape(-1, V).clone()
+    if allowed_token_ids is not None:
+        allowed = [int(t) for t in allowed_token_ids]
+        if not allowed or not all(0 <= t < V for t in allowed):
+            raise ValueError(f"allowed_token_ids must be a non-empty list of tokens in [0, vocab_size={V}) (got {allowed})")
+        mask = torch.full((1, V), float("-inf"), dtype=F32)
+        mask[0, allowed] = 0.0
+        bias = mask if bias is None else bias + mask.to(bias.device)
+    if bias is None and not (mp > 0 or mn > 0 or stops):
+        return None
+    out = dict(min_p=mp, min_new_tokens=mn, stop=stops)
+    if bias is not None:
+        out.update(logit_bias=bias.to(dev).contiguous(), bias_row=list(range(B)) if bias.size(0) > 1 else [0] * B)
+    return out
+
+
+def _constraint_keywords(cons: Optional[dict], gen_start, rows=None) -> dict:
+    """``DecodeSession.generate`` / ``speculate``'s constraint keywords from ``_constraint_set``'s result (``{}`` for
+    None), the rows' generated parts starting at ``gen_start``; ``rows``: the bias row of each session row instead."""
+    if cons is None:
+        return {}
+    out = dict(cons, gen_start=list(gen_start))
+    if rows is not None and "bias_row" in out:
+        out["bias_row"] = list(rows)
+    return out
 
 
 def _check_lens(lens, B: int, P: int) -> List[int]:
@@ -888,12 +1052,50 @@ class DecodeSession:
             raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
         return dict(repetition=rp, presence=pp, frequency=fp, gen_start=start)
 
+    def _constraints(self, logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, hist, name: str,
+                     last: int, done=None) -> dict:
+        """The constraint keywords of the C entries (``{}`` when nothing is on): ``logit_bias`` a device fp32
+        [rows, V] tensor read by row ``bias_row[b]`` (None: b; -1: none), ``hist`` the history buffer (argument
+        ``name``) the stop sequences are matched in, ``last`` the largest position a draw of the call reaches."""
+        mp, mn, stops = _check_constraints(logit_bias, min_p, min_new_tokens, stop, eos_token_id, self.cfg.vocab_size)
+        rows = None
+        if logit_bias is not None:
+            if (not isinstance(logit_bias, torch.Tensor) or logit_bias.dtype != F32 or logit_bias.dim() != 2
+                    or logit_bias.stride(1) != 1 or not logit_bias.is_cuda):
+                raise ValueError(f"logit_bias must be a device fp32 [rows, V={self.cfg.vocab_size}] tensor with contiguous rows")
+            rows = list(range(self.B)) if bias_row is None else [int(r) for r in bias_row]
+            if len(rows) != self.B or not all(-1 <= r < logit_bias.size(0) for r in rows):
+                raise ValueError(f"bias_row {rows} must be B={self.B} ints in [-1, {logit_bias.size(0)}) (None: row b reads "
+                                 f"bias row b)")
+        elif bias_row is not None:
+            raise ValueError("bias_row goes with logit_bias")
+        if not (mp > 0 or mn > 0 or stops or (rows is not None and any(r >= 0 for r in rows))):
+            return {}
+        if stops:
+            if hist is None:
+                raise ValueError(f"stop sequences are matched in the rows' tokens: pass {name}, int64 [B={self.B}, T], "
+                                 f"holding row b's tokens at [0, lens[b])")
+            if (hist.dtype != torch.int64 or hist.dim() != 2 or hist.size(0) != self.B or hist.stride(1) != 1
+                    or not hist.is_cuda or hist.size(1) < last):
+                raise ValueError(f"{name} must be a device int64 [B={self.B}, >= {last}] with contiguous rows")
+            if done is None:
+                raise ValueError(f"stop sequences need done, uint8 [B={self.B}]")
+        start = [0] * self.B if gen_start is None else [int(g) for g in gen_start]
+        if len(start) != self.B or not all(0 <= g <= m for g, m in zip(start, self.lens)):
+            raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
+        bias = {} if rows is None else dict(logit_bias=logit_bias, bias_row=rows)
+        return dict(bias, min_p=mp, min_new_tokens=mn, stop=stops, gen_start=start)
+
     def _draw(self, logits, pos, out, temperature, top_k, top_p, seed, pen: dict, hist=None, lp: Optional[dict] = None,
-              **kw) -> None:
+              con: Optional[dict] = None, **kw) -> None:
         """One token per row of ``logits`` at ``pos`` into ``out``: gpt2mi_sample_ragged, or with ``pen`` (``_penalties``'
         keywords, not empty) gpt2mi_sample_penalized over the history ``hist``. ``kw``: row_id, eos, done. With ``lp``
-        (logprob, top_ids, top_logprobs and optionally col) gpt2mi_sample_logprobs: the same draw and its values."""
-        if lp is not None:
+        (logprob, top_ids, top_logprobs and optionally col) gpt2mi_sample_logprobs: the same draw and its values. With
+        ``con`` (``_constraints``' keywords, not empty) gpt2mi_sample_constrained, beside whatever of the others."""
+        if con:
+            K.sample_constrained(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **(lp or {}), **kw,
+                                 **{"hist": hist, **pen, **con})
+        elif lp is not None:
             K.sample_logprobs(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **lp, **kw,
                               **({"hist": hist, **pen} if pen else {}))
         elif pen:
@@ -902,10 +1104,15 @@ class DecodeSession:
         else:
             K.sample_ragged(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **kw)
 
-    def _loop(self, n: int, temperature, top_k, top_p, seed, pen: dict, lp: Optional[dict] = None, **kw) -> None:
+    def _loop(self, n: int, temperature, top_k, top_p, seed, pen: dict, lp: Optional[dict] = None,
+              con: Optional[dict] = None, **kw) -> None:
         """``n`` sample-then-step rounds from ``lens`` into ``_tok``: gpt2mi_decode_generate_ragged, or with ``pen``
-        gpt2mi_decode_generate_penalized, or with ``lp`` (a LogprobBuffer's tensors) gpt2mi_decode_generate_logprobs.
-        ``kw``: row_id, eos, seq, done."""
+        gpt2mi_decode_generate_penalized, or with ``lp`` (a LogprobBuffer's tensors) gpt2mi_decode_generate_logprobs, or
+        with ``con`` gpt2mi_decode_generate_constrained. ``kw``: row_id, eos, seq, done."""
+        if con:
+            K.decode_generate_constrained(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
+                                          self._tok, **kw, **(lp or {}), **{**pen, **con})
+            return
         if lp is not None:
             kw = {**kw, **lp}
         loop = K.decode_generate_logprobs if lp is not None else (K.decode_generate_penalized if pen
@@ -934,7 +1141,10 @@ class DecodeSession:
     def sample(self, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
                seed: int = 0, row_id: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
                presence_penalty: float = 0.0, frequency_penalty: float = 0.0, gen_start: Optional[Sequence[int]] = None,
-               history: Optional[torch.Tensor] = None, logprobs: Optional[int] = None):
+               history: Optional[torch.Tensor] = None, logprobs: Optional[int] = None,
+               logit_bias: Optional[torch.Tensor] = None, bias_row: Optional[Sequence[int]] = None,
+               min_p: Optional[float] = None, min_new_tokens: int = 0, stop=None, eos_token_id: Optional[int] = None,
+               done: Optional[torch.Tensor] = None):
         """Tokens [B] (int64, device) for position ``lens[b]`` from the logits of the last ``prefill`` / ``step``: one
         launch, no host synchronisation. Row b's token is a function of (its logits, the parameters, seed, its draw key,
         its position): ``sample_reference`` with ``uniform_at(seed, row_id[b], lens[b])``; ``row_id`` (B ints, default
@@ -946,20 +1156,31 @@ class DecodeSession:
 
         ``logprobs=n`` (0 <= n <= 20) returns ``(tokens, logprob [B], top_ids [B, n], top_logprobs [B, n])``: the raw
         distribution's values of ``token_logprobs``, from the same launch (gpt2mi_sample_logprobs); the tokens are those
-        of the call without."""
+        of the call without.
+
+        Constraints (gpt2mi_sample_constrained; ``apply_constraints``, ``sample_reference``'s ``min_p`` and
+        ``stop_match`` are the rule), after the penalties: ``logit_bias`` (device fp32 [rows, V]) adds row
+        ``bias_row[b]`` (None: b; -1: none) to row b's logits, -inf banning a token; ``min_new_tokens`` holds
+        ``eos_token_id`` back while ``lens[b] - gen_start[b]`` is below it; ``min_p`` drops the tokens less than that
+        fraction as likely as the most likely one; ``stop`` (up to 8 lists of up to 16 tokens) sets ``done[b]`` (uint8
+        [B]) when the drawn token completes one of them inside ``history[b, gen_start[b]:]``. With ``eos_token_id`` and
+        ``done`` a row whose flag is set draws eos, and one that draws eos gets it set."""
         self._check_sampler(temperature, top_p, seed)
         if self._drawn:
             raise RuntimeError("the logits are those generate() drew its last token from: step() that token first")
         pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, history, "history",
                               max(self.lens))
+        con = self._constraints(logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, history,
+                                "history", max(self.lens), done)
+        ends = {} if eos_token_id is None else dict(eos=eos_token_id, done=done)
         out = torch.empty(self.B, dtype=torch.int64, device=self.logits.device)
         if logprobs is None:
-            self._draw(self.logits, self.lens, out, temperature, top_k, top_p, seed, pen, history,
-                       row_id=_check_row_id(row_id, self.B))
+            self._draw(self.logits, self.lens, out, temperature, top_k, top_p, seed, pen, history, con=con,
+                       row_id=_check_row_id(row_id, self.B), **ends)
             return out
         buf = LogprobBuffer(self.B, 1, logprobs, self.logits.device)
         self._draw(self.logits, self.lens, out, temperature, top_k, top_p, seed, pen, history,
-                   dict(buf.tensors(), col=[0] * self.B), row_id=_check_row_id(row_id, self.B))
+                   dict(buf.tensors(), col=[0] * self.B), con, row_id=_check_row_id(row_id, self.B), **ends)
         return out, buf.logprob[:, 0], buf.top_ids[:, 0], buf.top_logprobs[:, 0]
 
     @torch.no_grad()
@@ -967,7 +1188,9 @@ class DecodeSession:
                  seed: int = 0, eos_token_id: Optional[int] = None, seq: Optional[torch.Tensor] = None,
                  done: Optional[torch.Tensor] = None, row_id: Optional[Sequence[int]] = None,
                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                 gen_start: Optional[Sequence[int]] = None, logprobs: Optional["LogprobBuffer"] = None) -> torch.Tensor:
+                 gen_start: Optional[Sequence[int]] = None, logprobs: Optional["LogprobBuffer"] = None,
+                 logit_bias: Optional[torch.Tensor] = None, bias_row: Optional[Sequence[int]] = None,
+                 min_p: Optional[float] = None, min_new_tokens: int = 0, stop=None) -> torch.Tensor:
         """Draw row b's tokens of positions ``lens[b] .. lens[b] + n - 1`` in one C call (gpt2mi_decode_generate_ragged:
         sample, step, sample, ... on the stream, no Python and no synchronisation in between). The tokens go to column
         ``lens[b] + i`` of ``seq`` (int64 [B, >= max(lens) + n], optional); with ``eos_token_id``, ``done`` (uint8 [B])
@@ -981,7 +1204,12 @@ class DecodeSession:
 
         ``logprobs`` (a ``LogprobBuffer`` of B rows and as many columns as the call reaches) receives, in the column each
         token goes to in ``seq``, the token's raw log-probability and alternatives (gpt2mi_decode_generate_logprobs: the
-        same launches with the sampling kernel's LP form, nothing more read back); a finished row's eos has 0."""
+        same launches with the sampling kernel's LP form, nothing more read back); a finished row's eos has 0.
+
+        ``logit_bias`` / ``bias_row`` / ``min_p`` / ``min_new_tokens`` / ``stop`` as for ``sample``, still one C call
+        (gpt2mi_decode_generate_constrained): ``seq`` is the history the stop sequences are matched in (required with
+        them, as ``eos_token_id`` and ``done`` are), ``gen_start[b]`` where the row's generated part begins; a row that
+        completes a stop sequence keeps its tokens and emits eos from the next position on."""
         self._check_sampler(temperature, top_p, seed)
         n = int(n)
         if n < 1:
@@ -989,7 +1217,9 @@ class DecodeSession:
         row_id, done, pen = self._check_run(n, row_id, eos_token_id, seq, done,
                                             (repetition_penalty, presence_penalty, frequency_penalty), gen_start,
                                             logprobs)
-        self._loop(n, temperature, top_k, top_p, seed, pen, None if logprobs is None else logprobs.tensors(),
+        con = self._constraints(logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, seq, "seq",
+                                max(self.lens) + n - 1, done)
+        self._loop(n, temperature, top_k, top_p, seed, pen, None if logprobs is None else logprobs.tensors(), con,
                    row_id=row_id, eos=eos_token_id, seq=seq, done=done)
         self.lens = [m + n - 1 for m in self.lens]
         self._drawn = True
@@ -1120,7 +1350,7 @@ class DecodeSession:
         their logits, row r at position ``poss[r] + 1`` with draw key ``keys[r]``; the R tokens, read back.
 
         ``sampler`` is (temperature, top_k, top_p, seed) or, penalised, those and (the penalty keywords, seq): see
-        ``verify_history``. With ``logprobs=n`` the draw is gpt2mi_sample_logprobs into buffers of R rows and one
+        ``verify_history``; constrained, also (the constraint keywords, eos): see ``verify_constraints``. With ``logprobs=n`` the draw is gpt2mi_sample_logprobs into buffers of R rows and one
         column (col 0, ld 1) and the result is (the tokens, (logprob [R], top_ids [R, n], top_logprobs [R, n])), the
         values left on the device."""
         V = self.cfg.vocab_size
@@ -1132,13 +1362,15 @@ class DecodeSession:
         K.decode_extend(plan, tok_t, seqs, poss)
         out = torch.empty(R, dtype=torch.int64, device=self.device)
         temperature, top_k, top_p, seed = sampler[:4]
+        con, ends = verify_constraints(sampler, seqs)
         if logprobs is None:
             self._draw(scratch["logits"][:R], [p + 1 for p in poss], out, temperature, top_k, top_p, seed,
-                       verify_history(sampler, tok_t, seqs, poss), row_id=keys)
+                       verify_history(sampler, tok_t, seqs, poss), con=con, row_id=keys, **ends)
             return out.tolist()
         buf = LogprobBuffer(R, 1, logprobs, self.device)
         self._draw(scratch["logits"][:R], [p + 1 for p in poss], out, temperature, top_k, top_p, seed,
-                   verify_history(sampler, tok_t, seqs, poss), lp=dict(buf.tensors(), col=[0] * R), row_id=keys)
+                   verify_history(sampler, tok_t, seqs, poss), lp=dict(buf.tensors(), col=[0] * R), con=con, row_id=keys,
+                   **ends)
         return out.tolist(), (buf.logprob[:, 0], buf.top_ids[:, 0], buf.top_logprobs[:, 0])
 
     @torch.no_grad()
@@ -1147,7 +1379,9 @@ class DecodeSession:
                   seq: Optional[torch.Tensor] = None, done: Optional[torch.Tensor] = None,
                   row_id: Optional[Sequence[int]] = None, repetition_penalty: float = 1.0,
                   presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
-                  gen_start: Optional[Sequence[int]] = None, logprobs: Optional["LogprobBuffer"] = None) -> dict:
+                  gen_start: Optional[Sequence[int]] = None, logprobs: Optional["LogprobBuffer"] = None,
+                  logit_bias: Optional[torch.Tensor] = None, bias_row: Optional[Sequence[int]] = None,
+                  min_p: Optional[float] = None, min_new_tokens: int = 0, stop=None) -> dict:
         """``generate(n, ...)`` with up to ``k`` drafted tokens of every row verified per pass over the weights: the same
         tokens in ``seq``, the same ``done`` flags and, with the last token drawn and not stepped, the same ``_tok``,
         ``lens`` and ``logits``, in fewer passes when the drafts are right. ``B * (k + 1) <= 64``.
@@ -1174,7 +1408,12 @@ class DecodeSession:
 
         ``logprobs`` as for ``generate``, with the same bits: the first draw and every verify call run the sampler's LP
         form, an accepted row's value goes to its token's column and a rejected draft's is dropped with its token; the
-        columns after a row's eos hold 0."""
+        columns after a row's eos hold 0.
+
+        Constraints as for ``generate``, and as exact: the bias, min-p and the minimum length are functions of (row,
+        position), so a verify call applies them to its rows as the loop does at those positions; stop sequences are
+        matched on the host (``stop_match``) in the tokens read back, and an accepted run ends at the token that
+        completes one, as it does at eos."""
         n, k = int(n), int(k)
         if n < 1 or k < 0:
             raise ValueError(f"speculate takes n >= 1 and k >= 0 (got n={n}, k={k})")
@@ -1184,6 +1423,8 @@ class DecodeSession:
         row_id, done, pen = self._check_run(n, row_id, eos_token_id, seq, done,
                                             (repetition_penalty, presence_penalty, frequency_penalty), gen_start,
                                             logprobs)
+        con = self._constraints(logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, seq, "seq",
+                                max(self.lens) + n - 1, done)
         lens0 = list(self.lens)
         if logprobs is not None:  # the call's columns: what no accepted row writes (after a row's eos) is 0
             at = torch.arange(logprobs.T, device=self.device)[None] - torch.tensor(lens0, device=self.device)[:, None]
@@ -1191,18 +1432,25 @@ class DecodeSession:
             for t in (logprobs.logprob, logprobs.top_ids, logprobs.top_logprobs):
                 t.masked_fill_(~keep if t.dim() == 2 else ~keep[..., None], 0)
         self._draw(self.logits, self.lens, self._tok, temperature, top_k, top_p, seed, pen, seq,
-                   None if logprobs is None else logprobs.tensors(), row_id=row_id, eos=eos_token_id, done=done)
+                   None if logprobs is None else logprobs.tensors(), con, row_id=row_id, eos=eos_token_id, done=done)
         first = self._tok.tolist()
         history = [[] for _ in range(self.B)] if seq is None else [r[:m] for r, m in zip(seq.tolist(), lens0)]
         keys = list(range(self.B)) if row_id is None else row_id
-        new, stats = speculate_loop(self, n, k, draft_fn or ngram_draft, eos_token_id, history, first, keys,
-                                    (temperature, top_k, top_p, seed) + (((pen, seq),) if pen else ()),
-                                    **({} if logprobs is None else {"logprobs": logprobs}))
+        sampler = (temperature, top_k, top_p, seed) + (((pen, seq),) if pen or con else ())
+        more = {} if logprobs is None else {"logprobs": logprobs}
+        stopped = [False] * self.B
+        if con:
+            sampler += ((con, eos_token_id),)
+            if con["stop"]:
+                more.update(stop=(con["stop"], con["gen_start"], con["min_new_tokens"]), stopped=stopped)
+        new, stats = speculate_loop(self, n, k, draft_fn or ngram_draft, eos_token_id, history, first, keys, sampler,
+                                    **more)
         self._tok.copy_(torch.tensor([t[-1] for t in new], dtype=torch.int64))
         self._drawn = True
         if eos_token_id is not None:
             new = [t + [eos_token_id] * (n - len(t)) for t in new]  # a finished row keeps emitting eos
-            done.copy_(torch.tensor([int(eos_token_id in t) for t in new], dtype=torch.uint8))
+            done.copy_(torch.tensor([int(eos_token_id in t or stopped[b]) for b, t in enumerate(new)],
+                                    dtype=torch.uint8))
         if seq is not None:
             cols = torch.tensor(lens0, device=self.device)[:, None] + torch.arange(n, device=self.device)[None]
             seq.scatter_(1, cols, torch.tensor(new, dtype=torch.int64, device=self.device))
@@ -1216,11 +1464,25 @@ def verify_history(sampler, tok_t: torch.Tensor, seqs: List[int], poss: List[int
     overwritten). That is the history the one-token loop has at that position, so the draws stay those of the loop.
     Returns gpt2mi_sample_penalized's keywords: the values, ``hist = seq``, ``hist_row = seqs`` and each row's
     ``gen_start``, its sequence's."""
-    if len(sampler) < 5:
+    if len(sampler) < 5 or not sampler[4][0]:
         return {}
     pen, seq = sampler[4]
     seq.index_put_((torch.tensor(seqs, device=seq.device), torch.tensor(poss, device=seq.device)), tok_t)
     return dict(pen, hist=seq, hist_row=list(seqs), gen_start=[pen["gen_start"][b] for b in seqs])
+
+
+def verify_constraints(sampler, seqs: List[int]):
+    """The constraints of a verify call, as (``_draw``'s ``con``, its eos keyword); ``({}, {})`` when ``sampler`` has no
+    sixth entry, (the session's constraint keywords, eos). Row r is a position of sequence ``seqs[r]``: it reads that
+    sequence's bias row and ``gen_start``. The bias, min-p and the minimum length are functions of (row, position) and
+    stay; the stop sequences are left out, ``speculate_loop`` matches them in the tokens it reads back."""
+    if len(sampler) < 6:
+        return {}, {}
+    con, eos = sampler[5]
+    rows = dict(con, stop=[], gen_start=[con["gen_start"][b] for b in seqs])
+    if "bias_row" in con:
+        rows["bias_row"] = [con["bias_row"][b] for b in seqs]
+    return rows, {"eos": eos}
 
 
 def ngram_draft(history: List[int], k: int, max_ngram: int = 3) -> List[int]:
@@ -1240,7 +1502,8 @@ def ngram_draft(history: List[int], k: int, max_ngram: int = 3) -> List[int]:
     return []
 
 
-def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first, keys, sampler, logprobs=None):
+def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first, keys, sampler, logprobs=None,
+                   stop=None, stopped=None):
     """The bookkeeping of ``DecodeSession.speculate`` over a session (anything with ``B``, ``lens``, ``_verify`` and
     ``_accept``): ``first[b]`` is row b's first token, drawn and not stepped. Returns (the tokens of each row: n of
     them, or fewer ending in eos; the stats). A draft counts as accepted iff it equals the token drawn before it and
@@ -1248,13 +1511,24 @@ def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first,
 
     With ``logprobs`` (a ``LogprobBuffer``; the first tokens' values are in it already) ``_verify`` is asked for the
     values too (``logprobs=top_n``, returning (tokens, values)); the value of the token drawn from row r belongs to
-    column ``poss[r] + 1`` of its sequence and is put there iff the token is taken."""
+    column ``poss[r] + 1`` of its sequence and is put there iff the token is taken.
+
+    With ``stop`` = (the stop sequences, each row's ``gen_start``, ``min_new_tokens``) a row also ends, as at eos, at
+    the token that completes a stop sequence (``stop_match`` over ``history[b]`` and the row's tokens): an accepted run
+    is cut there. ``stopped`` (a list of B bools) is set for such a row."""
     B = sess.B
     new = [[int(first[b])] for b in range(B)]
     stats = dict(calls=0, drafted=0, accepted=0, tokens=0)
+    stopped = [False] * B if stopped is None else stopped
+
+    def hit(b, toks):
+        return stop is not None and toks[-1] != eos_token_id and stop_match(history[b] + toks, stop[1][b], stop[0], stop[2])
+
+    for b in range(B):
+        stopped[b] = hit(b, new[b])
 
     def live(b):
-        return len(new[b]) < n and new[b][-1] != eos_token_id
+        return len(new[b]) < n and new[b][-1] != eos_token_id and not stopped[b]
 
     while any(live(b) for b in range(B)):
         toks, seqs, poss, ks, spans = [], [], [], [], []
@@ -1273,6 +1547,10 @@ def speculate_loop(sess, n: int, k: int, draft_fn, eos_token_id, history, first,
             a = 0
             while a < len(drafts) and drafts[a] == drawn[r0 + a] != eos_token_id:
                 a += 1
+            for i in range(a + 1 if stop is not None else 0):  # the run ends at the first token that completes a stop
+                if hit(b, new[b] + [int(t) for t in drawn[r0:r0 + i + 1]]):
+                    a, stopped[b] = i, True
+                    break
             new[b] += [int(t) for t in drawn[r0:r0 + a + 1]]
             sess.lens[b] += a + 1
             src.append(r0 + a), dst.append(b)
@@ -1308,7 +1586,8 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
              pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None, draft_fn=None,
              repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
              frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1, logprobs=None,
-             num_beams: Optional[int] = None, length_penalty: float = 1.0, num_return_sequences: int = 1):
+             num_beams: Optional[int] = None, length_penalty: float = 1.0, num_return_sequences: int = 1,
+             logit_bias=None, allowed_token_ids=None, min_p: Optional[float] = None, min_new_tokens: int = 0, stop=None):
     """``GPT2.generate``: see there."""
     check_kv_dtype(kv_dtype)
     if num_beams is not None:
@@ -1318,7 +1597,11 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
                                     top_k=(top_k, None), top_p=(top_p, None), draft_tokens=(draft_tokens, None),
                                     draft_fn=(draft_fn, None), repetition_penalty=(repetition_penalty, 1.0),
                                     presence_penalty=(presence_penalty, 0.0), frequency_penalty=(frequency_penalty, 0.0),
-                                    num_samples=(num_samples, 1), logprobs=(logprobs, None)))
+                                    num_samples=(num_samples, 1), logprobs=(logprobs, None),
+                                    logit_bias=(None if logit_bias is None else "given", None),
+                                    allowed_token_ids=(None if allowed_token_ids is None else "given", None),
+                                    min_p=(min_p or None, None), min_new_tokens=(min_new_tokens, 0),
+                                    stop=(stop or None, None)))
     if length_penalty != 1.0 or num_return_sequences != 1:
         raise ValueError("length_penalty and num_return_sequences go with num_beams")
     top_n = _check_logprobs(logprobs)
@@ -1343,6 +1626,10 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
             prompt_lens = [int(m) for m in (prompt_lens.tolist() if isinstance(prompt_lens, torch.Tensor)
                                             else prompt_lens) for _ in range(s)]
         B *= s
+    cons = _constraint_set(logit_bias, allowed_token_ids, min_p, min_new_tokens, stop, eos_token_id,
+                           model.config.vocab_size, B // s, idx.device)
+    if cons is not None and s > 1 and "bias_row" in cons:  # a prompt's bias row is its samples'
+        cons["bias_row"] = [r for r in cons["bias_row"] for _ in range(s)]
     n = int(max_new_tokens)
     if n < 0:
         raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
@@ -1372,7 +1659,7 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
     if prompt_lens is None and n == 0:
         return idx.clone() if top_n is None else _no_logprobs(idx.clone(), top_n)
     return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad,
-                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype, s, top_n)
+                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype, s, top_n, cons)
 
 
 def _generate_beams(model, idx, max_new_tokens, num_beams, length_penalty, num_return_sequences, eos_token_id,
@@ -1447,7 +1734,7 @@ def _no_logprobs(tokens: torch.Tensor, top_n: int) -> GenerateOutput:
 
 
 def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad, draft=None,
-              penalties=(1.0, 0.0, 0.0, False), kv_dtype="bf16", samples=1, top_n=None):
+              penalties=(1.0, 0.0, 0.0, False), kv_dtype="bf16", samples=1, top_n=None, cons=None):
     """The token loop of ``generate``: [B, P + m], row b = its prompt, its m new tokens from column lens[b] on, then
     ``pad`` (``lens`` None: every row holds P tokens and nothing is padded). m = n, or with eos the number of tokens by
     which every row has emitted it. Host sampler: new tokens are collected per step and scattered into the buffer that
@@ -1458,7 +1745,10 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     ``top_n`` (None: off) returns a ``GenerateOutput``: the device sampler writes each token's log-probability and
     ``top_n`` alternatives to the token's column of a ``LogprobBuffer``, the host sampler takes them from
     ``token_logprobs`` of the step's logits, before the penalties; columns that hold no generated token (prompt, pad,
-    after a row's eos) are 0."""
+    after a row's eos) are 0.
+    ``cons`` (``_constraint_set``'s result, None: off): the device sampler takes them as keywords and matches the stop
+    sequences in the buffer; the host sampler passes its logits through ``apply_constraints`` after the penalties, gives
+    ``min_p`` to ``sample_next`` and matches the stop sequences with ``stop_match`` in the tokens it has drawn."""
     B, P = idx.shape
     dev = idx.device
     if eos_token_id is not None and seed is not None and not 0 <= eos_token_id < model.config.vocab_size:
@@ -1481,7 +1771,7 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
             sess.fork(b, range(b + 1, b + samples))
         logits = sess.logits[:, :model.config.vocab_size].clone()
     rp, pp, fp, on = penalties
-    pen = _penalty_keywords(penalties, lens_t.tolist())
+    pen = {**_penalty_keywords(penalties, lens_t.tolist()), **_constraint_keywords(cons, lens_t.tolist())}
     if seed is not None:
         done = None if eos_token_id is None else torch.zeros(B, dtype=torch.uint8, device=dev)
         if draft is None:
@@ -1495,18 +1785,32 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     else:
         toks = []
         done = torch.zeros(B, dtype=torch.bool, device=dev)
+        c = cons or {}
+        starts = lens_t.tolist()
+        told = [r[:m] for r, m in zip(seq.tolist(), starts)] if c.get("stop") else None  # each row's tokens so far
         for i in range(n):
             raw = logits  # (the model's own row: what the log-probabilities are taken from)
             if on:
                 logits = apply_penalties(logits, seq, lens_t + i, lens_t, rp, pp, fp)
-            nxt = sample_next(logits, temperature, top_k, generator, top_p)
+            if cons is not None:
+                logits = apply_constraints(logits, lens_t + i, lens_t, c.get("logit_bias"), c.get("bias_row"),
+                                           c["min_new_tokens"], eos_token_id)
+            nxt = sample_next(logits, temperature, top_k, generator, top_p, c.get("min_p"))
             if eos_token_id is not None:
                 nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)  # a finished row keeps emitting eos
+            if told is not None:  # a row that completes a stop sequence is finished from the next step on
+                was, hits = done.tolist(), []
+                for b, t in enumerate(nxt.tolist()):
+                    told[b].append(t)
+                    hits.append(not was[b] and stop_match(told[b], starts[b], c["stop"], c["min_new_tokens"]))
+                stop_hit = torch.tensor(hits, device=dev)
             if buf is not None:  # (a row finished before this step: 0, as the device sampler writes)
                 live = list(range(B)) if eos_token_id is None else (~done).nonzero()[:, 0].tolist()
                 buf.put(live, [int(m) + i for m in lens_t[live].tolist()], token_logprobs(raw, nxt, top_n), live)
             if eos_token_id is not None:
                 done = done | (nxt == eos_token_id)
+            if told is not None:
+                done = done | stop_hit
             toks.append(nxt)
             if on:  # the next step's history
                 seq.scatter_(1, (lens_t + i)[:, None], nxt[:, None])
@@ -1518,7 +1822,14 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
         made = new.size(1)
         seq.scatter_(1, lens_t[:, None] + torch.arange(made, device=dev)[None], new)
     if eos_token_id is not None:
-        finished = ((new == eos_token_id).cumsum(1) > 0).all(0)  # steps by which every row has emitted eos
+        ended = (new == eos_token_id).cumsum(1) > 0
+        if cons is not None and cons["stop"]:  # a row that completed a stop sequence has ended from that column on
+            rows = seq[:, :P + made].tolist()
+            for b, m in enumerate(lens_t.tolist()):
+                at = first_stop(rows[b][:m + made], m, cons["stop"], cons["min_new_tokens"], eos_token_id)
+                if at is not None:
+                    ended[b, at - m:] = True
+        finished = ended.all(0)  # steps by which every row has emitted eos (or completed a stop sequence)
         if bool(finished.any()):
             made = int(finished.int().argmax()) + 1
     keep = cols[:, :P + made] < (lens_t + made)[:, None]
@@ -1553,7 +1864,8 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
                   top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
                   eos_token_id: Optional[int] = None, generator: Optional[torch.Generator] = None,
                   repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
-                  frequency_penalty: float = 0.0, kv_dtype: str = "bf16", logprobs=None) -> list:
+                  frequency_penalty: float = 0.0, kv_dtype: str = "bf16", logprobs=None, logit_bias=None,
+                  allowed_token_ids=None, min_p: Optional[float] = None, min_new_tokens: int = 0, stop=None) -> list:
     """``GPT2.generate_many``: see there."""
     check_kv_dtype(kv_dtype)
     top_n = _check_logprobs(logprobs)
@@ -1578,6 +1890,10 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
         raise ValueError(f"seed must be an int (got {seed!r})")
     if eos_token_id is not None and not 0 <= eos_token_id < model.config.vocab_size:
         raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={model.config.vocab_size})")
+    cons = _constraint_set(logit_bias, allowed_token_ids, min_p, min_new_tokens, stop, eos_token_id,
+                           model.config.vocab_size, int(batch_size), model.arena.device, per_row=False)
+    if cons is not None:
+        lp["constraints"] = cons
     if not prompts or n == 0:
         return [p.long().clone() if top_n is None else _no_logprobs(p.long().clone(), top_n) for p in prompts]
     _check_model(model)
@@ -1589,7 +1905,8 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
 
 
 def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, eos_token_id,
-                  penalties=(1.0, 0.0, 0.0, False), logprobs: Optional[int] = None) -> list:
+                  penalties=(1.0, 0.0, 0.0, False), logprobs: Optional[int] = None,
+                  constraints: Optional[dict] = None) -> list:
     """The loop of ``generate_many`` over a session (anything with DecodeSession's ``B``, ``Tcap``, ``lens``,
     ``device``, ``refill``, ``generate`` and ``flush``). Rows are slots: a slot holds prompt ``owner[row]`` (None: a
     dummy of one token whose output is dropped) and draws with ``row_id = owner[row]``. The device loop runs in chunks
@@ -1604,9 +1921,14 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
 
     ``logprobs=top_n`` (None: off) gives ``generate`` a ``LogprobBuffer`` beside ``seq``; a harvested prompt is then a
     ``GenerateOutput`` cut where its tokens are cut (0 in the prompt's columns), and a slot's row of the buffer is
-    cleared when the slot is filled."""
+    cleared when the slot is filled.
+
+    ``constraints`` (``_constraint_set``'s result, None: off): every slot reads the one bias row, the generated part
+    starts at the prompt's length, and with stop sequences ``seq`` holds the prompts as with penalties; a harvested
+    prompt is cut after the token that completed a stop sequence, as after eos."""
     B, dev = sess.B, sess.device
-    on = penalties[3]
+    stops = constraints["stop"] if constraints else []
+    on = penalties[3] or bool(stops)
     out: List[Optional[torch.Tensor]] = [None] * len(prompts)
     pending = list(range(len(prompts)))[::-1]  # (pop() serves them in input order)
     owner: List[Optional[int]] = [None] * B
@@ -1637,7 +1959,8 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
             if owner[r] is None and sess.lens[r] + m + 1 > sess.Tcap:
                 fill(r)
         sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done,
-                      row_id=[DUMMY_ID if o is None else o for o in owner], **_penalty_keywords(penalties, start), **lp)
+                      row_id=[DUMMY_ID if o is None else o for o in owner],
+                      **{**_penalty_keywords(penalties, start), **_constraint_keywords(constraints, start)}, **lp)
         sess.flush()  # every row's logits are now those of its next position: a refilled row joins on equal terms
         host = torch.cat([done.to(torch.int64)[:, None], seq], dim=1).cpu()  # the one read of the chunk
         for r in range(B):
@@ -1649,6 +1972,9 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
                 hits = (new == eos_token_id).nonzero()
                 if hits.numel():
                     new = new[:int(hits[0]) + 1]
+                at = first_stop(new.tolist(), 0, stops, constraints["min_new_tokens"], eos_token_id) if stops else None
+                if at is not None:
+                    new = new[:at + 1]
             out[owner[r]] = torch.cat([prompts[owner[r]].to(dev), new.to(dev)])
             if buf is not None:  # (device slices: nothing more is read back)
                 end = start[r] + new.numel()

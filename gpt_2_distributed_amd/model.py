@@ -349,7 +349,9 @@ class GPT2(nn.Module):
                  pad_token_id: Optional[int] = None, draft_tokens: Optional[int] = None,
                  draft_fn=None, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0, kv_dtype: str = "bf16", num_samples: int = 1, logprobs=None,
-                 num_beams: Optional[int] = None, length_penalty: float = 1.0, num_return_sequences: int = 1):
+                 num_beams: Optional[int] = None, length_penalty: float = 1.0, num_return_sequences: int = 1,
+                 logit_bias=None, allowed_token_ids=None, min_p: Optional[float] = None, min_new_tokens: int = 0,
+                 stop=None):
         """nanoGPT's ``generate``: continue the prompts ``idx`` [B, P] by ``max_new_tokens`` tokens; returns the int64
         sequences [B, P + n]. ``temperature == 0`` is greedy; otherwise ``logits / temperature``, optional ``top_k``
         filter, softmax, optional nucleus (``top_p``) filter and ``torch.multinomial`` with ``generator``
@@ -383,6 +385,19 @@ class GPT2(nn.Module):
         was generated in this call and ``presence_penalty`` if it was at all are subtracted (the OpenAI / vLLM
         convention: the prompt does not count; 0 off). They move the logits in front of the greedy argmax, temperature,
         ``top_k`` and ``top_p``. A value that is not finite, or ``repetition_penalty <= 0``, raises ``ValueError``.
+
+        Constraints, for both samplers, ``prompt_lens``, ``draft_tokens``, ``num_samples``, ``kv_dtype`` and
+        ``logprobs`` alike (``generation.apply_constraints``, ``sample_reference``'s ``min_p`` and
+        ``generation.stop_match`` are the rule; with ``seed`` they run inside the sampling kernel and the loop still
+        never returns to the host), applied after the penalties in this order: ``logit_bias``, a ``{token: value}``
+        dict, a ``[V]`` tensor or a ``[B, V]`` tensor, is added to the logits (-inf bans a token; +inf and NaN raise
+        ``ValueError``; a dict or ``[V]`` is one device row every row reads), ``allowed_token_ids=[...]`` being short
+        for -inf everywhere else; ``min_new_tokens=n`` keeps ``eos_token_id`` at -inf until a row holds n new tokens;
+        then temperature, ``top_k`` and ``top_p`` as ever; ``min_p`` in (0, 1] also drops every token less than
+        ``min_p`` times as likely as the most likely one (greedy ignores it); ``stop=[[ids], ...]`` (at most 8
+        sequences of at most 16 tokens) ends a row at the token that completes one of them inside its new tokens, once
+        it holds ``min_new_tokens``: the stop tokens stay in the output and the row goes on as after eos.
+        ``min_new_tokens`` and ``stop`` need an ``eos_token_id``. The log-probabilities stay those of the raw row.
 
         ``kv_dtype="fp8"`` keeps the key/value cache as OCP e4m3 codes with one power-of-two scale per (layer, K or V,
         sequence, head, position): 68 bytes where bf16 takes 128 (``generation.kv_quantize`` is the rule). Every key and
@@ -430,8 +445,9 @@ class GPT2(nn.Module):
         finishes. ``ValueError``, naming the argument: ``num_beams`` outside [1, 20] or above ``vocab_size``,
         ``B * num_beams > 64``, ``num_return_sequences`` outside [1, num_beams], a non-finite ``length_penalty``, and
         any of ``seed``, ``generator``, ``temperature != 1``, ``top_k``, ``top_p``, the penalties, ``draft_tokens``,
-        ``num_samples > 1`` and ``logprobs`` given with ``num_beams``. Not offered: beams in ``generate_many``, the
-        per-token log-probabilities of a beam, sampling and diverse beam search. ``num_beams=None`` (the default) is
+        ``num_samples > 1``, ``logprobs`` and the constraints given with ``num_beams``. Not offered: beams in
+        ``generate_many``, the per-token log-probabilities of a beam, sampling and diverse beam search, and constraints
+        (``logit_bias``, ``min_p``, ``min_new_tokens``, ``stop``) on beams. ``num_beams=None`` (the default) is
         the call without it, on the same code path.
 
         Always computes in bf16 with fp32 accumulation and the fp32 residual stream (the autocast path), whatever
@@ -445,13 +461,14 @@ class GPT2(nn.Module):
         return generate(self, idx, max_new_tokens, temperature, top_k, generator, eos_token_id, top_p, seed,
                         prompt_lens, pad_token_id, draft_tokens, draft_fn, repetition_penalty, presence_penalty,
                         frequency_penalty, kv_dtype, num_samples, logprobs, num_beams, length_penalty,
-                        num_return_sequences)
+                        num_return_sequences, logit_bias, allowed_token_ids, min_p, min_new_tokens, stop)
 
     def generate_many(self, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                       top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
                       eos_token_id: Optional[int] = None, generator=None, repetition_penalty: float = 1.0,
                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, kv_dtype: str = "bf16",
-                      logprobs=None):
+                      logprobs=None, logit_bias=None, allowed_token_ids=None, min_p: Optional[float] = None,
+                      min_new_tokens: int = 0, stop=None):
         """Continue any number of 1-D ``prompts`` of any lengths by up to ``max_new_tokens`` tokens each; returns a list
         in input order, each entry the prompt plus its new tokens, cut after the first ``eos_token_id``.
 
@@ -469,10 +486,14 @@ class GPT2(nn.Module):
         history is its own prompt and new tokens, so the guarantee holds with them. ``kv_dtype`` as for ``generate``: a
         row of the fp8 cache is a function of that row's values alone, so the guarantee holds with it too.
         ``logprobs`` as for ``generate``: each entry is then such a tuple for its prompt, cut where its tokens are cut;
-        the values are functions of the row's logits, so the guarantee covers them."""
+        the values are functions of the row's logits, so the guarantee covers them. ``logit_bias`` (a dict or a ``[V]``
+        tensor: one row for every prompt), ``allowed_token_ids``, ``min_p``, ``min_new_tokens`` and ``stop`` as for
+        ``generate``: functions of the row's own logits, position and tokens, so the guarantee holds with them; an entry
+        is cut after the token that completes a stop sequence, as after eos."""
         from .generation import generate_many
         return generate_many(self, prompts, max_new_tokens, batch_size, temperature, top_k, top_p, seed, eos_token_id,
-                             generator, repetition_penalty, presence_penalty, frequency_penalty, kv_dtype, logprobs)
+                             generator, repetition_penalty, presence_penalty, frequency_penalty, kv_dtype, logprobs,
+                             logit_bias, allowed_token_ids, min_p, min_new_tokens, stop)
 
     # ---- optimizer (nanoGPT-style name the north star uses) -----------------------------------------
     def configure_optimizers(self, weight_decay: float = 0.1, learning_rate: float = 1e-4,

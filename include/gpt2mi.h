@@ -28,7 +28,7 @@ extern "C" {
 
 #define GPT2MI_ABI_VERSION 24
 /* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
-#define GPT2MI_ABI_MINOR 3
+#define GPT2MI_ABI_MINOR 4
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -675,6 +675,59 @@ int gpt2mi_beam_reorder(void* kcache, void* vcache, float* kscale, float* vscale
 int gpt2mi_decode_beam_search(const gpt2mi_decode_plan* plan, int V, int W, int64_t eos, const int* pos0, const int* lo,
                               int n, int64_t* tok, int64_t* seq, int ld_seq, float* cum, uint8_t* done, int32_t* parents,
                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- v24.4: logit bias, min-p, a minimum number of new tokens and stop sequences in the sampler (csrc/sample_con.hip,
+ * csrc/decode.hip). The executable specification is gpt_2_distributed_amd/generation.py apply_constraints,
+ * sample_reference(min_p=) and stop_match. On a row drawn at pos whose generated part starts at gen_start (pen's, 0
+ * without), in this order, every arithmetic step one IEEE fp32 operation rounded to nearest:
+ *   1 the raw row: the log-probabilities of v24.1 keep coming from it;
+ *   2 the penalties of v22;
+ *   3 bias: x_i = x_i + bias[bias_row[b]][i] where the row has a bias row (-inf bans a token; +inf and NaN are outside
+ *     the contract);
+ *   4 min_new > 0 and pos - gen_start < min_new: x_eos = -inf;
+ *   5 logits_out receives the row as it stands; then the temperature division, top-k and top-p as ever;
+ *   6 min_p > 0, sampled form only: with lmp = fp32(log(double(min_p))) and mx the row maximum after the division, token
+ *     i is kept iff x_i >= fl32(mx + lmp), intersected with what top-k and top-p kept;
+ *   7 the draw;
+ *   8 stop sequences: a row that was not done and drew t != eos gets its done flag set when for some sequence s of length
+ *     n the tokens hist[pos - n + 1 .. pos - 1] followed by t equal s, with pos - n + 1 >= gen_start (the match lies in
+ *     the generated part) and pos - gen_start + 1 >= min_new. From then on the row emits eos, as a row that drew eos.
+ * A row with no finite value left gives token 0 in both kernel forms.
+ * The kernels are instantiations of the sampling kernel of their own (the others are compiled as before): the bias is a
+ * streaming add of one coalesced load per element, the stop table travels by value and thread 0 compares at most 15
+ * history entries per sequence with it; no float atomics, two calls give the same bits. ---- */
+#define GPT2MI_STOP_MAX_SEQS 8
+#define GPT2MI_STOP_MAX_LEN 16
+typedef struct gpt2mi_constraints {
+  const float* bias;   /* device fp32 [bias_rows][ld_bias]; NULL: none */
+  int ld_bias, bias_rows;
+  const int* bias_row; /* HOST [B]; -1: the row has no bias; NULL: row b reads bias row b */
+  float min_p;         /* 0: off; (0, 1] */
+  int min_new;         /* 0: off */
+  int n_stop;          /* 0 .. GPT2MI_STOP_MAX_SEQS */
+  const int32_t* stop; /* HOST [n_stop][GPT2MI_STOP_MAX_LEN] */
+  const int* stop_len; /* HOST [n_stop], each 1 .. GPT2MI_STOP_MAX_LEN */
+} gpt2mi_constraints;
+/* gpt2mi_sample_logprobs under the rule above. pen supplies hist / hist_row / gen_start (its values neutral if unused;
+ * NULL: no history, gen_start 0); lp may be NULL. con == NULL, or one with nothing on (no row with a bias row, min_p 0,
+ * min_new 0, n_stop 0), is gpt2mi_sample_logprobs exactly, on the same kernels. Refused with 22 and a message naming the
+ * entry and the index, before any launch, beside the forwarded checks: min_p outside [0, 1] or NaN; min_new < 0, or
+ * min_new > 0 with eos < 0; n_stop outside [0, GPT2MI_STOP_MAX_SEQS]; a stop_len outside [1, GPT2MI_STOP_MAX_LEN]; a stop
+ * token outside [0, V); n_stop > 0 with eos < 0, a NULL done, a NULL hist (or stop / stop_len), ld_hist < pos[b] or
+ * hist_row[b] outside [0, hist_rows); a bias with ld_bias < V or bias_rows < 1; bias_row[b] outside [-1, bias_rows); a
+ * NULL bias_row with bias_rows < B; gen_start[b] outside [0, pos[b]]. */
+int gpt2mi_sample_constrained(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
+                              uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
+                              int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out,
+                              const gpt2mi_penalties* pen, float* logits_out, const gpt2mi_logprobs* lp,
+                              const gpt2mi_constraints* con, void* stream);
+/* gpt2mi_decode_generate_logprobs likewise (con == NULL or neutral: that entry exactly): seq is the history, hist_row
+ * the identity, and with n_stop > 0 a NULL seq is refused. */
+int gpt2mi_decode_generate_constrained(const gpt2mi_decode_plan* plan, int V, float temperature, int top_k, float top_p,
+                                       uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
+                                       int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream,
+                                       float repetition, float presence, float frequency, const int* gen_start,
+                                       const gpt2mi_logprobs* lp, const gpt2mi_constraints* con);
 
 #ifdef __cplusplus
 }
