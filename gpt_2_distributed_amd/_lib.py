@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
 # additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
-ABI_MINOR = 4
+ABI_MINOR = 5
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -159,13 +159,22 @@ _SIGS = {
                                   _p, _p, _p, _c_int, _p, _p, _p, _p, _p, _p],
     "gpt2mi_decode_generate_constrained": [_p, _c_int, _c_float, _c_int, _c_float, _c_u64, ctypes.c_int64, _p, _p, _c_int,
                                            _p, _p, _c_int, _p, _p, _c_float, _c_float, _c_float, _p, _p, _p],
+    # v24.5 document masking: idx, B, T, T_valid, eot, eot_begin, start, end, stream; the attention lists with doc_start
+    # (forward) or (doc_start, doc_end) (backward) before B
+    "gpt2mi_doc_bounds": [_p, _c_int, _c_int, _c_int, ctypes.c_int64, _c_int, _p, _p, _p],
+    "gpt2mi_attn_fwd_doc": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
+    "gpt2mi_attn_bwd_doc": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
+    "gpt2mi_attn_fwd_f32_doc": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
+    "gpt2mi_attn_bwd_f32_doc": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64,
+                                _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
                 "gpt2mi_beam_select": 2, "gpt2mi_beam_reorder_workspace": 2, "gpt2mi_beam_reorder": 2,
                 "gpt2mi_decode_beam_search": 2, "gpt2mi_gemm_wgrad_batch": 3, "gpt2mi_gemm_wgrad_batch_scratch": 3,
                 "gpt2mi_gemm_wgrad_batch_max": 3, "gpt2mi_sample_constrained": 4,
-                "gpt2mi_decode_generate_constrained": 4}
+                "gpt2mi_decode_generate_constrained": 4, "gpt2mi_doc_bounds": 5, "gpt2mi_attn_fwd_doc": 5,
+                "gpt2mi_attn_bwd_doc": 5, "gpt2mi_attn_fwd_f32_doc": 5, "gpt2mi_attn_bwd_f32_doc": 5}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
              "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size}
@@ -446,14 +455,50 @@ def wgrad_splits(M, N, K, cus=256):
     return best
 
 
-def attn_fwd(qkv, out, lse, B, T, H, D, p_drop=0.0, seed=0):
-    _call("gpt2mi_attn_fwd_f32" if _f32(qkv) else "gpt2mi_attn_fwd", _ptr(qkv), _ptr(out), _ptr(lse), B, T, H, D, p_drop, seed, _stream())
+def _doc_ptrs(doc, B, T):
+    """(start, end) pointers of a packing.DocBounds for the _doc attention entries, its tensors checked against [B, T]
+    (metadata only: no host synchronisation). A None member stays None: the C entry's NULL refusal."""
+    start, end = doc
+    for name, t in (("start", start), ("end", end)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (B, T) or not t.is_contiguous()):
+            raise KernelError(f"doc bounds: {name} must be a contiguous int32 [B={B}, T={T}] tensor "
+                              f"(got {t.dtype} {tuple(t.shape)})")
+    return _ptr(start), _ptr(end)
 
 
-def attn_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, D, p_drop=0.0, seed=0, colsum=None):
-    """colsum: optional fp32 [B*T/32, 3C] partial column sums of dqkv (bf16 path; sum rows with colsum_bf16)."""
-    _call("gpt2mi_attn_bwd_f32" if _f32(qkv) else "gpt2mi_attn_bwd", _ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse),
-          _ptr(delta), _ptr(dqkv), _ptr(colsum), B, T, H, D, p_drop, seed, _stream())
+def doc_bounds(idx, eot, eot_begin, start, end, T_valid=None):
+    """gpt2mi_doc_bounds (packing.doc_bounds_reference is the rule): the document [start, end) of every position of idx
+    int64 [B, T] into the int32 [B, T] tensors start / end; eot_begin False: eot closes a document, True: it opens one."""
+    B, T = idx.shape
+    if idx.dtype != torch.int64 or not idx.is_contiguous():
+        raise KernelError("doc_bounds: idx must be a contiguous int64 [B, T] tensor")
+    s, e = _doc_ptrs((start, end), B, T)
+    _call("gpt2mi_doc_bounds", _ptr(idx), B, T, T if T_valid is None else T_valid, int(eot), int(bool(eot_begin)), s, e,
+          _stream())
+
+
+def attn_fwd(qkv, out, lse, B, T, H, D, p_drop=0.0, seed=0, doc=None):
+    """doc: a packing.DocBounds (int32 [B, T] start, end) -> the document-masked entry; None: the call as it was."""
+    f32 = _f32(qkv)
+    if doc is None:
+        _call("gpt2mi_attn_fwd_f32" if f32 else "gpt2mi_attn_fwd", _ptr(qkv), _ptr(out), _ptr(lse), B, T, H, D, p_drop, seed, _stream())
+        return
+    start, _ = _doc_ptrs(doc, B, T)
+    _call("gpt2mi_attn_fwd_f32_doc" if f32 else "gpt2mi_attn_fwd_doc", _ptr(qkv), _ptr(out), _ptr(lse), start, B, T, H,
+          D, p_drop, seed, _stream())
+
+
+def attn_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, D, p_drop=0.0, seed=0, colsum=None, doc=None):
+    """colsum: optional fp32 [B*T/32, 3C] partial column sums of dqkv (bf16 path; sum rows with colsum_bf16).
+    doc: as attn_fwd."""
+    f32 = _f32(qkv)
+    if doc is None:
+        _call("gpt2mi_attn_bwd_f32" if f32 else "gpt2mi_attn_bwd", _ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse),
+              _ptr(delta), _ptr(dqkv), _ptr(colsum), B, T, H, D, p_drop, seed, _stream())
+        return
+    start, end = _doc_ptrs(doc, B, T)
+    _call("gpt2mi_attn_bwd_f32_doc" if f32 else "gpt2mi_attn_bwd_doc", _ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse),
+          _ptr(delta), _ptr(dqkv), _ptr(colsum), start, end, B, T, H, D, p_drop, seed, _stream())
 
 
 def xent_fwd(logits, ld, labels, loss_rows, lse, dlogits, ldd, M, V, loss, inv_count, ignore_index=-100):

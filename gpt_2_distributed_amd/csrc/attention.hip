@@ -189,11 +189,32 @@ __device__ __forceinline__ void attn_block(int& bh, int& blk) {
   blk = L / BH;
 }
 
+// Document masking (packing.py: query t attends key k iff doc_start[t] <= k <= t, which for k <= t is t < doc_end[k]).
+// The masked kernels are the same three templates with the bounds as a trailing parameter pack `Doc` (one const int*:
+// doc_start [B, T] in forward / dQ, doc_end [B, T] in dK/dV); without it the signature, and so the kernel, is the
+// unmasked one, instruction for instruction. Every line of the mask sits under `if constexpr (DOC)`. The masked
+// instantiations keep the budget of the unmasked ones (no scratch, 3 waves / SIMD; tests/test_kernel_resources.py
+// matches them by name), which in the backward takes some care: see the notes at the masks.
+__device__ __forceinline__ const int* doc_ptr() { return nullptr; }
+__device__ __forceinline__ const int* doc_ptr(const int* p) { return p; }
+// a bound as a wave-uniform value, clamped into [lo, hi]: bounds that break the contract may give wrong numbers,
+// never a tile index out of range
+__device__ __forceinline__ int doc_bound_u(const int* row, int i, int lo, int hi) {
+  return __builtin_amdgcn_readfirstlane(min(max(row[i], lo), hi));
+}
+// The running max of a masked forward starts here, not at -inf: a query whose document starts after a visited tile
+// has all its scores of that tile at -inf, and -inf - (-inf) would be NaN (this file is built with -fno-honor-nans:
+// no NaN may be formed). With a finite start exp2(-inf - m) = 0 and the correction exp2(m - first real max) = 0
+// multiply accumulators that are still zero, the same bits as the -inf start gives when key 0 is visible.
+constexpr float kDocMaxInit = -1e30f;
+
 // ---------------------------------------------------------------------------------------------
-template <bool DROP>
+template <bool DROP, class... Doc>
 __global__ __launch_bounds__(kThreads, 3) void attn_fwd_kernel(const bf16* __restrict__ qkv, bf16* __restrict__ out,
                                                                float* __restrict__ lse, int T, int H, float scale,
-                                                               uint64_t seed, uint32_t thr, float inv_keep) {
+                                                               uint64_t seed, uint32_t thr, float inv_keep,
+                                                               Doc... doc) {
+  constexpr bool DOC = sizeof...(Doc) != 0;
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * BKV * 128];  // 2 stages x (K, V)
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4;
   const int nqb = (T + BQ - 1) / BQ;
@@ -216,6 +237,24 @@ __global__ __launch_bounds__(kThreads, 3) void attn_fwd_kernel(const bf16* __res
           base + (size_t)min(q_lo + 16 * qg + (lane & 15), T - 1) * ld + h * D + 32 * kk + 8 * g);
   const float sl2 = scale * kLog2e;
   float m[2] = {-INFINITY, -INFINITY};
+  // DOC: doc_start of the lane's two queries; of the block's first query as its first key tile j0 (the bounds do not
+  // decrease along a row); of the wave's first / last query (ws_lo / ws_hi: the least / greatest of the wave)
+  [[maybe_unused]] int ds[2] = {0, 0};
+  [[maybe_unused]] int ws_lo = 0, ws_hi = 0;
+  int j0 = 0;
+  if constexpr (DOC) {
+    const int* drow = doc_ptr(doc...) + (size_t)b * T;
+#pragma unroll
+    for (int qg = 0; qg < 2; ++qg) {
+      const int q = min(q_lo + 16 * qg + (lane & 15), T - 1);
+      ds[qg] = min(max(drow[q], 0), q);
+    }
+    j0 = doc_bound_u(drow, qb * BQ, 0, qb * BQ) / BKV;
+    const int qw = min(q_lo, T - 32);
+    ws_lo = doc_bound_u(drow, qw, 0, qw);
+    ws_hi = doc_bound_u(drow, qw + 31, 0, qw + 31);
+    m[0] = m[1] = kDocMaxInit;
+  }
   // o[qg][4] holds the row sums l = P.1 of the group's queries: one more PV-shaped MFMA against a
   // ones operand (the MFMA pipe has slack; 32 VALU adds per tile do not). Every row of it is l.
   f32x4 o[2][5];
@@ -230,16 +269,16 @@ __global__ __launch_bounds__(kThreads, 3) void attn_fwd_kernel(const bf16* __res
   const uint32_t loff = tile_dma_off(ld, lane);
   const int wu = __builtin_amdgcn_readfirstlane(w);
   const __amdgpu_buffer_rsrc_t rs = qkv_rsrc(base);
-  kv_tile_dma(smem, rs, 0, C, h * D, (int)ld, loff, wu);
+  kv_tile_dma(smem, rs, j0 * BKV, C, h * D, (int)ld, loff, wu);
   __syncthreads();  // waits for this wave's DMAs (vmcnt(0)), then for every wave's
 
-  for (int j = 0; j < nkv; ++j) {
-    const int cur = j & 1;
+  for (int j = j0; j < nkv; ++j) {
+    const int cur = (j - j0) & 1;
     const char* Ks = smem + cur * 2 * BKV * 128;
     const char* Vs = Ks + BKV * 128;
     const int k_lo = j * BKV;
     // wave-uniform: a key of the tile is visible to a query of the wave
-    const bool active = wave_valid && k_lo <= q_lo + 31;
+    const bool active = wave_valid && k_lo <= q_lo + 31 && (!DOC || k_lo + BKV - 1 >= ws_lo);
     f32x4 s[2][4];
     if (active) {
 #pragma unroll
@@ -257,15 +296,18 @@ __global__ __launch_bounds__(kThreads, 3) void attn_fwd_kernel(const bf16* __res
     // issued behind S = K Q^T; it lands while this tile's softmax and P.V run
     if (j + 1 < nkv) kv_tile_dma(smem + (cur ^ 1) * 2 * BKV * 128, rs, (j + 1) * BKV, C, h * D, (int)ld, loff, wu);
     if (active) {
-      const bool diag = k_lo + BKV - 1 > q_lo;
+      // DOC: and on the tiles that hold a document boundary of one of the wave's queries
+      const bool diag = k_lo + BKV - 1 > q_lo || (DOC && k_lo < ws_hi);
       if (diag) {  // causal mask only on the diagonal tiles (wave-uniform branch)
 #pragma unroll
         for (int qg = 0; qg < 2; ++qg)
 #pragma unroll
           for (int fi = 0; fi < 4; ++fi)
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (k_lo + 16 * fi + 4 * g + r > q_lo + 16 * qg + (lane & 15)) s[qg][fi][r] = -INFINITY;
+            for (int r = 0; r < 4; ++r) {
+              const int key = k_lo + 16 * fi + 4 * g + r;
+              if (key > q_lo + 16 * qg + (lane & 15) || (DOC && key < ds[qg])) s[qg][fi][r] = -INFINITY;
+            }
       }
 #pragma unroll
       for (int qg = 0; qg < 2; ++qg) {
@@ -276,9 +318,27 @@ __global__ __launch_bounds__(kThreads, 3) void attn_fwd_kernel(const bf16* __res
         // "every lane's own 16 keys pass" is the same decision as "every query's 64 keys pass". The cross-lane
         // max is formed only when a rescale is taken (the cand, bit for bit, of a max over all 64 keys).
         const float lmax = max16(s[qg]);
-        if (!__all(lmax * sl2 <= m[qg] + kRescaleThr)) {
+        bool take;
+        [[maybe_unused]] bool mine = true;
+        if constexpr (DOC) {
+          // A query that meets its first visible key here (its max still at kDocMaxInit) must take that key's score
+          // as its max, but that is no growth of the group: the queries that have a max keep it unless one of THEM
+          // grew past the threshold, as in the unmasked kernel. So a group whose queries lie in several documents (or
+          // in a row's padding) moves the max of the earlier document's queries exactly when the unmasked kernel
+          // would, and one document per row gives the unmasked kernel's bits.
+          const bool fresh = m[qg] == kDocMaxInit;
+          const bool grow = lmax * sl2 > m[qg] + kRescaleThr;
+          const bool grown = __any(!fresh && grow);
+          take = grown || __any(fresh && grow);
+          mine = grown || fresh;
+        } else {
+          take = !__all(lmax * sl2 <= m[qg] + kRescaleThr);
+        }
+        if (take) {
           const float cand = xor_max(lmax) * sl2;
-          const float mn = fmaxf(m[qg], cand);  // finite: tile 0 holds key 0, visible to every query
+          // finite: tile 0 holds key 0, visible to every query (DOC: m starts finite, kDocMaxInit)
+          float mn = fmaxf(m[qg], cand);
+          if constexpr (DOC) mn = mine ? mn : m[qg];
           const float corr = __builtin_amdgcn_exp2f(m[qg] - mn);
 #pragma unroll
           for (int f = 0; f < 4; ++f)
@@ -353,16 +413,15 @@ __global__ __launch_bounds__(kThreads, 3) void attn_fwd_kernel(const bf16* __res
 // the dK/dV kernel, which runs after this one. A 64-key tile runs as two 32-key halves, the second half's S / dP MFMAs
 // issued ahead of the first half's dQ MFMAs so that those run beside the second half's elementwise VALU work (a
 // software pipeline inside one wave; the half-size S / dP registers also bring the kernel to 160 VGPRs: 3 waves / SIMD).
-template <bool DROP>
-__global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(const bf16* __restrict__ qkv,
-                                                                  const bf16* __restrict__ out,
-                                                                  const bf16* __restrict__ dout,
-                                                                  const float* __restrict__ lse,
-                                                                  float* __restrict__ delta,
-                                                                  bf16* __restrict__ dqkv, float* __restrict__ csum,
-                                                                  int T, int H, float scale, uint64_t seed,
-                                                                  uint32_t thr, float inv_keep) {
-  __shared__ __attribute__((aligned(16))) char smem[2 * 2 * BKV * 128];
+template <bool DROP, class... Doc>
+__global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(
+    const bf16* __restrict__ qkv, const bf16* __restrict__ out, const bf16* __restrict__ dout,
+    const float* __restrict__ lse, float* __restrict__ delta, bf16* __restrict__ dqkv, float* __restrict__ csum, int T,
+    int H, float scale, uint64_t seed, uint32_t thr, float inv_keep, Doc... doc) {
+  constexpr bool DOC = sizeof...(Doc) != 0;
+  // DOC: + span[BQ], query q's count of visible keys q - doc_start[q] + 1, in LDS and read in the masked tiles only
+  // (no register held across the tile loop)
+  __shared__ __attribute__((aligned(16))) char smem[2 * 2 * BKV * 128 + (DOC ? BQ * 4 : 0)];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4;
   const int nqb = (T + BQ - 1) / BQ;
   int bh, blk;
@@ -399,6 +458,19 @@ __global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(const bf16* __
   }
   const float sl2 = scale * kLog2e;
   [[maybe_unused]] const uint32_t tk2 = drop_tk2(thr > 0u ? thr : 1u);
+  [[maybe_unused]] int ws_lo = 0, ws_hi = 0;  // DOC: as in the forward
+  int j0 = 0;
+  if constexpr (DOC) {
+    const int* drow = doc_ptr(doc...) + (size_t)b * T;
+    if (threadIdx.x < BQ) {  // published by the barrier behind the first tile's DMA
+      const int q = min(qb * BQ + (int)threadIdx.x, T - 1);
+      reinterpret_cast<int*>(smem + 2 * 2 * BKV * 128)[threadIdx.x] = q - min(max(drow[q], 0), q) + 1;
+    }
+    j0 = doc_bound_u(drow, qb * BQ, 0, qb * BQ) / BKV;
+    const int qw = min(q_lo, T - 32);
+    ws_lo = doc_bound_u(drow, qw, 0, qw);
+    ws_hi = doc_bound_u(drow, qw + 31, 0, qw + 31);
+  }
   f32x4 dq[2][4];
 #pragma unroll
   for (int qg = 0; qg < 2; ++qg)
@@ -409,17 +481,17 @@ __global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(const bf16* __
   const uint32_t loff = tile_dma_off(ld, lane);
   const int wu = __builtin_amdgcn_readfirstlane(w);
   const __amdgpu_buffer_rsrc_t rs = qkv_rsrc(base);
-  kv_tile_dma(smem, rs, 0, C, h * D, (int)ld, loff, wu);
+  kv_tile_dma(smem, rs, j0 * BKV, C, h * D, (int)ld, loff, wu);
   __syncthreads();
-  for (int j = 0; j < nkv; ++j) {
-    const int cur = j & 1;
+  for (int j = j0; j < nkv; ++j) {
+    const int cur = (j - j0) & 1;
     const char* Ks = smem + cur * 2 * BKV * 128;
     const char* Vs = Ks + BKV * 128;
     // next K/V tile by LDS-DMA into the stage released by tile j-1's barrier
     if (j + 1 < nkv) kv_tile_dma(smem + (cur ^ 1) * 2 * BKV * 128, rs, (j + 1) * BKV, C, h * D, (int)ld, loff, wu);
     const int k_lo = j * BKV;
-    if (wave_valid && k_lo <= q_lo + 31) {
-      const bool diag = k_lo + BKV - 1 > q_lo;
+    if (wave_valid && k_lo <= q_lo + 31 && (!DOC || k_lo + BKV - 1 >= ws_lo)) {
+      const bool diag = k_lo + BKV - 1 > q_lo || (DOC && k_lo < ws_hi);  // DOC: or a document boundary in the tile
       [[maybe_unused]] uint32_t pre = 0;
       if constexpr (DROP)
         pre = drop_pre(seed32(seed), ((uint32_t)bh * T + q_lo + (lane & 15)) * (uint32_t)T + k_lo + 4 * g);
@@ -446,6 +518,25 @@ __global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(const bf16* __
       // dS of half kk, packed per query group
       auto elem = [&](auto diag_c, int kk, f32x4 (&s)[2][2], const f32x4 (&dp)[2][2], bf16x8 (&pk)[2]) {
         constexpr bool DIAG = decltype(diag_c)::value;
+        // DOC: the causal and the document mask on the scores, ahead of the exponentials (exp2(-inf) = 0: the masked
+        // P is exactly the 0 the select below gives, and the +inf of a key far above the row's lse is never formed);
+        // here, before the dropout masks are live, it fits the register budget. Visible iff 0 <= q - key < span[q].
+        if constexpr (DIAG && DOC) {
+          // (lq opaque: the LDS address and the q - key base are formed here, in the rare tile, not hoisted out of the
+          // tile loop into registers the kernel does not have)
+          int lq = lane & 15;
+          asm volatile("" : "+v"(lq));
+#pragma unroll
+          for (int qg = 0; qg < 2; ++qg) {
+            const uint32_t sp = reinterpret_cast<const uint32_t*>(smem + 2 * 2 * BKV * 128)[32 * w + 16 * qg + lq];
+            const int qk = q_lo + 16 * qg + lq - (k_lo + 32 * kk + 4 * g);
+#pragma unroll
+            for (int f = 0; f < 2; ++f)
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if ((uint32_t)(qk - 16 * f - r) >= sp) s[qg][f][r] = -INFINITY;
+          }
+        }
 #pragma unroll
         for (int f = 0; f < 2; ++f) {
           const int fi = 2 * kk + f;
@@ -464,7 +555,8 @@ __global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(const bf16* __
               f32x2 d = {dp[qg][f][r], dp[qg][f][r + 1]};
 #pragma unroll
               for (int e = 0; e < 2; ++e) {
-                if constexpr (DIAG) p[e] = (k_lo + 16 * fi + 4 * g + r + e > q_lo + 16 * qg + (lane & 15)) ? 0.f : p[e];
+                // selected, never multiplied: p of a future key may be +inf
+                if constexpr (DIAG && !DOC) p[e] = (k_lo + 16 * fi + 4 * g + r + e > q_lo + 16 * qg + (lane & 15)) ? 0.f : p[e];
                 if constexpr (DROP) d[e] = sel_mask(km[e][qg], d[e], -dl[qg]);
               }
               const f32x2 v = p * d;
@@ -520,18 +612,21 @@ __global__ __launch_bounds__(kThreads, 3) void attn_bwd_dq_kernel(const bf16* __
 // tile, instead of holding them in registers: 166 VGPRs, 3 waves / SIMD (the round-3 kernel held K / V in 32 VGPRs
 // and took 64-query tiles at 224 VGPRs, 2 waves / SIMD: 339-354 -> 315 us per layer in the step, profiles/r4s/).
 constexpr int BQ3 = 32;
-template <bool DROP>
+template <bool DROP, class... Doc>
 __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __restrict__ qkv,
                                                                  const bf16* __restrict__ dout,
                                                                  const float* __restrict__ lse,
                                                                  const float* __restrict__ delta,
                                                                  bf16* __restrict__ dqkv, float* __restrict__ csum,
                                                                  int T, int H, float scale, uint64_t seed,
-                                                                 uint32_t thr, float inv_keep) {
+                                                                 uint32_t thr, float inv_keep, Doc... doc) {
+  constexpr bool DOC = sizeof...(Doc) != 0;
   constexpr int kKV = BKB * 128;            // [128 keys][64 d] bf16
   constexpr int kTile = BQ3 * 128;          // [32 queries][64 d] bf16
   constexpr int kStage = 2 * kTile + 2 * BQ3 * 4;  // Q, dO, lse, delta
-  __shared__ __attribute__((aligned(16))) char smem[2 * kKV + 2 * kStage];
+  // DOC: + len[BKB], key k's count of queries that see it, doc_end[k] - k, in LDS and read in the masked tiles only
+  // (as dQ's span)
+  __shared__ __attribute__((aligned(16))) char smem[2 * kKV + 2 * kStage + (DOC ? BKB * 4 : 0)];
   char* const Kl = smem;
   char* const Vl = smem + kKV;
   char* const stg = smem + 2 * kKV;
@@ -574,36 +669,59 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
   const int wu = __builtin_amdgcn_readfirstlane(w);
   const __amdgpu_buffer_rsrc_t rsq = qkv_rsrc(base), rsd = qkv_rsrc(dout + (size_t)b * T * C);
   // Q / dO tiles (32 rows: one DMA instruction per wave and array); lse / delta by registers
+  constexpr bool kLate = DOC && DROP;
   auto gload = [&](int i, char* st) {
     tile_dma<8>(st, rsq, i * BQ3, h * D, (int)ld, qoff, wu);
     tile_dma<8>(st + kTile, rsd, i * BQ3, h * D, C, doff, wu);
-    if (threadIdx.x < BQ3) {
+    if (!kLate && threadIdx.x < BQ3) {
       rl = lrow[i * BQ3 + threadIdx.x];
       rdl = drow[i * BQ3 + threadIdx.x];
     }
   };
-  auto sstore = [&](char* st) {
+  // (kLate, the masked kernel with dropout: lse / delta of tile i are loaded here, behind the arithmetic of the tile
+  // before it, not ahead of it; the two registers that carry them across it are what that instantiation lacks)
+  auto sstore = [&](int i, char* st) {
     if (threadIdx.x < BQ3) {
+      if constexpr (kLate) {
+        rl = lrow[i * BQ3 + threadIdx.x];
+        rdl = drow[i * BQ3 + threadIdx.x];
+      }
       // both negated: the FMA addend and the dropped-key value of dP - delta as stored (no per-tile negations)
       reinterpret_cast<float*>(st + 2 * kTile)[threadIdx.x] = -(rl * kLog2e);
       reinterpret_cast<float*>(st + 2 * kTile + BQ3 * 4)[threadIdx.x] = -rdl;
     }
   };
   const int i0 = kb * 128 / BQ3;
+  // DOC: doc_end of the block's last valid key as the end of its query tiles (the bounds do
+  // not decrease along a row); of the wave's first / last key (we_lo / we_hi: the least / greatest of the wave)
+  [[maybe_unused]] int we_lo = T, we_hi = T;
+  int iend = nqt;
+  if constexpr (DOC) {
+    const int* erow = doc_ptr(doc...) + (size_t)b * T;
+    if (threadIdx.x < BKB) {  // published by the barrier behind the first tile's loads
+      const int key = min(kb * 128 + (int)threadIdx.x, T - 1);
+      reinterpret_cast<int*>(smem + 2 * kKV + 2 * kStage)[threadIdx.x] = min(max(erow[key], key + 1), T) - key;
+    }
+    const int klast = min(kb * 128 + 127, T - 1);
+    iend = (doc_bound_u(erow, klast, klast + 1, T) + BQ3 - 1) / BQ3;
+    const int kw = min(k_lo, T - 32);
+    we_lo = doc_bound_u(erow, kw, kw + 1, T);
+    we_hi = doc_bound_u(erow, kw + 31, kw + 32, T);
+  }
   gload(i0, stg);
-  sstore(stg);
+  sstore(i0, stg);
   __syncthreads();
   const char* Kw = Kl + 32 * w * 128;  // this wave's 32 keys
   const char* Vw = Vl + 32 * w * 128;
-  for (int i = i0; i < nqt; ++i) {
+  for (int i = i0; i < iend; ++i) {
     const int cur = (i - i0) & 1;
     const char* Qs = stg + cur * kStage;
     const char* Ds = Qs + kTile;
     const float* Ls = reinterpret_cast<const float*>(Qs + 2 * kTile);
     const float* Dl = Ls + BQ3;
-    if (i + 1 < nqt) gload(i + 1, stg + (cur ^ 1) * kStage);
+    if (i + 1 < iend) gload(i + 1, stg + (cur ^ 1) * kStage);
     const int q0 = i * BQ3;
-    if (wave_valid && q0 + BQ3 - 1 >= k_lo) {
+    if (wave_valid && q0 + BQ3 - 1 >= k_lo && (!DOC || q0 < we_hi)) {
       const bool diag = q0 < k_lo + 31;
       const uint32_t pre_t = DROP ? drop_pre(seed32(seed), ((uint32_t)bh * T + q0 + 4 * g) * (uint32_t)T + k_lo + (lane & 15)) : 0u;
       f32x4 s[2][2], dp[2][2];  // [kg][fl]: S[q = q0 + 16fl + 4g + r][key = k_lo + 16kg + (l&15)]
@@ -615,6 +733,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
         s[0][fl] = s[1][fl] = f32x4{0.f, 0.f, 0.f, 0.f};
         dp[0][fl] = dp[1][fl] = nd4[fl];
       }
+      // (DOC: the LDS reads' lane offsets are formed per tile, a few VALU operations, instead of living in registers
+      // across the loop: with the mask the dropout instantiation does not have them)
+      int lt = lane;
+      if constexpr (DOC) asm volatile("" : "+v"(lt));
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
         bf16x8 kfr[2], vfr[2];
@@ -625,8 +747,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
         }
 #pragma unroll
         for (int fl = 0; fl < 2; ++fl) {
-          const bf16x8 qa = row_frag(Qs, 16 * fl, kk, lane);
-          const bf16x8 da = row_frag(Ds, 16 * fl, kk, lane);
+          const bf16x8 qa = row_frag(Qs, 16 * fl, kk, lt);
+          const bf16x8 da = row_frag(Ds, 16 * fl, kk, lt);
 #pragma unroll
           for (int kg = 0; kg < 2; ++kg) {
             s[kg][fl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qa, kfr[kg], s[kg][fl], 0, 0, 0);
@@ -661,6 +783,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
 #pragma unroll
             for (int fl = 0; fl < 2; ++fl) {
               float p = __builtin_amdgcn_exp2f(s[kg][fl][r]);
+              // selected, never multiplied: p of a future query's key may be +inf
               if constexpr (DIAG) p = (q0 + 16 * fl + 4 * g + r < key) ? 0.f : p;
               float pdv = p, d = dp[kg][fl][r];
               if constexpr (DROP) {
@@ -675,19 +798,51 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkdv_kernel(const bf16* __res
       };
       if (diag) elementwise(std::true_type{});
       else elementwise(std::false_type{});
-      const bf16x8 p0 = pack_perm(dp[0], 0), p1 = pack_perm(dp[1], 0);
-      const bf16x8 s0 = pack_perm(s[0], 0), s1 = pack_perm(s[1], 0);
+      bf16x8 p0 = pack_perm(dp[0], 0), p1 = pack_perm(dp[1], 0);
+      bf16x8 s0 = pack_perm(s[0], 0), s1 = pack_perm(s[1], 0);
+      // DOC, a tile that holds the end of a document of the wave's keys: the packed P and dS of the pairs in different
+      // documents are cleared bit-wise (a select whatever the bits: P of such a pair may have overflowed to +inf, and
+      // its dS with it). Here, behind the dropout masks, the compares fit the register budget; inside the elementwise
+      // pass they spill. Visible iff 0 <= q - key < len[key]; element j of a fragment is query 16(j >> 2) + 4g + (j & 3).
+      if constexpr (DOC) {
+        if (q0 + BQ3 - 1 >= we_lo) {
+          // (the lane id opaque and the wave id scalar: the LDS address and the q - key base are formed here, in the
+          // rare tile, not hoisted out of the tile loop into registers the kernel does not have; the halves' masks by
+          // shifts of inline constants for the same reason)
+          int lo = lane;
+          asm volatile("" : "+v"(lo));
+          const int lk = lo & 15;
+          auto clear = [&](int kg, bf16x8& pf, bf16x8& sf) {
+            const uint32_t ln = reinterpret_cast<const uint32_t*>(smem + 2 * kKV + 2 * kStage)[32 * wu + 16 * kg + lk];
+            const int qk = q0 - (kb * 128 + 32 * wu + 16 * kg) + 4 * (lo >> 4) - lk;
+            u32x4 pw = __builtin_bit_cast(u32x4, pf), sw = __builtin_bit_cast(u32x4, sf);
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+              const int o = 16 * (d >> 1) + 2 * (d & 1);
+              const uint32_t keep = (((uint32_t)(qk + o) < ln ? ~0u : 0u) >> 16) |
+                                    (((uint32_t)(qk + o + 1) < ln ? ~0u : 0u) << 16);
+              pw[d] &= keep;
+              sw[d] &= keep;
+            }
+            pf = __builtin_bit_cast(bf16x8, pw);
+            sf = __builtin_bit_cast(bf16x8, sw);
+          };
+          clear(0, p0, s0);
+          clear(1, p1, s1);
+          __builtin_amdgcn_sched_barrier(0);  // (the fragment reads below stay below: their registers are free only here)
+        }
+      }
 #pragma unroll
       for (int fd = 0; fd < 4; ++fd) {
-        const bf16x8 dot = tr_frag(Ds, 0, 16 * fd, lane);
-        const bf16x8 qt = tr_frag(Qs, 0, 16 * fd, lane);
+        const bf16x8 dot = tr_frag(Ds, 0, 16 * fd, lt);
+        const bf16x8 qt = tr_frag(Qs, 0, 16 * fd, lt);
         dv[0][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot, p0, dv[0][fd], 0, 0, 0);
         dv[1][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(dot, p1, dv[1][fd], 0, 0, 0);
         dk[0][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt, s0, dk[0][fd], 0, 0, 0);
         dk[1][fd] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qt, s1, dk[1][fd], 0, 0, 0);
       }
     }
-    if (i + 1 < nqt) sstore(stg + (cur ^ 1) * kStage);
+    if (i + 1 < iend) sstore(i + 1, stg + (cur ^ 1) * kStage);
     __syncthreads();
   }
   if (!wave_valid) return;
@@ -727,43 +882,82 @@ static void launch_by_drop(uint32_t thr, Launch&& launch) {
   else launch(std::false_type{});
 }
 
-}  // namespace
-
-GPT2MI_EXPORT int gpt2mi_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int head_dim,
-                                  float p_drop, uint64_t seed, void* stream) {
-  if (const int rc = attn_check("attn_fwd", B, T, H, head_dim, p_drop)) return rc;
+// The forward of both entries: doc... is empty (gpt2mi_attn_fwd) or doc_start (gpt2mi_attn_fwd_doc)
+template <class... Doc>
+static int attn_fwd_launch(const char* what, const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H,
+                           int head_dim, float p_drop, uint64_t seed, void* stream, Doc... doc) {
+  if (const int rc = attn_check(what, B, T, H, head_dim, p_drop)) return rc;
   const float scale = 1.f / sqrtf((float)head_dim);
   dim3 grid((T + BQ - 1) / BQ, B * H);
   const uint32_t thr = drop_threshold(p_drop);
   const float ik = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
   launch_by_drop(thr, [&](auto drop) {
-    attn_fwd_kernel<decltype(drop)::value><<<grid, kThreads, 0, (hipStream_t)stream>>>(
-        (const bf16*)qkv, (bf16*)out, lse, T, H, scale, seed, thr, ik);
+    attn_fwd_kernel<decltype(drop)::value, Doc...><<<grid, kThreads, 0, (hipStream_t)stream>>>(
+        (const bf16*)qkv, (bf16*)out, lse, T, H, scale, seed, thr, ik, doc...);
   });
-  return gpt2mi::check_launch("attn_fwd");
+  return gpt2mi::check_launch(what);
 }
 
-GPT2MI_EXPORT int gpt2mi_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
-                                  float* delta, uint16_t* dqkv, float* dqkv_colsum, int B, int T, int H,
-                                  int head_dim, float p_drop, uint64_t seed, void* stream) {
-  if (const int rc = attn_check("attn_bwd", B, T, H, head_dim, p_drop)) return rc;
+// The backward of both entries: start_end... is empty, or doc_start (dQ) and doc_end (dK/dV)
+template <class... Doc>
+static int attn_bwd_launch(const char* what, const uint16_t* qkv, const uint16_t* out, const uint16_t* dout,
+                           const float* lse, float* delta, uint16_t* dqkv, float* dqkv_colsum, int B, int T, int H,
+                           int head_dim, float p_drop, uint64_t seed, void* stream, Doc... start_end) {
+  if (const int rc = attn_check(what, B, T, H, head_dim, p_drop)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const float scale = 1.f / sqrtf((float)head_dim);
   const uint32_t thr = drop_threshold(p_drop);
   const float ik = p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f;
   // dQ first: it forms delta (dO . O per query) for the dK/dV kernel
   const dim3 gq((T + BQ - 1) / BQ, B * H);
-  launch_by_drop(thr, [&](auto drop) {
-    attn_bwd_dq_kernel<decltype(drop)::value><<<gq, kThreads, 0, s>>>(
-        (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, dqkv_colsum, T, H, scale, seed,
-        thr, ik);
-  });
-  int rc = gpt2mi::check_launch("attn_bwd_dq");
-  if (rc) return rc;
   const dim3 gkv((T + BKB - 1) / BKB, B * H);
+  int rc = 0;
   launch_by_drop(thr, [&](auto drop) {
-    attn_bwd_dkdv_kernel<decltype(drop)::value><<<gkv, 256, 0, s>>>(
-        (const bf16*)qkv, (const bf16*)dout, lse, delta, (bf16*)dqkv, dqkv_colsum, T, H, scale, seed, thr, ik);
+    constexpr bool DROP = decltype(drop)::value;
+    if constexpr (sizeof...(Doc) == 0) {
+      attn_bwd_dq_kernel<DROP><<<gq, kThreads, 0, s>>>((const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse,
+                                                        delta, (bf16*)dqkv, dqkv_colsum, T, H, scale, seed, thr, ik);
+      if ((rc = gpt2mi::check_launch("attn_bwd_dq"))) return;
+      attn_bwd_dkdv_kernel<DROP><<<gkv, 256, 0, s>>>((const bf16*)qkv, (const bf16*)dout, lse, delta, (bf16*)dqkv,
+                                                      dqkv_colsum, T, H, scale, seed, thr, ik);
+    } else {
+      const int* const se[] = {start_end...};
+      attn_bwd_dq_kernel<DROP, const int*><<<gq, kThreads, 0, s>>>(
+          (const bf16*)qkv, (const bf16*)out, (const bf16*)dout, lse, delta, (bf16*)dqkv, dqkv_colsum, T, H, scale,
+          seed, thr, ik, se[0]);
+      if ((rc = gpt2mi::check_launch("attn_bwd_dq"))) return;
+      attn_bwd_dkdv_kernel<DROP, const int*><<<gkv, 256, 0, s>>>(
+          (const bf16*)qkv, (const bf16*)dout, lse, delta, (bf16*)dqkv, dqkv_colsum, T, H, scale, seed, thr, ik, se[1]);
+    }
   });
-  return gpt2mi::check_launch("attn_bwd_dkdv");
+  return rc ? rc : gpt2mi::check_launch("attn_bwd_dkdv");
+}
+
+}  // namespace
+
+GPT2MI_EXPORT int gpt2mi_attn_fwd(const uint16_t* qkv, uint16_t* out, float* lse, int B, int T, int H, int head_dim,
+                                  float p_drop, uint64_t seed, void* stream) {
+  return attn_fwd_launch("attn_fwd", qkv, out, lse, B, T, H, head_dim, p_drop, seed, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse,
+                                  float* delta, uint16_t* dqkv, float* dqkv_colsum, int B, int T, int H,
+                                  int head_dim, float p_drop, uint64_t seed, void* stream) {
+  return attn_bwd_launch("attn_bwd", qkv, out, dout, lse, delta, dqkv, dqkv_colsum, B, T, H, head_dim, p_drop, seed,
+                         stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_fwd_doc(const uint16_t* qkv, uint16_t* out, float* lse, const int* doc_start, int B,
+                                      int T, int H, int head_dim, float p_drop, uint64_t seed, void* stream) {
+  GPT2MI_REQUIRE(doc_start != nullptr, "attn_fwd_doc: doc_start is NULL");
+  return attn_fwd_launch("attn_fwd_doc", qkv, out, lse, B, T, H, head_dim, p_drop, seed, stream, doc_start);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_bwd_doc(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout,
+                                      const float* lse, float* delta, uint16_t* dqkv, float* dqkv_colsum,
+                                      const int* doc_start, const int* doc_end, int B, int T, int H, int head_dim,
+                                      float p_drop, uint64_t seed, void* stream) {
+  GPT2MI_REQUIRE(doc_start != nullptr && doc_end != nullptr, "attn_bwd_doc: doc_start / doc_end is NULL");
+  return attn_bwd_launch("attn_bwd_doc", qkv, out, dout, lse, delta, dqkv, dqkv_colsum, B, T, H, head_dim, p_drop,
+                         seed, stream, doc_start, doc_end);
 }

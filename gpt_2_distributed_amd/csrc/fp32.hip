@@ -183,10 +183,17 @@ __device__ __forceinline__ void st16(float* p, const float* d, float scale) {
                                                  d[4 * i + 3] * scale};
 }
 
+// Document masking (packing.py), DOC: query q attends key iff doc_start[q] <= key <= q, which for key <= q is
+// q < doc_end[key]. The bounds are clamped (start into [0, q], end into [key + 1, T]) and the tile loops start / end
+// at the bound of the workgroup's first query / last key (the bounds do not decrease along a row).
+__device__ __forceinline__ int doc_clamp(const int* row, int i, int lo, int hi) { return min(max(row[i], lo), hi); }
+
 // Forward: workgroup = (64 queries, one head); out = softmax(q k^T * scale, causal) (dropout) v.
+template <bool DOC>
 __global__ __launch_bounds__(kAThreads) void attn_fwd_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                  float* __restrict__ lse, int T, int H, float scale,
-                                                                 uint64_t seed, uint32_t thr, float inv_keep) {
+                                                                 uint64_t seed, uint32_t thr, float inv_keep,
+                                                                 const int* __restrict__ doc_start) {
   __shared__ __attribute__((aligned(16))) float kv[2][RT * HD];
   const int qt = gridDim.x - 1 - blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H;
   const int C = H * HD;
@@ -200,7 +207,13 @@ __global__ __launch_bounds__(kAThreads) void attn_fwd_f32_kernel(const float* __
 #pragma unroll
   for (int d = 0; d < 16; ++d) acc[d] = 0.f;
   float m = -INFINITY, l = 0.f;
-  for (int kt = 0; kt <= qt; ++kt) {
+  [[maybe_unused]] int ds = 0;
+  int kt0 = 0;
+  if constexpr (DOC) {
+    ds = doc_clamp(doc_start + (size_t)b * T, q, 0, q);
+    kt0 = doc_clamp(doc_start + (size_t)b * T, qt * RT, 0, qt * RT) / RT;
+  }
+  for (int kt = kt0; kt <= qt; ++kt) {
     __syncthreads();
     a_tile(kv[0], base + (size_t)kt * RT * ld + C + h * HD, ld);
     a_tile(kv[1], base + (size_t)kt * RT * ld + 2 * C + h * HD, ld);
@@ -217,12 +230,13 @@ __global__ __launch_bounds__(kAThreads) void attn_fwd_f32_kernel(const float* __
 #pragma unroll
         for (int d = 0; d < 16; ++d) p += qv[d] * kr[d];
         p = quad_sum(p) * scale;
-        if (kt * RT + jc + j > q) p = -INFINITY;
+        if (kt * RT + jc + j > q || (DOC && kt * RT + jc + j < ds)) p = -INFINITY;
         s[j] = p;
         tmax = fmaxf(tmax, p);
       }
       const float mn = fmaxf(m, tmax);
-      if (mn == -INFINITY) continue;  // whole chunk masked and nothing seen yet: cannot happen at jc = 0
+      // whole chunk masked and nothing seen yet: cannot happen at jc = 0 (DOC: in every chunk before the document)
+      if (mn == -INFINITY) continue;
       const float corr = __expf(m - mn);
       l *= corr;
 #pragma unroll
@@ -256,10 +270,11 @@ __global__ __launch_bounds__(256) void attn_delta_f32_kernel(const float* __rest
 }
 
 // dK, dV: workgroup = (64 keys, one head), loops over the query tiles at or after its key tile.
+template <bool DOC>
 __global__ __launch_bounds__(kAThreads) void attn_bwd_dkdv_f32_kernel(
     const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, float* __restrict__ dqkv, int T, int H, float scale, uint64_t seed, uint32_t thr,
-    float inv_keep) {
+    float inv_keep, const int* __restrict__ doc_end) {
   __shared__ __attribute__((aligned(16))) float qo[2][RT * HD];
   __shared__ float sl[RT], sd[RT];
   const int kt = blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H;
@@ -275,7 +290,12 @@ __global__ __launch_bounds__(kAThreads) void attn_bwd_dkdv_f32_kernel(
   ld16(vr, base + (size_t)key * ld + 2 * C + h * HD + 16 * qd);
 #pragma unroll
   for (int d = 0; d < 16; ++d) dk[d] = dv[d] = 0.f;
-  const int nqt = T / RT;
+  int nqt = T / RT;
+  [[maybe_unused]] int de = T;
+  if constexpr (DOC) {
+    de = doc_clamp(doc_end + (size_t)b * T, key, key + 1, T);
+    nqt = (doc_clamp(doc_end + (size_t)b * T, kt * RT + RT - 1, kt * RT + RT, T) + RT - 1) / RT;
+  }
   for (int qt = kt; qt < nqt; ++qt) {
     __syncthreads();
     a_tile(qo[0], base + (size_t)qt * RT * ld + h * HD, ld);
@@ -288,7 +308,7 @@ __global__ __launch_bounds__(kAThreads) void attn_bwd_dkdv_f32_kernel(
 #pragma unroll 4
     for (int i = 0; i < RT; ++i) {
       const int q = qt * RT + i;
-      if (q < key) continue;  // row-uniform within the 4 lanes
+      if (q < key || (DOC && q >= de)) continue;  // row-uniform within the 4 lanes
       const float* qr = qo[0] + i * HD + 16 * qd;
       const float* gr = qo[1] + i * HD + 16 * qd;
       float s = 0.f, dp = 0.f;
@@ -320,10 +340,11 @@ __global__ __launch_bounds__(kAThreads) void attn_bwd_dkdv_f32_kernel(
 }
 
 // dQ: workgroup = (64 queries, one head), loops over the key tiles at or before its query tile.
+template <bool DOC>
 __global__ __launch_bounds__(kAThreads) void attn_bwd_dq_f32_kernel(
     const float* __restrict__ qkv, const float* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, float* __restrict__ dqkv, int T, int H, float scale, uint64_t seed, uint32_t thr,
-    float inv_keep) {
+    float inv_keep, const int* __restrict__ doc_start) {
   __shared__ __attribute__((aligned(16))) float kv[2][RT * HD];
   const int qt = gridDim.x - 1 - blockIdx.x, bh = blockIdx.y, b = bh / H, h = bh % H;
   const int C = H * HD;
@@ -338,7 +359,13 @@ __global__ __launch_bounds__(kAThreads) void attn_bwd_dq_f32_kernel(
 #pragma unroll
   for (int d = 0; d < 16; ++d) dq[d] = 0.f;
   const float lq = lse[(size_t)bh * T + q], dl = delta[(size_t)bh * T + q];
-  for (int kt = 0; kt <= qt; ++kt) {
+  [[maybe_unused]] int ds = 0;
+  int kt0 = 0;
+  if constexpr (DOC) {
+    ds = doc_clamp(doc_start + (size_t)b * T, q, 0, q);
+    kt0 = doc_clamp(doc_start + (size_t)b * T, qt * RT, 0, qt * RT) / RT;
+  }
+  for (int kt = kt0; kt <= qt; ++kt) {
     __syncthreads();
     a_tile(kv[0], base + (size_t)kt * RT * ld + C + h * HD, ld);
     a_tile(kv[1], base + (size_t)kt * RT * ld + 2 * C + h * HD, ld);
@@ -347,6 +374,7 @@ __global__ __launch_bounds__(kAThreads) void attn_bwd_dq_f32_kernel(
     for (int j = 0; j < RT; ++j) {
       const int key = kt * RT + j;
       if (key > q) break;  // row-uniform
+      if (DOC && key < ds) continue;  // (before the exponential: P of a key of an earlier document may overflow)
       const float* kr = kv[0] + j * HD + 16 * qd;
       const float* vr = kv[1] + j * HD + 16 * qd;
       float s = 0.f, dp = 0.f;
@@ -424,26 +452,30 @@ GPT2MI_EXPORT int gpt2mi_gemm_f32(int layout, int epilogue, int M, int N, int K,
   }
 }
 
-GPT2MI_EXPORT int gpt2mi_attn_fwd_f32(const float* qkv, float* out, float* lse, int B, int T, int H, int head_dim,
-                                      float p_drop, uint64_t seed, void* stream) {
-  GPT2MI_REQUIRE(head_dim == HD, "attn_fwd_f32: head_dim=%d (only 64 is built)", head_dim);
+// The forward / backward of both fp32 attention entries: DOC false with NULL bounds, or true with doc_start / doc_end
+template <bool DOC>
+static int attn_fwd_f32_launch(const char* what, const float* qkv, float* out, float* lse, const int* doc_start, int B,
+                               int T, int H, int head_dim, float p_drop, uint64_t seed, void* stream) {
+  GPT2MI_REQUIRE(head_dim == HD, "%s: head_dim=%d (only 64 is built)", what, head_dim);
   GPT2MI_REQUIRE(p_drop <= 0.f || (size_t)B * H * T * T < (1ull << 32),
-                 "attn_fwd_f32: B*H*T*T exceeds the 32-bit dropout hash index");
-  GPT2MI_REQUIRE(T % RT == 0 && T > 0, "attn_fwd_f32: T=%d must be a multiple of 64", T);
-  attn_fwd_f32_kernel<<<dim3(T / RT, B * H), kAThreads, 0, (hipStream_t)stream>>>(
+                 "%s: B*H*T*T exceeds the 32-bit dropout hash index", what);
+  GPT2MI_REQUIRE(T % RT == 0 && T > 0, "%s: T=%d must be a multiple of 64", what, T);
+  attn_fwd_f32_kernel<DOC><<<dim3(T / RT, B * H), kAThreads, 0, (hipStream_t)stream>>>(
       qkv, out, lse, T, H, 1.f / sqrtf((float)head_dim), seed, drop_threshold(p_drop),
-      p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f);
-  return gpt2mi::check_launch("attn_fwd_f32");
+      p_drop > 0.f ? 1.f / (1.f - p_drop) : 1.f, doc_start);
+  return gpt2mi::check_launch(what);
 }
 
-GPT2MI_EXPORT int gpt2mi_attn_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse,
-                                      float* delta, float* dqkv, float* dqkv_colsum, int B, int T, int H,
-                                      int head_dim, float p_drop, uint64_t seed, void* stream) {
-  GPT2MI_REQUIRE(head_dim == HD, "attn_bwd_f32: head_dim=%d (only 64 is built)", head_dim);
+template <bool DOC>
+static int attn_bwd_f32_launch(const char* what, const float* qkv, const float* out, const float* dout,
+                               const float* lse, float* delta, float* dqkv, float* dqkv_colsum, const int* doc_start,
+                               const int* doc_end, int B, int T, int H, int head_dim, float p_drop, uint64_t seed,
+                               void* stream) {
+  GPT2MI_REQUIRE(head_dim == HD, "%s: head_dim=%d (only 64 is built)", what, head_dim);
   GPT2MI_REQUIRE(p_drop <= 0.f || (size_t)B * H * T * T < (1ull << 32),
-                 "attn_bwd_f32: B*H*T*T exceeds the 32-bit dropout hash index");
-  GPT2MI_REQUIRE(dqkv_colsum == nullptr, "attn_bwd_f32: the fused bias-gradient partials are bf16-path only");
-  GPT2MI_REQUIRE(T % RT == 0 && T > 0, "attn_bwd_f32: T=%d must be a multiple of 64", T);
+                 "%s: B*H*T*T exceeds the 32-bit dropout hash index", what);
+  GPT2MI_REQUIRE(dqkv_colsum == nullptr, "%s: the fused bias-gradient partials are bf16-path only", what);
+  GPT2MI_REQUIRE(T % RT == 0 && T > 0, "%s: T=%d must be a multiple of 64", what, T);
   hipStream_t s = (hipStream_t)stream;
   const float scale = 1.f / sqrtf((float)head_dim);
   const uint32_t thr = drop_threshold(p_drop);
@@ -451,11 +483,39 @@ GPT2MI_EXPORT int gpt2mi_attn_bwd_f32(const float* qkv, const float* out, const 
   attn_delta_f32_kernel<<<(B * T * H + 3) / 4, 256, 0, s>>>(out, dout, delta, B, T, H);
   int rc = gpt2mi::check_launch("attn_delta_f32");
   if (rc) return rc;
-  attn_bwd_dkdv_f32_kernel<<<dim3(T / RT, B * H), kAThreads, 0, s>>>(qkv, dout, lse, delta, dqkv, T, H, scale, seed,
-                                                                      thr, ik);
+  attn_bwd_dkdv_f32_kernel<DOC><<<dim3(T / RT, B * H), kAThreads, 0, s>>>(qkv, dout, lse, delta, dqkv, T, H, scale,
+                                                                           seed, thr, ik, doc_end);
   rc = gpt2mi::check_launch("attn_bwd_dkdv_f32");
   if (rc) return rc;
-  attn_bwd_dq_f32_kernel<<<dim3(T / RT, B * H), kAThreads, 0, s>>>(qkv, dout, lse, delta, dqkv, T, H, scale, seed, thr,
-                                                                    ik);
+  attn_bwd_dq_f32_kernel<DOC><<<dim3(T / RT, B * H), kAThreads, 0, s>>>(qkv, dout, lse, delta, dqkv, T, H, scale, seed,
+                                                                         thr, ik, doc_start);
   return gpt2mi::check_launch("attn_bwd_dq_f32");
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_fwd_f32(const float* qkv, float* out, float* lse, int B, int T, int H, int head_dim,
+                                      float p_drop, uint64_t seed, void* stream) {
+  return attn_fwd_f32_launch<false>("attn_fwd_f32", qkv, out, lse, nullptr, B, T, H, head_dim, p_drop, seed, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_bwd_f32(const float* qkv, const float* out, const float* dout, const float* lse,
+                                      float* delta, float* dqkv, float* dqkv_colsum, int B, int T, int H,
+                                      int head_dim, float p_drop, uint64_t seed, void* stream) {
+  return attn_bwd_f32_launch<false>("attn_bwd_f32", qkv, out, dout, lse, delta, dqkv, dqkv_colsum, nullptr, nullptr, B,
+                                    T, H, head_dim, p_drop, seed, stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_fwd_f32_doc(const float* qkv, float* out, float* lse, const int* doc_start, int B, int T,
+                                          int H, int head_dim, float p_drop, uint64_t seed, void* stream) {
+  GPT2MI_REQUIRE(doc_start != nullptr, "attn_fwd_f32_doc: doc_start is NULL");
+  return attn_fwd_f32_launch<true>("attn_fwd_f32_doc", qkv, out, lse, doc_start, B, T, H, head_dim, p_drop, seed,
+                                   stream);
+}
+
+GPT2MI_EXPORT int gpt2mi_attn_bwd_f32_doc(const float* qkv, const float* out, const float* dout, const float* lse,
+                                          float* delta, float* dqkv, float* dqkv_colsum, const int* doc_start,
+                                          const int* doc_end, int B, int T, int H, int head_dim, float p_drop,
+                                          uint64_t seed, void* stream) {
+  GPT2MI_REQUIRE(doc_start != nullptr && doc_end != nullptr, "attn_bwd_f32_doc: doc_start / doc_end is NULL");
+  return attn_bwd_f32_launch<true>("attn_bwd_f32_doc", qkv, out, dout, lse, delta, dqkv, dqkv_colsum, doc_start,
+                                   doc_end, B, T, H, head_dim, p_drop, seed, stream);
 }

@@ -50,6 +50,7 @@ from ._lib import wgrad_batch_plan as K_wgrad_batch_plan
 from ._lib import wgrad_group_splits as K_wgrad_group_splits
 from ._lib import wgrad_splits as K_wgrad_splits
 from .dropout_keys import MULTIPLIERS
+from .packing import DocBounds, check_bounds_meta, pad_bounds
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -351,13 +352,14 @@ class _Saved:
     pa: float
     seeds: dict
     act: torch.dtype
+    doc: Optional[DocBounds] = None  # document bounds [B, Tp] (padded), None: plain causal attention
 
 
 class _GPT2Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, engine, idx, labels, *params):
+    def forward(ctx, engine, idx, labels, doc, *params):
         ctx.set_materialize_grads(False)
-        logits, loss = engine._forward(idx, labels, True)
+        logits, loss = engine._forward(idx, labels, True, doc)
         ctx.engine = engine
         ctx.token = engine._fwd_token
         ctx.n_params = len(params)
@@ -370,16 +372,16 @@ class _GPT2Step(torch.autograd.Function):
             raise RuntimeError("GPT2 activations were overwritten by a later forward before this backward "
                                "(one forward/backward in flight per model)")
         eng._backward(grad_logits, grad_loss)
-        return (None, None, None) + (None,) * ctx.n_params
+        return (None, None, None, None) + (None,) * ctx.n_params
 
 
 class _TrunkFn(torch.autograd.Function):
     """GPT2Backbone.forward(idx) (model.py:275-313): embedding -> blocks -> ln_f, fp32 output."""
 
     @staticmethod
-    def forward(ctx, engine, idx, *params):
+    def forward(ctx, engine, idx, doc, *params):
         ctx.set_materialize_grads(False)
-        out = engine._trunk_forward_module(idx, True)
+        out = engine._trunk_forward_module(idx, True, doc)
         ctx.engine = engine
         ctx.token = engine._fwd_token
         ctx.n_params = len(params)
@@ -391,16 +393,16 @@ class _TrunkFn(torch.autograd.Function):
         if ctx.token != eng._fwd_token:
             raise RuntimeError("GPT2 activations were overwritten by a later forward before this backward")
         eng._trunk_backward_module(dy)
-        return (None, None) + (None,) * ctx.n_params
+        return (None, None, None) + (None,) * ctx.n_params
 
 
 class _SubFn(torch.autograd.Function):
     """A stand-alone block / MLP / attention call (its own activations; grads into the arena)."""
 
     @staticmethod
-    def forward(ctx, engine, kind, layer, x, *params):
+    def forward(ctx, engine, kind, layer, x, doc, *params):
         ctx.set_materialize_grads(False)
-        y, state = engine._sub_forward(kind, layer, x, True)
+        y, state = engine._sub_forward(kind, layer, x, True, doc)
         ctx.engine, ctx.kind, ctx.layer, ctx.state, ctx.n_params = engine, kind, layer, state, len(params)
         ctx.x_dtype = x.dtype
         return y
@@ -411,7 +413,7 @@ class _SubFn(torch.autograd.Function):
         if dy is not None:
             dx = ctx.engine._sub_backward(ctx.kind, ctx.layer, ctx.state, dy).to(ctx.x_dtype)
         ctx.state = None
-        return (None, None, None, dx) + (None,) * ctx.n_params
+        return (None, None, None, dx, None) + (None,) * ctx.n_params
 
 
 class GradHooks:
@@ -785,24 +787,26 @@ class Engine:
         return torch.is_grad_enabled() and any(p.requires_grad for p in self._params)
 
     # ---- public entry -------------------------------------------------------------------------------
-    def forward(self, idx: torch.Tensor, labels: Optional[torch.Tensor]):
+    def forward(self, idx: torch.Tensor, labels: Optional[torch.Tensor], doc: Optional[DocBounds] = None):
+        """doc: packing.DocBounds of idx (document-masked attention), carried through autograd as a non-differentiable
+        input; None: plain causal attention, the launches as they were."""
         if self._grad_enabled():
-            return _GPT2Step.apply(self, idx, labels, *self._params)
+            return _GPT2Step.apply(self, idx, labels, doc, *self._params)
         with torch.no_grad():
-            return self._forward(idx, labels, False)
+            return self._forward(idx, labels, False, doc)
 
     # (autograd.Function.forward runs with grad mode off: whether a backward will follow is decided here)
-    def backbone_forward(self, idx: torch.Tensor) -> torch.Tensor:
+    def backbone_forward(self, idx: torch.Tensor, doc: Optional[DocBounds] = None) -> torch.Tensor:
         if self._grad_enabled():
-            return _TrunkFn.apply(self, idx, *self._params)
+            return _TrunkFn.apply(self, idx, doc, *self._params)
         with torch.no_grad():
-            return self._trunk_forward_module(idx, False)
+            return self._trunk_forward_module(idx, False, doc)
 
-    def sub_forward(self, kind: str, layer: int, x: torch.Tensor) -> torch.Tensor:
+    def sub_forward(self, kind: str, layer: int, x: torch.Tensor, doc: Optional[DocBounds] = None) -> torch.Tensor:
         if self._grad_enabled() or x.requires_grad:
-            return _SubFn.apply(self, kind, layer, x, *self._params)
+            return _SubFn.apply(self, kind, layer, x, doc, *self._params)
         with torch.no_grad():
-            return self._sub_forward(kind, layer, x, False)[0]
+            return self._sub_forward(kind, layer, x, False, doc)[0]
 
     # ---- shared kernel sequences --------------------------------------------------------------------
     def _dropout(self):
@@ -825,15 +829,16 @@ class Engine:
             K.layernorm_fwd(x, self.p(pre + ".weight"), self.p(pre + ".bias"), None, out_f32, mean, rstd, M,
                             cfg.n_embd, cfg.layer_norm_eps)
 
-    def _attn_fwd(self, l, A, resid, out, B, T, act, pr, pa, seeds):
-        """A.ln1 -> qkv GEMM -> flash attention -> proj GEMM: out = resid + drop(proj(attn))."""
+    def _attn_fwd(self, l, A, resid, out, B, T, act, pr, pa, seeds, doc=None):
+        """A.ln1 -> qkv GEMM -> flash attention -> proj GEMM: out = resid + drop(proj(attn)). doc: DocBounds [B, T]
+        for the document-masked kernels, None for the causal ones."""
         C, H = self.cfg.n_embd, self.cfg.n_head
         M = B * T
         pre = f"transformer.h.{l}."
         self._gemm(K.FWD, K.EPI_BF16, M, 3 * C, C, A.ln1, C, self.w(pre + "attn.qkv.weight", act), C, A.qkv, 3 * C,
                bias=self.p(pre + "attn.qkv.bias"))
         with self._probe("attn_fwd"):
-            K.attn_fwd(A.qkv, A.ao, A.lse, B, T, H, C // H, pa, seeds[("attn", l)])
+            K.attn_fwd(A.qkv, A.ao, A.lse, B, T, H, C // H, pa, seeds[("attn", l)], doc=doc)
         self._gemm(K.FWD, K.EPI_RESID, M, C, C, A.ao, C, self.w(pre + "attn.proj.weight", act), C, out, C,
                bias=self.p(pre + "attn.proj.bias"), resid=resid, p_drop=pr, seed=seeds[("proj", l)])
 
@@ -847,15 +852,15 @@ class Engine:
         self._gemm(K.FWD, K.EPI_RESID, M, C, 4 * C, A.h, 4 * C, self.w(pre + "mlp.fc2.weight", act), 4 * C, out, C,
                bias=self.p(pre + "mlp.fc2.bias"), resid=resid, p_drop=pr, seed=seeds[("fc2", l)])
 
-    def _block_fwd(self, l, A, x_in, x_out, B, T, act, pr, pa, seeds):
+    def _block_fwd(self, l, A, x_in, x_out, B, T, act, pr, pa, seeds, doc=None):
         M = B * T
         pre = f"transformer.h.{l}."
         self._ln_fwd(x_in, pre + "ln1", A.ln1, A.m1, A.r1, M)
-        self._attn_fwd(l, A, x_in, A.xmid, B, T, act, pr, pa, seeds)
+        self._attn_fwd(l, A, x_in, A.xmid, B, T, act, pr, pa, seeds, doc)
         self._ln_fwd(A.xmid, pre + "ln2", A.ln2, A.m2, A.r2, M)
         self._mlp_fwd(l, A, A.xmid, x_out, M, act, pr, seeds)
 
-    def _trunk_fwd(self, ws, idx, B, T, T_valid, act, pr, pa, seeds, lnf_f32=None):
+    def _trunk_fwd(self, ws, idx, B, T, T_valid, act, pr, pa, seeds, lnf_f32=None, doc=None):
         C, L = self.cfg.n_embd, self.cfg.n_layer
         x = ws.x
         self._unit("embed")
@@ -863,7 +868,7 @@ class Engine:
                     seeds["embd"], T_valid=T_valid)
         for l in range(L):
             self._unit(f"h.{l}")
-            self._block_fwd(l, ws.blocks[l], x[l], x[l + 1], B, T, act, pr, pa, seeds)
+            self._block_fwd(l, ws.blocks[l], x[l], x[l + 1], B, T, act, pr, pa, seeds, doc)
         self._unit("head")
         self._ln_fwd(x[L], "transformer.ln_f", ws.lnf, ws.mf, ws.rf, B * T, out_f32=lnf_f32)
 
@@ -954,7 +959,7 @@ class Engine:
             self._wgrad_group(S, M, defer)
             defer.clear()
 
-    def _attn_bwd(self, l, A, S, dY, dx_out, B, T, act, pa, seeds, defer=None):
+    def _attn_bwd(self, l, A, S, dY, dx_out, B, T, act, pa, seeds, defer=None, doc=None):
         """dY = grad of the proj output with resid_drop applied -> dx_out = grad of the attention input."""
         C, H = self.cfg.n_embd, self.cfg.n_head
         M = B * T
@@ -962,7 +967,7 @@ class Engine:
         self._dgrad(act, M, dx_out, dY, pre + "attn.proj.weight", C, C)
         self._wgrad_or_defer(S, act, C, C, M, dY, C, A.ao, C, self.g(pre + "attn.proj.weight"), defer)
         K.attn_bwd(A.qkv, A.ao, dx_out, A.lse, S.delta, S.dqkv, B, T, H, C // H, pa, seeds[("attn", l)],
-                   colsum=S.dqkv_cs)
+                   colsum=S.dqkv_cs, doc=doc)
         self._dgrad(act, M, dx_out, S.dqkv, pre + "attn.qkv.weight", C, 3 * C)
         self._wgrad_or_defer(S, act, 3 * C, C, M, S.dqkv, 3 * C, A.ln1, C, self.g(pre + "attn.qkv.weight"), defer)
         if S.dqkv_cs is not None:  # qkv bias grad: sum the attention backward's 32-token partials
@@ -970,7 +975,7 @@ class Engine:
         else:
             K.colsum_bf16(S.dqkv, self.g(pre + "attn.qkv.bias"), M, 3 * C, 3 * C)
 
-    def _block_bwd(self, l, A, S, x_in, B, T, act, pr, pa, seeds, last, D=None, probs=None):
+    def _block_bwd(self, l, A, S, x_in, B, T, act, pr, pa, seeds, last, D=None, probs=None, doc=None):
         """S.dres = grad of the block output; S.dres_bf = its fc2 branch grad (drop2 applied) ->
         S.dres = grad of the block input; unless `last`, S.dres_bf = the fc2 branch grad of block l-1.
         D (the deferred mode, Workspace.deferred): the block's operands live in D.blocks[l] (its dres_bf the fc2 branch
@@ -989,7 +994,7 @@ class Engine:
         K.layernorm_bwd(A.xmid, self.p(pre + "ln2.weight"), A.m2, A.r2, S.dln, S.dres, self.g(pre + "ln2.weight"),
                         self.g(pre + "ln2.bias"), dproj, self.g(pre + "attn.proj.bias"), M, C, pr,
                         seeds[("proj", l)])
-        self._attn_bwd(l, A, S, dproj, S.dln, B, T, act, pa, seeds, grp)
+        self._attn_bwd(l, A, S, dproj, S.dln, B, T, act, pa, seeds, grp, doc)
         if grp and D is None:  # proj + qkv, before LN1's backward overwrites dres_bf (the proj wgrad's operand)
             self._wgrad_group(S, M, grp)
         if not last:
@@ -1019,7 +1024,8 @@ class Engine:
         self._ready("head")
         for l in reversed(range(L)):
             self._unit_bwd(f"h.{l}")
-            self._block_bwd(l, ws.blocks[l], ws, x[l], B, T, act, pr, pa, seeds, last=(l == 0), D=D, probs=probs)
+            self._block_bwd(l, ws.blocks[l], ws, x[l], B, T, act, pr, pa, seeds, last=(l == 0), D=D, probs=probs,
+                            doc=sv.doc)
             if D is None:
                 self._ready(f"h.{l}")
         if D is not None:
@@ -1033,6 +1039,14 @@ class Engine:
         self._ready("embed")
 
     # ---- the whole step ------------------------------------------------------------------------------
+    def _pad_doc(self, doc, idx, Tp):
+        """The caller's bounds (of the unpadded idx [B, T]) checked by their metadata, no host synchronisation, and
+        extended over the padding, which is one document [T, Tp) of its own."""
+        if doc is None:
+            return None
+        B, T = idx.shape
+        return pad_bounds(check_bounds_meta(doc, B, T, idx.device), Tp)
+
     def _pad(self, idx, labels):
         B, T = idx.shape
         if idx.dtype != torch.int64:
@@ -1049,10 +1063,11 @@ class Engine:
                 labels = F.pad(labels, (0, Tp - T), value=-100)
         return idx, labels, T
 
-    def _forward(self, idx, labels, need_grad):
+    def _forward(self, idx, labels, need_grad, doc=None):
         cfg = self.cfg
         self.gemm_sched = self.base_sched  # (a backward that raised midway left its flags)
         V, Vp, C = cfg.vocab_size, self.vpad, cfg.n_embd
+        doc = self._pad_doc(doc, idx, padded_len(idx.shape[1]))
         idx, labels, T = self._pad(idx, labels)
         B, Tp = idx.shape
         M = B * Tp
@@ -1062,8 +1077,8 @@ class Engine:
         pr, pa = self._dropout()
         seeds = self._next_seeds()
         self._fwd_token += 1
-        self._saved = _Saved(idx, labels, T, pr, pa, seeds, act)
-        self._trunk_fwd(ws, idx, B, Tp, T, act, pr, pa, seeds)
+        self._saved = _Saved(idx, labels, T, pr, pa, seeds, act, doc)
+        self._trunk_fwd(ws, idx, B, Tp, T, act, pr, pa, seeds, doc=doc)
         logits = torch.empty(M, Vp, dtype=act, device=self.device)  # fresh: the caller may keep it
         with self._probe("lm_head_fwd"):
             self._gemm(K.FWD, K.EPI_BF16, M, Vp, C, ws.lnf, C, self.w("transformer.wte.weight", act), C, logits, Vp)
@@ -1078,7 +1093,7 @@ class Engine:
         return out[..., :V], loss
 
     # ---- evaluation: forward only, nothing kept, nothing of the training state touched --------------------
-    def score(self, idx, labels, acc=None):
+    def score(self, idx, labels, acc=None, doc=None):
         """Per-token negative log-likelihoods of ``labels`` [B, T] without a backward, a logits tensor or the training
         workspace. Dropout is off whatever ``model.training`` is (fixed seeds, p = 0), and the dropout stream
         (_step_seed), _fwd_token, _saved, gemm_sched and the grad arena are left as found: no state that a later
@@ -1094,20 +1109,21 @@ class Engine:
         self.gemm_sched = self.base_sched
         try:
             with torch.no_grad():
-                return self._score(idx, labels, acc)
+                return self._score(idx, labels, acc, doc)
         finally:
             self.gemm_sched = sched
 
-    def _score(self, idx, labels, acc):
+    def _score(self, idx, labels, acc, doc=None):
         cfg = self.cfg
         V, Vp, C = cfg.vocab_size, self.vpad, cfg.n_embd
+        doc = self._pad_doc(doc, idx, padded_len(idx.shape[1]))
         idx, labels, T = self._pad(idx, labels)
         B, Tp = idx.shape
         M = B * Tp
         act = self.compute_dtype()
         self._sync_shadows(act, False)
         ws = self.eval_workspace(B, Tp, act)
-        self._trunk_fwd(ws, idx, B, Tp, T, act, 0.0, 0.0, self._seeds(0))
+        self._trunk_fwd(ws, idx, B, Tp, T, act, 0.0, 0.0, self._seeds(0), doc=doc)
         wte = self.w("transformer.wte.weight", act)
         if acc is None:
             s, n = torch.empty(1, dtype=F32, device=self.device), torch.empty(1, dtype=F32, device=self.device)
@@ -1181,8 +1197,9 @@ class Engine:
         self._end_grads()
 
     # ---- GPT2Backbone.forward on its own -------------------------------------------------------------
-    def _trunk_forward_module(self, idx, need_grad):
+    def _trunk_forward_module(self, idx, need_grad, doc=None):
         self.gemm_sched = self.base_sched  # (a backward that raised midway left its flags)
+        doc = self._pad_doc(doc, idx, padded_len(idx.shape[1]))
         idx, _, T = self._pad(idx, None)
         B, Tp = idx.shape
         act = self.compute_dtype()
@@ -1191,9 +1208,9 @@ class Engine:
         pr, pa = self._dropout()
         seeds = self._next_seeds()
         self._fwd_token += 1
-        self._saved = _Saved(idx, None, T, pr, pa, seeds, act)
+        self._saved = _Saved(idx, None, T, pr, pa, seeds, act, doc)
         out = torch.empty(B * Tp, self.cfg.n_embd, dtype=F32, device=self.device)
-        self._trunk_fwd(ws, idx, B, Tp, T, act, pr, pa, seeds, lnf_f32=out)
+        self._trunk_fwd(ws, idx, B, Tp, T, act, pr, pa, seeds, lnf_f32=out, doc=doc)
         return out.view(B, Tp, -1)[:, :T]
 
     def _trunk_backward_module(self, dy):
@@ -1214,7 +1231,7 @@ class Engine:
         self._end_grads()
 
     # ---- GPT2Block / MLP / CausalMultiHeadSelfAttention forward on their own --------------------------
-    def _sub_forward(self, kind, l, x, need_grad):
+    def _sub_forward(self, kind, l, x, need_grad, doc=None):
         """kind: "block" (x = residual stream, model.py:213-219), "mlp" (x = ln2 output, model.py:186-192),
         "attn" (x = ln1 output, model.py:110-159). Returns (y, saved state)."""
         self.gemm_sched = self.base_sched  # (a backward that raised midway left its flags)
@@ -1232,6 +1249,10 @@ class Engine:
             raise ValueError(f"Sequence length {T} > model max {cfg.n_positions}")
         Tp = padded_len(T)
         M = B * Tp
+        if doc is not None:
+            if kind == "mlp":
+                raise ValueError("doc_bounds: the MLP has no attention to mask")
+            doc = pad_bounds(check_bounds_meta(doc, B, T, x.device), Tp)
         act = self.compute_dtype()
         self._sync_shadows(act, need_grad)
         xf = x.to(F32)
@@ -1245,7 +1266,7 @@ class Engine:
         y = torch.empty(M, C, dtype=F32, device=self.device)
         self._unit(f"h.{l}")
         if kind == "block":
-            self._block_fwd(l, A, xf, y, B, Tp, act, pr, pa, seeds)
+            self._block_fwd(l, A, xf, y, B, Tp, act, pr, pa, seeds, doc)
         else:
             zero = torch.zeros(M, C, dtype=F32, device=self.device)
             if kind == "mlp":
@@ -1253,10 +1274,10 @@ class Engine:
                 self._mlp_fwd(l, A, zero, y, M, act, pr, seeds)
             elif kind == "attn":
                 A.ln1 = self._to_act(xf, act)
-                self._attn_fwd(l, A, zero, y, B, Tp, act, pr, pa, seeds)
+                self._attn_fwd(l, A, zero, y, B, Tp, act, pr, pa, seeds, doc)
             else:
                 raise ValueError(kind)
-        state = (A, xf, B, Tp, T, act, pr, pa, seeds)
+        state = (A, xf, B, Tp, T, act, pr, pa, seeds, doc)
         out = y.view(B, Tp, C)[:, :T]
         if kind != "block":  # the branch output is a linear's output: bf16 under autocast (model.py:158,191)
             out = out.to(act)
@@ -1271,7 +1292,7 @@ class Engine:
         return out
 
     def _sub_backward(self, kind, l, state, dy):
-        A, xf, B, Tp, T, act, pr, pa, seeds = state
+        A, xf, B, Tp, T, act, pr, pa, seeds, doc = state
         C = self.cfg.n_embd
         M = B * Tp
         S = Scratch(self.cfg, B, Tp, self.vpad, self.device, act, head=False)
@@ -1285,7 +1306,7 @@ class Engine:
         pre = f"transformer.h.{l}."
         if kind == "block":
             K.branch_bwd(S.dres, S.dres_bf, self.g(pre + "mlp.fc2.bias"), M, C, pr, seeds[("fc2", l)])
-            self._block_bwd(l, A, S, xf, B, Tp, act, pr, pa, seeds, last=True)
+            self._block_bwd(l, A, S, xf, B, Tp, act, pr, pa, seeds, last=True, doc=doc)
             dx = S.dres
         else:
             site, bias = ("fc2", "mlp.fc2.bias") if kind == "mlp" else ("proj", "attn.proj.bias")
@@ -1293,7 +1314,7 @@ class Engine:
             if kind == "mlp":
                 self._mlp_bwd(l, A, S, S.dres_bf, S.dln, M, act)
             else:
-                self._attn_bwd(l, A, S, S.dres_bf, S.dln, B, Tp, act, pa, seeds)
+                self._attn_bwd(l, A, S, S.dres_bf, S.dln, B, Tp, act, pa, seeds, doc=doc)
             if act == BF16:
                 dx = torch.empty(M, C, dtype=F32, device=self.device)
                 K.cast_bf16_f32(S.dln, dx, M * C)

@@ -37,6 +37,8 @@ import torch
 import torch.nn as nn
 
 from .arena import ArenaLayout, round_up
+from .packing import EOT_POSITIONS, DocBounds, check_bounds_meta
+from .packing import doc_bounds as _doc_bounds
 
 
 @dataclass(frozen=True)
@@ -87,9 +89,22 @@ class _OwnedByGPT2:
         return owner.engine()
 
 
+def _checked_bounds(doc_bounds, x) -> Optional[DocBounds]:
+    """``doc_bounds`` checked against the leading [B, T] of ``x`` (idx or activations) and its device: ValueError on a
+    wrong shape, dtype or device; the tensors are not read."""
+    if doc_bounds is None:
+        return None
+    if x.dim() < 2:
+        raise ValueError(f"doc_bounds go with a [B, T, ...] input, got shape {tuple(x.shape)}")
+    return check_bounds_meta(doc_bounds, x.shape[0], x.shape[1], x.device)
+
+
 class CausalMultiHeadSelfAttention(_OwnedByGPT2, nn.Module):
     """Causal multi-head self-attention (model.py:80-159): qkv, proj, attn/resid dropout. ``forward(x)``
-    takes the ln1 output [B,T,C] and returns drop(proj(attention)) (bf16 under autocast)."""
+    takes the ln1 output [B,T,C] and returns drop(proj(attention)) (bf16 under autocast). ``doc_bounds``: a
+    ``packing.DocBounds`` of the rows, for document-masked attention (every ``doc_bounds`` keyword of this module:
+    int32 [B, T] tensors on the input's device, checked by shape, dtype and device without a host synchronisation;
+    ``packing.check_bounds`` validates the values)."""
 
     def __init__(self, cfg: GPT2Config):
         super().__init__()
@@ -101,8 +116,9 @@ class CausalMultiHeadSelfAttention(_OwnedByGPT2, nn.Module):
         self.attn_drop = nn.Dropout(cfg.attn_pdrop)
         self.resid_drop = nn.Dropout(cfg.resid_pdrop)
 
-    def forward(self, x):
-        return self._owner_engine().sub_forward("attn", self._layer, x)
+    def forward(self, x, doc_bounds: Optional[DocBounds] = None):
+        doc_bounds = _checked_bounds(doc_bounds, x)
+        return self._owner_engine().sub_forward("attn", self._layer, x, doc_bounds)
 
 
 class MLP(_OwnedByGPT2, nn.Module):
@@ -133,8 +149,9 @@ class GPT2Block(_OwnedByGPT2, nn.Module):
         self.ln2 = nn.LayerNorm(cfg.n_embd, eps=cfg.layer_norm_eps)
         self.mlp = MLP(cfg)
 
-    def forward(self, x):
-        return self._owner_engine().sub_forward("block", self._layer, x)
+    def forward(self, x, doc_bounds: Optional[DocBounds] = None):
+        doc_bounds = _checked_bounds(doc_bounds, x)
+        return self._owner_engine().sub_forward("block", self._layer, x, doc_bounds)
 
 
 class GPT2Backbone(_OwnedByGPT2, nn.Module):
@@ -162,8 +179,9 @@ class GPT2Backbone(_OwnedByGPT2, nn.Module):
     def max_seq_len(self):
         return self.cfg.n_positions
 
-    def forward(self, idx: torch.Tensor) -> torch.Tensor:
+    def forward(self, idx: torch.Tensor, doc_bounds: Optional[DocBounds] = None) -> torch.Tensor:
         """Embeddings -> blocks -> ln_f (model.py:275-313); returns the fp32 ln_f output [B,T,C]."""
+        doc_bounds = _checked_bounds(doc_bounds, idx)
         B, T = idx.size()
         if T > self.cfg.n_positions:
             raise ValueError(f"Sequence length {T} > model max {self.cfg.n_positions}")
@@ -171,7 +189,7 @@ class GPT2Backbone(_OwnedByGPT2, nn.Module):
         if not idx.is_cuda:
             raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda "
                                "device (there is no CPU fallback)")
-        return eng.backbone_forward(idx)
+        return eng.backbone_forward(idx, doc_bounds)
 
 
 class GPT2(nn.Module):
@@ -258,18 +276,23 @@ class GPT2(nn.Module):
 
     # ---- forward -----------------------------------------------------------------------------------
     def forward(self, idx: torch.Tensor, labels: Optional[torch.Tensor] = None,
-                targets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                targets: Optional[torch.Tensor] = None, *,
+                doc_bounds: Optional[DocBounds] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """``doc_bounds``: the ``packing.DocBounds`` of ``idx`` (``packing.doc_bounds(idx, eot_token_id)`` forms them on
+        the device): every token attends only to the earlier tokens of its own document. Positions stay absolute.
+        ``None``: plain causal attention, the kernel launches as they were."""
         if targets is not None:
             if labels is not None:
                 raise ValueError("pass labels or targets, not both")
             labels = targets
+        doc_bounds = _checked_bounds(doc_bounds, idx)
         B, T = idx.size()
         if T > self.config.n_positions:
             raise ValueError(f"Sequence length {T} > model max {self.config.n_positions}")
         if not idx.is_cuda or not self._arena.is_cuda:
             raise RuntimeError("gpt_2_distributed_amd.GPT2 runs only on the MI355X HIP path: move the model and "
                                "inputs to a cuda device (there is no CPU fallback)")
-        return self.engine().forward(idx, labels)
+        return self.engine().forward(idx, labels, doc_bounds)
 
     # ---- evaluation (the reference has none) ----------------------------------------------------------------
     def _check_inputs(self, idx):
@@ -280,10 +303,11 @@ class GPT2(nn.Module):
             raise RuntimeError("gpt_2_distributed_amd.GPT2 runs only on the MI355X HIP path: move the model and "
                                "inputs to a cuda device (there is no CPU fallback)")
 
-    def score(self, idx: torch.Tensor, labels: torch.Tensor, reduction: str = "mean") -> torch.Tensor:
+    def score(self, idx: torch.Tensor, labels: torch.Tensor, reduction: str = "mean",
+              doc_bounds: Optional[DocBounds] = None) -> torch.Tensor:
         """The negative log-likelihood of ``labels`` [B, T] under the model, forward only: ``"none"`` the fp32 per-token
         values [B, T] (0 where the label is -100), ``"sum"`` their sum, ``"mean"`` sum / number of labels != -100 (what
-        ``forward(idx, labels)[1]`` computes in eval mode). Same argument checks as ``forward``.
+        ``forward(idx, labels)[1]`` computes in eval mode). Same argument checks as ``forward``; ``doc_bounds`` as there.
 
         Under bf16 autocast (or ``precision == "bf16"``) the lm_head runs fused with the cross-entropy
         (``gpt2mi_lm_loss``): no logits tensor exists and the label's logit and the log-sum-exp are taken from the fp32
@@ -293,19 +317,28 @@ class GPT2(nn.Module):
         reads (weights, shadows, gradients, optimizer state, dropout stream, training workspace). Not differentiable: the results carry no graph, whatever the grad mode."""
         if reduction not in ("mean", "sum", "none"):
             raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
+        doc_bounds = _checked_bounds(doc_bounds, idx)
         self._check_inputs(idx)
-        rows, s, _, mean = self.engine().score(idx, labels)
+        rows, s, _, mean = self.engine().score(idx, labels, doc=doc_bounds)
         if reduction == "none":
             return rows.clone()
         return (s if reduction == "sum" else mean).reshape(()).clone()
 
-    def evaluate(self, batches, max_batches: Optional[int] = None) -> dict:
+    def evaluate(self, batches, max_batches: Optional[int] = None, eot_token_id: Optional[int] = None,
+                 eot: str = "end") -> dict:
         """``{"loss", "ppl", "tokens"}`` over the ``(idx, labels)`` pairs of ``batches`` (at most ``max_batches``):
         loss = sum of the token losses / number of tokens over ALL batches (token-weighted, not a mean of batch means),
         ppl = exp(loss). The sums stay on the device (``gpt2mi_lm_loss``'s accumulate mode) and the host synchronises
         once, at the end. With ``torch.distributed`` initialised the two sums are all-reduced before the division, so
-        every rank returns the same numbers; every rank must then be given the same number of batches (a collective)."""
+        every rank returns the same numbers; every rank must then be given the same number of batches (a collective).
+        With ``eot_token_id`` every batch is scored under document masking: its bounds are formed on the device from its
+        ``idx`` (``packing.doc_bounds(idx, eot_token_id, eot)``, ``eot`` = ``"end"`` or ``"begin"``)."""
         import torch.distributed as dist
+        if eot not in EOT_POSITIONS:
+            raise ValueError(f"eot must be one of {EOT_POSITIONS}, got {eot!r}")
+        if eot_token_id is not None and (isinstance(eot_token_id, bool) or not isinstance(eot_token_id, int)
+                                         or eot_token_id < 0):
+            raise ValueError(f"eot_token_id must be a non-negative int or None, got {eot_token_id!r}")
         dev = self._arena.device
         eng = self.engine()
         acc = (torch.zeros(1, dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev))
@@ -323,7 +356,8 @@ class GPT2(nn.Module):
                 acc[0].zero_()
                 acc[1].zero_()
                 pending = 0
-            eng.score(idx, labels, acc=acc)
+            doc = None if eot_token_id is None else _doc_bounds(idx, eot_token_id, eot)
+            eng.score(idx, labels, acc=acc, doc=doc)
             pending += idx.numel()
         total += torch.cat(acc).double()
         if dist.is_available() and dist.is_initialized():

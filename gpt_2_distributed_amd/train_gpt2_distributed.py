@@ -12,6 +12,10 @@
         and after the last one every rank runs model.evaluate over the first K batches of its share of the split's
         windows (dataloader.iter_eval_batches) and rank 0 prints one more JSON line {"step", "val_loss", "val_ppl",
         "val_tokens", "eval_s"}; the evaluation changes no state that a later training step reads
+    packed sequences: --doc_mask [--eot_token_id 50256] [--eot_position end|begin]: document masking, a token attends
+        only to the earlier tokens of its own document; the bounds of every micro-batch are formed on the device from
+        its tokens (packing.doc_bounds), for the training forward and for --eval_every alike; end: the separator closes
+        a document (nanoGPT's data preparation), begin: it opens one (llm.c's). Positions stay absolute
 
 Loop semantics follow the reference (:374-457): seed 42; loss/grad_accum; backward; every
 grad_accum micro-steps the fused AdamW step (which also yields the clip_grad_norm_(inf) value);
@@ -40,6 +44,7 @@ import torch.distributed as dist
 from . import dataloader as gpt2_dataloader
 from .lr_schedule import KINDS, lr_at
 from .model import GPT2, GPT2Config, MODEL_SIZES
+from .packing import EOT_POSITIONS, doc_bounds
 from .parallel import DistributedDataParallel, FullyShardedDataParallel, init_distributed, is_primary
 
 SEED = 42
@@ -90,7 +95,26 @@ def build_parser():
     p.add_argument("--eval_steps", type=int, default=20, help="batches per rank per evaluation")
     p.add_argument("--eval_batch", type=int, default=None, help="evaluation batch size (default --batch)")
     p.add_argument("--val_split", type=str, default="val", help="shards whose file name contains this are the val split")
+    add_doc_mask_arguments(p)
     return p
+
+
+def add_doc_mask_arguments(p) -> None:
+    """The document-masking flags, shared with evaluate.py (off by default)."""
+    p.add_argument("--doc_mask", action="store_true",
+                   help="attend within documents only: the rows are split at --eot_token_id")
+    p.add_argument("--eot_token_id", type=int, default=50256, help="the document separator (GPT-2's <|endoftext|>)")
+    p.add_argument("--eot_position", choices=list(EOT_POSITIONS), default="end",
+                   help="end: the separator is the last token of the document it closes; begin: it opens a document")
+
+
+def doc_mask_from_args(args) -> dict:
+    """{} without --doc_mask, else evaluate()'s keywords eot_token_id / eot (validated once, before anything is built)."""
+    if not args.doc_mask:
+        return {}
+    if args.eot_token_id < 0:
+        raise SystemExit("--eot_token_id must be >= 0")
+    return dict(eot_token_id=args.eot_token_id, eot=args.eot_position)
 
 
 def eval_from_args(args) -> dict:
@@ -120,12 +144,14 @@ def val_shards(data_dir, ev: dict, seq_len: int, world: int):
     return paths
 
 
-def run_eval(model, paths, ev: dict, seq_len: int, rank: int, world: int):
-    """model.evaluate over this rank's first ev["steps"] validation batches; (result, seconds). Collective."""
+def run_eval(model, paths, ev: dict, seq_len: int, rank: int, world: int, doc: dict = None):
+    """model.evaluate over this rank's first ev["steps"] validation batches; (result, seconds). Collective.
+    doc: doc_mask_from_args' keywords."""
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     with torch.autocast("cuda", dtype=torch.bfloat16):
-        res = model.evaluate(gpt2_dataloader.iter_eval_batches(paths, seq_len, ev["batch"], rank, world, ev["steps"]))
+        res = model.evaluate(gpt2_dataloader.iter_eval_batches(paths, seq_len, ev["batch"], rank, world, ev["steps"]),
+                             **(doc or {}))
     return res, time.perf_counter() - t0
 
 
@@ -229,6 +255,7 @@ def main(argv=None):
     scheduled = sched["kind"] != "constant"
     clip = args.max_grad_norm > 0
     ev = eval_from_args(args)
+    doc = doc_mask_from_args(args)
     if ev and not args.synthetic:  # (synthetic runs write their val shard below)
         val_paths = val_shards(args.data_dir or "", ev, args.seq_len, int(os.environ.get("WORLD_SIZE", 1))
                                if args.training_mode != "local" else 1)
@@ -303,7 +330,7 @@ def main(argv=None):
 
     def validate():
         nonlocal t_last, evaluated_at
-        res, secs = run_eval(model, val_paths, ev, args.seq_len, rank, world)
+        res, secs = run_eval(model, val_paths, ev, args.seq_len, rank, world, doc)
         evaluated_at = global_step
         t_last += secs  # the logged tok/s stays the training throughput
         if is_primary():
@@ -336,7 +363,10 @@ def main(argv=None):
                                       and not getattr(model, "reshard_after_forward", False)) else _Null()
             with ctx:
                 with torch.autocast("cuda", dtype=torch.bfloat16):  # as train_gpt2_distributed.py:404
-                    _, loss = model(x, labels=y)
+                    if doc:
+                        _, loss = model(x, labels=y, doc_bounds=doc_bounds(x, doc["eot_token_id"], doc["eot"]))
+                    else:
+                        _, loss = model(x, labels=y)
                     loss = loss / args.grad_accum_steps
                 loss.backward()
             micro += 1

@@ -28,7 +28,7 @@ extern "C" {
 
 #define GPT2MI_ABI_VERSION 24
 /* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
-#define GPT2MI_ABI_MINOR 4
+#define GPT2MI_ABI_MINOR 5
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -728,6 +728,38 @@ int gpt2mi_decode_generate_constrained(const gpt2mi_decode_plan* plan, int V, fl
                                        int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream,
                                        float repetition, float presence, float frequency, const int* gen_start,
                                        const gpt2mi_logprobs* lp, const gpt2mi_constraints* con);
+
+/* ---- v24.5: document masking for packed sequences (csrc/packing.hip, csrc/attention.hip, csrc/fp32.hip). The
+ * executable specification is gpt_2_distributed_amd/packing.py: doc_bounds_reference and doc_attention_reference.
+ * A row of T tokens is partitioned into documents, contiguous intervals [s, e); doc_start / doc_end are int32 [B, T]
+ * with 0 <= doc_start[b,t] <= t < doc_end[b,t] <= T, both constant over [doc_start[b,t], doc_end[b,t]). Query t attends
+ * key k iff doc_start[b,t] <= k <= t, which for k <= t is t < doc_end[b,k]; the softmax, its statistics and the dropout
+ * decision of a pair are those of the unmasked entries. No row is fully masked (key t is visible to query t). ---- */
+/* The bounds of idx int64 [B, T] from its separator tokens. eot_begin = 0: eot is the last token of the document it
+ * closes (a document begins at p when idx[p - 1] == eot); 1: eot opens a document (one begins at p when idx[p] == eot).
+ * Only positions < T_valid count: start[t] = the last beginning <= t, or 0; end[t] = the first beginning > t, or
+ * T_valid; positions >= T_valid (the engine's padding to the attention tile) form one document [T_valid, T). One
+ * workgroup per row, any T; no atomics, no host synchronisation. Refused with 22: a NULL pointer, B or T < 1, T_valid
+ * outside [1, T], eot_begin outside {0, 1}. */
+int gpt2mi_doc_bounds(const int64_t* idx, int B, int T, int T_valid, int64_t eot, int eot_begin, int* start, int* end,
+                      void* stream);
+/* gpt2mi_attn_fwd / gpt2mi_attn_bwd under the mask: the same contracts (T % 64 == 0, head_dim 64, the same dqkv_colsum
+ * partials) and, with one document per row, the same bits. Key tiles (forward, dQ) before the document of a workgroup's
+ * first query and query tiles (dK/dV) after the document of its last key are not visited, and a wave skips the tiles
+ * that lie wholly in other documents. Bounds outside the contract are clamped where they are read (start into [0, t],
+ * end into [t + 1, T]): they may give wrong numbers, never an access out of range. NULL bounds are refused with 22
+ * before any launch. */
+int gpt2mi_attn_fwd_doc(const uint16_t* qkv, uint16_t* out, float* lse, const int* doc_start, int B, int T, int H,
+                        int head_dim, float p_drop, uint64_t seed, void* stream);
+int gpt2mi_attn_bwd_doc(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout, const float* lse, float* delta,
+                        uint16_t* dqkv, float* dqkv_colsum, const int* doc_start, const int* doc_end, int B, int T,
+                        int H, int head_dim, float p_drop, uint64_t seed, void* stream);
+/* The fp32 family likewise (dqkv_colsum must be NULL, as in gpt2mi_attn_bwd_f32). */
+int gpt2mi_attn_fwd_f32_doc(const float* qkv, float* out, float* lse, const int* doc_start, int B, int T, int H,
+                            int head_dim, float p_drop, uint64_t seed, void* stream);
+int gpt2mi_attn_bwd_f32_doc(const float* qkv, const float* out, const float* dout, const float* lse, float* delta,
+                            float* dqkv, float* dqkv_colsum, const int* doc_start, const int* doc_end, int B, int T,
+                            int H, int head_dim, float p_drop, uint64_t seed, void* stream);
 
 #ifdef __cplusplus
 }
