@@ -9,6 +9,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import os
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -824,33 +825,6 @@ def decode_step_ragged(plan: DecodePlan, tok, pos):
     _call("gpt2mi_decode_step_ragged", plan.ref(), _ptr(tok), _positions(pos, plan.B), _stream())
 
 
-def _sample_call(name, logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out, *tail):
-    """The argument list of the per-row sampler entries (`scalars`: _sampler_args'); `tail` goes before the stream."""
-    (t, k, p, s, e), B = scalars, logits.size(0)
-    _call(name, _ptr(logits), logits.stride(0), B, V, t, k, p, s, _positions(pos, B), _row_ids(row_id, B), e, _ptr(done),
-          _ptr(tok_out), _ptr(seq_out), 0 if seq_out is None else seq_out.stride(0), _ptr(probs_out), *tail, _stream())
-
-
-def _generate_call(name, plan, V, scalars, pos0, n, tok, row_id, seq, done, *tail):
-    """The argument list of the per-row generate loops; `tail` goes behind the stream."""
-    _call(name, plan.ref(), V, *scalars, _positions(pos0, plan.B), _row_ids(row_id, plan.B), n, _ptr(tok),
-          _ptr(seq), 0 if seq is None else seq.stride(0), _ptr(done), _stream(), *tail)
-
-
-def sample_ragged(logits, V, temperature, top_k, top_p, seed, pos, tok_out, row_id=None, eos=None, done=None,
-                  seq_out=None, probs_out=None):
-    """gpt2mi_sample_ragged: `sample` with row b drawing from (seed, row_id[b] (None: b), pos[b]) into column pos[b]."""
-    _sample_call("gpt2mi_sample_ragged", logits, V, _sampler_args(temperature, top_k, top_p, seed, eos), pos, tok_out,
-                 row_id, done, seq_out, probs_out)
-
-
-def decode_generate_ragged(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, row_id=None, eos=None,
-                           seq=None, done=None):
-    """gpt2mi_decode_generate_ragged: n sample-then-step rounds with row b starting at pos0[b]."""
-    _generate_call("gpt2mi_decode_generate_ragged", plan, V, _sampler_args(temperature, top_k, top_p, seed, eos), pos0,
-                   n, tok, row_id, seq, done)
-
-
 # ---- v21: several rows of a launch in one sequence (csrc/decode.hip) -----------------------------------
 def attn_extend(qkv, kcache, vcache, out, workspace, R, B, H, D, Tcap, seq, pos, kscale=None, vscale=None):
     """gpt2mi_attn_extend: attention of R rows, row r at position pos[r] of sequence seq[r] (host sequences of R ints);
@@ -909,29 +883,6 @@ def _penalties_arg(B, repetition, presence, frequency, hist, hist_row, gen_start
     return pen, (rows, starts)
 
 
-def sample_penalized(logits, V, temperature, top_k, top_p, seed, pos, tok_out, row_id=None, eos=None, done=None,
-                     seq_out=None, probs_out=None, repetition=1.0, presence=0.0, frequency=0.0, hist=None,
-                     hist_row=None, gen_start=None, logits_out=None):
-    """gpt2mi_sample_penalized: `sample_ragged` with row b's logits moved by its history hist[hist_row[b], :pos[b]]
-    (int64 [rows, ld]; hist_row None: b), the generated part from gen_start[b] (None: 0); logits_out (fp32 [B, V]) takes
-    the penalised logits."""
-    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
-    B = logits.size(0)
-    pen, _alive_pen = _penalties_arg(B, repetition, presence, frequency, hist, hist_row, gen_start)
-    _sample_call("gpt2mi_sample_penalized", logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out,
-                 ctypes.byref(pen), _ptr(logits_out))
-
-
-def decode_generate_penalized(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, row_id=None, eos=None,
-                              seq=None, done=None, repetition=1.0, presence=0.0, frequency=0.0, gen_start=None):
-    """gpt2mi_decode_generate_penalized: `decode_generate_ragged` with seq as the history the sampler reads."""
-    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
-    if gen_start is not None and len(gen_start) != plan.B:
-        raise KernelError(f"gen_start has {len(gen_start)} entries for B={plan.B} rows")
-    _generate_call("gpt2mi_decode_generate_penalized", plan, V, scalars, pos0, n, tok, row_id, seq, done,
-                   float(repetition), float(presence), float(frequency), _host_ints(gen_start))
-
-
 # ---- v24: rows that share a prompt cache (csrc/decode.hip) -------------------------------------------
 def attn_decode_shared(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, pos, share_group=None, share_len=None,
                        kscale=None, vscale=None):
@@ -977,34 +928,6 @@ def _logprobs_arg(logprob, top_ids, top_logprobs, col, B):
     return ctypes.byref(lp), (lp, cols)
 
 
-def sample_logprobs(logits, V, temperature, top_k, top_p, seed, pos, tok_out, logprob=None, top_ids=None,
-                    top_logprobs=None, col=None, row_id=None, eos=None, done=None, seq_out=None, probs_out=None,
-                    repetition=1.0, presence=0.0, frequency=0.0, hist=None, hist_row=None, gen_start=None,
-                    logits_out=None):
-    """gpt2mi_sample_logprobs: `sample_penalized`, and row b's raw log-probability of the token it draws into
-    logprob[b, col[b]] (col None: pos[b]), its top_n alternatives into top_ids / top_logprobs[b, col[b]]
-    (generation.token_logprobs). logprob None: lp = NULL, gpt2mi_sample_penalized itself under this entry's name."""
-    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
-    B = logits.size(0)
-    pen, _alive_pen = _penalties_arg(B, repetition, presence, frequency, hist, hist_row, gen_start)
-    lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, col, B)
-    _sample_call("gpt2mi_sample_logprobs", logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out,
-                 ctypes.byref(pen), _ptr(logits_out), lp)
-
-
-def decode_generate_logprobs(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, logprob=None,
-                             top_ids=None, top_logprobs=None, row_id=None, eos=None, seq=None, done=None, repetition=1.0,
-                             presence=0.0, frequency=0.0, gen_start=None):
-    """gpt2mi_decode_generate_logprobs: `decode_generate_penalized`, step i writing column pos0[b] + i of logprob /
-    top_ids / top_logprobs as it does of seq."""
-    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
-    if gen_start is not None and len(gen_start) != plan.B:
-        raise KernelError(f"gen_start has {len(gen_start)} entries for B={plan.B} rows")
-    lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, None, plan.B)
-    _generate_call("gpt2mi_decode_generate_logprobs", plan, V, scalars, pos0, n, tok, row_id, seq, done,
-                   float(repetition), float(presence), float(frequency), _host_ints(gen_start), lp)
-
-
 # ---- v24.4: logit bias, min-p, minimum length and stop sequences in the sampler (csrc/sample_con.hip, csrc/decode.hip) --
 STOP_MAX_SEQS, STOP_MAX_LEN = 8, 16  # gpt2mi.h GPT2MI_STOP_MAX_SEQS / GPT2MI_STOP_MAX_LEN
 
@@ -1038,36 +961,111 @@ def _constraints_arg(logit_bias, bias_row, min_p, min_new_tokens, stop, B):
     return ctypes.byref(con), (con, rows, lens, table)
 
 
-def sample_constrained(logits, V, temperature, top_k, top_p, seed, pos, tok_out, logprob=None, top_ids=None,
-                       top_logprobs=None, col=None, row_id=None, eos=None, done=None, seq_out=None, probs_out=None,
-                       repetition=1.0, presence=0.0, frequency=0.0, hist=None, hist_row=None, gen_start=None,
-                       logits_out=None, logit_bias=None, bias_row=None, min_p=0.0, min_new_tokens=0, stop=None):
+# ---- the per-row sampler entries and generate loops: v19 ragged, v22 penalized, v24.1 logprobs, v24.4 constrained --------
+# Each entry takes its predecessor's keywords and C arguments and adds a block of its own: below, per block, the keywords
+# with their neutral values and the C arguments they become (before the sampler's stream, behind the loop's).
+_ENTRIES = ("ragged", "penalized", "logprobs", "constrained")
+_CON_OPTIONS = dict(logit_bias=None, bias_row=None, min_p=0.0, min_new_tokens=0, stop=None)
+_SAMPLE_OPTIONS = (dict(row_id=None, eos=None, done=None, seq_out=None, probs_out=None),
+                   dict(repetition=1.0, presence=0.0, frequency=0.0, hist=None, hist_row=None, gen_start=None,
+                        logits_out=None),                                                    # pen, logits_out
+                   dict(logprob=None, top_ids=None, top_logprobs=None, col=None), _CON_OPTIONS)  # lp; con
+_GENERATE_OPTIONS = (dict(row_id=None, eos=None, seq=None, done=None),
+                     dict(repetition=1.0, presence=0.0, frequency=0.0, gen_start=None),      # the four themselves
+                     dict(logprob=None, top_ids=None, top_logprobs=None), _CON_OPTIONS)       # lp; con
+_SAMPLE_TAIL, _GENERATE_TAIL = (0, 2, 3, 4), (0, 4, 5, 6)  # how much of the full tail an entry's C signature has
+
+
+def _entry_options(name, blocks, given):
+    """(the level of entry `name` in _ENTRIES, every block's keywords: `given` over the neutral values). A keyword of a
+    later entry is a TypeError, as from a signature without it."""
+    level = _ENTRIES.index(name.rsplit("_", 1)[1])
+    for key in given:
+        if not any(key in block for block in blocks[:level + 1]):
+            raise TypeError(f"{name}() got an unexpected keyword argument '{key}'")
+    return level, SimpleNamespace(**{**{k: v for block in blocks for k, v in block.items()}, **given})
+
+
+def _sample_entry(name, logits, V, temperature, top_k, top_p, seed, pos, tok_out, **given):
+    """gpt2mi_<name>, one of the four per-row sampler entries: one token per row of fp32 logits [B, ldl] (V valid
+    columns) into tok_out (int64 [B]), row b drawing from (seed, row_id[b] (None: b), pos[b]) into column pos[b] of
+    seq_out (int64 [B, ld_seq]); probs_out (fp32 [B, V], tests). The keywords: the forwarders below."""
+    level, o = _entry_options(name, _SAMPLE_OPTIONS, given)
+    (t, k, p, s, e), B = _sampler_args(temperature, top_k, top_p, seed, o.eos), logits.size(0)
+    pen, _alive_pen = _penalties_arg(B, o.repetition, o.presence, o.frequency, o.hist, o.hist_row, o.gen_start)
+    lp, _alive_lp = _logprobs_arg(o.logprob, o.top_ids, o.top_logprobs, o.col, B)
+    con, _alive_con = _constraints_arg(o.logit_bias, o.bias_row, o.min_p, o.min_new_tokens, o.stop, B)
+    tail = (ctypes.byref(pen), _ptr(o.logits_out), lp, con)[:_SAMPLE_TAIL[level]]
+    _call("gpt2mi_" + name, _ptr(logits), logits.stride(0), B, V, t, k, p, s, _positions(pos, B), _row_ids(o.row_id, B), e,
+          _ptr(o.done), _ptr(tok_out), _ptr(o.seq_out), 0 if o.seq_out is None else o.seq_out.stride(0),
+          _ptr(o.probs_out), *tail, _stream())
+
+
+def _generate_entry(name, plan, V, temperature, top_k, top_p, seed, pos0, n, tok, **given):
+    """gpt2mi_<name>, one of the four per-row generate loops: n sample-then-step rounds from plan.logits without leaving
+    C, row b starting at pos0[b], the tokens into tok and seq as the sampler writes tok_out and seq_out."""
+    level, o = _entry_options(name, _GENERATE_OPTIONS, given)
+    scalars, B = _sampler_args(temperature, top_k, top_p, seed, o.eos), plan.B
+    if o.gen_start is not None and len(o.gen_start) != B:
+        raise KernelError(f"gen_start has {len(o.gen_start)} entries for B={B} rows")
+    lp, _alive_lp = _logprobs_arg(o.logprob, o.top_ids, o.top_logprobs, None, B)
+    con, _alive_con = _constraints_arg(o.logit_bias, o.bias_row, o.min_p, o.min_new_tokens, o.stop, B)
+    tail = (float(o.repetition), float(o.presence), float(o.frequency), _host_ints(o.gen_start), lp, con)
+    _call("gpt2mi_" + name, plan.ref(), V, *scalars, _positions(pos0, B), _row_ids(o.row_id, B), n, _ptr(tok), _ptr(o.seq),
+          0 if o.seq is None else o.seq.stride(0), _ptr(o.done), _stream(), *tail[:_GENERATE_TAIL[level]])
+
+
+# The public names: (logits, V, temperature, top_k, top_p, seed, pos, tok_out, **keywords) and
+# (plan, V, temperature, top_k, top_p, seed, pos0, n, tok, **keywords), the keywords being the entry's blocks above.
+def sample_ragged(*head, **keywords):
+    """gpt2mi_sample_ragged: `sample` with row b drawing from (seed, row_id[b] (None: b), pos[b]) into column pos[b];
+    row_id, eos, done, seq_out, probs_out."""
+    _sample_entry("sample_ragged", *head, **keywords)
+
+
+def sample_penalized(*head, **keywords):
+    """gpt2mi_sample_penalized: `sample_ragged` with row b's logits moved (repetition, presence, frequency) by its
+    history hist[hist_row[b], :pos[b]] (int64 [rows, ld]; hist_row None: b), the generated part from gen_start[b] (None:
+    0); logits_out (fp32 [B, V]) takes the penalised logits."""
+    _sample_entry("sample_penalized", *head, **keywords)
+
+
+def sample_logprobs(*head, **keywords):
+    """gpt2mi_sample_logprobs: `sample_penalized`, and row b's raw log-probability of the token it draws into
+    logprob[b, col[b]] (col None: pos[b]), its top_n alternatives into top_ids / top_logprobs[b, col[b]]
+    (generation.token_logprobs). logprob None: lp = NULL, gpt2mi_sample_penalized itself under this entry's name."""
+    _sample_entry("sample_logprobs", *head, **keywords)
+
+
+def sample_constrained(*head, **keywords):
     """gpt2mi_sample_constrained: `sample_logprobs` under generation.apply_constraints (logit_bias fp32 [rows, V], row b
     reading row bias_row[b]; min_new_tokens holding eos back while pos[b] - gen_start[b] < it), sample_reference's min_p
     and generation.stop_match over hist (stop: up to 8 lists of up to 16 tokens; a match sets done[b]). logits_out takes
     the row after the bias and the eos suppression. Every keyword neutral: sample_logprobs itself under this name."""
-    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
-    B = logits.size(0)
-    pen, _alive_pen = _penalties_arg(B, repetition, presence, frequency, hist, hist_row, gen_start)
-    lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, col, B)
-    con, _alive_con = _constraints_arg(logit_bias, bias_row, min_p, min_new_tokens, stop, B)
-    _sample_call("gpt2mi_sample_constrained", logits, V, scalars, pos, tok_out, row_id, done, seq_out, probs_out,
-                 ctypes.byref(pen), _ptr(logits_out), lp, con)
+    _sample_entry("sample_constrained", *head, **keywords)
 
 
-def decode_generate_constrained(plan: DecodePlan, V, temperature, top_k, top_p, seed, pos0, n, tok, logprob=None,
-                                top_ids=None, top_logprobs=None, row_id=None, eos=None, seq=None, done=None,
-                                repetition=1.0, presence=0.0, frequency=0.0, gen_start=None, logit_bias=None,
-                                bias_row=None, min_p=0.0, min_new_tokens=0, stop=None):
-    """gpt2mi_decode_generate_constrained: `decode_generate_logprobs` with sample_constrained's keywords, seq the history
-    the stop sequences are matched in."""
-    scalars = _sampler_args(temperature, top_k, top_p, seed, eos)
-    if gen_start is not None and len(gen_start) != plan.B:
-        raise KernelError(f"gen_start has {len(gen_start)} entries for B={plan.B} rows")
-    lp, _alive = _logprobs_arg(logprob, top_ids, top_logprobs, None, plan.B)
-    con, _alive_con = _constraints_arg(logit_bias, bias_row, min_p, min_new_tokens, stop, plan.B)
-    _generate_call("gpt2mi_decode_generate_constrained", plan, V, scalars, pos0, n, tok, row_id, seq, done,
-                   float(repetition), float(presence), float(frequency), _host_ints(gen_start), lp, con)
+def decode_generate_ragged(*head, **keywords):
+    """gpt2mi_decode_generate_ragged: `decode_generate` with row b starting at pos0[b]; row_id, eos, seq, done."""
+    _generate_entry("decode_generate_ragged", *head, **keywords)
+
+
+def decode_generate_penalized(*head, **keywords):
+    """gpt2mi_decode_generate_penalized: `decode_generate_ragged` with repetition, presence, frequency and gen_start, seq
+    as the history the sampler reads."""
+    _generate_entry("decode_generate_penalized", *head, **keywords)
+
+
+def decode_generate_logprobs(*head, **keywords):
+    """gpt2mi_decode_generate_logprobs: `decode_generate_penalized`, step i writing column pos0[b] + i of logprob /
+    top_ids / top_logprobs as it does of seq."""
+    _generate_entry("decode_generate_logprobs", *head, **keywords)
+
+
+def decode_generate_constrained(*head, **keywords):
+    """gpt2mi_decode_generate_constrained: `decode_generate_logprobs` with sample_constrained's keywords (logit_bias,
+    bias_row, min_p, min_new_tokens, stop), seq the history the stop sequences are matched in."""
+    _generate_entry("decode_generate_constrained", *head, **keywords)
 
 
 # ---- v24.2: beam search on the device (csrc/beam.hip) ---------------------------------------------------------

@@ -36,23 +36,47 @@ int check_launch(const char* what);
 int check_penalty_values(const char* what, float repetition, float presence, float frequency, bool* on);
 // what of a gpt2mi_logprobs (gpt2mi.h v24.1) does not depend on the rows: top_n and the three pointers (csrc/sample.hip)
 int check_logprobs(const char* what, const gpt2mi_logprobs* lp, int V);
-// The launch of the LP sampling kernels (csrc/sample_lp.hip) for sample_rows of csrc/sample.hip, which has checked
-// everything: pos, row_id and col are B values each; pen is NULL when the penalties are neutral, else hist_row and
-// gen_start are B values too.
-int launch_sample_lp(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k,
-                     float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
-                     int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, const gpt2mi_penalties* pen,
-                     const int* hist_row, const int* gen_start, float* logits_out, const gpt2mi_logprobs* lp,
-                     const int* col, void* stream);
-// The launch of the constrained sampling kernels (csrc/sample_con.hip), likewise: hist_row, gen_start and bias_row
-// (-1: no bias row) are B values each, col too with lp; pen may be NULL (no history), pen_on says whether its values
-// are non-neutral; lmp = fp32(log(min_p)), -inf for min_p = 0.
-int launch_sample_con(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k,
-                      float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
-                      int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, const gpt2mi_penalties* pen,
-                      bool pen_on, const int* hist_row, const int* gen_start, float* logits_out,
-                      const gpt2mi_logprobs* lp, const int* col, const gpt2mi_constraints* con, const int* bias_row,
-                      float lmp, void* stream);
+// One sampling call, from a C entry to the launch. An entry (or the token loop of csrc/decode.hip) fills the first
+// two groups as gpt2mi_sample_constrained takes them (an entry without an option block leaves it NULL) and the rest
+// zero; sample_rows checks them and fills the third, which is all the launches read beside the first two. The row
+// tables are plain arrays, B values each: the kernels' by-value structs (sample_row.h) are every unit's own types.
+struct SampleCall {
+  const float* logits;
+  int ldl, B, V;
+  float temperature;
+  int top_k;
+  float top_p;
+  uint64_t seed;
+  const int* pos;          // host, B ints
+  const uint32_t* row_id;  // host, B values, or NULL: the row number
+  int64_t eos;
+  uint8_t* done;
+  int64_t *tok_out, *seq_out;
+  int ld_seq;
+  float* probs_out;
+  void* stream;
+  const gpt2mi_penalties* pen;  // the option blocks, each may be NULL; logits_out goes with pen
+  float* logits_out;
+  const gpt2mi_logprobs* lp;
+  const gpt2mi_constraints* con;
+  // checked: whether pen's values / anything of con is non-neutral; fp32(log(min_p)), -inf for min_p = 0; per row the
+  // position and draw key, with pen_on or con_on the row of hist (0 when nothing reads the history) and where the
+  // generated part starts, with lp the column, with con the bias row (-1: none)
+  bool pen_on, con_on;
+  float lmp;
+  int key_pos[GPT2MI_DECODE_MAX_B];
+  uint32_t key_row[GPT2MI_DECODE_MAX_B];
+  int hist_row[GPT2MI_DECODE_MAX_B], gen_start[GPT2MI_DECODE_MAX_B], col[GPT2MI_DECODE_MAX_B];
+  int bias_row[GPT2MI_DECODE_MAX_B];
+};
+// Every check of a sampling call under the entry name `what`, then its launch (csrc/sample.hip). A record may be used
+// again with other positions (the token loop of csrc/decode.hip): every call fills what its launch reads.
+int sample_rows(const char* what, SampleCall& call);
+// The launches of the LP and of the constrained sampling kernels (csrc/sample_lp.hip, csrc/sample_con.hip) for
+// sample_rows, which has checked everything. The LP one reads pen only with pen_on; the constrained one takes a call
+// whose pen is NULL (no history) and one with lp NULL.
+int launch_sample_lp(const char* what, const SampleCall& call);
+int launch_sample_con(const char* what, const SampleCall& call);
 // What of a gpt2mi_constraints (gpt2mi.h v24.4) does not depend on the rows' positions: the values, the stop table and
 // the bias rows of B rows into bias_row[] (-1: none); *on = whether anything is non-neutral (csrc/sample.hip)
 int check_constraints(const char* what, const gpt2mi_constraints* con, int B, int V, int64_t eos, const uint8_t* done,

@@ -945,71 +945,92 @@ GPT2MI_EXPORT int gpt2mi_decode_extend(const gpt2mi_decode_plan* P, int R, const
 }
 
 namespace {
+// The arguments of a token loop as gpt2mi_decode_generate_constrained takes them; an entry without the penalty values,
+// lp or con leaves them at these neutral ones.
+struct GenerateCall {
+  const gpt2mi_decode_plan* plan;
+  int V;
+  float temperature;
+  int top_k;
+  float top_p;
+  uint64_t seed;
+  int64_t eos;
+  const int* pos0;
+  const uint32_t* row_id;
+  int n;
+  int64_t *tok, *seq;
+  int ld_seq;
+  uint8_t* done;
+  void* stream;
+  float repetition = 1.f, presence = 0.f, frequency = 0.f;
+  const int* gen_start = nullptr;
+  const gpt2mi_logprobs* lp = nullptr;
+  const gpt2mi_constraints* con = nullptr;
+};
+
 // The token loop with row b starting at pos0[b]: sample, then (but for the last token) step, n times. With non-neutral
 // penalty values (gpt2mi_decode_generate_penalized) seq is the history the sampler reads, row b's own row of it. With
 // `lp` (gpt2mi_decode_generate_logprobs; may be NULL) step i writes column pos0[b] + i of it: its col is NULL, the
 // sampler's "col[b] = pos[b]". With a non-neutral `con` (gpt2mi_decode_generate_constrained; may be NULL) the draws are
 // gpt2mi_sample_constrained's, seq again the history and gen_start where a row's generated part begins.
-int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
-                         float top_p, uint64_t seed, int64_t eos, const int* pos0, const uint32_t* row_id, int n,
-                         int64_t* tok, int64_t* seq, int ld_seq, uint8_t* done, void* stream, float repetition = 1.f,
-                         float presence = 0.f, float frequency = 0.f, const int* gen_start = nullptr,
-                         const gpt2mi_logprobs* lp = nullptr, const gpt2mi_constraints* con = nullptr) {
+// The draws are sample_rows' (csrc/sample.hip) on one record, under the name of the sampler entry that takes what is on.
+int decode_generate_rows(const char* what, const GenerateCall& g) {
+  const gpt2mi_decode_plan* P = g.plan;
+  const int V = g.V, n = g.n;
   GPT2MI_REQUIRE(P != nullptr, "%s: plan is NULL", what);
   GPT2MI_REQUIRE(V >= 1 && V <= P->Vp, "%s: V=%d not in [1, Vp=%d]", what, V, P->Vp);
   GPT2MI_REQUIRE(n >= 0, "%s: n=%d must be >= 0", what, n);
   RowPos rp;
   int max_pos;
-  if (const int rc = row_positions(what, pos0, P->B, P->Tcap, &rp, &max_pos)) return rc;
+  if (const int rc = row_positions(what, g.pos0, P->B, P->Tcap, &rp, &max_pos)) return rc;
   for (int b = 0; b < P->B; ++b)
-    GPT2MI_REQUIRE(pos0[b] >= 1, "%s: pos0[%d]=%d must be >= 1 (after a prefill)", what, b, pos0[b]);
+    GPT2MI_REQUIRE(g.pos0[b] >= 1, "%s: pos0[%d]=%d must be >= 1 (after a prefill)", what, b, g.pos0[b]);
   ShareMap sm;  // at pos0: the positions only grow from there, so a map that passes here passes at every step
   if (const int rc = share_map(what, P->share_group, P->share_len, P->B, rp, &sm)) return rc;
   GPT2MI_REQUIRE((long long)max_pos + n <= P->Tcap, "%s: max pos0=%d + n=%d exceeds the cache length Tcap=%d", what,
                  max_pos, n, P->Tcap);
-  GPT2MI_REQUIRE(!seq || (long long)max_pos + n <= ld_seq, "%s: max pos0=%d + n=%d exceeds ld_seq=%d", what, max_pos, n,
-                 ld_seq);
+  GPT2MI_REQUIRE(!g.seq || (long long)max_pos + n <= g.ld_seq, "%s: max pos0=%d + n=%d exceeds ld_seq=%d", what, max_pos,
+                 n, g.ld_seq);
   bool on;
-  if (const int rc = gpt2mi::check_penalty_values(what, repetition, presence, frequency, &on)) return rc;
-  const gpt2mi_penalties pen = {repetition, presence, frequency, seq, ld_seq, P->B, nullptr, gen_start};
+  if (const int rc = gpt2mi::check_penalty_values(what, g.repetition, g.presence, g.frequency, &on)) return rc;
+  const gpt2mi_penalties pen = {g.repetition, g.presence, g.frequency, g.seq, g.ld_seq, P->B, nullptr, g.gen_start};
   if (on) {
-    GPT2MI_REQUIRE(seq != nullptr, "%s: penalties need seq, the history buffer: it is NULL", what);
-    for (int b = 0; b < P->B && gen_start; ++b)
-      GPT2MI_REQUIRE(gen_start[b] >= 0 && gen_start[b] <= pos0[b], "%s: gen_start[%d]=%d not in [0, pos0=%d]", what, b,
-                     gen_start[b], pos0[b]);
+    GPT2MI_REQUIRE(g.seq != nullptr, "%s: penalties need seq, the history buffer: it is NULL", what);
     GPT2MI_REQUIRE((long long)max_pos + n - 1 <= GPT2MI_PENALTY_MAX_HISTORY,
                    "%s: max pos0=%d + n=%d - 1 above the history cap %d", what, max_pos, n, GPT2MI_PENALTY_MAX_HISTORY);
   }
-  if (lp) {
-    if (const int rc = gpt2mi::check_logprobs(what, lp, V)) return rc;
-    GPT2MI_REQUIRE(lp->col == nullptr, "%s: logprobs col must be NULL in the loop (step i writes column pos0[b] + i)",
+  if (g.lp) {
+    if (const int rc = gpt2mi::check_logprobs(what, g.lp, V)) return rc;
+    GPT2MI_REQUIRE(g.lp->col == nullptr, "%s: logprobs col must be NULL in the loop (step i writes column pos0[b] + i)",
                    what);
-    GPT2MI_REQUIRE((long long)max_pos + n <= lp->ld, "%s: max pos0=%d + n=%d exceeds the logprobs ld=%d", what, max_pos,
-                   n, lp->ld);
+    GPT2MI_REQUIRE((long long)max_pos + n <= g.lp->ld, "%s: max pos0=%d + n=%d exceeds the logprobs ld=%d", what, max_pos,
+                   n, g.lp->ld);
   }
   bool con_on = false;
-  if (con) {
+  if (g.con) {
     int bias_row[GPT2MI_DECODE_MAX_B];
-    if (const int rc = gpt2mi::check_constraints(what, con, P->B, V, eos, done, bias_row, &con_on)) return rc;
-    GPT2MI_REQUIRE(con->n_stop == 0 || seq != nullptr, "%s: stop sequences need seq, the history buffer: it is NULL", what);
-    for (int b = 0; b < P->B && gen_start && con_on; ++b)
-      GPT2MI_REQUIRE(gen_start[b] >= 0 && gen_start[b] <= pos0[b], "%s: gen_start[%d]=%d not in [0, pos0=%d]", what, b,
-                     gen_start[b], pos0[b]);
+    if (const int rc = gpt2mi::check_constraints(what, g.con, P->B, V, g.eos, g.done, bias_row, &con_on)) return rc;
+    GPT2MI_REQUIRE(g.con->n_stop == 0 || g.seq != nullptr, "%s: stop sequences need seq, the history buffer: it is NULL",
+                   what);
   }
-  GPT2MI_REQUIRE(tok != nullptr && P->logits != nullptr, "%s: tok and plan->logits must not be NULL", what);
+  for (int b = 0; b < P->B && g.gen_start && (on || con_on); ++b)
+    GPT2MI_REQUIRE(g.gen_start[b] >= 0 && g.gen_start[b] <= g.pos0[b], "%s: gen_start[%d]=%d not in [0, pos0=%d]", what, b,
+                   g.gen_start[b], g.pos0[b]);
+  GPT2MI_REQUIRE(g.tok != nullptr && P->logits != nullptr, "%s: tok and plan->logits must not be NULL", what);
   if (const int rc = plan_shape(what, P)) return rc;  // (before the first draw, not only before the first step)
+  // the sampler entry that takes what is on: a neutral pen or con is not passed on, as that entry would not get it
+  const char* draw = con_on ? "sample_constrained" : g.lp ? "sample_logprobs" : "sample_penalized";
+  gpt2mi::SampleCall c = {.logits = P->logits, .ldl = P->Vp, .B = P->B, .V = V, .temperature = g.temperature,
+                          .top_k = g.top_k, .top_p = g.top_p, .seed = g.seed, .pos = rp.v, .row_id = g.row_id,
+                          .eos = g.eos, .done = g.done, .tok_out = g.tok, .seq_out = g.seq, .ld_seq = g.ld_seq,
+                          .stream = g.stream, .pen = on || con_on ? &pen : nullptr, .lp = g.lp,
+                          .con = con_on ? g.con : nullptr};
   for (int i = 0; i < n; ++i) {
-    for (int b = 0; b < P->B; ++b) rp.v[b] = pos0[b] + i;
-    int rc = con_on
-                 ? gpt2mi_sample_constrained(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
-                                             done, tok, seq, ld_seq, nullptr, &pen, nullptr, lp, con, stream)
-             : lp ? gpt2mi_sample_logprobs(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
-                                         done, tok, seq, ld_seq, nullptr, on ? &pen : nullptr, nullptr, lp, stream)
-                : gpt2mi_sample_penalized(P->logits, P->Vp, P->B, V, temperature, top_k, top_p, seed, rp.v, row_id, eos,
-                                          done, tok, seq, ld_seq, nullptr, on ? &pen : nullptr, nullptr, stream);
+    for (int b = 0; b < P->B; ++b) rp.v[b] = g.pos0[b] + i;
+    int rc = gpt2mi::sample_rows(draw, c);
     if (rc) return rc;
     if (i + 1 < n) {
-      rc = decode_step_rows(what, P, tok, rp.v, stream);
+      rc = decode_step_rows(what, P, g.tok, rp.v, g.stream);
       if (rc) return rc;
     }
   }
@@ -1017,12 +1038,17 @@ int decode_generate_rows(const char* what, const gpt2mi_decode_plan* P, int V, f
 }
 }  // namespace
 
+#define GENERATE_CALL_ARGS                                                                                            \
+  .plan = P, .V = V, .temperature = temperature, .top_k = top_k, .top_p = top_p, .seed = seed, .eos = eos, .pos0 = pos0, \
+  .row_id = row_id, .n = n, .tok = tok, .seq = seq, .ld_seq = ld_seq, .done = done, .stream = stream
+#define GENERATE_CALL_PENALTIES \
+  .repetition = repetition, .presence = presence, .frequency = frequency, .gen_start = gen_start
+
 GPT2MI_EXPORT int gpt2mi_decode_generate_ragged(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
                                                 float top_p, uint64_t seed, int64_t eos, const int* pos0,
                                                 const uint32_t* row_id, int n, int64_t* tok, int64_t* seq, int ld_seq,
                                                 uint8_t* done, void* stream) {
-  return decode_generate_rows("decode_generate_ragged", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n, tok,
-                              seq, ld_seq, done, stream);
+  return decode_generate_rows("decode_generate_ragged", {GENERATE_CALL_ARGS});
 }
 
 GPT2MI_EXPORT int gpt2mi_decode_generate_penalized(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
@@ -1030,8 +1056,7 @@ GPT2MI_EXPORT int gpt2mi_decode_generate_penalized(const gpt2mi_decode_plan* P, 
                                                    const uint32_t* row_id, int n, int64_t* tok, int64_t* seq,
                                                    int ld_seq, uint8_t* done, void* stream, float repetition,
                                                    float presence, float frequency, const int* gen_start) {
-  return decode_generate_rows("decode_generate_penalized", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n,
-                              tok, seq, ld_seq, done, stream, repetition, presence, frequency, gen_start);
+  return decode_generate_rows("decode_generate_penalized", {GENERATE_CALL_ARGS, GENERATE_CALL_PENALTIES});
 }
 
 GPT2MI_EXPORT int gpt2mi_decode_generate_logprobs(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
@@ -1039,8 +1064,7 @@ GPT2MI_EXPORT int gpt2mi_decode_generate_logprobs(const gpt2mi_decode_plan* P, i
                                                   const uint32_t* row_id, int n, int64_t* tok, int64_t* seq, int ld_seq,
                                                   uint8_t* done, void* stream, float repetition, float presence,
                                                   float frequency, const int* gen_start, const gpt2mi_logprobs* lp) {
-  return decode_generate_rows("decode_generate_logprobs", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n,
-                              tok, seq, ld_seq, done, stream, repetition, presence, frequency, gen_start, lp);
+  return decode_generate_rows("decode_generate_logprobs", {GENERATE_CALL_ARGS, GENERATE_CALL_PENALTIES, .lp = lp});
 }
 
 GPT2MI_EXPORT int gpt2mi_decode_generate_constrained(const gpt2mi_decode_plan* P, int V, float temperature, int top_k,
@@ -1049,17 +1073,21 @@ GPT2MI_EXPORT int gpt2mi_decode_generate_constrained(const gpt2mi_decode_plan* P
                                                      int ld_seq, uint8_t* done, void* stream, float repetition,
                                                      float presence, float frequency, const int* gen_start,
                                                      const gpt2mi_logprobs* lp, const gpt2mi_constraints* con) {
-  return decode_generate_rows("decode_generate_constrained", P, V, temperature, top_k, top_p, seed, eos, pos0, row_id, n,
-                              tok, seq, ld_seq, done, stream, repetition, presence, frequency, gen_start, lp, con);
+  return decode_generate_rows("decode_generate_constrained",
+                              {GENERATE_CALL_ARGS, GENERATE_CALL_PENALTIES, .lp = lp, .con = con});
 }
 
 GPT2MI_EXPORT int gpt2mi_decode_generate(const gpt2mi_decode_plan* P, int V, float temperature, int top_k, float top_p,
-                                         uint64_t seed, int64_t eos, int pos0, int n, int64_t* tok, int64_t* seq,
+                                         uint64_t seed, int64_t eos, int pos, int n, int64_t* tok, int64_t* seq,
                                          int ld_seq, uint8_t* done, void* stream) {
   GPT2MI_REQUIRE(P != nullptr, "decode_generate: plan is NULL");
-  GPT2MI_REQUIRE(n >= 0 && pos0 >= 1, "decode_generate: n=%d must be >= 0 and pos0=%d >= 1 (after a prefill)", n, pos0);
-  GPT2MI_REQUIRE((long long)pos0 + n <= P->Tcap, "decode_generate: pos0=%d + n=%d exceeds the cache length Tcap=%d", pos0,
+  GPT2MI_REQUIRE(n >= 0 && pos >= 1, "decode_generate: n=%d must be >= 0 and pos0=%d >= 1 (after a prefill)", n, pos);
+  GPT2MI_REQUIRE((long long)pos + n <= P->Tcap, "decode_generate: pos0=%d + n=%d exceeds the cache length Tcap=%d", pos,
                  n, P->Tcap);
-  return decode_generate_rows("decode_generate", P, V, temperature, top_k, top_p, seed, eos, SamePos(pos0).v, nullptr, n,
-                              tok, seq, ld_seq, done, stream);
+  const SamePos same(pos);
+  const int* pos0 = same.v;
+  const uint32_t* row_id = nullptr;
+  return decode_generate_rows("decode_generate", {GENERATE_CALL_ARGS});
 }
+#undef GENERATE_CALL_ARGS
+#undef GENERATE_CALL_PENALTIES

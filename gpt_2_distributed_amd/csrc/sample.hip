@@ -40,6 +40,10 @@
 // penalties, the eos held back below a minimum length, min-p as one more bound on thr, and stop sequences matched by
 // thread 0 against the history and the token it drew (gpt2mi.h v24.4, generation.py apply_constraints / stop_match).
 // sample_rows below checks a gpt2mi_constraints and sends only a non-neutral one there.
+//
+// The host path: every entry (and the token loop of decode.hip) fills one gpt2mi::SampleCall (common.h); sample_rows
+// checks it, fills its row tables and launches a kernel of this unit or hands the record to launch_sample_lp /
+// launch_sample_con; each kernel family's argument list is written once, in launch_rows (sample_row.h) and its caller.
 #include "sample_row.h"
 
 namespace {
@@ -70,117 +74,86 @@ __global__ __launch_bounds__(SM_THREADS) void penalized_kernel(const float* __re
                                   rows.gen_start[b], rp, pp, fp, logits_out);
 }
 
-// gpt2mi_sample_ragged, and gpt2mi_sample with every pos[b] equal and no row_id; `what` is the entry's name in messages.
-// `pen` (may be NULL) and logits_out: gpt2mi_sample_penalized's; `lpo` (may be NULL): gpt2mi_sample_logprobs'; `con` (may
-// be NULL): gpt2mi_sample_constrained's, and only a non-neutral one leaves the launches below.
-int sample_rows(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
-                uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done, int64_t* tok_out,
-                int64_t* seq_out, int ld_seq, float* probs_out, void* stream, const gpt2mi_penalties* pen = nullptr,
-                float* logits_out = nullptr, const gpt2mi_logprobs* lpo = nullptr,
-                const gpt2mi_constraints* con = nullptr) {
-  GPT2MI_REQUIRE(B >= 1 && B <= GPT2MI_DECODE_MAX_B && V >= 1, "%s: B=%d not in [1, %d] or V=%d not positive", what, B,
-                 GPT2MI_DECODE_MAX_B, V);
-  GPT2MI_REQUIRE(V <= GPT2MI_SAMPLE_MAX_V, "%s: V=%d above the kernel's row capacity %d", what, V, GPT2MI_SAMPLE_MAX_V);
-  GPT2MI_REQUIRE(ldl >= V, "%s: ldl=%d < V=%d", what, ldl, V);
-  GPT2MI_REQUIRE(temperature >= 0.f, "%s: temperature=%g must be >= 0", what, (double)temperature);  // (NaN fails too)
-  GPT2MI_REQUIRE(top_p > 0.f, "%s: top_p=%g must be > 0 (>= 1: off)", what, (double)top_p);
-  GPT2MI_REQUIRE(pos != nullptr, "%s: the position array (host, B ints) is NULL", what);
-  GPT2MI_REQUIRE(eos >= -1 && eos < V, "%s: eos=%lld not in [-1, V=%d)", what, (long long)eos, V);
-  RowKeys keys = {};
-  for (int b = 0; b < B; ++b) {
-    GPT2MI_REQUIRE(pos[b] >= 0, "%s: pos[%d]=%d is negative", what, b, pos[b]);
-    GPT2MI_REQUIRE(!seq_out || ld_seq > pos[b], "%s: ld_seq=%d does not reach pos[%d]=%d", what, ld_seq, b, pos[b]);
-    keys.pos[b] = pos[b];
-    keys.row_id[b] = row_id ? row_id[b] : (uint32_t)b;
-  }
-  bool on = false;
-  PenRows rows = {};
-  if (pen) {
-    if (const int rc = gpt2mi::check_penalty_values(what, pen->repetition, pen->presence, pen->frequency, &on)) return rc;
-    if (on) {
-      GPT2MI_REQUIRE(pen->hist != nullptr, "%s: penalties need the history buffer: hist is NULL", what);
-      for (int b = 0; b < B; ++b) {
-        const int hr = pen->hist_row ? pen->hist_row[b] : b, gs = pen->gen_start ? pen->gen_start[b] : 0;
-        GPT2MI_REQUIRE(pos[b] <= GPT2MI_PENALTY_MAX_HISTORY, "%s: pos[%d]=%d above the history cap %d", what, b, pos[b],
-                       GPT2MI_PENALTY_MAX_HISTORY);
-        GPT2MI_REQUIRE(pen->ld_hist >= pos[b], "%s: ld_hist=%d < pos[%d]=%d", what, pen->ld_hist, b, pos[b]);
-        GPT2MI_REQUIRE(hr >= 0 && hr < pen->hist_rows, "%s: hist_row[%d]=%d not in [0, hist_rows=%d)", what, b, hr,
-                       pen->hist_rows);
-        GPT2MI_REQUIRE(gs >= 0 && gs <= pos[b], "%s: gen_start[%d]=%d not in [0, pos=%d]", what, b, gs, pos[b]);
-        rows.hist_row[b] = hr;
-        rows.gen_start[b] = gs;
-      }
-    }
-  }
-  int col[GPT2MI_DECODE_MAX_B] = {};
-  if (lpo) {
-    if (const int rc = gpt2mi::check_logprobs(what, lpo, V)) return rc;
-    for (int b = 0; b < B; ++b) {
-      const int c = lpo->col ? lpo->col[b] : pos[b];
-      GPT2MI_REQUIRE(c >= 0 && c < lpo->ld, "%s: logprobs %s[%d]=%d not in [0, ld=%d)", what, lpo->col ? "col" : "pos", b,
-                     c, lpo->ld);
-      col[b] = c;
-    }
-  }
-  bool con_on = false;
-  int bias_row[GPT2MI_DECODE_MAX_B] = {};
-  if (con) {
-    if (const int rc = gpt2mi::check_constraints(what, con, B, V, eos, done, bias_row, &con_on)) return rc;
-    const bool reads = con->n_stop > 0;  // the history, whatever the penalty values
-    GPT2MI_REQUIRE(!reads || (pen && pen->hist), "%s: stop sequences need the history buffer: hist is NULL", what);
-    for (int b = 0; b < B && con_on && !on; ++b) {  // (with penalty values on, the rows are checked above)
-      const int hr = pen && pen->hist_row ? pen->hist_row[b] : b, gs = pen && pen->gen_start ? pen->gen_start[b] : 0;
-      GPT2MI_REQUIRE(!reads || pen->ld_hist >= pos[b], "%s: ld_hist=%d < pos[%d]=%d", what, pen->ld_hist, b, pos[b]);
-      GPT2MI_REQUIRE(!reads || (hr >= 0 && hr < pen->hist_rows), "%s: hist_row[%d]=%d not in [0, hist_rows=%d)", what, b,
-                     hr, pen->hist_rows);
-      GPT2MI_REQUIRE(gs >= 0 && gs <= pos[b], "%s: gen_start[%d]=%d not in [0, pos=%d]", what, b, gs, pos[b]);
-      rows.hist_row[b] = reads ? hr : 0;
-      rows.gen_start[b] = gs;
-    }
-  }
-  GPT2MI_REQUIRE(logits && tok_out, "%s: logits and tok_out must not be NULL", what);
-  if (con_on) {
-    const float lmp = con->min_p > 0.f ? (float)log((double)con->min_p) : -INFINITY;
-    return gpt2mi::launch_sample_con(what, logits, ldl, B, V, temperature, top_k, top_p, seed, keys.pos, keys.row_id, eos,
-                                     done, tok_out, seq_out, ld_seq, probs_out, pen, on, rows.hist_row, rows.gen_start,
-                                     logits_out, lpo, col, con, bias_row, lmp, stream);
-  }
-  if (on) {
-    if (lpo)
-      return gpt2mi::launch_sample_lp(what, logits, ldl, B, V, temperature, top_k, top_p, seed, keys.pos, keys.row_id,
-                                      eos, done, tok_out, seq_out, ld_seq, probs_out, pen, rows.hist_row, rows.gen_start,
-                                      logits_out, lpo, col, stream);
-    if (temperature == 0.f)
-      penalized_kernel<true><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(
-          logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out,
-          pen->hist, pen->ld_hist, rows, pen->repetition, pen->presence, pen->frequency, logits_out);
-    else
-      penalized_kernel<false><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(
-          logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out,
-          pen->hist, pen->ld_hist, rows, pen->repetition, pen->presence, pen->frequency, logits_out);
-    return gpt2mi::check_launch(what);
-  }
-  if (logits_out) {  // neutral values: the logits themselves
-    const hipError_t e = hipMemcpy2DAsync(logits_out, sizeof(float) * V, logits, sizeof(float) * ldl, sizeof(float) * V,
-                                          B, hipMemcpyDeviceToDevice, (hipStream_t)stream);
-    GPT2MI_REQUIRE(e == hipSuccess, "%s: copying the logits to logits_out: %s", what, hipGetErrorString(e));
-  }
-  if (lpo)
-    return gpt2mi::launch_sample_lp(what, logits, ldl, B, V, temperature, top_k, top_p, seed, keys.pos, keys.row_id, eos,
-                                    done, tok_out, seq_out, ld_seq, probs_out, nullptr, nullptr, nullptr, nullptr, lpo,
-                                    col, stream);
-  if (temperature == 0.f)
-    sample_kernel<true><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(logits, ldl, V, temperature, top_k, top_p, seed, keys,
-                                                                   eos, done, tok_out, seq_out, ld_seq, probs_out);
-  else
-    sample_kernel<false><<<B, SM_THREADS, 0, (hipStream_t)stream>>>(logits, ldl, V, temperature, top_k, top_p, seed,
-                                                                    keys, eos, done, tok_out, seq_out, ld_seq, probs_out);
-  return gpt2mi::check_launch(what);
-}
-
 }  // namespace
 
 namespace gpt2mi {
+// A call as its entry filled it (common.h SampleCall): gpt2mi_sample_ragged's arguments, and gpt2mi_sample's with every
+// pos[b] equal and no row_id; `what` is the entry's name in messages. pen (may be NULL) and logits_out:
+// gpt2mi_sample_penalized's; lp (may be NULL): gpt2mi_sample_logprobs'; con (may be NULL): gpt2mi_sample_constrained's,
+// and only a non-neutral one leaves the launches below.
+int sample_rows(const char* what, SampleCall& c) {
+  const int B = c.B, V = c.V;
+  const int* pos = c.pos;
+  const gpt2mi_penalties* pen = c.pen;
+  GPT2MI_REQUIRE(B >= 1 && B <= GPT2MI_DECODE_MAX_B && V >= 1, "%s: B=%d not in [1, %d] or V=%d not positive", what, B,
+                 GPT2MI_DECODE_MAX_B, V);
+  GPT2MI_REQUIRE(V <= GPT2MI_SAMPLE_MAX_V, "%s: V=%d above the kernel's row capacity %d", what, V, GPT2MI_SAMPLE_MAX_V);
+  GPT2MI_REQUIRE(c.ldl >= V, "%s: ldl=%d < V=%d", what, c.ldl, V);
+  GPT2MI_REQUIRE(c.temperature >= 0.f, "%s: temperature=%g must be >= 0", what, (double)c.temperature);  // (NaN fails too)
+  GPT2MI_REQUIRE(c.top_p > 0.f, "%s: top_p=%g must be > 0 (>= 1: off)", what, (double)c.top_p);
+  GPT2MI_REQUIRE(pos != nullptr, "%s: the position array (host, B ints) is NULL", what);
+  GPT2MI_REQUIRE(c.eos >= -1 && c.eos < V, "%s: eos=%lld not in [-1, V=%d)", what, (long long)c.eos, V);
+  for (int b = 0; b < B; ++b) {
+    GPT2MI_REQUIRE(pos[b] >= 0, "%s: pos[%d]=%d is negative", what, b, pos[b]);
+    GPT2MI_REQUIRE(!c.seq_out || c.ld_seq > pos[b], "%s: ld_seq=%d does not reach pos[%d]=%d", what, c.ld_seq, b, pos[b]);
+    c.key_pos[b] = pos[b];
+    c.key_row[b] = c.row_id ? c.row_id[b] : (uint32_t)b;
+  }
+  c.pen_on = c.con_on = false;
+  if (pen) {
+    if (const int rc = check_penalty_values(what, pen->repetition, pen->presence, pen->frequency, &c.pen_on)) return rc;
+    GPT2MI_REQUIRE(!c.pen_on || pen->hist != nullptr, "%s: penalties need the history buffer: hist is NULL", what);
+  }
+  if (c.lp) {
+    if (const int rc = check_logprobs(what, c.lp, V)) return rc;
+    for (int b = 0; b < B; ++b) {
+      const int col = c.lp->col ? c.lp->col[b] : pos[b];
+      GPT2MI_REQUIRE(col >= 0 && col < c.lp->ld, "%s: logprobs %s[%d]=%d not in [0, ld=%d)", what,
+                     c.lp->col ? "col" : "pos", b, col, c.lp->ld);
+      c.col[b] = col;
+    }
+  }
+  bool stops = false;  // stop sequences read the history, whatever the penalty values
+  if (c.con) {
+    if (const int rc = check_constraints(what, c.con, B, V, c.eos, c.done, c.bias_row, &c.con_on)) return rc;
+    stops = c.con->n_stop > 0;
+    GPT2MI_REQUIRE(!stops || (pen && pen->hist), "%s: stop sequences need the history buffer: hist is NULL", what);
+  }
+  // the rows of a call that reads the history or gen_start (min_new counts from it): the cap is the penalties' LDS table's
+  for (int b = 0; b < B && (c.pen_on || c.con_on); ++b) {
+    const bool reads = c.pen_on || stops;
+    const int hr = pen && pen->hist_row ? pen->hist_row[b] : b, gs = pen && pen->gen_start ? pen->gen_start[b] : 0;
+    GPT2MI_REQUIRE(!c.pen_on || pos[b] <= GPT2MI_PENALTY_MAX_HISTORY, "%s: pos[%d]=%d above the history cap %d", what, b,
+                   pos[b], GPT2MI_PENALTY_MAX_HISTORY);
+    GPT2MI_REQUIRE(!reads || pen->ld_hist >= pos[b], "%s: ld_hist=%d < pos[%d]=%d", what, pen->ld_hist, b, pos[b]);
+    GPT2MI_REQUIRE(!reads || (hr >= 0 && hr < pen->hist_rows), "%s: hist_row[%d]=%d not in [0, hist_rows=%d)", what, b, hr,
+                   pen->hist_rows);
+    GPT2MI_REQUIRE(gs >= 0 && gs <= pos[b], "%s: gen_start[%d]=%d not in [0, pos=%d]", what, b, gs, pos[b]);
+    c.hist_row[b] = reads ? hr : 0;
+    c.gen_start[b] = gs;
+  }
+  GPT2MI_REQUIRE(c.logits && c.tok_out, "%s: logits and tok_out must not be NULL", what);
+  const bool greedy = c.temperature == 0.f;
+  if (c.con_on) {
+    c.lmp = c.con->min_p > 0.f ? (float)log((double)c.con->min_p) : -INFINITY;
+    return launch_sample_con(what, c);
+  }
+  if (c.pen_on) {
+    if (c.lp) return launch_sample_lp(what, c);
+    launch_rows(c, greedy ? penalized_kernel<true> : penalized_kernel<false>, pen->hist, pen->ld_hist, pen_rows(c),
+                pen->repetition, pen->presence, pen->frequency, c.logits_out);
+    return check_launch(what);
+  }
+  if (c.logits_out) {  // neutral values: the logits themselves
+    const hipError_t e = hipMemcpy2DAsync(c.logits_out, sizeof(float) * V, c.logits, sizeof(float) * c.ldl,
+                                          sizeof(float) * V, B, hipMemcpyDeviceToDevice, (hipStream_t)c.stream);
+    GPT2MI_REQUIRE(e == hipSuccess, "%s: copying the logits to logits_out: %s", what, hipGetErrorString(e));
+  }
+  if (c.lp) return launch_sample_lp(what, c);
+  launch_rows(c, greedy ? sample_kernel<true> : sample_kernel<false>);
+  return check_launch(what);
+}
+
 int check_penalty_values(const char* what, float repetition, float presence, float frequency, bool* on) {
   GPT2MI_REQUIRE(repetition > 0.f && repetition < INFINITY, "%s: repetition=%g must be finite and > 0 (1: off)", what,
                  (double)repetition);  // (NaN fails too)
@@ -240,13 +213,19 @@ int check_constraints(const char* what, const gpt2mi_constraints* con, int B, in
 }
 }  // namespace gpt2mi
 
+// The entries: each fills the call's record with what it takes (the option blocks it lacks stay NULL).
+#define SAMPLE_CALL_ARGS                                                                                               \
+  .logits = logits, .ldl = ldl, .B = B, .V = V, .temperature = temperature, .top_k = top_k, .top_p = top_p, .seed = seed, \
+  .pos = pos, .row_id = row_id, .eos = eos, .done = done, .tok_out = tok_out, .seq_out = seq_out, .ld_seq = ld_seq,    \
+  .probs_out = probs_out, .stream = stream
+
 GPT2MI_EXPORT int gpt2mi_sample_constrained(const float* logits, int ldl, int B, int V, float temperature, int top_k,
                                             float top_p, uint64_t seed, const int* pos, const uint32_t* row_id,
                                             int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq,
                                             float* probs_out, const gpt2mi_penalties* pen, float* logits_out,
                                             const gpt2mi_logprobs* lp, const gpt2mi_constraints* con, void* stream) {
-  return sample_rows("sample_constrained", logits, ldl, B, V, temperature, top_k, top_p, seed, pos, row_id, eos, done,
-                     tok_out, seq_out, ld_seq, probs_out, stream, pen, logits_out, lp, con);
+  gpt2mi::SampleCall c = {SAMPLE_CALL_ARGS, .pen = pen, .logits_out = logits_out, .lp = lp, .con = con};
+  return gpt2mi::sample_rows("sample_constrained", c);
 }
 
 GPT2MI_EXPORT int gpt2mi_sample_penalized(const float* logits, int ldl, int B, int V, float temperature, int top_k,
@@ -254,8 +233,8 @@ GPT2MI_EXPORT int gpt2mi_sample_penalized(const float* logits, int ldl, int B, i
                                           int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq,
                                           float* probs_out, const gpt2mi_penalties* pen, float* logits_out,
                                           void* stream) {
-  return sample_rows("sample_penalized", logits, ldl, B, V, temperature, top_k, top_p, seed, pos, row_id, eos, done,
-                     tok_out, seq_out, ld_seq, probs_out, stream, pen, logits_out);
+  gpt2mi::SampleCall c = {SAMPLE_CALL_ARGS, .pen = pen, .logits_out = logits_out};
+  return gpt2mi::sample_rows("sample_penalized", c);
 }
 
 GPT2MI_EXPORT int gpt2mi_sample_logprobs(const float* logits, int ldl, int B, int V, float temperature, int top_k,
@@ -263,23 +242,27 @@ GPT2MI_EXPORT int gpt2mi_sample_logprobs(const float* logits, int ldl, int B, in
                                          uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq,
                                          float* probs_out, const gpt2mi_penalties* pen, float* logits_out,
                                          const gpt2mi_logprobs* lp, void* stream) {
-  return sample_rows("sample_logprobs", logits, ldl, B, V, temperature, top_k, top_p, seed, pos, row_id, eos, done,
-                     tok_out, seq_out, ld_seq, probs_out, stream, pen, logits_out, lp);
+  gpt2mi::SampleCall c = {SAMPLE_CALL_ARGS, .pen = pen, .logits_out = logits_out, .lp = lp};
+  return gpt2mi::sample_rows("sample_logprobs", c);
 }
 
 GPT2MI_EXPORT int gpt2mi_sample_ragged(const float* logits, int ldl, int B, int V, float temperature, int top_k,
                                        float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos,
                                        uint8_t* done, int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out,
                                        void* stream) {
-  return sample_rows("sample_ragged", logits, ldl, B, V, temperature, top_k, top_p, seed, pos, row_id, eos, done,
-                     tok_out, seq_out, ld_seq, probs_out, stream);
+  gpt2mi::SampleCall c = {SAMPLE_CALL_ARGS};
+  return gpt2mi::sample_rows("sample_ragged", c);
 }
 
 GPT2MI_EXPORT int gpt2mi_sample(const float* logits, int ldl, int B, int V, float temperature, int top_k, float top_p,
-                                uint64_t seed, int pos, int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out,
+                                uint64_t seed, int pos0, int64_t eos, uint8_t* done, int64_t* tok_out, int64_t* seq_out,
                                 int ld_seq, float* probs_out, void* stream) {
-  GPT2MI_REQUIRE(pos >= 0, "sample: pos=%d is negative", pos);
-  GPT2MI_REQUIRE(!seq_out || ld_seq > pos, "sample: ld_seq=%d does not reach pos=%d", ld_seq, pos);
-  return sample_rows("sample", logits, ldl, B, V, temperature, top_k, top_p, seed, gpt2mi::SamePos(pos).v, nullptr, eos,
-                     done, tok_out, seq_out, ld_seq, probs_out, stream);
+  GPT2MI_REQUIRE(pos0 >= 0, "sample: pos=%d is negative", pos0);
+  GPT2MI_REQUIRE(!seq_out || ld_seq > pos0, "sample: ld_seq=%d does not reach pos=%d", ld_seq, pos0);
+  const gpt2mi::SamePos same(pos0);
+  const int* pos = same.v;
+  const uint32_t* row_id = nullptr;
+  gpt2mi::SampleCall c = {SAMPLE_CALL_ARGS};
+  return gpt2mi::sample_rows("sample", c);
 }
+#undef SAMPLE_CALL_ARGS

@@ -1,7 +1,8 @@
 // The constrained instantiations of the sampling kernel (csrc/sample.hip, sample_row.h): logit bias, min-p, a minimum
 // number of new tokens and stop sequences in the launch that draws the token (gpt2mi.h v24.4; generation.py
 // apply_constraints, sample_reference's min_p and stop_match are the rule). A unit of its own, as sample_lp.hip is: the
-// plain, penalised and LP kernels keep their code, and a call whose constraints are all neutral never gets here.
+// plain, penalised and LP kernels keep their code, and a call whose constraints are all neutral never gets here:
+// sample_rows of sample.hip hands the checked record (common.h SampleCall) to the launch below.
 // One kernel per (greedy, penalised, LP) form; all take the same arguments, a form reads what it uses.
 #include "sample_row.h"
 
@@ -30,53 +31,29 @@ __global__ __launch_bounds__(SM_THREADS) void constrained_kernel(const float* __
 }  // namespace
 
 namespace gpt2mi {
-int launch_sample_con(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k,
-                      float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
-                      int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, const gpt2mi_penalties* pen,
-                      bool pen_on, const int* hist_row, const int* gen_start, float* logits_out,
-                      const gpt2mi_logprobs* lp, const int* col, const gpt2mi_constraints* con, const int* bias_row,
-                      float lmp, void* stream) {
-  RowKeys keys = {};
-  PenRows rows = {};
-  LpRows L = {};
-  if (lp) L = {lp->logprob, lp->top_id, lp->top_logprob, lp->ld, lp->top_n, {}};
+int launch_sample_con(const char* what, const SampleCall& c) {
+  const gpt2mi_penalties* pen = c.pen;
+  const gpt2mi_constraints* con = c.con;
   ConRows C = {};
   C.bias = con->bias;
   C.ld_bias = con->ld_bias;
-  C.lmp = lmp;
+  C.lmp = c.lmp;
   C.min_new = con->min_new;
   C.n_stop = con->n_stop;
-  for (int b = 0; b < B; ++b) {
-    keys.pos[b] = pos[b];
-    keys.row_id[b] = row_id[b];
-    rows.hist_row[b] = hist_row[b];
-    rows.gen_start[b] = gen_start[b];
-    if (lp) L.col[b] = col[b];
-    C.bias_row[b] = bias_row[b];
-  }
+  memcpy(C.bias_row, c.bias_row, sizeof C.bias_row);
   for (int s = 0; s < con->n_stop; ++s) {
     C.stop_len[s] = con->stop_len[s];
     for (int j = 0; j < con->stop_len[s]; ++j) C.stop[s][j] = con->stop[s * GPT2MI_STOP_MAX_LEN + j];
   }
-  const int64_t* hist = pen ? pen->hist : nullptr;
-  const int ld_hist = pen ? pen->ld_hist : 0;
-  const float rp = pen_on ? pen->repetition : 1.f, pp = pen_on ? pen->presence : 0.f, fp = pen_on ? pen->frequency : 0.f;
-  const hipStream_t st = (hipStream_t)stream;
-  auto launch = [&](auto kernel) {
-    kernel<<<B, SM_THREADS, 0, st>>>(logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out,
-                                     ld_seq, probs_out, hist, ld_hist, rows, rp, pp, fp, logits_out, L, C);
-  };
-  const bool greedy = temperature == 0.f;
-  switch ((greedy ? 4 : 0) | (pen_on ? 2 : 0) | (lp ? 1 : 0)) {
-    case 0: launch(constrained_kernel<false, false, false>); break;
-    case 1: launch(constrained_kernel<false, false, true>); break;
-    case 2: launch(constrained_kernel<false, true, false>); break;
-    case 3: launch(constrained_kernel<false, true, true>); break;
-    case 4: launch(constrained_kernel<true, false, false>); break;
-    case 5: launch(constrained_kernel<true, false, true>); break;
-    case 6: launch(constrained_kernel<true, true, false>); break;
-    default: launch(constrained_kernel<true, true, true>); break;
-  }
+  // the kernel of (greedy, penalised, LP) at index 4 greedy + 2 pen_on + lp
+  static constexpr decltype(&constrained_kernel<false, false, false>) forms[8] = {
+      constrained_kernel<false, false, false>, constrained_kernel<false, false, true>,
+      constrained_kernel<false, true, false>,  constrained_kernel<false, true, true>,
+      constrained_kernel<true, false, false>,  constrained_kernel<true, false, true>,
+      constrained_kernel<true, true, false>,   constrained_kernel<true, true, true>};
+  launch_rows(c, forms[(c.temperature == 0.f ? 4 : 0) | (c.pen_on ? 2 : 0) | (c.lp ? 1 : 0)], pen ? pen->hist : nullptr,
+              pen ? pen->ld_hist : 0, pen_rows(c), c.pen_on ? pen->repetition : 1.f, c.pen_on ? pen->presence : 0.f,
+              c.pen_on ? pen->frequency : 0.f, c.logits_out, lp_rows(c), C);
   return check_launch(what);
 }
 }  // namespace gpt2mi

@@ -1,6 +1,7 @@
 // The LP instantiations of the sampling kernel (csrc/sample.hip, sample_row.h): the four forms of the draw, each with
 // the log-probability of the drawn token and the top_n alternatives (gpt2mi.h v24.1). A unit of its own: sample.hip
-// keeps the kernels it had, compiled as before; its sample_rows checks the arguments and calls the launch below.
+// keeps the kernels it had, compiled as before; its sample_rows checks the call (common.h SampleCall), fills the row
+// tables and hands the record to the launch below.
 #include "sample_row.h"
 
 namespace {
@@ -40,40 +41,13 @@ __global__ __launch_bounds__(SM_THREADS) void penalized_lp_kernel(const float* _
 }  // namespace
 
 namespace gpt2mi {
-int launch_sample_lp(const char* what, const float* logits, int ldl, int B, int V, float temperature, int top_k,
-                     float top_p, uint64_t seed, const int* pos, const uint32_t* row_id, int64_t eos, uint8_t* done,
-                     int64_t* tok_out, int64_t* seq_out, int ld_seq, float* probs_out, const gpt2mi_penalties* pen,
-                     const int* hist_row, const int* gen_start, float* logits_out, const gpt2mi_logprobs* lp,
-                     const int* col, void* stream) {
-  RowKeys keys = {};
-  PenRows rows = {};
-  LpRows L = {lp->logprob, lp->top_id, lp->top_logprob, lp->ld, lp->top_n, {}};
-  for (int b = 0; b < B; ++b) {
-    keys.pos[b] = pos[b];
-    keys.row_id[b] = row_id[b];
-    L.col[b] = col[b];
-    if (pen) {
-      rows.hist_row[b] = hist_row[b];
-      rows.gen_start[b] = gen_start[b];
-    }
-  }
-  const hipStream_t st = (hipStream_t)stream;
-  if (pen) {
-    if (temperature == 0.f)
-      penalized_lp_kernel<true><<<B, SM_THREADS, 0, st>>>(
-          logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out,
-          pen->hist, pen->ld_hist, rows, pen->repetition, pen->presence, pen->frequency, logits_out, L);
-    else
-      penalized_lp_kernel<false><<<B, SM_THREADS, 0, st>>>(
-          logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done, tok_out, seq_out, ld_seq, probs_out,
-          pen->hist, pen->ld_hist, rows, pen->repetition, pen->presence, pen->frequency, logits_out, L);
-  } else if (temperature == 0.f) {
-    sample_lp_kernel<true><<<B, SM_THREADS, 0, st>>>(logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done,
-                                                     tok_out, seq_out, ld_seq, probs_out, L);
-  } else {
-    sample_lp_kernel<false><<<B, SM_THREADS, 0, st>>>(logits, ldl, V, temperature, top_k, top_p, seed, keys, eos, done,
-                                                      tok_out, seq_out, ld_seq, probs_out, L);
-  }
+int launch_sample_lp(const char* what, const SampleCall& c) {
+  const bool greedy = c.temperature == 0.f;
+  if (c.pen_on)
+    launch_rows(c, greedy ? penalized_lp_kernel<true> : penalized_lp_kernel<false>, c.pen->hist, c.pen->ld_hist,
+                pen_rows(c), c.pen->repetition, c.pen->presence, c.pen->frequency, c.logits_out, lp_rows(c));
+  else
+    launch_rows(c, greedy ? sample_lp_kernel<true> : sample_lp_kernel<false>, lp_rows(c));
   return check_launch(what);
 }
 }  // namespace gpt2mi

@@ -536,5 +536,34 @@ struct LpRows {
   __device__ size_t at(int b) const { return (size_t)b * ld + col[b]; }
 };
 
+// Host: the structs above from a checked call's row tables (common.h SampleCall), and the launch all the kernels share:
+// one workgroup per row, the arguments every kernel begins with, then `tail`, what its family takes behind probs_out.
+inline RowKeys row_keys(const gpt2mi::SampleCall& c) {
+  RowKeys keys;
+  memcpy(keys.pos, c.key_pos, sizeof keys.pos);
+  memcpy(keys.row_id, c.key_row, sizeof keys.row_id);
+  return keys;
+}
+inline PenRows pen_rows(const gpt2mi::SampleCall& c) {
+  PenRows rows;
+  memcpy(rows.hist_row, c.hist_row, sizeof rows.hist_row);
+  memcpy(rows.gen_start, c.gen_start, sizeof rows.gen_start);
+  return rows;
+}
+inline LpRows lp_rows(const gpt2mi::SampleCall& c) {  // (lp NULL: a form that does not read it)
+  LpRows L = {};
+  if (c.lp) {
+    L = {c.lp->logprob, c.lp->top_id, c.lp->top_logprob, c.lp->ld, c.lp->top_n, {}};
+    memcpy(L.col, c.col, sizeof L.col);
+  }
+  return L;
+}
+template <class Kernel, class... Tail>
+void launch_rows(const gpt2mi::SampleCall& c, Kernel kernel, const Tail&... tail) {
+  kernel<<<c.B, SM_THREADS, 0, (hipStream_t)c.stream>>>(c.logits, c.ldl, c.V, c.temperature, c.top_k, c.top_p, c.seed,
+                                                        row_keys(c), c.eos, c.done, c.tok_out, c.seq_out, c.ld_seq,
+                                                        c.probs_out, tail...);
+}
+
 }  // namespace
 #endif  // GPT2MI_SAMPLE_ROW_H

@@ -704,6 +704,12 @@ class ShareGroups:
             self.group[m], self.length[m] = rows[0], n
 
 
+def _entry(pen: dict, lp: Optional[dict], con: Optional[dict]) -> str:
+    """Which of the four sampler entries / generate loops a call goes to: the first that takes everything that is on
+    (``pen`` and ``con`` empty when neutral, ``lp`` None without log-probabilities); it names itself in refusals."""
+    return "constrained" if con else "logprobs" if lp is not None else "penalized" if pen else "ragged"
+
+
 class DecodeSession:
     """The key/value cache of ``batch_size`` sequences of up to ``max_len`` tokens, and the step that extends them.
 
@@ -1030,26 +1036,35 @@ class DecodeSession:
                                       f"(vocab_size {self.cfg.vocab_size})")
         self._ready(False)
 
+    def _check_history(self, hist, name: str, reader: str, last: Optional[int] = None):
+        """``hist`` (argument ``name``) as the history buffer of what ``reader`` names; with ``last``, reaching it."""
+        if hist is None:
+            raise ValueError(f"{reader} the rows' tokens: pass {name}, int64 [B={self.B}, T], holding row b's "
+                             f"tokens at [0, lens[b])")
+        if (hist.dtype != torch.int64 or hist.dim() != 2 or hist.size(0) != self.B or hist.stride(1) != 1
+                or not hist.is_cuda or (last is not None and hist.size(1) < last)):
+            shape = f"[B={self.B}, T]" if last is None else f"[B={self.B}, >= {last}]"
+            raise ValueError(f"{name} must be a device int64 {shape} with contiguous rows")
+
+    def _gen_start(self, gen_start) -> List[int]:
+        start = [0] * self.B if gen_start is None else [int(g) for g in gen_start]
+        if len(start) != self.B or not all(0 <= g <= m for g, m in zip(start, self.lens)):
+            raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
+        return start
+
     def _penalties(self, repetition_penalty, presence_penalty, frequency_penalty, gen_start, hist, name: str, last: int):
         """The penalty keywords of the C entries (``{}`` when the values are neutral): ``hist`` is the history buffer
         (argument ``name``), ``last`` the largest position a draw of the call reads its history up to."""
         rp, pp, fp, on = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
         if not on:
             return {}
-        if hist is None:
-            raise ValueError(f"penalties read the rows' tokens: pass {name}, int64 [B={self.B}, T], holding row b's "
-                             f"tokens at [0, lens[b])")
-        if (hist.dtype != torch.int64 or hist.dim() != 2 or hist.size(0) != self.B or hist.stride(1) != 1
-                or not hist.is_cuda):
-            raise ValueError(f"{name} must be a device int64 [B={self.B}, T] with contiguous rows")
+        self._check_history(hist, name, "penalties read")
         if last > K.PENALTY_MAX_HISTORY:
             raise NotImplementedError(f"the penalised sampler reads a history of up to {K.PENALTY_MAX_HISTORY} tokens "
                                       f"(GPT2MI_PENALTY_MAX_HISTORY); this call reaches position {last}")
         if hist.size(1) < last:
             raise ValueError(f"{name} holds {hist.size(1)} positions, the call reads up to {last}")
-        start = [0] * self.B if gen_start is None else [int(g) for g in gen_start]
-        if len(start) != self.B or not all(0 <= g <= m for g, m in zip(start, self.lens)):
-            raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
+        start = self._gen_start(gen_start)
         return dict(repetition=rp, presence=pp, frequency=fp, gen_start=start)
 
     def _constraints(self, logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, hist, name: str,
@@ -1072,17 +1087,10 @@ class DecodeSession:
         if not (mp > 0 or mn > 0 or stops or (rows is not None and any(r >= 0 for r in rows))):
             return {}
         if stops:
-            if hist is None:
-                raise ValueError(f"stop sequences are matched in the rows' tokens: pass {name}, int64 [B={self.B}, T], "
-                                 f"holding row b's tokens at [0, lens[b])")
-            if (hist.dtype != torch.int64 or hist.dim() != 2 or hist.size(0) != self.B or hist.stride(1) != 1
-                    or not hist.is_cuda or hist.size(1) < last):
-                raise ValueError(f"{name} must be a device int64 [B={self.B}, >= {last}] with contiguous rows")
+            self._check_history(hist, name, "stop sequences are matched in", last)
             if done is None:
                 raise ValueError(f"stop sequences need done, uint8 [B={self.B}]")
-        start = [0] * self.B if gen_start is None else [int(g) for g in gen_start]
-        if len(start) != self.B or not all(0 <= g <= m for g, m in zip(start, self.lens)):
-            raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
+        start = self._gen_start(gen_start)
         bias = {} if rows is None else dict(logit_bias=logit_bias, bias_row=rows)
         return dict(bias, min_p=mp, min_new_tokens=mn, stop=stops, gen_start=start)
 
@@ -1092,32 +1100,19 @@ class DecodeSession:
         keywords, not empty) gpt2mi_sample_penalized over the history ``hist``. ``kw``: row_id, eos, done. With ``lp``
         (logprob, top_ids, top_logprobs and optionally col) gpt2mi_sample_logprobs: the same draw and its values. With
         ``con`` (``_constraints``' keywords, not empty) gpt2mi_sample_constrained, beside whatever of the others."""
-        if con:
-            K.sample_constrained(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **(lp or {}), **kw,
-                                 **{"hist": hist, **pen, **con})
-        elif lp is not None:
-            K.sample_logprobs(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **lp, **kw,
-                              **({"hist": hist, **pen} if pen else {}))
-        elif pen:
-            K.sample_penalized(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **kw,
-                               **{"hist": hist, **pen})
-        else:
-            K.sample_ragged(logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out, **kw)
+        history = {"hist": hist} if pen or con else {}
+        getattr(K, "sample_" + _entry(pen, lp, con))(
+            logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out,
+            **{**kw, **(lp or {}), **history, **pen, **(con or {})})
 
     def _loop(self, n: int, temperature, top_k, top_p, seed, pen: dict, lp: Optional[dict] = None,
               con: Optional[dict] = None, **kw) -> None:
         """``n`` sample-then-step rounds from ``lens`` into ``_tok``: gpt2mi_decode_generate_ragged, or with ``pen``
         gpt2mi_decode_generate_penalized, or with ``lp`` (a LogprobBuffer's tensors) gpt2mi_decode_generate_logprobs, or
         with ``con`` gpt2mi_decode_generate_constrained. ``kw``: row_id, eos, seq, done."""
-        if con:
-            K.decode_generate_constrained(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n,
-                                          self._tok, **kw, **(lp or {}), **{**pen, **con})
-            return
-        if lp is not None:
-            kw = {**kw, **lp}
-        loop = K.decode_generate_logprobs if lp is not None else (K.decode_generate_penalized if pen
-                                                                  else K.decode_generate_ragged)
-        loop(self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n, self._tok, **kw, **pen)
+        getattr(K, "decode_generate_" + _entry(pen, lp, con))(
+            self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n, self._tok,
+            **{**kw, **(lp or {}), **pen, **(con or {})})
 
     def _check_run(self, n: int, row_id, eos_token_id, seq, done, penalties, gen_start, logprobs=None):
         """The argument checks ``generate`` and ``speculate`` share, then ``flush``; (row_id, done, pen) as checked:
