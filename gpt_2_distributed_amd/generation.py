@@ -45,6 +45,8 @@ forward re-allocates, and (b) it must not be called between a forward and its ba
 from __future__ import annotations
 
 import ctypes
+import inspect
+from dataclasses import dataclass, field, replace
 from typing import List, NamedTuple, Optional, Sequence
 
 import torch
@@ -499,9 +501,13 @@ def beam_pick(tokens, cum, lengths, W: int, length_penalty: float = 1.0, num_ret
                       lengths[rows].view(B, r))
 
 
-def _check_beams(num_beams, length_penalty, num_return_sequences, B: int, vocab_size: int, others: dict):
+WITH_BEAMS = ("model", "idx", "max_new_tokens", "eos_token_id", "prompt_lens", "pad_token_id", "kv_dtype", "num_beams",
+              "length_penalty", "num_return_sequences")  # (of generate's parameters)
+
+
+def _check_beams(num_beams, length_penalty, num_return_sequences, B: int, vocab_size: int, given: dict):
     """``generate``'s beam keywords as (W, length_penalty, num_return_sequences), or the ValueError naming the one that is
-    wrong; ``others``: the sampler's keywords by name, each (value, neutral value)."""
+    wrong. Of ``given``, ``generate``'s arguments by name, all but ``WITH_BEAMS`` must be neutral (``Sampler()``'s value)."""
     W = int(num_beams)
     if not 1 <= W <= K.LOGPROBS_MAX_TOP:
         raise ValueError(f"num_beams must lie in [1, {K.LOGPROBS_MAX_TOP}] (got {num_beams})")
@@ -516,8 +522,10 @@ def _check_beams(num_beams, length_penalty, num_return_sequences, B: int, vocab_
     lp = float(length_penalty)
     if not abs(lp) < float("inf"):  # (NaN too)
         raise ValueError(f"length_penalty must be finite (got {length_penalty})")
-    for name, (value, neutral) in others.items():
-        if value is not None and value != neutral:
+    neutral = Sampler()
+    for name, p in inspect.signature(generate).parameters.items():
+        value = "given" if name in ("logit_bias", "allowed_token_ids") and given[name] is not None else given[name]
+        if name not in WITH_BEAMS and value is not None and value != p.default and value != getattr(neutral, name, p.default):
             raise ValueError(f"{name} does not go with num_beams: beam search is deterministic and ranks the model's own "
                              f"distribution (got {name}={value!r})")
     return W, lp, r
@@ -567,54 +575,127 @@ def kv_dequantize(codes: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return codes.view(torch.float8_e4m3fn).float() * scale[..., None]
 
 
-def _penalty_keywords(penalties, gen_start) -> dict:
-    """``DecodeSession.generate`` / ``speculate``'s penalty keywords from ``_check_penalties``' tuple (``{}`` when the
-    values are neutral), the rows' generated parts starting at ``gen_start``."""
-    rp, pp, fp, on = penalties
-    return dict(repetition_penalty=rp, presence_penalty=pp, frequency_penalty=fp, gen_start=list(gen_start)) if on else {}
+def _check_token(name: str, token: int, vocab_size: int) -> None:
+    if not 0 <= int(token) < vocab_size:
+        raise ValueError(f"{name} {token} not in [0, vocab_size={vocab_size})")
 
 
-def _constraint_set(logit_bias, allowed_token_ids, min_p, min_new_tokens, stop, eos_token_id, V: int, B: int, dev,
-                    per_row: bool = True) -> Optional[dict]:
-    """``generate`` / ``generate_many``'s constraint keywords as ``DecodeSession.generate``'s (without ``gen_start``), or
-    None when nothing is on. ``logit_bias`` is a ``{token: value}`` dict, a [V] tensor or (``per_row``) a [B, V] tensor;
-    ``allowed_token_ids`` adds -inf everywhere else. A dict, a [V] tensor and the allowed list make one device row every
-    row reads (``bias_row`` all 0); a [B, V] tensor gives row b its own."""
-    mp, mn, stops = _check_constraints(logit_bias, min_p, min_new_tokens, stop, eos_token_id, V)
-    bias = None
-    if isinstance(logit_bias, dict):
-        bias = torch.zeros(1, V, dtype=F32)
-        for t, v in logit_bias.items():
-            bias[0, int(t)] = float(v)
-    elif logit_bias is not None:
-        if logit_bias.dim() not in (1, 2) or (logit_bias.dim() == 2 and (not per_row or logit_bias.size(0) != B)):
-            raise ValueError(f"logit_bias must be a dict, a [V={V}] tensor{f' or a [B={B}, V] tensor' if per_row else ''} "
-                             f"(got {tuple(logit_bias.shape)})")
-        bias = logit_bias.detach().float().reshape(-1, V).clone()
-    if allowed_token_ids is not None:
-        allowed = [int(t) for t in allowed_token_ids]
-        if not allowed or not all(0 <= t < V for t in allowed):
-            raise ValueError(f"allowed_token_ids must be a non-empty list of tokens in [0, vocab_size={V}) (got {allowed})")
-        mask = torch.full((1, V), float("-inf"), dtype=F32)
-        mask[0, allowed] = 0.0
-        bias = mask if bias is None else bias + mask.to(bias.device)
-    if bias is None and not (mp > 0 or mn > 0 or stops):
-        return None
-    out = dict(min_p=mp, min_new_tokens=mn, stop=stops)
-    if bias is not None:
-        out.update(logit_bias=bias.to(dev).contiguous(), bias_row=list(range(B)) if bias.size(0) > 1 else [0] * B)
-    return out
+@dataclass(frozen=True, eq=False)
+class Sampler:
+    """What decides a draw: the checked values (``of`` checks) that make a token a function of (logits, this record,
+    draw key, position). The defaults are neutral; ``seed`` None is the host sampler (``sample_next`` from a
+    ``torch.Generator``), ``logit_bias`` a device fp32 [rows, V] tensor read by row ``bias_row[b]`` (None: row b; -1:
+    none). What belongs to one call is not here and stays an argument: ``gen_start``, ``row_id``, the history / ``seq``
+    buffer, ``done`` and the ``LogprobBuffer`` (an output, not a rule)."""
+    temperature: float = 1.0
+    top_k: Optional[int] = None
+    top_p: Optional[float] = None
+    seed: Optional[int] = None
+    eos_token_id: Optional[int] = None
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    min_p: float = 0.0
+    min_new_tokens: int = 0
+    stop: List[List[int]] = field(default_factory=list)
+    logit_bias: Optional[torch.Tensor] = None
+    bias_row: Optional[List[int]] = None
 
+    @classmethod
+    def of(cls, temperature=1.0, top_k=None, top_p=None, seed=None, eos_token_id=None, repetition_penalty=1.0,
+           presence_penalty=0.0, frequency_penalty=0.0, min_p=None, min_new_tokens=0, stop=None, logit_bias=None,
+           bias_row=None, *, vocab_size: Optional[int] = None, allowed_token_ids=None, rows: Optional[int] = None,
+           device=None, per_row: bool = True) -> "Sampler":
+        """The record of these values, or the ValueError naming the one that is wrong; ``vocab_size`` bounds the stop and
+        bias tokens. A session passes ``logit_bias`` / ``bias_row`` as its C entries read them; that tensor lies on the
+        device, and its values are read back and checked where it is bound (``DecodeSession._bind``), after the host-side
+        checks, which then run beside the previous launch. ``generate`` / ``generate_many`` pass ``rows``, the number of
+        prompts: ``logit_bias`` is then a ``{token: value}`` dict, a [V] tensor or (``per_row``) a [rows, V] tensor, and
+        ``allowed_token_ids`` adds -inf everywhere else: one row on ``device`` that every prompt reads (``bias_row`` all
+        0), or with a [rows, V] tensor prompt b's own. With a ``seed`` that form also checks ``eos_token_id``'s range."""
+        if temperature < 0:
+            raise ValueError(f"temperature must be >= 0 (got {temperature})")
+        _check_top_p(top_p)
+        if seed is not None and not isinstance(seed, int):
+            raise ValueError(f"seed must be an int (got {seed!r})")
+        rp, pp, fp, _ = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
+        mp, mn, stops = _check_constraints(logit_bias if rows is not None or isinstance(logit_bias, dict) else None, min_p,
+                                           min_new_tokens, stop, eos_token_id, vocab_size)
+        if rows is not None:
+            V = vocab_size
+            if seed is not None and eos_token_id is not None:
+                _check_token("eos_token_id", eos_token_id, V)
+            bias = None
+            if isinstance(logit_bias, dict):
+                bias = torch.zeros(1, V, dtype=F32)
+                for t, v in logit_bias.items():
+                    bias[0, int(t)] = float(v)
+            elif logit_bias is not None:
+                if logit_bias.dim() not in (1, 2) or (logit_bias.dim() == 2 and (not per_row or logit_bias.size(0) != rows)):
+                    raise ValueError(f"logit_bias must be a dict, a [V={V}] tensor"
+                                     f"{f' or a [B={rows}, V] tensor' if per_row else ''} (got {tuple(logit_bias.shape)})")
+                bias = logit_bias.detach().float().reshape(-1, V).clone()
+            if allowed_token_ids is not None:
+                allowed = [int(t) for t in allowed_token_ids]
+                if not allowed or not all(0 <= t < V for t in allowed):
+                    raise ValueError(f"allowed_token_ids must be a non-empty list of tokens in [0, vocab_size={V}) (got "
+                                     f"{allowed})")
+                mask = torch.full((1, V), float("-inf"), dtype=F32)
+                mask[0, allowed] = 0.0
+                bias = mask if bias is None else bias + mask.to(bias.device)
+            logit_bias = bias
+            if bias is not None:
+                logit_bias, bias_row = bias.to(device).contiguous(), range(rows) if bias.size(0) > 1 else [0] * rows
+        return cls(temperature, top_k, top_p, seed, eos_token_id, rp, pp, fp, mp, mn, stops, logit_bias,
+                   None if bias_row is None else [int(r) for r in bias_row])
 
-def _constraint_keywords(cons: Optional[dict], gen_start, rows=None) -> dict:
-    """``DecodeSession.generate`` / ``speculate``'s constraint keywords from ``_constraint_set``'s result (``{}`` for
-    None), the rows' generated parts starting at ``gen_start``; ``rows``: the bias row of each session row instead."""
-    if cons is None:
-        return {}
-    out = dict(cons, gen_start=list(gen_start))
-    if rows is not None and "bias_row" in out:
-        out["bias_row"] = list(rows)
-    return out
+    @property
+    def penalised(self) -> bool:
+        return (self.repetition_penalty, self.presence_penalty, self.frequency_penalty) != (1.0, 0.0, 0.0)
+
+    @property
+    def constrained(self) -> bool:
+        return bool(self.min_p > 0 or self.min_new_tokens > 0 or self.stop or (
+            self.logit_bias is not None and (self.bias_row is None or any(r >= 0 for r in self.bias_row))))
+
+    def blocks(self, gen_start: List[int], bias_row: Optional[List[int]] = None, seqs: Optional[List[int]] = None,
+               hist: Optional[torch.Tensor] = None):
+        """The sampler bindings' two keyword blocks (penalties, constraints), ``{}`` for a neutral one; ``gen_start`` and
+        ``bias_row`` one per row of the call. With
+        ``seqs`` the call is a verify call whose row r is a position of sequence ``seqs[r]`` and the two tables are the
+        sequences': row r reads its sequence's entries, and its history is row ``seqs[r]`` of ``hist``. The bias, min-p
+        and the minimum length are functions of (row, position) and stay; the stop sequences are left out,
+        ``speculate_loop`` matches them in the tokens it reads back."""
+        pen = con = {}
+        pick = (lambda t: t) if seqs is None else (lambda t: t and [t[b] for b in seqs])  # a table, by sequence
+        if self.penalised:
+            pen = dict(repetition=self.repetition_penalty, presence=self.presence_penalty,
+                       frequency=self.frequency_penalty, gen_start=pick(gen_start))
+            if seqs is not None:
+                pen.update(hist=hist, hist_row=list(seqs))
+        if self.constrained:
+            bias = {} if self.logit_bias is None else dict(logit_bias=self.logit_bias, bias_row=pick(bias_row))
+            con = dict(bias, min_p=self.min_p, min_new_tokens=self.min_new_tokens,
+                       stop=self.stop if seqs is None else [], gen_start=pick(gen_start))
+        return pen, con
+
+    def keywords(self, gen_start) -> dict:
+        """``DecodeSession.generate`` / ``speculate``'s keywords after ``eos_token_id``, the rows' generated parts starting
+        at ``gen_start``: ``blocks`` under the session's names, so a neutral family is left out, ``gen_start`` with both."""
+        pen, con = self.blocks(list(gen_start), self.bias_row)
+        return {**{k + "_penalty" * (k != "gen_start"): v for k, v in pen.items()}, **con}
+
+    def write_verify_history(self, seq: torch.Tensor, tok_t: torch.Tensor, seqs: List[int], poss: List[int],
+                             gen_start: List[int]) -> dict:
+        """The penalty block of a verify call, after writing the history it reads (``{}`` and nothing written without
+        penalties): row r draws at ``poss[r] + 1`` from the tokens of sequence ``seqs[r]`` up to and including its own,
+        ``tok_t[r]``, which one index write puts at ``seq[seqs[r], poss[r]]`` (a rejected draft stays above ``lens``,
+        where nothing reads it before it is overwritten). That is the history the one-token loop has at that position,
+        so the draws stay those of the loop. Returns ``blocks``' first, over ``hist = seq`` and ``hist_row = seqs``."""
+        if not self.penalised:
+            return {}
+        seq.index_put_((torch.tensor(seqs, device=seq.device), torch.tensor(poss, device=seq.device)), tok_t)
+        return self.blocks(gen_start, None, seqs, seq)[0]
 
 
 def _check_lens(lens, B: int, P: int) -> List[int]:
@@ -710,6 +791,17 @@ def _entry(pen: dict, lp: Optional[dict], con: Optional[dict]) -> str:
     return "constrained" if con else "logprobs" if lp is not None else "penalized" if pen else "ragged"
 
 
+class _Call(NamedTuple):
+    """A ``Sampler`` bound to a session for one call (``DecodeSession._bind``): the record, the bindings' keyword blocks
+    ``pen`` / ``con`` (over the checked ``gen_start`` and bias rows) / ``ends``, the draw keys and the history buffer."""
+    sampler: Sampler
+    pen: dict
+    con: dict
+    ends: dict
+    row_id: Optional[List[int]]
+    hist: Optional[torch.Tensor]
+
+
 class DecodeSession:
     """The key/value cache of ``batch_size`` sequences of up to ``max_len`` tokens, and the step that extends them.
 
@@ -761,6 +853,7 @@ class DecodeSession:
         self._refill_ws = None            # (Tp, engine.Workspace) of the last refill's one-sequence prefill
         self._plan = self._build_plan({n: getattr(self, n) for n in SCRATCH}, 0)
         self._rows = None                 # (scratch of MAX_BATCH rows, its plan): extend / speculate, on first use
+        self._last = None                 # (the sampling keywords of the last call, their Sampler): _record
         self._beam_ws = None              # beam_search's workspace (top-W, parents, the reorder's staging), on first use
         self.share = ShareGroups(self.B)
         self._share_arrays = ((ctypes.c_int * self.B)(), (ctypes.c_int * self.B)())  # what the plan points at
@@ -1023,19 +1116,6 @@ class DecodeSession:
         return self.logits[:, :self.cfg.vocab_size].clone()
 
     # ---- device-side sampling (gpt2mi_sample_ragged, gpt2mi_decode_generate_ragged): nothing below returns to the host ----
-    def _check_sampler(self, temperature, top_p, seed):
-        if min(self.lens) == 0:
-            raise RuntimeError("sampling before prefill: there are no logits")
-        if temperature < 0:
-            raise ValueError(f"temperature must be >= 0 (got {temperature})")
-        _check_top_p(top_p)
-        if not isinstance(seed, int):
-            raise ValueError(f"seed must be an int (got {seed!r})")
-        if self.cfg.vocab_size > K.SAMPLE_MAX_V:
-            raise NotImplementedError(f"the sampling kernel holds rows of up to {K.SAMPLE_MAX_V} logits "
-                                      f"(vocab_size {self.cfg.vocab_size})")
-        self._ready(False)
-
     def _check_history(self, hist, name: str, reader: str, last: Optional[int] = None):
         """``hist`` (argument ``name``) as the history buffer of what ``reader`` names; with ``last``, reaching it."""
         if hist is None:
@@ -1046,91 +1126,109 @@ class DecodeSession:
             shape = f"[B={self.B}, T]" if last is None else f"[B={self.B}, >= {last}]"
             raise ValueError(f"{name} must be a device int64 {shape} with contiguous rows")
 
-    def _gen_start(self, gen_start) -> List[int]:
-        start = [0] * self.B if gen_start is None else [int(g) for g in gen_start]
+    def _record(self, *values) -> Sampler:
+        """``Sampler.of`` of a call's sampling keywords. A token loop passes the same values call after call: the last record
+        is returned while they compare equal; none with a stop table or a bias, which a caller can change in place."""
+        fixed = not values[10] and values[11] is None and values[12] is None
+        if fixed and self._last is not None and self._last[0] == values:
+            return self._last[1]
+        s = Sampler.of(*values, vocab_size=self.cfg.vocab_size)
+        self._last = (values, s) if fixed else None
+        return s
+
+    def _check_start(self, start: List[int]) -> None:
         if len(start) != self.B or not all(0 <= g <= m for g, m in zip(start, self.lens)):
             raise ValueError(f"gen_start {start} must be B={self.B} ints in [0, lens={self.lens}]")
-        return start
 
-    def _penalties(self, repetition_penalty, presence_penalty, frequency_penalty, gen_start, hist, name: str, last: int):
-        """The penalty keywords of the C entries (``{}`` when the values are neutral): ``hist`` is the history buffer
-        (argument ``name``), ``last`` the largest position a draw of the call reads its history up to."""
-        rp, pp, fp, on = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-        if not on:
-            return {}
-        self._check_history(hist, name, "penalties read")
-        if last > K.PENALTY_MAX_HISTORY:
-            raise NotImplementedError(f"the penalised sampler reads a history of up to {K.PENALTY_MAX_HISTORY} tokens "
-                                      f"(GPT2MI_PENALTY_MAX_HISTORY); this call reaches position {last}")
-        if hist.size(1) < last:
-            raise ValueError(f"{name} holds {hist.size(1)} positions, the call reads up to {last}")
-        start = self._gen_start(gen_start)
-        return dict(repetition=rp, presence=pp, frequency=fp, gen_start=start)
-
-    def _constraints(self, logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, hist, name: str,
-                     last: int, done=None) -> dict:
-        """The constraint keywords of the C entries (``{}`` when nothing is on): ``logit_bias`` a device fp32
-        [rows, V] tensor read by row ``bias_row[b]`` (None: b; -1: none), ``hist`` the history buffer (argument
-        ``name``) the stop sequences are matched in, ``last`` the largest position a draw of the call reaches."""
-        mp, mn, stops = _check_constraints(logit_bias, min_p, min_new_tokens, stop, eos_token_id, self.cfg.vocab_size)
-        rows = None
-        if logit_bias is not None:
-            if (not isinstance(logit_bias, torch.Tensor) or logit_bias.dtype != F32 or logit_bias.dim() != 2
-                    or logit_bias.stride(1) != 1 or not logit_bias.is_cuda):
-                raise ValueError(f"logit_bias must be a device fp32 [rows, V={self.cfg.vocab_size}] tensor with contiguous rows")
-            rows = list(range(self.B)) if bias_row is None else [int(r) for r in bias_row]
-            if len(rows) != self.B or not all(-1 <= r < logit_bias.size(0) for r in rows):
-                raise ValueError(f"bias_row {rows} must be B={self.B} ints in [-1, {logit_bias.size(0)}) (None: row b reads "
+    def _bind(self, s: Sampler, n: Optional[int], hist, row_id, gen_start, done, logprobs=None) -> "_Call":
+        """A record bound to this session for one call: ``sample`` (``n`` None: one draw at ``lens``, ``hist`` its
+        ``history``) or a run of ``n`` tokens (``generate`` / ``speculate``, ``hist`` their ``seq``; the token the previous
+        call ended on is flushed). Every check that needs the session, in the order they always had, then ``_Call``."""
+        V, name = self.cfg.vocab_size, "history" if n is None else "seq"
+        if min(self.lens) == 0:
+            raise RuntimeError("sampling before prefill: there are no logits")
+        if s.seed is None:
+            raise ValueError(f"seed must be an int (got {s.seed!r})")
+        if V > K.SAMPLE_MAX_V:
+            raise NotImplementedError(f"the sampling kernel holds rows of up to {K.SAMPLE_MAX_V} logits (vocab_size {V})")
+        self._ready(False)
+        row_id = _check_row_id(row_id, self.B)
+        pen_on, con_on = s.penalised, s.constrained
+        start = [0] * self.B if gen_start is None else [int(g) for g in gen_start]
+        if n is None:
+            if self._drawn:
+                raise RuntimeError("the logits are those generate() drew its last token from: step() that token first")
+            last = max(self.lens) if pen_on or s.stop else None  # (the position the history is read up to)
+        else:
+            reach = max(self.lens) + int(self._drawn) + n
+            if reach > self.Tcap:
+                raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
+            if hist is not None and (hist.dtype != torch.int64 or hist.dim() != 2 or hist.size(0) != self.B
+                                     or hist.stride(1) != 1):
+                raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
+            if s.eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
+                raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
+            last = reach - 1
+        if pen_on:
+            self._check_history(hist, name, "penalties read")
+            if last > K.PENALTY_MAX_HISTORY:
+                raise NotImplementedError(f"the penalised sampler reads a history of up to {K.PENALTY_MAX_HISTORY} tokens "
+                                          f"(GPT2MI_PENALTY_MAX_HISTORY); this call reaches position {last}")
+            if hist.size(1) < last:
+                raise ValueError(f"{name} holds {hist.size(1)} positions, the call reads up to {last}")
+            self._check_start(start)
+        if logprobs is not None and (not isinstance(logprobs, LogprobBuffer) or logprobs.B != self.B
+                                     or logprobs.T < last + 1):
+            raise ValueError(f"logprobs must be a LogprobBuffer of B={self.B} rows and at least {last + 1} columns")
+        if n is not None:
+            self.flush()  # the token the previous call ended on: what follows sees lens with it, as before
+        bias, rows = s.logit_bias, None
+        if bias is not None:
+            _check_constraints(bias, vocab_size=V)  # (reads the device back: after the host-side checks above)
+            if (not isinstance(bias, torch.Tensor) or bias.dtype != F32 or bias.dim() != 2 or bias.stride(1) != 1
+                    or not bias.is_cuda):
+                raise ValueError(f"logit_bias must be a device fp32 [rows, V={V}] tensor with contiguous rows")
+            rows = list(range(self.B)) if s.bias_row is None else s.bias_row
+            if len(rows) != self.B or not all(-1 <= r < bias.size(0) for r in rows):
+                raise ValueError(f"bias_row {rows} must be B={self.B} ints in [-1, {bias.size(0)}) (None: row b reads "
                                  f"bias row b)")
-        elif bias_row is not None:
+        elif s.bias_row is not None:
             raise ValueError("bias_row goes with logit_bias")
-        if not (mp > 0 or mn > 0 or stops or (rows is not None and any(r >= 0 for r in rows))):
-            return {}
-        if stops:
+        if con_on and s.stop:
             self._check_history(hist, name, "stop sequences are matched in", last)
             if done is None:
                 raise ValueError(f"stop sequences need done, uint8 [B={self.B}]")
-        start = self._gen_start(gen_start)
-        bias = {} if rows is None else dict(logit_bias=logit_bias, bias_row=rows)
-        return dict(bias, min_p=mp, min_new_tokens=mn, stop=stops, gen_start=start)
+        if con_on and not pen_on:  # (with penalties it was checked against the shorter lens before the flush)
+            self._check_start(start)
+        pen, con = s.blocks(start, rows) if pen_on or con_on else ({}, {})
+        ends = {} if s.eos_token_id is None else dict(eos=s.eos_token_id, done=done)
+        return _Call(s, pen, con, ends, row_id, hist)
 
-    def _draw(self, logits, pos, out, temperature, top_k, top_p, seed, pen: dict, hist=None, lp: Optional[dict] = None,
-              con: Optional[dict] = None, **kw) -> None:
-        """One token per row of ``logits`` at ``pos`` into ``out``: gpt2mi_sample_ragged, or with ``pen`` (``_penalties``'
-        keywords, not empty) gpt2mi_sample_penalized over the history ``hist``. ``kw``: row_id, eos, done. With ``lp``
-        (logprob, top_ids, top_logprobs and optionally col) gpt2mi_sample_logprobs: the same draw and its values. With
-        ``con`` (``_constraints``' keywords, not empty) gpt2mi_sample_constrained, beside whatever of the others."""
-        history = {"hist": hist} if pen or con else {}
-        getattr(K, "sample_" + _entry(pen, lp, con))(
-            logits, self.cfg.vocab_size, temperature, top_k, top_p, seed, pos, out,
-            **{**kw, **(lp or {}), **history, **pen, **(con or {})})
+    def _draw(self, logits, pos, out, call: "_Call", lp: Optional[dict] = None) -> None:
+        """One token per row of ``logits`` at ``pos`` into ``out``: gpt2mi_sample_ragged, or with ``call.pen`` (not
+        empty) gpt2mi_sample_penalized over the history ``call.hist``. With ``lp`` (logprob, top_ids, top_logprobs,
+        optionally col) gpt2mi_sample_logprobs: the draw and its values. With ``call.con`` gpt2mi_sample_constrained."""
+        s, history = call.sampler, {"hist": call.hist} if call.pen or call.con else {}
+        getattr(K, "sample_" + _entry(call.pen, lp, call.con))(
+            logits, self.cfg.vocab_size, s.temperature, s.top_k, s.top_p, s.seed, pos, out,
+            **{"row_id": call.row_id, **call.ends, **(lp or {}), **history, **call.pen, **call.con})
 
-    def _loop(self, n: int, temperature, top_k, top_p, seed, pen: dict, lp: Optional[dict] = None,
-              con: Optional[dict] = None, **kw) -> None:
-        """``n`` sample-then-step rounds from ``lens`` into ``_tok``: gpt2mi_decode_generate_ragged, or with ``pen``
-        gpt2mi_decode_generate_penalized, or with ``lp`` (a LogprobBuffer's tensors) gpt2mi_decode_generate_logprobs, or
-        with ``con`` gpt2mi_decode_generate_constrained. ``kw``: row_id, eos, seq, done."""
-        getattr(K, "decode_generate_" + _entry(pen, lp, con))(
-            self._plan, self.cfg.vocab_size, temperature, top_k, top_p, seed, self.lens, n, self._tok,
-            **{**kw, **(lp or {}), **pen, **(con or {})})
+    def _draw_new(self, logits, pos, call: "_Call", top_n: Optional[int]):
+        """``_draw`` into a new tensor [R]: (the tokens, None), or with ``top_n`` (the tokens, their values (logprob [R],
+        top_ids [R, n], top_logprobs [R, n])) from buffers of R rows and one column (col 0, ld 1)."""
+        R = logits.size(0)
+        out = torch.empty(R, dtype=torch.int64, device=self.device)
+        buf = None if top_n is None else LogprobBuffer(R, 1, top_n, self.device)
+        self._draw(logits, pos, out, call, None if buf is None else dict(buf.tensors(), col=[0] * R))
+        return out, None if buf is None else (buf.logprob[:, 0], buf.top_ids[:, 0], buf.top_logprobs[:, 0])
 
-    def _check_run(self, n: int, row_id, eos_token_id, seq, done, penalties, gen_start, logprobs=None):
-        """The argument checks ``generate`` and ``speculate`` share, then ``flush``; (row_id, done, pen) as checked:
-        ``done`` is None without eos, ``pen`` is ``_penalties``' keywords over ``seq``."""
-        row_id = _check_row_id(row_id, self.B)
-        if max(self.lens) + int(self._drawn) + n > self.Tcap:
-            raise ValueError(f"{n} more tokens do not fit the cache ({self.Tcap} positions): reset() or a larger max_len")
-        if seq is not None and (seq.dtype != torch.int64 or seq.dim() != 2 or seq.size(0) != self.B or seq.stride(1) != 1):
-            raise ValueError(f"seq must be int64 [B={self.B}, T] with contiguous rows")
-        if eos_token_id is not None and (done is None or done.dtype != torch.uint8 or done.shape != (self.B,)):
-            raise ValueError(f"eos_token_id needs done, uint8 [B={self.B}]")
-        pen = self._penalties(*penalties, gen_start, seq, "seq", max(self.lens) + int(self._drawn) + n - 1)
-        if logprobs is not None and (not isinstance(logprobs, LogprobBuffer) or logprobs.B != self.B
-                                     or logprobs.T < max(self.lens) + int(self._drawn) + n):
-            raise ValueError(f"logprobs must be a LogprobBuffer of B={self.B} rows and at least "
-                             f"{max(self.lens) + int(self._drawn) + n} columns")
-        self.flush()  # the token the previous call ended on
-        return row_id, done if eos_token_id is not None else None, pen
+    def _loop(self, n: int, call: "_Call", lp: Optional[dict] = None) -> None:
+        """``n`` sample-then-step rounds from ``lens`` into ``_tok``: gpt2mi_decode_generate_ragged, or its penalized form
+        with ``call.pen``, logprobs form with ``lp`` (a LogprobBuffer's tensors), constrained form with ``call.con``."""
+        s = call.sampler
+        getattr(K, "decode_generate_" + _entry(call.pen, lp, call.con))(
+            self._plan, self.cfg.vocab_size, s.temperature, s.top_k, s.top_p, s.seed, self.lens, n, self._tok,
+            **{"row_id": call.row_id, "seq": call.hist, **call.ends, **(lp or {}), **call.pen, **call.con})
 
     @torch.no_grad()
     def sample(self, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
@@ -1160,23 +1258,11 @@ class DecodeSession:
         fraction as likely as the most likely one; ``stop`` (up to 8 lists of up to 16 tokens) sets ``done[b]`` (uint8
         [B]) when the drawn token completes one of them inside ``history[b, gen_start[b]:]``. With ``eos_token_id`` and
         ``done`` a row whose flag is set draws eos, and one that draws eos gets it set."""
-        self._check_sampler(temperature, top_p, seed)
-        if self._drawn:
-            raise RuntimeError("the logits are those generate() drew its last token from: step() that token first")
-        pen = self._penalties(repetition_penalty, presence_penalty, frequency_penalty, gen_start, history, "history",
-                              max(self.lens))
-        con = self._constraints(logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, history,
-                                "history", max(self.lens), done)
-        ends = {} if eos_token_id is None else dict(eos=eos_token_id, done=done)
-        out = torch.empty(self.B, dtype=torch.int64, device=self.logits.device)
-        if logprobs is None:
-            self._draw(self.logits, self.lens, out, temperature, top_k, top_p, seed, pen, history, con=con,
-                       row_id=_check_row_id(row_id, self.B), **ends)
-            return out
-        buf = LogprobBuffer(self.B, 1, logprobs, self.logits.device)
-        self._draw(self.logits, self.lens, out, temperature, top_k, top_p, seed, pen, history,
-                   dict(buf.tensors(), col=[0] * self.B), con, row_id=_check_row_id(row_id, self.B), **ends)
-        return out, buf.logprob[:, 0], buf.top_ids[:, 0], buf.top_logprobs[:, 0]
+        s = self._record(temperature, top_k, top_p, seed, eos_token_id, repetition_penalty, presence_penalty,
+                         frequency_penalty, min_p, min_new_tokens, stop, logit_bias, bias_row)
+        call = self._bind(s, None, history, row_id, gen_start, done)
+        out, values = self._draw_new(self.logits, self.lens, call, logprobs)
+        return out if values is None else (out, *values)
 
     @torch.no_grad()
     def generate(self, n: int, temperature: float = 1.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
@@ -1205,17 +1291,13 @@ class DecodeSession:
         (gpt2mi_decode_generate_constrained): ``seq`` is the history the stop sequences are matched in (required with
         them, as ``eos_token_id`` and ``done`` are), ``gen_start[b]`` where the row's generated part begins; a row that
         completes a stop sequence keeps its tokens and emits eos from the next position on."""
-        self._check_sampler(temperature, top_p, seed)
+        s = self._record(temperature, top_k, top_p, seed, eos_token_id, repetition_penalty, presence_penalty,
+                         frequency_penalty, min_p, min_new_tokens, stop, logit_bias, bias_row)
         n = int(n)
         if n < 1:
             raise ValueError(f"generate takes n >= 1 (got {n})")
-        row_id, done, pen = self._check_run(n, row_id, eos_token_id, seq, done,
-                                            (repetition_penalty, presence_penalty, frequency_penalty), gen_start,
-                                            logprobs)
-        con = self._constraints(logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, seq, "seq",
-                                max(self.lens) + n - 1, done)
-        self._loop(n, temperature, top_k, top_p, seed, pen, None if logprobs is None else logprobs.tensors(), con,
-                   row_id=row_id, eos=eos_token_id, seq=seq, done=done)
+        call = self._bind(s, n, seq, row_id, gen_start, done, logprobs)
+        self._loop(n, call, None if logprobs is None else logprobs.tensors())
         self.lens = [m + n - 1 for m in self.lens]
         self._drawn = True
         return self._tok
@@ -1339,15 +1421,13 @@ class DecodeSession:
         self.logits.index_copy_(0, torch.tensor(dst, device=self.device),
                                 rows.index_select(0, torch.tensor(src, device=self.device)))
 
-    def _verify(self, toks: List[int], seqs: List[int], poss: List[int], keys: List[int], sampler,
+    def _verify(self, toks: List[int], seqs: List[int], poss: List[int], keys: List[int], call: _Call,
                 logprobs: Optional[int] = None):
         """One ``gpt2mi_decode_extend`` over the rows (token, sequence, position) and one ``gpt2mi_sample_ragged`` over
         their logits, row r at position ``poss[r] + 1`` with draw key ``keys[r]``; the R tokens, read back.
 
-        ``sampler`` is (temperature, top_k, top_p, seed) or, penalised, those and (the penalty keywords, seq): see
-        ``verify_history``; constrained, also (the constraint keywords, eos): see ``verify_constraints``. With ``logprobs=n`` the draw is gpt2mi_sample_logprobs into buffers of R rows and one
-        column (col 0, ld 1) and the result is (the tokens, (logprob [R], top_ids [R, n], top_logprobs [R, n])), the
-        values left on the device."""
+        ``call`` is the run's bound call, whose per-row tables the record re-indexes by ``seqs`` (``Sampler.blocks``). With
+        ``logprobs=n`` the draw is gpt2mi_sample_logprobs and the result (the tokens, their values left on the device)."""
         V = self.cfg.vocab_size
         if not all(0 <= t < V for t in toks):
             raise ValueError(f"draft tokens must lie in [0, vocab_size={V}) (got {toks})")
@@ -1355,18 +1435,12 @@ class DecodeSession:
         R = len(toks)
         tok_t = torch.tensor(toks, dtype=torch.int64, device=self.device)
         K.decode_extend(plan, tok_t, seqs, poss)
-        out = torch.empty(R, dtype=torch.int64, device=self.device)
-        temperature, top_k, top_p, seed = sampler[:4]
-        con, ends = verify_constraints(sampler, seqs)
-        if logprobs is None:
-            self._draw(scratch["logits"][:R], [p + 1 for p in poss], out, temperature, top_k, top_p, seed,
-                       verify_history(sampler, tok_t, seqs, poss), con=con, row_id=keys, **ends)
-            return out.tolist()
-        buf = LogprobBuffer(R, 1, logprobs, self.device)
-        self._draw(scratch["logits"][:R], [p + 1 for p in poss], out, temperature, top_k, top_p, seed,
-                   verify_history(sampler, tok_t, seqs, poss), lp=dict(buf.tensors(), col=[0] * R), con=con, row_id=keys,
-                   **ends)
-        return out.tolist(), (buf.logprob[:, 0], buf.top_ids[:, 0], buf.top_logprobs[:, 0])
+        s, start = call.sampler, (call.pen or call.con).get("gen_start")
+        pen = s.write_verify_history(call.hist, tok_t, seqs, poss, start)
+        con = s.blocks(start, call.con.get("bias_row"), seqs)[1]
+        rows = call._replace(pen=pen, con=con, ends={"eos": s.eos_token_id} if con else {}, row_id=keys, hist=None)
+        out, values = self._draw_new(scratch["logits"][:R], [p + 1 for p in poss], rows, logprobs)
+        return out.tolist() if values is None else (out.tolist(), values)
 
     @torch.no_grad()
     def speculate(self, n: int, k: int, draft_fn=None, temperature: float = 1.0, top_k: Optional[int] = None,
@@ -1414,32 +1488,24 @@ class DecodeSession:
             raise ValueError(f"speculate takes n >= 1 and k >= 0 (got n={n}, k={k})")
         if self.B * (k + 1) > MAX_BATCH:
             raise ValueError(f"B={self.B} rows of {k} drafts + 1 exceed the {MAX_BATCH} rows of a call")
-        self._check_sampler(temperature, top_p, seed)
-        row_id, done, pen = self._check_run(n, row_id, eos_token_id, seq, done,
-                                            (repetition_penalty, presence_penalty, frequency_penalty), gen_start,
-                                            logprobs)
-        con = self._constraints(logit_bias, bias_row, min_p, min_new_tokens, stop, eos_token_id, gen_start, seq, "seq",
-                                max(self.lens) + n - 1, done)
+        s = self._record(temperature, top_k, top_p, seed, eos_token_id, repetition_penalty, presence_penalty,
+                         frequency_penalty, min_p, min_new_tokens, stop, logit_bias, bias_row)
+        call = self._bind(s, n, seq, row_id, gen_start, done, logprobs)
         lens0 = list(self.lens)
         if logprobs is not None:  # the call's columns: what no accepted row writes (after a row's eos) is 0
             at = torch.arange(logprobs.T, device=self.device)[None] - torch.tensor(lens0, device=self.device)[:, None]
             keep = (at < 0) | (at >= n)
             for t in (logprobs.logprob, logprobs.top_ids, logprobs.top_logprobs):
                 t.masked_fill_(~keep if t.dim() == 2 else ~keep[..., None], 0)
-        self._draw(self.logits, self.lens, self._tok, temperature, top_k, top_p, seed, pen, seq,
-                   None if logprobs is None else logprobs.tensors(), con, row_id=row_id, eos=eos_token_id, done=done)
+        self._draw(self.logits, self.lens, self._tok, call, None if logprobs is None else logprobs.tensors())
         first = self._tok.tolist()
         history = [[] for _ in range(self.B)] if seq is None else [r[:m] for r, m in zip(seq.tolist(), lens0)]
-        keys = list(range(self.B)) if row_id is None else row_id
-        sampler = (temperature, top_k, top_p, seed) + (((pen, seq),) if pen or con else ())
+        keys = list(range(self.B)) if call.row_id is None else call.row_id
         more = {} if logprobs is None else {"logprobs": logprobs}
         stopped = [False] * self.B
-        if con:
-            sampler += ((con, eos_token_id),)
-            if con["stop"]:
-                more.update(stop=(con["stop"], con["gen_start"], con["min_new_tokens"]), stopped=stopped)
-        new, stats = speculate_loop(self, n, k, draft_fn or ngram_draft, eos_token_id, history, first, keys, sampler,
-                                    **more)
+        if s.constrained and s.stop:
+            more.update(stop=(s.stop, call.con["gen_start"], s.min_new_tokens), stopped=stopped)
+        new, stats = speculate_loop(self, n, k, draft_fn or ngram_draft, eos_token_id, history, first, keys, call, **more)
         self._tok.copy_(torch.tensor([t[-1] for t in new], dtype=torch.int64))
         self._drawn = True
         if eos_token_id is not None:
@@ -1450,34 +1516,6 @@ class DecodeSession:
             cols = torch.tensor(lens0, device=self.device)[:, None] + torch.arange(n, device=self.device)[None]
             seq.scatter_(1, cols, torch.tensor(new, dtype=torch.int64, device=self.device))
         return stats
-
-
-def verify_history(sampler, tok_t: torch.Tensor, seqs: List[int], poss: List[int]) -> dict:
-    """The history of a penalised verify call (``{}`` when ``sampler`` has no fifth entry): row r draws at
-    ``poss[r] + 1`` from the tokens of sequence ``seqs[r]`` up to and including its own, ``tok_t[r]``, which one index
-    write puts at ``seq[seqs[r], poss[r]]`` (a rejected draft stays above ``lens``, where nothing reads it before it is
-    overwritten). That is the history the one-token loop has at that position, so the draws stay those of the loop.
-    Returns gpt2mi_sample_penalized's keywords: the values, ``hist = seq``, ``hist_row = seqs`` and each row's
-    ``gen_start``, its sequence's."""
-    if len(sampler) < 5 or not sampler[4][0]:
-        return {}
-    pen, seq = sampler[4]
-    seq.index_put_((torch.tensor(seqs, device=seq.device), torch.tensor(poss, device=seq.device)), tok_t)
-    return dict(pen, hist=seq, hist_row=list(seqs), gen_start=[pen["gen_start"][b] for b in seqs])
-
-
-def verify_constraints(sampler, seqs: List[int]):
-    """The constraints of a verify call, as (``_draw``'s ``con``, its eos keyword); ``({}, {})`` when ``sampler`` has no
-    sixth entry, (the session's constraint keywords, eos). Row r is a position of sequence ``seqs[r]``: it reads that
-    sequence's bias row and ``gen_start``. The bias, min-p and the minimum length are functions of (row, position) and
-    stay; the stop sequences are left out, ``speculate_loop`` matches them in the tokens it reads back."""
-    if len(sampler) < 6:
-        return {}, {}
-    con, eos = sampler[5]
-    rows = dict(con, stop=[], gen_start=[con["gen_start"][b] for b in seqs])
-    if "bias_row" in con:
-        rows["bias_row"] = [con["bias_row"][b] for b in seqs]
-    return rows, {"eos": eos}
 
 
 def ngram_draft(history: List[int], k: int, max_ngram: int = 3) -> List[int]:
@@ -1574,6 +1612,54 @@ def _pad_prompts(prompts, pad: int):
     return idx, lens
 
 
+def _prompts(model, idx, max_new_tokens, prompt_lens, pad_token_id, eos_token_id, samples: int = 1, pad_always=False):
+    """``generate``'s prompts as ``(idx, lens, B, P, n, pad)``: ``idx`` int64 [B, P] (a list of 1-D prompts right-padded
+    with ``pad``: the pad token, else eos, else 0; checked with ``prompt_lens`` or ``pad_always``), ``lens`` the prompt
+    lengths (None: every row holds P tokens). With ``samples`` s > 1 row b * s + j is sample j of prompt b; B: the rows."""
+    pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
+    if isinstance(idx, (list, tuple)):
+        if prompt_lens is not None:
+            raise ValueError("a list of prompts carries its own lengths: prompt_lens goes with a padded idx [B, P]")
+        idx, prompt_lens = _pad_prompts(idx, pad)
+    if idx.dim() != 2:
+        raise ValueError(f"generate takes idx [B, P] (got {tuple(idx.shape)})")
+    B, P = idx.shape
+    if samples > 1:
+        if B * samples > MAX_BATCH:
+            raise ValueError(f"{B} prompts x num_samples={samples} = {B * samples} rows exceed the {MAX_BATCH} rows of a "
+                             f"decode session (MAX_BATCH)")
+        idx = idx.repeat_interleave(samples, dim=0)
+        if prompt_lens is not None:
+            prompt_lens = [int(m) for m in (prompt_lens.tolist() if isinstance(prompt_lens, torch.Tensor)
+                                            else prompt_lens) for _ in range(samples)]
+        B *= samples
+    n = int(max_new_tokens)
+    if n < 0:
+        raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
+    if prompt_lens is not None:
+        prompt_lens = _check_lens(prompt_lens, B, P)
+        P = max(prompt_lens)
+        idx = idx[:, :P]
+    if prompt_lens is not None or pad_always:
+        _check_token("pad_token_id", pad, model.config.vocab_size)
+    if P + n > model.config.n_positions:
+        raise ValueError(f"prompt length {P} + max_new_tokens {n} > n_positions {model.config.n_positions}")
+    return idx.long(), prompt_lens, B, P, n, pad
+
+
+def _chunks(n: int, eos_token_id, done, step) -> int:
+    """``step(m)`` until ``n`` tokens are issued; their number. Without eos one call and nothing read back; with eos
+    EOS_CHUNK at a time, ``done`` read once per chunk, until every row has emitted it (the caller cuts the result)."""
+    made = 0
+    while made < n:
+        m = n - made if eos_token_id is None else min(EOS_CHUNK, n - made)
+        step(m)
+        made += m
+        if eos_token_id is not None and bool(done.all()):
+            break
+    return made
+
+
 @torch.no_grad()
 def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: Optional[int] = None,
              generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
@@ -1584,59 +1670,24 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
              num_beams: Optional[int] = None, length_penalty: float = 1.0, num_return_sequences: int = 1,
              logit_bias=None, allowed_token_ids=None, min_p: Optional[float] = None, min_new_tokens: int = 0, stop=None):
     """``GPT2.generate``: see there."""
+    given = dict(locals())  # (the arguments by name: what the beam path refuses)
     check_kv_dtype(kv_dtype)
+    rules = (temperature, top_k, top_p, seed, eos_token_id, repetition_penalty, presence_penalty, frequency_penalty,
+             min_p, min_new_tokens, stop, logit_bias)
     if num_beams is not None:
         return _generate_beams(model, idx, max_new_tokens, num_beams, length_penalty, num_return_sequences, eos_token_id,
-                               prompt_lens, pad_token_id, kv_dtype,
-                               dict(seed=(seed, None), generator=(generator, None), temperature=(temperature, 1.0),
-                                    top_k=(top_k, None), top_p=(top_p, None), draft_tokens=(draft_tokens, None),
-                                    draft_fn=(draft_fn, None), repetition_penalty=(repetition_penalty, 1.0),
-                                    presence_penalty=(presence_penalty, 0.0), frequency_penalty=(frequency_penalty, 0.0),
-                                    num_samples=(num_samples, 1), logprobs=(logprobs, None),
-                                    logit_bias=(None if logit_bias is None else "given", None),
-                                    allowed_token_ids=(None if allowed_token_ids is None else "given", None),
-                                    min_p=(min_p or None, None), min_new_tokens=(min_new_tokens, 0),
-                                    stop=(stop or None, None)))
+                               prompt_lens, pad_token_id, kv_dtype, given)
     if length_penalty != 1.0 or num_return_sequences != 1:
         raise ValueError("length_penalty and num_return_sequences go with num_beams")
     top_n = _check_logprobs(logprobs)
     s = int(num_samples)
     if s < 1:
         raise ValueError(f"num_samples must be >= 1 (got {num_samples})")
-    penalties = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
-    pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
-    if isinstance(idx, (list, tuple)):
-        if prompt_lens is not None:
-            raise ValueError("a list of prompts carries its own lengths: prompt_lens goes with a padded idx [B, P]")
-        idx, prompt_lens = _pad_prompts(idx, pad)
-    if idx.dim() != 2:
-        raise ValueError(f"generate takes idx [B, P] (got {tuple(idx.shape)})")
-    B, P = idx.shape
-    if s > 1:  # row b * s + j is sample j of prompt b; from here on B is the number of rows
-        if B * s > MAX_BATCH:
-            raise ValueError(f"{B} prompts x num_samples={s} = {B * s} rows exceed the {MAX_BATCH} rows of a decode "
-                             f"session (MAX_BATCH)")
-        idx = idx.repeat_interleave(s, dim=0)
-        if prompt_lens is not None:
-            prompt_lens = [int(m) for m in (prompt_lens.tolist() if isinstance(prompt_lens, torch.Tensor)
-                                            else prompt_lens) for _ in range(s)]
-        B *= s
-    cons = _constraint_set(logit_bias, allowed_token_ids, min_p, min_new_tokens, stop, eos_token_id,
-                           model.config.vocab_size, B // s, idx.device)
-    if cons is not None and s > 1 and "bias_row" in cons:  # a prompt's bias row is its samples'
-        cons["bias_row"] = [r for r in cons["bias_row"] for _ in range(s)]
-    n = int(max_new_tokens)
-    if n < 0:
-        raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
-    if prompt_lens is not None:
-        prompt_lens = _check_lens(prompt_lens, B, P)
-        if not 0 <= pad < model.config.vocab_size:
-            raise ValueError(f"pad_token_id {pad} not in [0, vocab_size={model.config.vocab_size})")
-        P = max(prompt_lens)
-        idx = idx[:, :P]
-    if P + n > model.config.n_positions:
-        raise ValueError(f"prompt length {P} + max_new_tokens {n} > n_positions {model.config.n_positions}")
-    _check_top_p(top_p)
+    idx, lens, B, P, n, pad = _prompts(model, idx, max_new_tokens, prompt_lens, pad_token_id, eos_token_id, s)
+    sampler = Sampler.of(*rules, vocab_size=model.config.vocab_size, allowed_token_ids=allowed_token_ids, rows=B // s,
+                         device=idx.device)
+    if s > 1 and sampler.bias_row is not None:  # a prompt's bias row is its samples'
+        sampler = replace(sampler, bias_row=[r for r in sampler.bias_row for _ in range(s)])
     if seed is not None and generator is not None:
         raise ValueError("seed selects the device sampler, which draws from (seed, row, position): it takes no generator")
     if draft_tokens is None and draft_fn is not None:
@@ -1650,44 +1701,24 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
             raise ValueError(f"draft_tokens={draft_tokens} must be >= 1 with B * (draft_tokens + 1) <= {MAX_BATCH} rows "
                              f"(B={B})")
     _check_model(model)
-    idx = idx.long()
-    if prompt_lens is None and n == 0:
+    if lens is None and n == 0:
         return idx.clone() if top_n is None else _no_logprobs(idx.clone(), top_n)
-    return _generate(model, idx, prompt_lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad,
-                     None if draft_tokens is None else (int(draft_tokens), draft_fn), penalties, kv_dtype, s, top_n, cons)
+    return _generate(model, idx, lens, n, sampler, generator, pad,
+                     None if draft_tokens is None else (int(draft_tokens), draft_fn), kv_dtype, s, top_n)
 
 
 def _generate_beams(model, idx, max_new_tokens, num_beams, length_penalty, num_return_sequences, eos_token_id,
-                    prompt_lens, pad_token_id, kv_dtype, others: dict) -> BeamOutput:
+                    prompt_lens, pad_token_id, kv_dtype, given: dict) -> BeamOutput:
     """``generate(num_beams=W)``: every prompt through ``refill`` once and forked to its W rows (the ``num_samples``
-    path), ``DecodeSession.beam_search`` in one call, or with eos EOS_CHUNK tokens at a time with one read of the done
-    flags per chunk (as ``_device_loop``), then ``beam_rank`` on the host."""
-    pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
-    if isinstance(idx, (list, tuple)):
-        if prompt_lens is not None:
-            raise ValueError("a list of prompts carries its own lengths: prompt_lens goes with a padded idx [B, P]")
-        idx, prompt_lens = _pad_prompts(idx, pad)
-    if idx.dim() != 2:
-        raise ValueError(f"generate takes idx [B, P] (got {tuple(idx.shape)})")
-    B, P = idx.shape
+    path), ``DecodeSession.beam_search`` in one call, or with eos in chunks (``_chunks``), then ``beam_rank`` on the host."""
     V = model.config.vocab_size
-    W, lp, nret = _check_beams(num_beams, length_penalty, num_return_sequences, B, V, others)
-    n = int(max_new_tokens)
-    if n < 0:
-        raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
-    lens = [P] * B
-    if prompt_lens is not None:
-        lens = _check_lens(prompt_lens, B, P)
-        P = max(lens)
-        idx = idx[:, :P]
-    if not 0 <= pad < V:
-        raise ValueError(f"pad_token_id {pad} not in [0, vocab_size={V})")
-    if eos_token_id is not None and not 0 <= int(eos_token_id) < V:
-        raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={V})")
-    if P + n > model.config.n_positions:
-        raise ValueError(f"prompt length {P} + max_new_tokens {n} > n_positions {model.config.n_positions}")
+    idx, lens, B, P, n, pad = _prompts(model, idx, max_new_tokens, prompt_lens, pad_token_id, eos_token_id, pad_always=True)
+    W, lp, nret = _check_beams(num_beams, length_penalty, num_return_sequences, B, V, given)
+    if eos_token_id is not None:
+        _check_token("eos_token_id", eos_token_id, V)
     _check_model(model)
-    idx, dev, R = idx.long(), idx.device, B * W
+    lens = lens or [P] * B
+    dev, R = idx.device, B * W
     lens_t = torch.tensor(lens, device=dev).repeat_interleave(W)  # per row
     cols = torch.arange(P + n, device=dev)[None]
     seq = torch.full((R, P + n), pad, dtype=torch.int64, device=dev)
@@ -1701,12 +1732,7 @@ def _generate_beams(model, idx, max_new_tokens, num_beams, length_penalty, num_r
         for b in range(B):
             sess.refill(b * W, idx[b, :lens[b]])
             sess.fork(b * W, range(b * W + 1, b * W + W))
-        while made < n:
-            m = n - made if eos_token_id is None else min(EOS_CHUNK, n - made)
-            sess.beam_search(m, W, eos_token_id, seq, cum, done)
-            made += m
-            if eos_token_id is not None and bool(done.all()):
-                break
+        made = _chunks(n, eos_token_id, done, lambda m: sess.beam_search(m, W, eos_token_id, seq, cum, done))
     else:
         cum[:] = 0.0  # (nothing generated: every returned beam is the prompt)
     new = seq.gather(1, lens_t[:, None] + torch.arange(made, device=dev)[None])  # [R, made]
@@ -1728,26 +1754,23 @@ def _no_logprobs(tokens: torch.Tensor, top_n: int) -> GenerateOutput:
                           torch.zeros(shape + (top_n,), dtype=F32, device=dev))
 
 
-def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, eos_token_id, pad, draft=None,
-              penalties=(1.0, 0.0, 0.0, False), kv_dtype="bf16", samples=1, top_n=None, cons=None):
+def _generate(model, idx, lens, n, s: Sampler, generator, pad, draft=None, kv_dtype="bf16", samples=1, top_n=None):
     """The token loop of ``generate``: [B, P + m], row b = its prompt, its m new tokens from column lens[b] on, then
     ``pad`` (``lens`` None: every row holds P tokens and nothing is padded). m = n, or with eos the number of tokens by
     which every row has emitted it. Host sampler: new tokens are collected per step and scattered into the buffer that
     holds the prompts; device sampler: gpt2mi_sample_ragged writes row b's token of step i to column lens[b] + i of it.
-    ``penalties`` = (repetition, presence, frequency, any non-neutral): that buffer is then the history too, with the
-    generated part starting at lens[b]; the host sampler writes each step's tokens into it as it goes and passes its
-    logits through apply_penalties.
+    With penalties that buffer is the history too, with the generated part starting at lens[b]; the host sampler writes
+    each step's tokens into it as it goes and passes its logits through apply_penalties.
     ``top_n`` (None: off) returns a ``GenerateOutput``: the device sampler writes each token's log-probability and
     ``top_n`` alternatives to the token's column of a ``LogprobBuffer``, the host sampler takes them from
     ``token_logprobs`` of the step's logits, before the penalties; columns that hold no generated token (prompt, pad,
     after a row's eos) are 0.
-    ``cons`` (``_constraint_set``'s result, None: off): the device sampler takes them as keywords and matches the stop
-    sequences in the buffer; the host sampler passes its logits through ``apply_constraints`` after the penalties, gives
-    ``min_p`` to ``sample_next`` and matches the stop sequences with ``stop_match`` in the tokens it has drawn."""
+    Constraints: the device sampler takes them as keywords and matches the stop sequences in the buffer; the host
+    sampler passes its logits through ``apply_constraints`` after the penalties, gives ``min_p`` to ``sample_next`` and
+    matches the stop sequences with ``stop_match`` in the tokens it has drawn."""
+    eos_token_id = s.eos_token_id
     B, P = idx.shape
     dev = idx.device
-    if eos_token_id is not None and seed is not None and not 0 <= eos_token_id < model.config.vocab_size:
-        raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={model.config.vocab_size})")
     lens_t = torch.tensor([P] * B if lens is None else lens, device=dev)
     cols = torch.arange(P + n, device=dev)[None]
     seq = torch.full((B, P + n), pad, dtype=torch.int64, device=dev)
@@ -1765,14 +1788,14 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
             sess.refill(b, idx[b, :P if lens is None else lens[b]])
             sess.fork(b, range(b + 1, b + samples))
         logits = sess.logits[:, :model.config.vocab_size].clone()
-    rp, pp, fp, on = penalties
-    pen = {**_penalty_keywords(penalties, lens_t.tolist()), **_constraint_keywords(cons, lens_t.tolist())}
-    if seed is not None:
+    if s.seed is not None:
+        kw = s.keywords(lens_t.tolist())
         done = None if eos_token_id is None else torch.zeros(B, dtype=torch.uint8, device=dev)
         if draft is None:
-            made = _device_loop(sess, n, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen, **lp)
+            made = _chunks(n, eos_token_id, done, lambda m: sess.generate(
+                m, s.temperature, s.top_k, s.top_p, s.seed, eos_token_id, seq, done, **kw, **lp))
         else:  # (draft = (k, draft_fn): the same tokens, up to k + 1 of a row per pass over the weights)
-            sess.speculate(n, draft[0], draft[1], temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen, **lp)
+            sess.speculate(n, *draft, s.temperature, s.top_k, s.top_p, s.seed, eos_token_id, seq, done, **kw, **lp)
             made = n
         if eos_token_id is None:
             return seq if buf is None else GenerateOutput(seq, buf.logprob, buf.top_ids, buf.top_logprobs)
@@ -1780,24 +1803,24 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
     else:
         toks = []
         done = torch.zeros(B, dtype=torch.bool, device=dev)
-        c = cons or {}
-        starts = lens_t.tolist()
-        told = [r[:m] for r, m in zip(seq.tolist(), starts)] if c.get("stop") else None  # each row's tokens so far
+        on, starts = s.penalised, lens_t.tolist()
+        told = [r[:m] for r, m in zip(seq.tolist(), starts)] if s.constrained and s.stop else None  # the rows' tokens
         for i in range(n):
             raw = logits  # (the model's own row: what the log-probabilities are taken from)
             if on:
-                logits = apply_penalties(logits, seq, lens_t + i, lens_t, rp, pp, fp)
-            if cons is not None:
-                logits = apply_constraints(logits, lens_t + i, lens_t, c.get("logit_bias"), c.get("bias_row"),
-                                           c["min_new_tokens"], eos_token_id)
-            nxt = sample_next(logits, temperature, top_k, generator, top_p, c.get("min_p"))
+                logits = apply_penalties(logits, seq, lens_t + i, lens_t, s.repetition_penalty, s.presence_penalty,
+                                         s.frequency_penalty)
+            if s.constrained:
+                logits = apply_constraints(logits, lens_t + i, lens_t, s.logit_bias, s.bias_row, s.min_new_tokens,
+                                           eos_token_id)
+            nxt = sample_next(logits, s.temperature, s.top_k, generator, s.top_p, s.min_p)
             if eos_token_id is not None:
                 nxt = torch.where(done, torch.full_like(nxt, eos_token_id), nxt)  # a finished row keeps emitting eos
             if told is not None:  # a row that completes a stop sequence is finished from the next step on
                 was, hits = done.tolist(), []
                 for b, t in enumerate(nxt.tolist()):
                     told[b].append(t)
-                    hits.append(not was[b] and stop_match(told[b], starts[b], c["stop"], c["min_new_tokens"]))
+                    hits.append(not was[b] and stop_match(told[b], starts[b], s.stop, s.min_new_tokens))
                 stop_hit = torch.tensor(hits, device=dev)
             if buf is not None:  # (a row finished before this step: 0, as the device sampler writes)
                 live = list(range(B)) if eos_token_id is None else (~done).nonzero()[:, 0].tolist()
@@ -1818,10 +1841,10 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
         seq.scatter_(1, lens_t[:, None] + torch.arange(made, device=dev)[None], new)
     if eos_token_id is not None:
         ended = (new == eos_token_id).cumsum(1) > 0
-        if cons is not None and cons["stop"]:  # a row that completed a stop sequence has ended from that column on
+        if s.constrained and s.stop:  # a row that completed a stop sequence has ended from that column on
             rows = seq[:, :P + made].tolist()
             for b, m in enumerate(lens_t.tolist()):
-                at = first_stop(rows[b][:m + made], m, cons["stop"], cons["min_new_tokens"], eos_token_id)
+                at = first_stop(rows[b][:m + made], m, s.stop, s.min_new_tokens, eos_token_id)
                 if at is not None:
                     ended[b, at - m:] = True
         finished = ended.all(0)  # steps by which every row has emitted eos (or completed a stop sequence)
@@ -1839,21 +1862,6 @@ def _generate(model, idx, lens, n, temperature, top_k, top_p, generator, seed, e
                                     for t in (buf.logprob, buf.top_ids, buf.top_logprobs)))
 
 
-def _device_loop(sess: DecodeSession, n, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen) -> int:
-    """``n`` tokens per row with the sampler on the device, into ``seq``; the number issued. Without eos one C call and
-    nothing read back; with eos EOS_CHUNK tokens at a time, the done flags read once per chunk, until every row has
-    emitted it (the caller cuts the result after the column by which they all have). ``pen``: the penalty keywords
-    and, with log-probabilities, ``logprobs``."""
-    made = 0
-    while made < n:
-        m = n - made if eos_token_id is None else min(EOS_CHUNK, n - made)
-        sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done, **pen)
-        made += m
-        if eos_token_id is not None and bool(done.all()):
-            break
-    return made
-
-
 @torch.no_grad()
 def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, temperature: float = 1.0,
                   top_k: Optional[int] = None, top_p: Optional[float] = None, seed: int = 0,
@@ -1864,8 +1872,6 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
     """``GPT2.generate_many``: see there."""
     check_kv_dtype(kv_dtype)
     top_n = _check_logprobs(logprobs)
-    lp = {} if top_n is None else {"logprobs": top_n}
-    penalties = _check_penalties(repetition_penalty, presence_penalty, frequency_penalty)
     if generator is not None:
         raise ValueError("generate_many draws on the device from (seed, prompt index, position): a torch.Generator is "
                          "one stream shared by the rows of a batch, so its draws would depend on the batching")
@@ -1880,28 +1886,22 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
     longest = max((p.numel() for p in prompts), default=0)
     if longest + n > model.config.n_positions:
         raise ValueError(f"prompt length {longest} + max_new_tokens {n} > n_positions {model.config.n_positions}")
-    _check_top_p(top_p)
     if not isinstance(seed, int):
         raise ValueError(f"seed must be an int (got {seed!r})")
-    if eos_token_id is not None and not 0 <= eos_token_id < model.config.vocab_size:
-        raise ValueError(f"eos_token_id {eos_token_id} not in [0, vocab_size={model.config.vocab_size})")
-    cons = _constraint_set(logit_bias, allowed_token_ids, min_p, min_new_tokens, stop, eos_token_id,
-                           model.config.vocab_size, int(batch_size), model.arena.device, per_row=False)
-    if cons is not None:
-        lp["constraints"] = cons
+    sampler = Sampler.of(temperature, top_k, top_p, seed, eos_token_id, repetition_penalty, presence_penalty,
+                         frequency_penalty, min_p, min_new_tokens, stop, logit_bias, vocab_size=model.config.vocab_size,
+                         allowed_token_ids=allowed_token_ids, rows=int(batch_size), device=model.arena.device,
+                         per_row=False)
     if not prompts or n == 0:
         return [p.long().clone() if top_n is None else _no_logprobs(p.long().clone(), top_n) for p in prompts]
     _check_model(model)
     # (at least a chunk and two positions, so that a dummy row of one token need not start over within a chunk)
     sess = DecodeSession(model, int(batch_size), min(model.config.n_positions, max(longest + n, EOS_CHUNK + 2)),
                          kv_dtype)
-    return serve_prompts(sess, [p.long() for p in prompts], n, temperature, top_k, top_p, seed, eos_token_id, penalties,
-                         **lp)
+    return serve_prompts(sess, [p.long() for p in prompts], n, sampler, top_n)
 
 
-def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, eos_token_id,
-                  penalties=(1.0, 0.0, 0.0, False), logprobs: Optional[int] = None,
-                  constraints: Optional[dict] = None) -> list:
+def serve_prompts(sess, prompts, n: int, sampler: Sampler, logprobs: Optional[int] = None) -> list:
     """The loop of ``generate_many`` over a session (anything with DecodeSession's ``B``, ``Tcap``, ``lens``,
     ``device``, ``refill``, ``generate`` and ``flush``). Rows are slots: a slot holds prompt ``owner[row]`` (None: a
     dummy of one token whose output is dropped) and draws with ``row_id = owner[row]``. The device loop runs in chunks
@@ -1909,21 +1909,21 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
     tokens are read once, finished rows (eos, or n tokens) are harvested, cut after their first eos, and refilled with
     the next pending prompt.
 
-    ``penalties`` = (repetition, presence, frequency, any non-neutral). With them ``seq`` is the history the sampler
-    reads: a slot's prompt is written to ``seq[row, :len]`` when it is filled (otherwise seq holds generated tokens only)
-    and the generated part starts at the prompt's length. A row reads its own row below its own position only, so a
-    prompt's continuation still does not depend on what it is batched with.
+    With penalties in ``sampler`` ``seq`` is the history the sampler reads: a slot's prompt is written to
+    ``seq[row, :len]`` when it is filled (otherwise seq holds generated tokens only) and the generated part starts at
+    the prompt's length. A row reads its own row below its own position only, so a prompt's continuation still does
+    not depend on what it is batched with.
 
     ``logprobs=top_n`` (None: off) gives ``generate`` a ``LogprobBuffer`` beside ``seq``; a harvested prompt is then a
     ``GenerateOutput`` cut where its tokens are cut (0 in the prompt's columns), and a slot's row of the buffer is
     cleared when the slot is filled.
 
-    ``constraints`` (``_constraint_set``'s result, None: off): every slot reads the one bias row, the generated part
-    starts at the prompt's length, and with stop sequences ``seq`` holds the prompts as with penalties; a harvested
-    prompt is cut after the token that completed a stop sequence, as after eos."""
+    With constraints in ``sampler`` every slot reads the one bias row, the generated part starts at the prompt's length,
+    and with stop sequences ``seq`` holds the prompts as with penalties; a harvested prompt is cut after the token that
+    completed a stop sequence, as after eos."""
     B, dev = sess.B, sess.device
-    stops = constraints["stop"] if constraints else []
-    on = penalties[3] or bool(stops)
+    eos_token_id, stops = sampler.eos_token_id, sampler.stop
+    on = sampler.penalised or bool(stops)
     out: List[Optional[torch.Tensor]] = [None] * len(prompts)
     pending = list(range(len(prompts)))[::-1]  # (pop() serves them in input order)
     owner: List[Optional[int]] = [None] * B
@@ -1953,9 +1953,8 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
         for r in range(B):  # a dummy row that a chunk would take past the cache starts over
             if owner[r] is None and sess.lens[r] + m + 1 > sess.Tcap:
                 fill(r)
-        sess.generate(m, temperature, top_k, top_p, seed, eos_token_id, seq, done,
-                      row_id=[DUMMY_ID if o is None else o for o in owner],
-                      **{**_penalty_keywords(penalties, start), **_constraint_keywords(constraints, start)}, **lp)
+        sess.generate(m, sampler.temperature, sampler.top_k, sampler.top_p, sampler.seed, eos_token_id, seq, done,
+                      row_id=[DUMMY_ID if o is None else o for o in owner], **sampler.keywords(start), **lp)
         sess.flush()  # every row's logits are now those of its next position: a refilled row joins on equal terms
         host = torch.cat([done.to(torch.int64)[:, None], seq], dim=1).cpu()  # the one read of the chunk
         for r in range(B):
@@ -1967,7 +1966,7 @@ def serve_prompts(sess, prompts, n: int, temperature, top_k, top_p, seed: int, e
                 hits = (new == eos_token_id).nonzero()
                 if hits.numel():
                     new = new[:int(hits[0]) + 1]
-                at = first_stop(new.tolist(), 0, stops, constraints["min_new_tokens"], eos_token_id) if stops else None
+                at = first_stop(new.tolist(), 0, stops, sampler.min_new_tokens, eos_token_id) if stops else None
                 if at is not None:
                     new = new[:at + 1]
             out[owner[r]] = torch.cat([prompts[owner[r]].to(dev), new.to(dev)])

@@ -463,8 +463,9 @@ def test_serving_loop_returns_each_prompts_values_cut_where_its_tokens_are(batch
     lens = [3, 11, 1, 7, 20]
     prompts = [torch.arange(100 * i + 20, 100 * i + 20 + L) for i, L in enumerate(lens)]
     sess = ServeStub(batch_size, max(lens) + n)
-    outs = generation.serve_prompts(sess, prompts, n, 0.8, 20, None, 3, eos, logprobs=2)
-    plain = generation.serve_prompts(ServeStub(batch_size, max(lens) + n), prompts, n, 0.8, 20, None, 3, eos)
+    outs = generation.serve_prompts(sess, prompts, n, generation.Sampler.of(0.8, 20, None, 3, eos), logprobs=2)
+    plain = generation.serve_prompts(ServeStub(batch_size, max(lens) + n), prompts, n,
+                                    generation.Sampler.of(0.8, 20, None, 3, eos))
     assert all(k == ["logprobs"] for k in sess.kw)
     for i, (out, L) in enumerate(zip(outs, lens)):
         assert torch.equal(out.tokens, plain[i])               # the tokens of the call without
@@ -485,8 +486,8 @@ def test_serving_loop_without_logprobs_calls_generate_as_before():
     from tests.test_ragged_cpu import StubSession, expected, script
     prompts = [torch.arange(1, 6), torch.arange(1, 3)]
     sess = StubSession(2, 16, script)
-    outs = generation.serve_prompts(sess, prompts, 5, 1.0, None, None, 0, None)
+    outs = generation.serve_prompts(sess, prompts, 5, generation.Sampler.of(1.0, None, None, 0, None))
     assert [o.tolist() for o in outs] == [expected(i, p.tolist(), 5, None) for i, p in enumerate(prompts)]
     sess = ServeStub(2, 16)
-    generation.serve_prompts(sess, prompts, 5, 1.0, None, None, 0, None)
+    generation.serve_prompts(sess, prompts, 5, generation.Sampler.of(1.0, None, None, 0, None))
     assert sess.kw and all(k == [] for k in sess.kw)

@@ -314,7 +314,7 @@ def test_serving_loop_keeps_each_rows_prompt_in_the_history(batch_size):
     lens = [3, 11, 1, 7, 20]
     prompts = [torch.arange(100 * i + 1, 100 * i + 1 + L) for i, L in enumerate(lens)]
     sess = ServeStub(batch_size, max(lens) + n)
-    outs = generation.serve_prompts(sess, prompts, n, 0.8, 20, None, 3, None, (1.3, 0.5, 0.2, True))
+    outs = generation.serve_prompts(sess, prompts, n, generation.Sampler.of(0.8, 20, None, 3, None, 1.3, 0.5, 0.2))
     assert [o.tolist() for o in outs] == [serve_expected(p.tolist(), n) for p in prompts]
     assert all(s[:3] == (1.3, 0.5, 0.2) for s in sess.seen) and len(sess.seen) >= 2 * -(-len(lens) // batch_size)
 
@@ -325,12 +325,12 @@ def test_serving_loop_without_penalties_calls_generate_as_before():
     from tests.test_ragged_cpu import StubSession, expected, script
     prompts = [torch.arange(1, 6), torch.arange(1, 3)]
     sess = StubSession(2, 16, script)
-    outs = generation.serve_prompts(sess, prompts, 5, 1.0, None, None, 0, None, (1.0, 0.0, 0.0, False))
+    outs = generation.serve_prompts(sess, prompts, 5, generation.Sampler.of(1.0, None, None, 0, None, 1.0, 0.0, 0.0))
     assert [o.tolist() for o in outs] == [expected(i, p.tolist(), 5, None) for i, p in enumerate(prompts)]
 
 
 class SpecStub:
-    """DecodeSession's surface as speculate_loop uses it, with generation.verify_history doing what the session's
+    """DecodeSession's surface as speculate_loop uses it, with Sampler.write_verify_history doing what the session's
     _verify does before it samples. The token after a history h is nxt(h): the whole history decides it, as under
     penalties, so a verify row draws the loop's token iff seq holds the sequence's tokens up to and including its own."""
 
@@ -339,7 +339,8 @@ class SpecStub:
         self.rows = []
 
     def _verify(self, toks, seqs, poss, ks, sampler):
-        pen = generation.verify_history(sampler, torch.tensor(toks, dtype=torch.int64), seqs, poss)
+        record, seq, gen_start = sampler
+        pen = record.write_verify_history(seq, torch.tensor(toks, dtype=torch.int64), seqs, poss, gen_start)
         assert pen["hist"] is self.seq and pen["hist_row"] == list(seqs)
         assert pen["gen_start"] == [GEN_START[b] for b in seqs] and pen["repetition"] == 1.3
         out = []
@@ -386,14 +387,15 @@ def test_speculative_verify_reads_the_current_token_and_the_drafts(how):
         return [right[0] + 1] + right[1:] if bad and right else right
     sess = SpecStub(seq, [4, 2])
     first = [want[0][4], want[1][2]]
-    pen = dict(repetition=1.3, presence=0.5, frequency=0.2, gen_start=list(GEN_START))
+    record = generation.Sampler.of(0.8, None, None, 0, None, 1.3, 0.5, 0.2)
     new, stats = generation.speculate_loop(sess, n, k, draft, None, [list(p) for p in prompts], first, [0, 1],
-                                           (0.8, None, None, 0, (pen, seq)))
+                                           (record, seq, list(GEN_START)))
     assert [p + t for p, t in zip(prompts, new)] == want               # exactly the one-token loop's tokens
     assert stats["accepted"] == (stats["drafted"] if how == "right" else 0 if how == "wrong" else stats["accepted"])
     if how == "right":
         assert stats["calls"] < n - 1
     assert {b for b, _, _ in sess.rows} == {0, 1} and len(sess.rows) > stats["calls"]   # (runs of several rows)
-    # without the fifth entry nothing is written and nothing is returned
+    # a record without penalties writes nothing and returns {}
     before = seq.clone()
-    assert generation.verify_history((0.8, None, None, 0), torch.tensor([1]), [0], [0]) == {} and torch.equal(seq, before)
+    plain = generation.Sampler.of(0.8, None, None, 0)
+    assert plain.write_verify_history(seq, torch.tensor([1]), [0], [0], [0]) == {} and torch.equal(seq, before)

@@ -299,7 +299,7 @@ def test_serving_loop_bookkeeping(batch_size, eos):
     lens = [1, 5, 12, 3, 9, 20, 2]
     prompts = [torch.arange(30 * i + 1, 30 * i + 1 + L) for i, L in enumerate(lens)]  # (no token 0: the dummy's)
     sess = StubSession(batch_size, max(lens) + n, script)
-    outs = generation.serve_prompts(sess, prompts, n, 0.8, 20, None, 3, eos)
+    outs = generation.serve_prompts(sess, prompts, n, generation.Sampler.of(0.8, 20, None, 3, eos))
     assert len(outs) == 7
     for i, (o, p) in enumerate(zip(outs, prompts)):
         assert o.dtype == torch.int64 and o.tolist() == expected(i, p.tolist(), n, eos), i
@@ -320,7 +320,7 @@ def test_serving_loop_at_the_end_of_the_cache():
     n = 5
     prompts = [torch.arange(1, 12), torch.arange(1, 3), torch.arange(1, 8)]
     sess = StubSession(4, 16, script)
-    outs = generation.serve_prompts(sess, prompts, n, 1.0, None, None, 0, None)
+    outs = generation.serve_prompts(sess, prompts, n, generation.Sampler.of(1.0, None, None, 0, None))
     assert [o.tolist() for o in outs] == [expected(i, p.tolist(), n, None) for i, p in enumerate(prompts)]
 
 
