@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
 # additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
-ABI_MINOR = 5
+ABI_MINOR = 6
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -168,6 +168,9 @@ _SIGS = {
     "gpt2mi_attn_fwd_f32_doc": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
     "gpt2mi_attn_bwd_f32_doc": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64,
                                 _p],
+    # v24.6 positions per document: the embedding lists with doc_start before B
+    "gpt2mi_embed_fwd_doc": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
+    "gpt2mi_embed_bwd_doc": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
@@ -175,7 +178,8 @@ _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_deco
                 "gpt2mi_decode_beam_search": 2, "gpt2mi_gemm_wgrad_batch": 3, "gpt2mi_gemm_wgrad_batch_scratch": 3,
                 "gpt2mi_gemm_wgrad_batch_max": 3, "gpt2mi_sample_constrained": 4,
                 "gpt2mi_decode_generate_constrained": 4, "gpt2mi_doc_bounds": 5, "gpt2mi_attn_fwd_doc": 5,
-                "gpt2mi_attn_bwd_doc": 5, "gpt2mi_attn_fwd_f32_doc": 5, "gpt2mi_attn_bwd_f32_doc": 5}
+                "gpt2mi_attn_bwd_doc": 5, "gpt2mi_attn_fwd_f32_doc": 5, "gpt2mi_attn_bwd_f32_doc": 5,
+                "gpt2mi_embed_fwd_doc": 6, "gpt2mi_embed_bwd_doc": 6}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
              "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size}
@@ -283,6 +287,23 @@ def embed_fwd(idx, wte, wpe, x, B, T, C, p=0.0, seed=0, T_valid=None):
 def embed_bwd(idx, dres, dwte, dwpe, B, T, C, p=0.0, seed=0, T_valid=None):
     _call("gpt2mi_embed_bwd", _ptr(idx), _ptr(dres), _ptr(dwte), _ptr(dwpe), B, T, T if T_valid is None else T_valid,
           C, p, seed, _stream())
+
+
+def _doc_start(name, start, B, T):
+    if start.dtype != torch.int32 or tuple(start.shape) != (B, T) or not start.is_contiguous():
+        raise KernelError(f"{name}: start must be a contiguous int32 [B={B}, T={T}] tensor")
+    return _ptr(start)
+
+
+def embed_fwd_doc(idx, wte, wpe, x, start, B, T, C, p=0.0, seed=0, T_valid=None):
+    """embed_fwd with the position of (b, t) restarting at its document: wpe[t - start[b, t]] (packing.doc_positions)."""
+    _call("gpt2mi_embed_fwd_doc", _ptr(idx), _ptr(wte), _ptr(wpe), _ptr(x), _doc_start("embed_fwd_doc", start, B, T),
+          B, T, T if T_valid is None else T_valid, C, p, seed, _stream())
+
+
+def embed_bwd_doc(idx, dres, dwte, dwpe, start, B, T, C, p=0.0, seed=0, T_valid=None):
+    _call("gpt2mi_embed_bwd_doc", _ptr(idx), _ptr(dres), _ptr(dwte), _ptr(dwpe),
+          _doc_start("embed_bwd_doc", start, B, T), B, T, T if T_valid is None else T_valid, C, p, seed, _stream())
 
 
 def layernorm_fwd(x, w, b, y_bf16, y_f32, mean, rstd, M, C, eps):

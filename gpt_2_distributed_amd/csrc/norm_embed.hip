@@ -305,6 +305,203 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const int64_t* __restric
   dwpe[i] += s;
 }
 
+// Position of row t of a packed sequence: its offset in its document. A start outside [0, t] is clamped where it is
+// read, as the attention kernels clamp it, so the position is always in [0, t].
+__device__ __forceinline__ int doc_pos(int t, int start) { return t - min(max(start, 0), t); }
+
+// Embedding forward with positions restarting at every document (packing.py doc_positions):
+// x[b,t,:] = drop(wte[idx[b,t],:] + wpe[t - start[b,t],:]). embed_fwd_kernel's row body, the position read once per
+// row; padding rows are zeroed before start is looked at.
+template <int VEC, int NV>
+__global__ __launch_bounds__(256) void embed_fwd_doc_kernel(const int64_t* __restrict__ idx,
+                                                            const float* __restrict__ wte,
+                                                            const float* __restrict__ wpe, float* __restrict__ x,
+                                                            const int* __restrict__ start, int M, int T, int T_valid,
+                                                            int C, int nv, uint64_t seed, uint32_t thr,
+                                                            float inv_keep) {
+  const int lane = threadIdx.x & 63;
+  for (int row = blockIdx.x * kWaves + (threadIdx.x >> 6); row < M; row += gridDim.x * kWaves) {
+    const int t = row % T;
+    if (t >= T_valid) {
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        float z[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) z[j] = 0.f;
+        store_vec<VEC>(x + (size_t)row * C + VEC * (lane + 64 * i), z);
+      }
+      continue;
+    }
+    const int64_t tok = idx[row];
+    const int pos = doc_pos(t, start[row]);
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+      {
+        const int e = VEC * (lane + 64 * i);
+        float a[VEC], p[VEC];
+        load_vec<VEC>(wte + (size_t)tok * C + e, a);
+        load_vec<VEC>(wpe + (size_t)pos * C + e, p);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          a[j] += p[j];
+          if (thr) a[j] = drop_keep(seed, (uint64_t)row * C + e + j, thr) ? a[j] * inv_keep : 0.f;
+        }
+        store_vec<VEC>(x + (size_t)row * C + e, a);
+      }
+  }
+}
+
+// Embedding backward with restarting positions, two launches ("Positions per document").
+// The token table: embed_bwd_kernel's walk without its position sum, one thread per (t, c) over the batch,
+// dwte[idx[b,t],c] += g with fp32 atomics, spread over the whole device whatever the documents are.
+__global__ __launch_bounds__(256) void embed_bwd_doc_wte_kernel(const int64_t* __restrict__ idx,
+                                                                const float* __restrict__ dres,
+                                                                float* __restrict__ dwte, int B, int T, int T_valid,
+                                                                int C, uint64_t seed, uint32_t thr, float inv_keep) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= T_valid * C) return;
+  const int t = i / C, c = i % C;
+  auto one = [&](int b, float g, int64_t tok) {
+    const size_t row = (size_t)b * T + t;
+    if (thr) g = drop_keep(seed, row * C + c, thr) ? g * inv_keep : 0.f;
+    atomicAdd(dwte + (size_t)tok * C + c, g);
+  };
+  int b = 0;
+  for (; b + 4 <= B; b += 4) {  // the four rows' loads first
+    float g[4];
+    int64_t tok[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t row = (size_t)(b + u) * T + t;
+      g[u] = dres[row * C + c];
+      tok[u] = idx[row];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) one(b + u, g[u], tok[u]);
+  }
+  for (; b < B; ++b) one(b, dres[((size_t)b * T + t) * C + c], idx[(size_t)b * T + t]);
+}
+
+// The position table. dwpe[p] sums the rows (b, t) with t - start[b,t] == p, a set that differs from row to row, so
+// the block that owns position p (and 64 * kDocCh channels, blockIdx.y) finds them itself: it scans
+// start[b, p..T_valid) row by row, 256 * kDocScan positions a trip with the next trip's loads in flight, and compacts
+// the matching rows, in (b, t) order, into a list in LDS (wave ballots and a prefix over the per-wave counts; no LDS
+// atomics, so the order is fixed by the inputs). When the list is full, and at the end, each of the four waves walks
+// its quarter of the list kDocGroup rows at a time, loads first, a lane owning channels lane + 64 k:
+// s += dres[row,c]*keep/(1-p), no atomics. At the end the four waves' sums meet in LDS and are added in wave order:
+// dwpe[p,c] += ((s0 + s1) + s2) + s3, only if the position had a row: positions from the longest document's length
+// on are neither read nor written.
+constexpr int kDocScan = 4;     // positions scanned per thread and trip
+constexpr int kDocCh = 4;       // channels per lane: blockIdx.y covers 64 * kDocCh of them
+constexpr int kDocGroup = 8;    // rows whose loads are issued together
+constexpr int kDocList = 2048;  // list capacity (>= 2 * 256 * kDocScan: a trip always fits after a drain)
+
+__global__ __launch_bounds__(256) void embed_bwd_doc_wpe_kernel(const float* __restrict__ dres,
+                                                                const int* __restrict__ start,
+                                                                float* __restrict__ dwpe, int B, int T, int T_valid,
+                                                                int C, uint64_t seed, uint32_t thr, float inv_keep) {
+  __shared__ int list[kDocList];
+  __shared__ int cnt[2][kDocScan * kWaves];
+  __shared__ float part[kWaves][64 * kDocCh];
+  const int p = blockIdx.x;  // < T_valid
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int cb = blockIdx.y * (64 * kDocCh);
+  const int c0 = cb + lane;
+  float s[kDocCh];
+#pragma unroll
+  for (int k = 0; k < kDocCh; ++k) s[k] = 0.f;
+  int n = 0;         // rows in the list
+  bool any = false;  // the position has at least one row
+
+  auto one = [&](int row, int k, float g) {
+    if (thr) g = drop_keep(seed, (uint64_t)row * C + c0 + 64 * k, thr) ? g * inv_keep : 0.f;
+    s[k] += g;
+  };
+  auto drain = [&]() {  // all threads hold the same n
+    __syncthreads();
+    const int q = (n + kWaves - 1) / kWaves;
+    int j = wid * q;
+    const int j1 = min(n, j + q);
+    for (; j + kDocGroup <= j1; j += kDocGroup) {
+      float g[kDocGroup][kDocCh];
+#pragma unroll
+      for (int u = 0; u < kDocGroup; ++u) {
+        const int row = list[j + u];
+#pragma unroll
+        for (int k = 0; k < kDocCh; ++k)
+          if (c0 + 64 * k < C) g[u][k] = dres[(size_t)row * C + c0 + 64 * k];
+      }
+#pragma unroll
+      for (int u = 0; u < kDocGroup; ++u)
+#pragma unroll
+        for (int k = 0; k < kDocCh; ++k)
+          if (c0 + 64 * k < C) one(list[j + u], k, g[u][k]);
+    }
+    for (; j < j1; ++j) {
+      const int row = list[j];
+#pragma unroll
+      for (int k = 0; k < kDocCh; ++k)
+        if (c0 + 64 * k < C) one(row, k, dres[(size_t)row * C + c0 + 64 * k]);
+    }
+    any = any || n > 0;
+    n = 0;
+    __syncthreads();
+  };
+
+  const int tpr = (T_valid - p + 256 * kDocScan - 1) / (256 * kDocScan);  // trips per row, >= 1
+  const int trips = B * tpr;
+  auto fetch = [&](int i, int* v) {  // the starts of trip i; a position past the row counts as no hit below
+    const int b = i / tpr, t0 = p + (i % tpr) * (256 * kDocScan);
+#pragma unroll
+    for (int u = 0; u < kDocScan; ++u) {
+      const int t = t0 + 256 * u + threadIdx.x;
+      v[u] = t < T_valid ? start[(size_t)b * T + t] : 0;
+    }
+  };
+  int nxt[kDocScan];
+  fetch(0, nxt);
+  for (int i = 0; i < trips; ++i) {
+    int cur[kDocScan];
+#pragma unroll
+    for (int u = 0; u < kDocScan; ++u) cur[u] = nxt[u];
+    if (i + 1 < trips) fetch(i + 1, nxt);
+    if (n + 256 * kDocScan > kDocList) drain();
+    const int b = i / tpr, t0 = p + (i % tpr) * (256 * kDocScan);
+    bool hit[kDocScan];
+    uint64_t mask[kDocScan];
+#pragma unroll
+    for (int u = 0; u < kDocScan; ++u) {
+      const int t = t0 + 256 * u + threadIdx.x;
+      hit[u] = t < T_valid && doc_pos(t, cur[u]) == p;
+      mask[u] = __ballot(hit[u]);
+      if (lane == 0) cnt[i & 1][u * kWaves + wid] = __popcll(mask[u]);
+    }
+    __syncthreads();  // cnt[i & 1] is next written two trips on, after the barrier of the trip between
+    int before = 0, mine[kDocScan];  // mine[u]: hits of the trip ahead of this wave's in sub-chunk u
+#pragma unroll
+    for (int q = 0; q < kDocScan * kWaves; ++q) {
+      if (q % kWaves == wid) mine[q / kWaves] = before;
+      before += cnt[i & 1][q];
+    }
+#pragma unroll
+    for (int u = 0; u < kDocScan; ++u)
+      if (hit[u]) list[n + mine[u] + __popcll(mask[u] & ((1ull << lane) - 1))] = b * T + t0 + 256 * u + threadIdx.x;
+    n += before;
+  }
+  drain();
+  if (!any) return;
+#pragma unroll
+  for (int k = 0; k < kDocCh; ++k) part[wid][lane + 64 * k] = s[k];
+  __syncthreads();
+  const int c = cb + threadIdx.x;  // 256 threads, 64 * kDocCh channels
+  if (threadIdx.x < 64 * kDocCh && c < C) {
+    float sum = part[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) sum += part[w][threadIdx.x];
+    dwpe[(size_t)p * C + c] += sum;
+  }
+}
+
 // Column sums of a bf16 [M,N] matrix with row stride ld: db[n] += sum_m g[m,n]. Each thread owns
 // 4 adjacent columns (8-B loads); blockIdx.y splits rows; one atomic per column per block-row-chunk.
 template <typename TG>
@@ -434,6 +631,41 @@ GPT2MI_EXPORT int gpt2mi_embed_bwd(const int64_t* idx, const float* dres, float*
   const float ik = p > 0.f ? 1.f / (1.f - p) : 1.f;
   embed_bwd_kernel<<<(T_valid * C + 255) / 256, 256, 0, s>>>(idx, dres, dwte, dwpe, B, T, T_valid, C, seed, thr, ik);
   return gpt2mi::check_launch("embed_bwd");
+}
+
+GPT2MI_EXPORT int gpt2mi_embed_fwd_doc(const int64_t* idx, const float* wte, const float* wpe, float* x,
+                                       const int* start, int B, int T, int T_valid, int C, float p, uint64_t seed,
+                                       void* stream) {
+  int vec, nv;
+  GPT2MI_REQUIRE(start != nullptr, "embed_fwd_doc: start is null");
+  GPT2MI_REQUIRE(row_shape(C, &vec, &nv), "embed_fwd_doc: unsupported C=%d", C);
+  GPT2MI_REQUIRE(T_valid > 0 && T_valid <= T, "embed_fwd_doc: T_valid=%d not in [1, T=%d]", T_valid, T);
+  GPT2MI_REQUIRE(p <= 0.f || (size_t)B * T * C < (1ull << 33),
+                 "embed_fwd_doc: B*T*C exceeds the 32-bit dropout pair index");
+  hipStream_t s = (hipStream_t)stream;
+  const int M = B * T;
+  const uint32_t thr = drop_threshold(p);
+  const float ik = p > 0.f ? 1.f / (1.f - p) : 1.f;
+#define X(V, N) if (vec == V && nv == N) embed_fwd_doc_kernel<V, N><<<grid_rows(M), 256, 0, s>>>(idx, wte, wpe, x, start, M, T, T_valid, C, nv, seed, thr, ik);
+  GPT2MI_ROW_CASES(X)
+#undef X
+  return gpt2mi::check_launch("embed_fwd_doc");
+}
+
+GPT2MI_EXPORT int gpt2mi_embed_bwd_doc(const int64_t* idx, const float* dres, float* dwte, float* dwpe,
+                                       const int* start, int B, int T, int T_valid, int C, float p, uint64_t seed,
+                                       void* stream) {
+  GPT2MI_REQUIRE(start != nullptr, "embed_bwd_doc: start is null");
+  GPT2MI_REQUIRE(T_valid > 0 && T_valid <= T, "embed_bwd_doc: T_valid=%d not in [1, T=%d]", T_valid, T);
+  GPT2MI_REQUIRE(B > 0 && C > 0 && (size_t)B * T < (1ull << 31), "embed_bwd_doc: B=%d, T=%d, C=%d out of range", B, T,
+                 C);
+  hipStream_t s = (hipStream_t)stream;
+  const uint32_t thr = drop_threshold(p);
+  const float ik = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  embed_bwd_doc_wte_kernel<<<(T_valid * C + 255) / 256, 256, 0, s>>>(idx, dres, dwte, B, T, T_valid, C, seed, thr, ik);
+  const dim3 grid(T_valid, (C + 64 * kDocCh - 1) / (64 * kDocCh));
+  embed_bwd_doc_wpe_kernel<<<grid, 256, 0, s>>>(dres, start, dwpe, B, T, T_valid, C, seed, thr, ik);
+  return gpt2mi::check_launch("embed_bwd_doc");
 }
 
 template <typename TG>

@@ -353,13 +353,14 @@ class _Saved:
     seeds: dict
     act: torch.dtype
     doc: Optional[DocBounds] = None  # document bounds [B, Tp] (padded), None: plain causal attention
+    reset: bool = False        # positions restart at every document (the _doc embedding kernels read doc.start)
 
 
 class _GPT2Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, engine, idx, labels, doc, *params):
+    def forward(ctx, engine, idx, labels, doc, reset, *params):
         ctx.set_materialize_grads(False)
-        logits, loss = engine._forward(idx, labels, True, doc)
+        logits, loss = engine._forward(idx, labels, True, doc, reset)
         ctx.engine = engine
         ctx.token = engine._fwd_token
         ctx.n_params = len(params)
@@ -372,16 +373,16 @@ class _GPT2Step(torch.autograd.Function):
             raise RuntimeError("GPT2 activations were overwritten by a later forward before this backward "
                                "(one forward/backward in flight per model)")
         eng._backward(grad_logits, grad_loss)
-        return (None, None, None, None) + (None,) * ctx.n_params
+        return (None, None, None, None, None) + (None,) * ctx.n_params
 
 
 class _TrunkFn(torch.autograd.Function):
     """GPT2Backbone.forward(idx) (model.py:275-313): embedding -> blocks -> ln_f, fp32 output."""
 
     @staticmethod
-    def forward(ctx, engine, idx, doc, *params):
+    def forward(ctx, engine, idx, doc, reset, *params):
         ctx.set_materialize_grads(False)
-        out = engine._trunk_forward_module(idx, True, doc)
+        out = engine._trunk_forward_module(idx, True, doc, reset)
         ctx.engine = engine
         ctx.token = engine._fwd_token
         ctx.n_params = len(params)
@@ -393,7 +394,7 @@ class _TrunkFn(torch.autograd.Function):
         if ctx.token != eng._fwd_token:
             raise RuntimeError("GPT2 activations were overwritten by a later forward before this backward")
         eng._trunk_backward_module(dy)
-        return (None, None, None) + (None,) * ctx.n_params
+        return (None, None, None, None) + (None,) * ctx.n_params
 
 
 class _SubFn(torch.autograd.Function):
@@ -787,20 +788,24 @@ class Engine:
         return torch.is_grad_enabled() and any(p.requires_grad for p in self._params)
 
     # ---- public entry -------------------------------------------------------------------------------
-    def forward(self, idx: torch.Tensor, labels: Optional[torch.Tensor], doc: Optional[DocBounds] = None):
+    def forward(self, idx: torch.Tensor, labels: Optional[torch.Tensor], doc: Optional[DocBounds] = None,
+                reset: bool = False):
         """doc: packing.DocBounds of idx (document-masked attention), carried through autograd as a non-differentiable
-        input; None: plain causal attention, the launches as they were."""
+        input; None: plain causal attention, the launches as they were. reset: with doc, the position embedding of a
+        token is that of its offset in its document (packing.doc_positions); off, the embedding launches as they were."""
+        reset = self._check_reset(doc, reset)
         if self._grad_enabled():
-            return _GPT2Step.apply(self, idx, labels, doc, *self._params)
+            return _GPT2Step.apply(self, idx, labels, doc, reset, *self._params)
         with torch.no_grad():
-            return self._forward(idx, labels, False, doc)
+            return self._forward(idx, labels, False, doc, reset)
 
     # (autograd.Function.forward runs with grad mode off: whether a backward will follow is decided here)
-    def backbone_forward(self, idx: torch.Tensor, doc: Optional[DocBounds] = None) -> torch.Tensor:
+    def backbone_forward(self, idx: torch.Tensor, doc: Optional[DocBounds] = None, reset: bool = False) -> torch.Tensor:
+        reset = self._check_reset(doc, reset)
         if self._grad_enabled():
-            return _TrunkFn.apply(self, idx, doc, *self._params)
+            return _TrunkFn.apply(self, idx, doc, reset, *self._params)
         with torch.no_grad():
-            return self._trunk_forward_module(idx, False, doc)
+            return self._trunk_forward_module(idx, False, doc, reset)
 
     def sub_forward(self, kind: str, layer: int, x: torch.Tensor, doc: Optional[DocBounds] = None) -> torch.Tensor:
         if self._grad_enabled() or x.requires_grad:
@@ -860,12 +865,16 @@ class Engine:
         self._ln_fwd(A.xmid, pre + "ln2", A.ln2, A.m2, A.r2, M)
         self._mlp_fwd(l, A, A.xmid, x_out, M, act, pr, seeds)
 
-    def _trunk_fwd(self, ws, idx, B, T, T_valid, act, pr, pa, seeds, lnf_f32=None, doc=None):
+    def _trunk_fwd(self, ws, idx, B, T, T_valid, act, pr, pa, seeds, lnf_f32=None, doc=None, reset=False):
         C, L = self.cfg.n_embd, self.cfg.n_layer
         x = ws.x
         self._unit("embed")
-        K.embed_fwd(idx, self.p("transformer.wte.weight"), self.p("transformer.wpe.weight"), x[0], B, T, C, pr,
-                    seeds["embd"], T_valid=T_valid)
+        if reset:  # positions restart at every document: wpe[t - start[b, t]]
+            K.embed_fwd_doc(idx, self.p("transformer.wte.weight"), self.p("transformer.wpe.weight"), x[0], doc.start,
+                            B, T, C, pr, seeds["embd"], T_valid=T_valid)
+        else:
+            K.embed_fwd(idx, self.p("transformer.wte.weight"), self.p("transformer.wpe.weight"), x[0], B, T, C, pr,
+                        seeds["embd"], T_valid=T_valid)
         for l in range(L):
             self._unit(f"h.{l}")
             self._block_fwd(l, ws.blocks[l], x[l], x[l + 1], B, T, act, pr, pa, seeds, doc)
@@ -1034,11 +1043,21 @@ class Engine:
                 self._ready(f"h.{l}")
         # embedding backward: atomics into the tied wte grad (the lm_head wgrad already wrote it)
         self._unit_bwd("embed")
-        K.embed_bwd(idx, ws.dres, self.g("transformer.wte.weight"), self.g("transformer.wpe.weight"), B, T, C, pr,
-                    seeds["embd"], T_valid=sv.T)
+        if sv.reset:  # dwpe by document position, summed in a fixed order (no float atomics, as embed_bwd's)
+            K.embed_bwd_doc(idx, ws.dres, self.g("transformer.wte.weight"), self.g("transformer.wpe.weight"),
+                            sv.doc.start, B, T, C, pr, seeds["embd"], T_valid=sv.T)
+        else:
+            K.embed_bwd(idx, ws.dres, self.g("transformer.wte.weight"), self.g("transformer.wpe.weight"), B, T, C, pr,
+                        seeds["embd"], T_valid=sv.T)
         self._ready("embed")
 
     # ---- the whole step ------------------------------------------------------------------------------
+    @staticmethod
+    def _check_reset(doc, reset) -> bool:
+        if reset and doc is None:
+            raise ValueError("reset_positions=True needs doc_bounds: positions restart at the documents they describe")
+        return bool(reset)
+
     def _pad_doc(self, doc, idx, Tp):
         """The caller's bounds (of the unpadded idx [B, T]) checked by their metadata, no host synchronisation, and
         extended over the padding, which is one document [T, Tp) of its own."""
@@ -1063,7 +1082,7 @@ class Engine:
                 labels = F.pad(labels, (0, Tp - T), value=-100)
         return idx, labels, T
 
-    def _forward(self, idx, labels, need_grad, doc=None):
+    def _forward(self, idx, labels, need_grad, doc=None, reset=False):
         cfg = self.cfg
         self.gemm_sched = self.base_sched  # (a backward that raised midway left its flags)
         V, Vp, C = cfg.vocab_size, self.vpad, cfg.n_embd
@@ -1077,8 +1096,8 @@ class Engine:
         pr, pa = self._dropout()
         seeds = self._next_seeds()
         self._fwd_token += 1
-        self._saved = _Saved(idx, labels, T, pr, pa, seeds, act, doc)
-        self._trunk_fwd(ws, idx, B, Tp, T, act, pr, pa, seeds, doc=doc)
+        self._saved = _Saved(idx, labels, T, pr, pa, seeds, act, doc, reset)
+        self._trunk_fwd(ws, idx, B, Tp, T, act, pr, pa, seeds, doc=doc, reset=reset)
         logits = torch.empty(M, Vp, dtype=act, device=self.device)  # fresh: the caller may keep it
         with self._probe("lm_head_fwd"):
             self._gemm(K.FWD, K.EPI_BF16, M, Vp, C, ws.lnf, C, self.w("transformer.wte.weight", act), C, logits, Vp)
@@ -1093,7 +1112,7 @@ class Engine:
         return out[..., :V], loss
 
     # ---- evaluation: forward only, nothing kept, nothing of the training state touched --------------------
-    def score(self, idx, labels, acc=None, doc=None):
+    def score(self, idx, labels, acc=None, doc=None, reset=False):
         """Per-token negative log-likelihoods of ``labels`` [B, T] without a backward, a logits tensor or the training
         workspace. Dropout is off whatever ``model.training`` is (fixed seeds, p = 0), and the dropout stream
         (_step_seed), _fwd_token, _saved, gemm_sched and the grad arena are left as found: no state that a later
@@ -1105,15 +1124,16 @@ class Engine:
         mean [1]). acc = (sum, count) fp32 [1] tensors: this call's sum and count are ADDED to them (and returned).
         bf16: the fused lm_head + cross-entropy kernel (gpt2mi_lm_loss). fp32: the fp32 lm_head GEMM + cross-entropy
         over chunks of at most EVAL_F32_CHUNK rows into one reused buffer."""
+        reset = self._check_reset(doc, reset)
         sched = self.gemm_sched
         self.gemm_sched = self.base_sched
         try:
             with torch.no_grad():
-                return self._score(idx, labels, acc, doc)
+                return self._score(idx, labels, acc, doc, reset)
         finally:
             self.gemm_sched = sched
 
-    def _score(self, idx, labels, acc, doc=None):
+    def _score(self, idx, labels, acc, doc=None, reset=False):
         cfg = self.cfg
         V, Vp, C = cfg.vocab_size, self.vpad, cfg.n_embd
         doc = self._pad_doc(doc, idx, padded_len(idx.shape[1]))
@@ -1123,7 +1143,7 @@ class Engine:
         act = self.compute_dtype()
         self._sync_shadows(act, False)
         ws = self.eval_workspace(B, Tp, act)
-        self._trunk_fwd(ws, idx, B, Tp, T, act, 0.0, 0.0, self._seeds(0), doc=doc)
+        self._trunk_fwd(ws, idx, B, Tp, T, act, 0.0, 0.0, self._seeds(0), doc=doc, reset=reset)
         wte = self.w("transformer.wte.weight", act)
         if acc is None:
             s, n = torch.empty(1, dtype=F32, device=self.device), torch.empty(1, dtype=F32, device=self.device)
@@ -1197,7 +1217,7 @@ class Engine:
         self._end_grads()
 
     # ---- GPT2Backbone.forward on its own -------------------------------------------------------------
-    def _trunk_forward_module(self, idx, need_grad, doc=None):
+    def _trunk_forward_module(self, idx, need_grad, doc=None, reset=False):
         self.gemm_sched = self.base_sched  # (a backward that raised midway left its flags)
         doc = self._pad_doc(doc, idx, padded_len(idx.shape[1]))
         idx, _, T = self._pad(idx, None)
@@ -1208,9 +1228,9 @@ class Engine:
         pr, pa = self._dropout()
         seeds = self._next_seeds()
         self._fwd_token += 1
-        self._saved = _Saved(idx, None, T, pr, pa, seeds, act, doc)
+        self._saved = _Saved(idx, None, T, pr, pa, seeds, act, doc, reset)
         out = torch.empty(B * Tp, self.cfg.n_embd, dtype=F32, device=self.device)
-        self._trunk_fwd(ws, idx, B, Tp, T, act, pr, pa, seeds, lnf_f32=out, doc=doc)
+        self._trunk_fwd(ws, idx, B, Tp, T, act, pr, pa, seeds, lnf_f32=out, doc=doc, reset=reset)
         return out.view(B, Tp, -1)[:, :T]
 
     def _trunk_backward_module(self, dy):

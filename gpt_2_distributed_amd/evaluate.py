@@ -1,6 +1,6 @@
 """Evaluate a checkpoint on a token-shard split: ``python -m gpt_2_distributed_amd.evaluate --checkpoint out/step_0001000
 --model 124M --data_dir D [--split val] [--batch 8] [--seq_len 1024] [--max_batches N] [--per_token OUT.npy]
-[--doc_mask [--eot_token_id 50256] [--eot_position end|begin]]``.
+[--doc_mask [--eot_token_id 50256] [--eot_position end|begin] [--reset_positions]]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (as generate.py does), runs ``GPT2.evaluate`` under bf16 autocast
 over the split's windows in order (``dataloader.iter_eval_batches``, one rank) and prints one JSON line
@@ -8,10 +8,10 @@ over the split's windows in order (``dataloader.iter_eval_batches``, one rank) a
 trainer's ``--eval_batch`` / ``--eval_steps`` / ``--seq_len`` as ``--batch`` / ``--max_batches`` / ``--seq_len`` the loss
 is the ``val_loss`` a one-rank training run printed at that step. ``--per_token`` also saves the fp32 per-token values
 [batches * batch, seq_len] (``GPT2.score(reduction="none")``) as a .npy file. ``--doc_mask`` scores every window under
-document masking, as the trainer's flag of that name trains (the bounds from the window's own tokens)."""
+document masking, as the trainer's flag of that name trains (the bounds from the window's own tokens);
+``--reset_positions``, valid only with it, also restarts the position embedding at every document, as the trainer's."""
 from __future__ import annotations
 
-import argparse
 import json
 import os
 import pathlib
@@ -23,11 +23,11 @@ from . import dataloader as gpt2_dataloader
 from .generate import load_model
 from .model import MODEL_SIZES
 from .packing import doc_bounds
-from .train_gpt2_distributed import add_doc_mask_arguments, doc_mask_from_args
+from .train_gpt2_distributed import DocMaskParser, add_doc_mask_arguments, doc_mask_from_args
 
 
 def parse_args(argv=None):
-    p = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    p = DocMaskParser(description=__doc__.split("\n\n")[0])
     p.add_argument("--checkpoint", required=True, help="a step_XXXXXXX directory written by save_checkpoint")
     p.add_argument("--model", default="124M", choices=sorted(MODEL_SIZES) + ["auto"])
     p.add_argument("--data_dir", required=True)
@@ -60,7 +60,8 @@ def main(argv=None) -> int:
 
             def bounds(x):
                 return doc_bounds(x, doc["eot_token_id"], doc["eot"]) if doc else None
-            rows = [model.score(x, y.to("cuda:0"), reduction="none", doc_bounds=bounds(x)).cpu()
+            reset = doc.get("reset_positions", False)
+            rows = [model.score(x, y.to("cuda:0"), reduction="none", doc_bounds=bounds(x), reset_positions=reset).cpu()
                     for x, y in ((x.to("cuda:0"), y) for x, y in batches())]
             np.save(a.per_token, torch.cat(rows).numpy() if rows else np.zeros((0, a.seq_len), dtype=np.float32))
     if not res["tokens"]:

@@ -89,6 +89,13 @@ class _OwnedByGPT2:
         return owner.engine()
 
 
+def _checked_reset(reset_positions, given: bool, needs: str) -> bool:
+    """``reset_positions`` as a bool; ValueError when it is on without the bounds it restarts at."""
+    if reset_positions and not given:
+        raise ValueError(f"reset_positions=True needs {needs}: positions restart at document boundaries")
+    return bool(reset_positions)
+
+
 def _checked_bounds(doc_bounds, x) -> Optional[DocBounds]:
     """``doc_bounds`` checked against the leading [B, T] of ``x`` (idx or activations) and its device: ValueError on a
     wrong shape, dtype or device; the tensors are not read."""
@@ -179,8 +186,11 @@ class GPT2Backbone(_OwnedByGPT2, nn.Module):
     def max_seq_len(self):
         return self.cfg.n_positions
 
-    def forward(self, idx: torch.Tensor, doc_bounds: Optional[DocBounds] = None) -> torch.Tensor:
-        """Embeddings -> blocks -> ln_f (model.py:275-313); returns the fp32 ln_f output [B,T,C]."""
+    def forward(self, idx: torch.Tensor, doc_bounds: Optional[DocBounds] = None,
+                reset_positions: bool = False) -> torch.Tensor:
+        """Embeddings -> blocks -> ln_f (model.py:275-313); returns the fp32 ln_f output [B,T,C]. ``doc_bounds`` and
+        ``reset_positions`` as in ``GPT2.forward``."""
+        reset_positions = _checked_reset(reset_positions, doc_bounds is not None, "doc_bounds")
         doc_bounds = _checked_bounds(doc_bounds, idx)
         B, T = idx.size()
         if T > self.cfg.n_positions:
@@ -189,7 +199,7 @@ class GPT2Backbone(_OwnedByGPT2, nn.Module):
         if not idx.is_cuda:
             raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda "
                                "device (there is no CPU fallback)")
-        return eng.backbone_forward(idx, doc_bounds)
+        return eng.backbone_forward(idx, doc_bounds, reset_positions)
 
 
 class GPT2(nn.Module):
@@ -277,10 +287,15 @@ class GPT2(nn.Module):
     # ---- forward -----------------------------------------------------------------------------------
     def forward(self, idx: torch.Tensor, labels: Optional[torch.Tensor] = None,
                 targets: Optional[torch.Tensor] = None, *,
-                doc_bounds: Optional[DocBounds] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+                doc_bounds: Optional[DocBounds] = None,
+                reset_positions: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """``doc_bounds``: the ``packing.DocBounds`` of ``idx`` (``packing.doc_bounds(idx, eot_token_id)`` forms them on
-        the device): every token attends only to the earlier tokens of its own document. Positions stay absolute.
-        ``None``: plain causal attention, the kernel launches as they were."""
+        the device): every token attends only to the earlier tokens of its own document. ``None``: plain causal
+        attention, the kernel launches as they were. Positions stay absolute (``wpe[t]``) unless ``reset_positions``:
+        then, with ``doc_bounds``, a token takes the position embedding of its offset in its document
+        (``packing.doc_positions``), so a document sees the inputs it would see alone in the row; ValueError without
+        ``doc_bounds``. Off, the embedding launches are the ones they were."""
+        reset_positions = _checked_reset(reset_positions, doc_bounds is not None, "doc_bounds")
         if targets is not None:
             if labels is not None:
                 raise ValueError("pass labels or targets, not both")
@@ -292,7 +307,7 @@ class GPT2(nn.Module):
         if not idx.is_cuda or not self._arena.is_cuda:
             raise RuntimeError("gpt_2_distributed_amd.GPT2 runs only on the MI355X HIP path: move the model and "
                                "inputs to a cuda device (there is no CPU fallback)")
-        return self.engine().forward(idx, labels, doc_bounds)
+        return self.engine().forward(idx, labels, doc_bounds, reset_positions)
 
     # ---- evaluation (the reference has none) ----------------------------------------------------------------
     def _check_inputs(self, idx):
@@ -304,10 +319,11 @@ class GPT2(nn.Module):
                                "inputs to a cuda device (there is no CPU fallback)")
 
     def score(self, idx: torch.Tensor, labels: torch.Tensor, reduction: str = "mean",
-              doc_bounds: Optional[DocBounds] = None) -> torch.Tensor:
+              doc_bounds: Optional[DocBounds] = None, reset_positions: bool = False) -> torch.Tensor:
         """The negative log-likelihood of ``labels`` [B, T] under the model, forward only: ``"none"`` the fp32 per-token
         values [B, T] (0 where the label is -100), ``"sum"`` their sum, ``"mean"`` sum / number of labels != -100 (what
-        ``forward(idx, labels)[1]`` computes in eval mode). Same argument checks as ``forward``; ``doc_bounds`` as there.
+        ``forward(idx, labels)[1]`` computes in eval mode). Same argument checks as ``forward``; ``doc_bounds`` and
+        ``reset_positions`` as there.
 
         Under bf16 autocast (or ``precision == "bf16"``) the lm_head runs fused with the cross-entropy
         (``gpt2mi_lm_loss``): no logits tensor exists and the label's logit and the log-sum-exp are taken from the fp32
@@ -317,23 +333,26 @@ class GPT2(nn.Module):
         reads (weights, shadows, gradients, optimizer state, dropout stream, training workspace). Not differentiable: the results carry no graph, whatever the grad mode."""
         if reduction not in ("mean", "sum", "none"):
             raise ValueError(f"reduction must be 'mean', 'sum' or 'none' (got {reduction!r})")
+        reset_positions = _checked_reset(reset_positions, doc_bounds is not None, "doc_bounds")
         doc_bounds = _checked_bounds(doc_bounds, idx)
         self._check_inputs(idx)
-        rows, s, _, mean = self.engine().score(idx, labels, doc=doc_bounds)
+        rows, s, _, mean = self.engine().score(idx, labels, doc=doc_bounds, reset=reset_positions)
         if reduction == "none":
             return rows.clone()
         return (s if reduction == "sum" else mean).reshape(()).clone()
 
     def evaluate(self, batches, max_batches: Optional[int] = None, eot_token_id: Optional[int] = None,
-                 eot: str = "end") -> dict:
+                 eot: str = "end", reset_positions: bool = False) -> dict:
         """``{"loss", "ppl", "tokens"}`` over the ``(idx, labels)`` pairs of ``batches`` (at most ``max_batches``):
         loss = sum of the token losses / number of tokens over ALL batches (token-weighted, not a mean of batch means),
         ppl = exp(loss). The sums stay on the device (``gpt2mi_lm_loss``'s accumulate mode) and the host synchronises
         once, at the end. With ``torch.distributed`` initialised the two sums are all-reduced before the division, so
         every rank returns the same numbers; every rank must then be given the same number of batches (a collective).
         With ``eot_token_id`` every batch is scored under document masking: its bounds are formed on the device from its
-        ``idx`` (``packing.doc_bounds(idx, eot_token_id, eot)``, ``eot`` = ``"end"`` or ``"begin"``)."""
+        ``idx`` (``packing.doc_bounds(idx, eot_token_id, eot)``, ``eot`` = ``"end"`` or ``"begin"``), and with
+        ``reset_positions`` also with positions restarting at every document (ValueError without ``eot_token_id``)."""
         import torch.distributed as dist
+        reset_positions = _checked_reset(reset_positions, eot_token_id is not None, "eot_token_id")
         if eot not in EOT_POSITIONS:
             raise ValueError(f"eot must be one of {EOT_POSITIONS}, got {eot!r}")
         if eot_token_id is not None and (isinstance(eot_token_id, bool) or not isinstance(eot_token_id, int)
@@ -357,7 +376,7 @@ class GPT2(nn.Module):
                 acc[1].zero_()
                 pending = 0
             doc = None if eot_token_id is None else _doc_bounds(idx, eot_token_id, eot)
-            eng.score(idx, labels, acc=acc, doc=doc)
+            eng.score(idx, labels, acc=acc, doc=doc, reset=reset_positions)
             pending += idx.numel()
         total += torch.cat(acc).double()
         if dist.is_available() and dist.is_initialized():

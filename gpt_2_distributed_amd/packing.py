@@ -1,9 +1,11 @@
-"""Document masking for packed sequences: the rule, in plain torch, and the bounds kernel's binding.
+"""Document masking and per-document positions for packed sequences: the rules, in plain torch, and the bounds
+kernel's binding.
 
 A training row is a fixed window of a token stream, so it usually holds several unrelated documents separated by an
 end-of-text token. With document masking a token attends only to the earlier tokens of its own document
 (block-diagonal causal attention). This module states the contract of the kernels that implement it
-(csrc/packing.hip, the ``_doc`` entries of csrc/attention.hip and csrc/fp32.hip) as pure-torch functions.
+(csrc/packing.hip, the ``_doc`` entries of csrc/attention.hip, csrc/fp32.hip and csrc/norm_embed.hip) as pure-torch
+functions.
 
 The mask. Row ``b`` of a batch is partitioned into documents, contiguous intervals ``[s, e)``. ``DocBounds(start, end)``
 holds two contiguous int32 ``[B, T]`` device tensors with, for every ``t``::
@@ -13,7 +15,23 @@ holds two contiguous int32 ``[B, T]`` device tensors with, for every ``t``::
 Query ``t`` attends key ``k`` iff ``start[b, t] <= k <= t``; given ``k <= t`` that is the same as ``t < end[b, k]``
 (the forward and dQ kernels, which own queries, read ``start``; the dK/dV kernel, which owns keys, reads ``end``). The
 softmax, its fp32 statistics and the dropout decision of a pair (query, key) are those of the unmasked kernels, and
-no row is ever fully masked: key ``t`` is visible to query ``t``. Positions stay absolute (``wpe[t]``).
+no row is ever fully masked: key ``t`` is visible to query ``t``.
+
+Positions. By default they stay absolute: token ``t`` of a row takes ``wpe[t]`` whatever document it is in. The option
+(``reset_positions=True`` beside ``doc_bounds``) restarts them at every document, ``doc_positions(bounds)``::
+
+    pos[b, t] = t - start[b, t]
+    x[b, t]   = drop(wte[idx[b, t]] + wpe[pos[b, t]])                       for t < T_valid
+    dwte[idx[b, t]] += g[b, t],   dwpe[p] += sum of g[b, t] over the (b, t) with t < T_valid and pos[b, t] == p
+
+with ``g = drop'(dres)``. With it, and with dropout off, a document inside a packed row produces the activations, logits
+and loss terms it produces alone in a row, up to rounding. The dropout decision of an element stays the hash of
+``(seed, row * C + e)``: it depends on the row, not on the position. Padding rows ``t >= T_valid`` are exact zeros with no
+table read, whatever the bounds say there. Rows of ``wpe`` and ``dwpe`` from the longest document's length on are
+neither read nor written. ``dwpe`` is summed without floating-point atomics, in an order fixed by the inputs: two runs give the same
+bits. A ``start`` outside ``[0, t]`` is clamped into it where it is read (``gpt2mi_embed_fwd_doc`` /
+``gpt2mi_embed_bwd_doc``), as the attention kernels clamp it: wrong bounds give wrong numbers, never an access out of
+range.
 
 Bounds from tokens. A document begins at position ``p`` when ``idx[p - 1]`` is the separator (``eot="end"``: the
 separator is the last token of the document it closes, nanoGPT's data preparation) or when ``idx[p]`` is
@@ -180,6 +198,15 @@ def doc_mask(bounds: DocBounds) -> torch.Tensor:
     T = start.shape[1]
     k = torch.arange(T, device=start.device)
     return (k[None, None, :] >= start[:, :, None]) & (k[None, None, :] <= k[None, :, None])
+
+
+def doc_positions(bounds: DocBounds) -> torch.Tensor:
+    """The position of every token in its own document, int32 [B, T]: ``pos[b, t] = t - start[b, t]`` (0 at the first
+    token of every document). What ``reset_positions=True`` indexes ``wpe`` with."""
+    start = bounds.start
+    T = start.shape[1]
+    t = torch.arange(T, dtype=torch.int32, device=start.device)
+    return (t[None, :] - start.to(torch.int32)).contiguous()
 
 
 def doc_attention_reference(q, k, v, bounds: DocBounds, dO=None, scale=None, dtype=torch.float64):

@@ -15,7 +15,10 @@
     packed sequences: --doc_mask [--eot_token_id 50256] [--eot_position end|begin]: document masking, a token attends
         only to the earlier tokens of its own document; the bounds of every micro-batch are formed on the device from
         its tokens (packing.doc_bounds), for the training forward and for --eval_every alike; end: the separator closes
-        a document (nanoGPT's data preparation), begin: it opens one (llm.c's). Positions stay absolute
+        a document (nanoGPT's data preparation), begin: it opens one (llm.c's). Positions stay absolute unless
+        --reset_positions (valid only with --doc_mask): then a token takes the position embedding of its offset in its
+        document (packing.doc_positions), in the training forward and the --eval_every pass alike, so a document sees
+        the positions generate() shows it
 
 Loop semantics follow the reference (:374-457): seed 42; loss/grad_accum; backward; every
 grad_accum micro-steps the fused AdamW step (which also yields the clip_grad_norm_(inf) value);
@@ -51,8 +54,19 @@ SEED = 42
 PEAK_BF16 = 2.5166e15
 
 
+class DocMaskParser(argparse.ArgumentParser):
+    """An ArgumentParser that refuses --reset_positions without --doc_mask (add_doc_mask_arguments), as a usage error
+    at parse time: before anything is built or a device is touched. Shared with evaluate.py."""
+
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        if getattr(a, "reset_positions", False) and not getattr(a, "doc_mask", False):
+            self.error("--reset_positions needs --doc_mask: positions restart at the documents it finds")
+        return a
+
+
 def build_parser():
-    p = argparse.ArgumentParser()
+    p = DocMaskParser()
     p.add_argument("--data_dir", required=False, help="Path to data directory containing .bin files.")
     p.add_argument("--training_mode", choices=["fsdp", "ddp", "local"], default="local")
     p.add_argument("--device", default="cuda")
@@ -106,15 +120,21 @@ def add_doc_mask_arguments(p) -> None:
     p.add_argument("--eot_token_id", type=int, default=50256, help="the document separator (GPT-2's <|endoftext|>)")
     p.add_argument("--eot_position", choices=list(EOT_POSITIONS), default="end",
                    help="end: the separator is the last token of the document it closes; begin: it opens a document")
+    p.add_argument("--reset_positions", action="store_true",
+                   help="with --doc_mask: the position embedding restarts at 0 at every document")
 
 
 def doc_mask_from_args(args) -> dict:
-    """{} without --doc_mask, else evaluate()'s keywords eot_token_id / eot (validated once, before anything is built)."""
+    """{} without --doc_mask, else evaluate()'s keywords eot_token_id / eot, and reset_positions when that flag is set
+    (validated once, before anything is built)."""
     if not args.doc_mask:
         return {}
     if args.eot_token_id < 0:
         raise SystemExit("--eot_token_id must be >= 0")
-    return dict(eot_token_id=args.eot_token_id, eot=args.eot_position)
+    doc = dict(eot_token_id=args.eot_token_id, eot=args.eot_position)
+    if getattr(args, "reset_positions", False):
+        doc["reset_positions"] = True
+    return doc
 
 
 def eval_from_args(args) -> dict:
@@ -364,7 +384,8 @@ def main(argv=None):
             with ctx:
                 with torch.autocast("cuda", dtype=torch.bfloat16):  # as train_gpt2_distributed.py:404
                     if doc:
-                        _, loss = model(x, labels=y, doc_bounds=doc_bounds(x, doc["eot_token_id"], doc["eot"]))
+                        _, loss = model(x, labels=y, doc_bounds=doc_bounds(x, doc["eot_token_id"], doc["eot"]),
+                                        reset_positions=doc.get("reset_positions", False))
                     else:
                         _, loss = model(x, labels=y)
                     loss = loss / args.grad_accum_steps

@@ -28,7 +28,7 @@ extern "C" {
 
 #define GPT2MI_ABI_VERSION 24
 /* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
-#define GPT2MI_ABI_MINOR 5
+#define GPT2MI_ABI_MINOR 6
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -43,6 +43,16 @@ int gpt2mi_embed_fwd(const int64_t* idx, const float* wte, const float* wpe, flo
  * t >= T_valid are skipped. */
 int gpt2mi_embed_bwd(const int64_t* idx, const float* dres, float* dwte, float* dwpe, int B, int T, int T_valid,
                      int C, float p, uint64_t seed, void* stream);
+/* v24.6: the two above with positions that restart at every document of a packed row (packing.py doc_positions):
+ * x[b,t,:] = drop(wte[idx[b,t],:] + wpe[t - start[b,t],:]) and dwpe[p] += the sum of g[b,t] over the rows with
+ * t - start[b,t] == p, formed without floating-point atomics in an order fixed by the inputs. start is the int32 [B, T] doc_start of
+ * gpt2mi_doc_bounds; a value outside [0, t] is clamped where it is read. The dropout decision of an element is the
+ * one of the entries above. Rows t >= T_valid are padding as above (start is not read there); rows of wpe and dwpe
+ * from the longest document's length on are neither read nor written. */
+int gpt2mi_embed_fwd_doc(const int64_t* idx, const float* wte, const float* wpe, float* x, const int* start, int B,
+                         int T, int T_valid, int C, float p, uint64_t seed, void* stream);
+int gpt2mi_embed_bwd_doc(const int64_t* idx, const float* dres, float* dwte, float* dwpe, const int* start, int B,
+                         int T, int T_valid, int C, float p, uint64_t seed, void* stream);
 
 /* K2: nn.LayerNorm forward — model.py:204,210,247 (used :215,218,311). y_bf16 and/or y_f32 may be NULL. */
 int gpt2mi_layernorm_fwd(const float* x, const float* w, const float* b, uint16_t* y_bf16, float* y_f32,
