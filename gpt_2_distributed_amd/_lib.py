@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
 # additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
-ABI_MINOR = 6
+ABI_MINOR = 7
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -171,6 +171,16 @@ _SIGS = {
     # v24.6 positions per document: the embedding lists with doc_start before B
     "gpt2mi_embed_fwd_doc": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
     "gpt2mi_embed_bwd_doc": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p],
+    # v24.7 deterministic mode: the lists of the entries they replace with the workspace before the stream
+    "gpt2mi_det_workspace_bytes": [_c_int, _c_int, _c_int, _c_int],
+    "gpt2mi_colsum_det_bf16": [_p, _p, _c_int, _c_int, _c_int, _p, _p],
+    "gpt2mi_colsum_det_f32": [_p, _p, _c_int, _c_int, _c_int, _p, _p],
+    "gpt2mi_layernorm_bwd_det": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_float, _c_u64, _c_int, _p,
+                                 _p],
+    "gpt2mi_layernorm_bwd_det_f32": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _c_int, _c_int, _c_float, _c_u64, _c_int,
+                                     _p, _p],
+    "gpt2mi_embed_bwd_det": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p, _p],
+    "gpt2mi_embed_bwd_doc_det": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p, _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
@@ -179,10 +189,14 @@ _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_deco
                 "gpt2mi_gemm_wgrad_batch_max": 3, "gpt2mi_sample_constrained": 4,
                 "gpt2mi_decode_generate_constrained": 4, "gpt2mi_doc_bounds": 5, "gpt2mi_attn_fwd_doc": 5,
                 "gpt2mi_attn_bwd_doc": 5, "gpt2mi_attn_fwd_f32_doc": 5, "gpt2mi_attn_bwd_f32_doc": 5,
-                "gpt2mi_embed_fwd_doc": 6, "gpt2mi_embed_bwd_doc": 6}
+                "gpt2mi_embed_fwd_doc": 6, "gpt2mi_embed_bwd_doc": 6,
+                **{n: 7 for n in ("gpt2mi_det_workspace_bytes", "gpt2mi_colsum_det_bf16", "gpt2mi_colsum_det_f32",
+                                  "gpt2mi_layernorm_bwd_det", "gpt2mi_layernorm_bwd_det_f32", "gpt2mi_embed_bwd_det",
+                                  "gpt2mi_embed_bwd_doc_det")}}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
-             "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size}
+             "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size,
+             "gpt2mi_det_workspace_bytes": _c_size}
 
 EXPORTED = tuple(_SIGS)
 
@@ -322,6 +336,36 @@ def layernorm_bwd(x, w, mean, rstd, dy, dres, dw, db, out_bf16, dbias_out, M, C,
 
 def colsum_bf16(g, db, M, N, ld):
     _call("gpt2mi_colsum_f32" if _f32(g) else "gpt2mi_colsum_bf16", _ptr(g), _ptr(db), M, N, ld, _stream())
+
+
+# ---- the deterministic mode (gpt2mi.h v24.7): the bindings above with a workspace, sums in a fixed order -----------
+def det_workspace_bytes(B, T, C, Nmax) -> int:
+    """Bytes of the workspace that serves every ``*_det`` call on at most B * T rows of width C and column sums of at
+    most Nmax columns."""
+    return int(load().gpt2mi_det_workspace_bytes(B, T, C, Nmax))
+
+
+def colsum_det(g, db, M, N, ld, workspace):
+    _call("gpt2mi_colsum_det_f32" if _f32(g) else "gpt2mi_colsum_det_bf16", _ptr(g), _ptr(db), M, N, ld,
+          _ptr(workspace), _stream())
+
+
+def layernorm_bwd_det(x, w, mean, rstd, dy, dres, dw, db, out_bf16, dbias_out, M, C, p_out=0.0, seed_out=0,
+                      dres_init=False, workspace=None):
+    name = "gpt2mi_layernorm_bwd_det_f32" if _f32(dy) else "gpt2mi_layernorm_bwd_det"
+    _call(name, _ptr(x), _ptr(w), _ptr(mean), _ptr(rstd), _ptr(dy), _ptr(dres), _ptr(dw), _ptr(db), _ptr(out_bf16),
+          _ptr(dbias_out), M, C, p_out, seed_out, int(dres_init), _ptr(workspace), _stream())
+
+
+def embed_bwd_det(idx, dres, dwte, dwpe, B, T, C, p=0.0, seed=0, T_valid=None, workspace=None):
+    _call("gpt2mi_embed_bwd_det", _ptr(idx), _ptr(dres), _ptr(dwte), _ptr(dwpe), B, T,
+          T if T_valid is None else T_valid, C, p, seed, _ptr(workspace), _stream())
+
+
+def embed_bwd_doc_det(idx, dres, dwte, dwpe, start, B, T, C, p=0.0, seed=0, T_valid=None, workspace=None):
+    _call("gpt2mi_embed_bwd_doc_det", _ptr(idx), _ptr(dres), _ptr(dwte), _ptr(dwpe),
+          _doc_start("embed_bwd_doc_det", start, B, T), B, T, T if T_valid is None else T_valid, C, p, seed,
+          _ptr(workspace), _stream())
 
 
 def gemm(layout, epilogue, M, N, K, A, lda, B, ldb, C, ldc, bias=None, resid=None, aux=None, ldaux=0,

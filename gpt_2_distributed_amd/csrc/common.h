@@ -95,6 +95,17 @@ struct SamePos {
     for (int& p : v) p = pos;
   }
 };
+
+// The deterministic mode (csrc/deterministic.hip) reuses two launches of csrc/norm_embed.hip. The LayerNorm backward
+// with its flush redirected: block k's column sums of dw / db / dbias_out (those wanted) stored to parts[k][3][C],
+// *blocks = the number of blocks (<= 512); dy / out are bf16 or, with f32, float. And the position-table kernel of
+// gpt2mi_embed_bwd_doc alone.
+int layernorm_bwd_partials(int f32, const float* x, const float* w, const float* mean, const float* rstd,
+                           const void* dy, float* dres, bool want_dw, bool want_db, void* out, bool want_dbias, int M,
+                           int C, float p_out, uint64_t seed_out, int dres_init, float* parts, int* blocks,
+                           void* stream);
+int embed_bwd_doc_wpe(const float* dres, const int* start, float* dwpe, int B, int T, int T_valid, int C, float p,
+                      uint64_t seed, void* stream);
 }  // namespace gpt2mi
 
 #define GPT2MI_REQUIRE(cond, ...)                  \

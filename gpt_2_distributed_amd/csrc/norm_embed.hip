@@ -130,7 +130,11 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // and, for the NEXT backward GEMM of the residual branch below this LN, emits
 //   out_bf[m] = bf16(dres_new[m] * keep/(1-p))  and  dbias_out += colsum(out_bf)
 // (the branch's dropout mask regenerated from (seed,row*C+c); dbias_out = that branch's bias grad).
-template <int VEC, int NV, typename TG>
+// DET = false is the kernel as it always was: the flush adds the block's column sums with one float atomic per column.
+// DET = true is the deterministic mode's instantiation (csrc/deterministic.hip): dw / db / dbias_out then point at the
+// first block's rows of a partials table [blocks][3][C] and the flush stores the block's sums there; the table is
+// added up in a fixed order afterwards. Rows, waves and blocks are assigned alike, so dres and out_bf are the same bits.
+template <int VEC, int NV, typename TG, bool DET = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ mean,
     const float* __restrict__ rstd, const TG* __restrict__ dy, float* __restrict__ dres,
@@ -222,7 +226,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(
       float s = 0.f;
 #pragma unroll
       for (int q = 0; q < kWaves; ++q) s += smem[q * C + c];
-      atomicAdd(dst + c, s);
+      if constexpr (DET) dst[(size_t)blockIdx.x * 3 * C + c] = s;
+      else atomicAdd(dst + c, s);
     }
     __syncthreads();
   };
@@ -566,10 +571,14 @@ GPT2MI_EXPORT int gpt2mi_layernorm_fwd(const float* x, const float* w, const flo
   return gpt2mi::check_launch("layernorm_fwd");
 }
 
+// parts = nullptr: the atomic flush into dw / db / dbias_out. Otherwise the deterministic mode's launch: the blocks'
+// column sums go to parts[block][3][C] (the slots of dw, db, dbias_out; one whose pointer is null is not written) and
+// *blocks is the number of blocks, for the ordered sum that follows (csrc/deterministic.hip).
 template <typename TG>
 static int layernorm_bwd_t(const float* x, const float* w, const float* mean, const float* rstd, const TG* dy,
                            float* dres, float* dw, float* db, TG* out, float* dbias_out, int M, int C, float p_out,
-                           uint64_t seed_out, int dres_init, void* stream) {
+                           uint64_t seed_out, int dres_init, void* stream, float* parts = nullptr,
+                           int* blocks = nullptr) {
   int vec, nv;
   GPT2MI_REQUIRE(row_shape(C, &vec, &nv), "layernorm_bwd: unsupported C=%d", C);
   GPT2MI_REQUIRE(p_out <= 0.f || (size_t)M * C < (1ull << 33),
@@ -585,10 +594,45 @@ GPT2MI_PRODUCT_KNOB(LN_BWD_MAX_BLOCKS, 512);
   const size_t sh = (size_t)kWaves * C * sizeof(float);
   const uint32_t thr = drop_threshold(p_out);
   const float ik = p_out > 0.f ? 1.f / (1.f - p_out) : 1.f;
+  if (parts) {
+    *blocks = g;
+    float* pw = dw ? parts : nullptr;
+    float* pb = db ? parts + C : nullptr;
+    float* po = dbias_out ? parts + 2 * C : nullptr;
+#define X(V, N) if (vec == V && nv == N) ln_bwd_kernel<V, N, TG, true><<<g, 256, sh, s>>>(x, w, mean, rstd, dy, dres, pw, pb, out, po, M, C, nv, seed_out, thr, ik, dres_init);
+    GPT2MI_ROW_CASES(X)
+#undef X
+    return gpt2mi::check_launch("layernorm_bwd_det");
+  }
 #define X(V, N) if (vec == V && nv == N) ln_bwd_kernel<V, N, TG><<<g, 256, sh, s>>>(x, w, mean, rstd, dy, dres, dw, db, out, dbias_out, M, C, nv, seed_out, thr, ik, dres_init);
   GPT2MI_ROW_CASES(X)
 #undef X
   return gpt2mi::check_launch("layernorm_bwd");
+}
+
+// The deterministic mode's halves that live in this unit (gpt2mi namespace, common.h): the LayerNorm backward's
+// partials launch and the position-table kernel of the restarting-positions embedding backward, both reused as they are.
+int gpt2mi::layernorm_bwd_partials(int f32, const float* x, const float* w, const float* mean, const float* rstd,
+                                   const void* dy, float* dres, bool want_dw, bool want_db, void* out, bool want_dbias,
+                                   int M, int C, float p_out, uint64_t seed_out, int dres_init, float* parts,
+                                   int* blocks, void* stream) {
+  float* one = parts;  // any non-null pointer: layernorm_bwd_t only asks which of the three are wanted
+  if (f32)
+    return layernorm_bwd_t<float>(x, w, mean, rstd, (const float*)dy, dres, want_dw ? one : nullptr,
+                                  want_db ? one : nullptr, (float*)out, want_dbias ? one : nullptr, M, C, p_out,
+                                  seed_out, dres_init, stream, parts, blocks);
+  return layernorm_bwd_t<bf16>(x, w, mean, rstd, (const bf16*)dy, dres, want_dw ? one : nullptr,
+                               want_db ? one : nullptr, (bf16*)out, want_dbias ? one : nullptr, M, C, p_out, seed_out,
+                               dres_init, stream, parts, blocks);
+}
+
+int gpt2mi::embed_bwd_doc_wpe(const float* dres, const int* start, float* dwpe, int B, int T, int T_valid, int C,
+                              float p, uint64_t seed, void* stream) {
+  const uint32_t thr = drop_threshold(p);
+  const float ik = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const dim3 grid(T_valid, (C + 64 * kDocCh - 1) / (64 * kDocCh));
+  embed_bwd_doc_wpe_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(dres, start, dwpe, B, T, T_valid, C, seed, thr, ik);
+  return gpt2mi::check_launch("embed_bwd_doc_det");
 }
 
 GPT2MI_EXPORT int gpt2mi_layernorm_bwd(const float* x, const float* w, const float* mean, const float* rstd,

@@ -144,10 +144,14 @@ class BlockActs:
 class Scratch:
     """Backward scratch of one (B, T) shape (also used by the stand-alone sub-module backwards)."""
 
-    def __init__(self, cfg, B, T, vpad, device, act, head=True):
+    def __init__(self, cfg, B, T, vpad, device, act, head=True, det=False):
         C, H = cfg.n_embd, cfg.n_head
         M = B * T
         e = lambda *s, dt=act: act_empty(*s, dtype=dt, device=device)  # noqa: E731
+        # the deterministic mode (model.deterministic): the workspace of the ordered column sums, LayerNorm backward and
+        # token-table gradient (one launch at a time uses it); None = the default mode's launches
+        self.det_ws = torch.empty(K.det_workspace_bytes(B, T, C, 4 * C), dtype=torch.uint8, device=device) if det \
+            else None
         self.dres = e(M, C, dt=F32)
         self.dres_bf = e(M, C)
         self.dln = e(M, C)
@@ -171,8 +175,8 @@ class Scratch:
 
 
 class Workspace(Scratch):
-    def __init__(self, cfg, B: int, T: int, vpad: int, device, act=BF16):
-        super().__init__(cfg, B, T, vpad, device, act, head=True)
+    def __init__(self, cfg, B: int, T: int, vpad: int, device, act=BF16, det=False):
+        super().__init__(cfg, B, T, vpad, device, act, head=True, det=det)
         L, C = cfg.n_layer, cfg.n_embd
         M = B * T
         e = lambda *s, dt=act: act_empty(*s, dtype=dt, device=device)  # noqa: E731
@@ -232,6 +236,7 @@ class _DeferredBlock:
 
     def __init__(self, S, e, M, C):
         self.dres, self.dln, self.delta, self.dqkv_cs, self.wgrad_ws = S.dres, S.dln, S.delta, S.dqkv_cs, S.wgrad_ws
+        self.det_ws = S.det_ws
         self.dres_bf = e(M, C)  # the fc2 branch gradient (written by the LayerNorm backward of the block above)
         self.dproj = e(M, C)    # the proj branch gradient
         self.dU = e(M, 4 * C)
@@ -739,12 +744,50 @@ class Engine:
             self.grad_sync.end_backward()
 
     def workspace(self, B, T, act=BF16) -> Workspace:
+        det = self.deterministic(act)
         key = (B, T, act)
-        if key not in self._ws:
+        if key not in self._ws or (self._ws[key].det_ws is not None) != det:  # (the flag may change between steps)
             self._ws.clear()  # one live shape at a time keeps HBM use bounded
             torch.cuda.empty_cache()
-            self._ws[key] = Workspace(self.cfg, B, T, self.vpad, self.device, act)
+            self._ws[key] = Workspace(self.cfg, B, T, self.vpad, self.device, act, det=det)
         return self._ws[key]
+
+    # ---- the deterministic mode ------------------------------------------------------------------------
+    def deterministic(self, act) -> bool:
+        """``model.deterministic``: every sum of the backward in an order fixed by the inputs. The
+        scratch of a backward carries the mode (Scratch.det_ws); the helpers below launch by it. bf16 widths that are
+        not multiples of 64 form their weight gradients with float atomics (gemm EPI_ATOMIC) and have no ordered
+        replacement."""
+        if not getattr(self.model, "deterministic", False):
+            return False
+        if act == BF16 and self.cfg.n_embd % 64 != 0:
+            raise NotImplementedError(
+                f"deterministic=True with bf16 and n_embd={self.cfg.n_embd}: widths that are not multiples of 64 take "
+                "the atomic weight-gradient fallback (EPI_ATOMIC), which has no ordered replacement; use fp32 or a "
+                "width that is a multiple of 64")
+        return True
+
+    @staticmethod
+    def _ln_bwd(S, *a, **kw):
+        if S.det_ws is not None:
+            K.layernorm_bwd_det(*a, workspace=S.det_ws, **kw)
+        else:
+            K.layernorm_bwd(*a, **kw)
+
+    @staticmethod
+    def _colsum(S, g, db, M, N, ld):
+        if S.det_ws is not None:
+            K.colsum_det(g, db, M, N, ld, S.det_ws)
+        else:
+            K.colsum_bf16(g, db, M, N, ld)
+
+    @staticmethod
+    def _branch_bwd(S, dres, out, dbias, M, C, pr, seed):
+        if S.det_ws is not None:  # the kernel without its atomic bias sum, then the ordered sum of what it stored
+            K.branch_bwd(dres, out, None, M, C, pr, seed)
+            K.colsum_det(out, dbias, M, C, C, S.det_ws)
+        else:
+            K.branch_bwd(dres, out, dbias, M, C, pr, seed)
 
     def eval_workspace(self, B, T, act=BF16) -> EvalWorkspace:
         key = (B, T, act)
@@ -959,8 +1002,11 @@ class Engine:
         here when ``flush``) and the fc1 bias grad."""
         C = self.cfg.n_embd
         pre = f"transformer.h.{l}."
+        det = S.det_ws is not None  # then the fc1 bias grad is an ordered column sum of the stored dU
         self._dgrad(act, M, S.dU, dY, pre + "mlp.fc2.weight", 4 * C, C, K.EPI_GELU_BWD, aux=A.dgelu, ldaux=4 * C,
-                    dbias=self.g(pre + "mlp.fc1.bias"))
+                    dbias=None if det else self.g(pre + "mlp.fc1.bias"))
+        if det:
+            K.colsum_det(S.dU, self.g(pre + "mlp.fc1.bias"), M, 4 * C, 4 * C, S.det_ws)
         self._wgrad_or_defer(S, act, C, 4 * C, M, dY, C, A.h, 4 * C, self.g(pre + "mlp.fc2.weight"), defer)
         self._dgrad(act, M, dx_out, S.dU, pre + "mlp.fc1.weight", C, 4 * C)
         self._wgrad_or_defer(S, act, 4 * C, C, M, S.dU, 4 * C, A.ln2, C, self.g(pre + "mlp.fc1.weight"), defer)
@@ -980,9 +1026,9 @@ class Engine:
         self._dgrad(act, M, dx_out, S.dqkv, pre + "attn.qkv.weight", C, 3 * C)
         self._wgrad_or_defer(S, act, 3 * C, C, M, S.dqkv, 3 * C, A.ln1, C, self.g(pre + "attn.qkv.weight"), defer)
         if S.dqkv_cs is not None:  # qkv bias grad: sum the attention backward's 32-token partials
-            K.colsum_bf16(S.dqkv_cs, self.g(pre + "attn.qkv.bias"), M // 32, 3 * C, 3 * C)
+            self._colsum(S, S.dqkv_cs, self.g(pre + "attn.qkv.bias"), M // 32, 3 * C, 3 * C)
         else:
-            K.colsum_bf16(S.dqkv, self.g(pre + "attn.qkv.bias"), M, 3 * C, 3 * C)
+            self._colsum(S, S.dqkv, self.g(pre + "attn.qkv.bias"), M, 3 * C, 3 * C)
 
     def _block_bwd(self, l, A, S, x_in, B, T, act, pr, pa, seeds, last, D=None, probs=None, doc=None):
         """S.dres = grad of the block output; S.dres_bf = its fc2 branch grad (drop2 applied) ->
@@ -1000,19 +1046,18 @@ class Engine:
             dproj = dnext = S.dres_bf
             grp = [] if self._group_ok(act, M) else None
         self._mlp_bwd(l, A, S, S.dres_bf, S.dln, M, act, grp, flush=D is None)
-        K.layernorm_bwd(A.xmid, self.p(pre + "ln2.weight"), A.m2, A.r2, S.dln, S.dres, self.g(pre + "ln2.weight"),
-                        self.g(pre + "ln2.bias"), dproj, self.g(pre + "attn.proj.bias"), M, C, pr,
-                        seeds[("proj", l)])
+        self._ln_bwd(S, A.xmid, self.p(pre + "ln2.weight"), A.m2, A.r2, S.dln, S.dres, self.g(pre + "ln2.weight"),
+                     self.g(pre + "ln2.bias"), dproj, self.g(pre + "attn.proj.bias"), M, C, pr, seeds[("proj", l)])
         self._attn_bwd(l, A, S, dproj, S.dln, B, T, act, pa, seeds, grp, doc)
         if grp and D is None:  # proj + qkv, before LN1's backward overwrites dres_bf (the proj wgrad's operand)
             self._wgrad_group(S, M, grp)
         if not last:
-            K.layernorm_bwd(x_in, self.p(pre + "ln1.weight"), A.m1, A.r1, S.dln, S.dres,
-                            self.g(pre + "ln1.weight"), self.g(pre + "ln1.bias"), dnext,
-                            self.g(f"transformer.h.{l-1}.mlp.fc2.bias"), M, C, pr, seeds[("fc2", l - 1)])
+            self._ln_bwd(S, x_in, self.p(pre + "ln1.weight"), A.m1, A.r1, S.dln, S.dres,
+                         self.g(pre + "ln1.weight"), self.g(pre + "ln1.bias"), dnext,
+                         self.g(f"transformer.h.{l-1}.mlp.fc2.bias"), M, C, pr, seeds[("fc2", l - 1)])
         else:
-            K.layernorm_bwd(x_in, self.p(pre + "ln1.weight"), A.m1, A.r1, S.dln, S.dres,
-                            self.g(pre + "ln1.weight"), self.g(pre + "ln1.bias"), None, None, M, C)
+            self._ln_bwd(S, x_in, self.p(pre + "ln1.weight"), A.m1, A.r1, S.dln, S.dres,
+                         self.g(pre + "ln1.weight"), self.g(pre + "ln1.bias"), None, None, M, C)
 
     def _trunk_bwd(self, ws, sv: _Saved):
         """ws.dln = grad of the ln_f output -> every trunk gradient (ln_f, blocks, embeddings)."""
@@ -1026,10 +1071,10 @@ class Engine:
         probs = [] if D is not None else None
         # ln_f backward starts the residual gradient; emits the fc2 branch grad of the last block
         self._unit_bwd("head")
-        K.layernorm_bwd(x[L], self.p("transformer.ln_f.weight"), ws.mf, ws.rf, ws.dln, ws.dres,
-                        self.g("transformer.ln_f.weight"), self.g("transformer.ln_f.bias"),
-                        D.blocks[L - 1].dres_bf if D is not None else ws.dres_bf,
-                        self.g(f"transformer.h.{L-1}.mlp.fc2.bias"), M, C, pr, seeds[("fc2", L - 1)], dres_init=True)
+        self._ln_bwd(ws, x[L], self.p("transformer.ln_f.weight"), ws.mf, ws.rf, ws.dln, ws.dres,
+                     self.g("transformer.ln_f.weight"), self.g("transformer.ln_f.bias"),
+                     D.blocks[L - 1].dres_bf if D is not None else ws.dres_bf,
+                     self.g(f"transformer.h.{L-1}.mlp.fc2.bias"), M, C, pr, seeds[("fc2", L - 1)], dres_init=True)
         self._ready("head")
         for l in reversed(range(L)):
             self._unit_bwd(f"h.{l}")
@@ -1041,9 +1086,18 @@ class Engine:
             self._wgrad_deferred(D, M, probs)
             for l in reversed(range(L)):
                 self._ready(f"h.{l}")
-        # embedding backward: atomics into the tied wte grad (the lm_head wgrad already wrote it)
+        # embedding backward: atomics into the tied wte grad (the lm_head wgrad already wrote it); in the deterministic
+        # mode the sorted, chunked sum of csrc/deterministic.hip instead
         self._unit_bwd("embed")
-        if sv.reset:  # dwpe by document position, summed in a fixed order (no float atomics, as embed_bwd's)
+        if ws.det_ws is not None:
+            wte_g, wpe_g = self.g("transformer.wte.weight"), self.g("transformer.wpe.weight")
+            if sv.reset:
+                K.embed_bwd_doc_det(idx, ws.dres, wte_g, wpe_g, sv.doc.start, B, T, C, pr, seeds["embd"], T_valid=sv.T,
+                                    workspace=ws.det_ws)
+            else:
+                K.embed_bwd_det(idx, ws.dres, wte_g, wpe_g, B, T, C, pr, seeds["embd"], T_valid=sv.T,
+                                workspace=ws.det_ws)
+        elif sv.reset:  # dwpe by document position, summed in a fixed order (no float atomics, as embed_bwd's)
             K.embed_bwd_doc(idx, ws.dres, self.g("transformer.wte.weight"), self.g("transformer.wpe.weight"),
                             sv.doc.start, B, T, C, pr, seeds["embd"], T_valid=sv.T)
         else:
@@ -1116,9 +1170,10 @@ class Engine:
         """Per-token negative log-likelihoods of ``labels`` [B, T] without a backward, a logits tensor or the training
         workspace. Dropout is off whatever ``model.training`` is (fixed seeds, p = 0), and the dropout stream
         (_step_seed), _fwd_token, _saved, gemm_sched and the grad arena are left as found: no state that a later
-        training step reads is changed by a call of this between two steps (two runs of the training steps themselves
-        are not bit-reproducible, their LayerNorm and embedding backwards add with float atomics, so that, not equal
-        bits of two runs, is the guarantee; not between a forward and its backward when an FSDP wrapper reshards: the
+        training step reads is changed by a call of this between two steps (by default two runs of the training steps
+        themselves are not bit-reproducible, their LayerNorm and embedding backwards add with float atomics, so that,
+        not equal bits of two runs, is the guarantee; with ``model.deterministic`` they are, and a call of this between
+        two steps leaves their bits alone; not between a forward and its backward when an FSDP wrapper reshards: the
         forward re-gathers units). Returns device tensors, no host sync: (loss [B, T] fp32, a
         view of the workspace valid until the next score of this shape, 0 at ignore_index; sum [1]; count [1];
         mean [1]). acc = (sum, count) fp32 [1] tensors: this call's sum and count are ADDED to them (and returned).
@@ -1315,7 +1370,7 @@ class Engine:
         A, xf, B, Tp, T, act, pr, pa, seeds, doc = state
         C = self.cfg.n_embd
         M = B * Tp
-        S = Scratch(self.cfg, B, Tp, self.vpad, self.device, act, head=False)
+        S = Scratch(self.cfg, B, Tp, self.vpad, self.device, act, head=False, det=self.deterministic(act))
         gs = self._begin_grads(act)
         d = dy.to(F32)
         if Tp != T:
@@ -1325,12 +1380,12 @@ class Engine:
             K.scale_(S.dres, gs)
         pre = f"transformer.h.{l}."
         if kind == "block":
-            K.branch_bwd(S.dres, S.dres_bf, self.g(pre + "mlp.fc2.bias"), M, C, pr, seeds[("fc2", l)])
+            self._branch_bwd(S, S.dres, S.dres_bf, self.g(pre + "mlp.fc2.bias"), M, C, pr, seeds[("fc2", l)])
             self._block_bwd(l, A, S, xf, B, Tp, act, pr, pa, seeds, last=True, doc=doc)
             dx = S.dres
         else:
             site, bias = ("fc2", "mlp.fc2.bias") if kind == "mlp" else ("proj", "attn.proj.bias")
-            K.branch_bwd(S.dres, S.dres_bf, self.g(pre + bias), M, C, pr, seeds[(site, l)])
+            self._branch_bwd(S, S.dres, S.dres_bf, self.g(pre + bias), M, C, pr, seeds[(site, l)])
             if kind == "mlp":
                 self._mlp_bwd(l, A, S, S.dres_bf, S.dln, M, act)
             else:

@@ -214,6 +214,10 @@ class GPT2(nn.Module):
         self._pack_arena()
         self._engine = None
         self.precision = "auto"
+        # True: every sum of the backward in an order fixed by the inputs, so that two runs of the same steps give the
+        # same bits (ordered HIP kernels instead of the float-atomic ones). Read by the engine at every
+        # backward; a data-parallel wrapper sees it through the model it wraps.
+        self.deterministic = False
         self._bind_submodules()
 
     def _bind_submodules(self):

@@ -19,6 +19,9 @@
         --reset_positions (valid only with --doc_mask): then a token takes the position embedding of its offset in its
         document (packing.doc_positions), in the training forward and the --eval_every pass alike, so a document sees
         the positions generate() shows it
+    reproducible runs: --deterministic sets model.deterministic: every sum of the backward in an order fixed by the
+        inputs (ordered HIP kernels instead of the float-atomic ones), so the same command on the same machine logs the
+        same loss and grad_norm bits twice (one process or the same world size and topology)
 
 Loop semantics follow the reference (:374-457): seed 42; loss/grad_accum; backward; every
 grad_accum micro-steps the fused AdamW step (which also yields the clip_grad_norm_(inf) value);
@@ -109,6 +112,8 @@ def build_parser():
     p.add_argument("--eval_steps", type=int, default=20, help="batches per rank per evaluation")
     p.add_argument("--eval_batch", type=int, default=None, help="evaluation batch size (default --batch)")
     p.add_argument("--val_split", type=str, default="val", help="shards whose file name contains this are the val split")
+    p.add_argument("--deterministic", action="store_true",
+                   help="bit-reproducible training steps: the backward sums in a fixed order, without float atomics")
     add_doc_mask_arguments(p)
     return p
 
@@ -318,6 +323,7 @@ def main(argv=None):
         over.update(resid_pdrop=args.dropout, attn_pdrop=args.dropout)
     config = dataclasses.replace(GPT2Config(), n_positions=args.seq_len, **over)
     base = GPT2(config).to(device)
+    base.deterministic = args.deterministic
     if args.training_mode == "ddp":
         model = DistributedDataParallel(base, overlap_optimizer=True)  # the grad norm comes from the fused AdamW
     elif args.training_mode == "fsdp":

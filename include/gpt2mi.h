@@ -28,7 +28,7 @@ extern "C" {
 
 #define GPT2MI_ABI_VERSION 24
 /* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
-#define GPT2MI_ABI_MINOR 6
+#define GPT2MI_ABI_MINOR 7
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -770,6 +770,41 @@ int gpt2mi_attn_fwd_f32_doc(const float* qkv, float* out, float* lse, const int*
 int gpt2mi_attn_bwd_f32_doc(const float* qkv, const float* out, const float* dout, const float* lse, float* delta,
                             float* dqkv, float* dqkv_colsum, const int* doc_start, const int* doc_end, int B, int T,
                             int H, int head_dim, float p_drop, uint64_t seed, void* stream);
+
+/* ---- v24.7: the deterministic mode's backward (csrc/deterministic.hip) ------------------------------------------
+ * Replacements of the entries whose sums use floating-point atomics. Each adds in an order that is a function of its
+ * arguments' shapes and integer inputs alone, so two calls on the same inputs give the same bits; against the entry it
+ * replaces the result differs by summation order only. No float atomics, no host synchronisation, nothing read back.
+ * `workspace` is device memory of at least gpt2mi_det_workspace_bytes(B, T, C, Nmax) bytes with B * T >= the call's rows
+ * (M, or B * T), C the call's C and Nmax >= the call's N; its contents are scratch (nothing is kept between calls, and
+ * calls that share it must be ordered on one stream). One allocation per workspace shape serves every entry. */
+size_t gpt2mi_det_workspace_bytes(int B, int T, int C, int Nmax);
+/* db[n] += sum_m g[m,n] (gpt2mi_colsum_bf16 / _f32). The rows are cut into chunks of a size that depends on (M, N)
+ * only; a chunk's sum is formed as gpt2mi_colsum_* forms a block's and stored to workspace[chunk][N]; the chunks are
+ * then added in a fixed order (eight contiguous shares in chunk order, the shares in share order) and added to db.
+ * N and ld multiples of 4, ld >= N. */
+int gpt2mi_colsum_det_bf16(const uint16_t* g, float* db, int M, int N, int ld, void* workspace, void* stream);
+int gpt2mi_colsum_det_f32(const float* g, float* db, int M, int N, int ld, void* workspace, void* stream);
+/* gpt2mi_layernorm_bwd / _f32 with the same row body and the same row -> wave -> block assignment (at most 512
+ * blocks): dres and out are the same bits as theirs. Each block stores its column sums of dw, db and dbias_out to
+ * workspace[block][3][C]; the blocks' partials are then added in the fixed order above and added to dw / db /
+ * dbias_out. */
+int gpt2mi_layernorm_bwd_det(const float* x, const float* w, const float* mean, const float* rstd, const uint16_t* dy,
+                             float* dres, float* dw, float* db, uint16_t* out_bf16, float* dbias_out, int M, int C,
+                             float p_out, uint64_t seed_out, int dres_init, void* workspace, void* stream);
+int gpt2mi_layernorm_bwd_det_f32(const float* x, const float* w, const float* mean, const float* rstd, const float* dy,
+                                 float* dres, float* dw, float* db, float* out_f32, float* dbias_out, int M, int C,
+                                 float p_out, uint64_t seed_out, int dres_init, void* workspace, void* stream);
+/* gpt2mi_embed_bwd / gpt2mi_embed_bwd_doc: dwte[v,c] += sum over the rows (b,t) with idx[b,t] = v and t < T_valid of
+ * drop(dres[b,t,c]). The keys (token << 32) | (b*T + t) of the valid rows are sorted on the device; the sorted list is
+ * cut into chunks of 32 entries; within a chunk a token's rows are added in ascending b*T + t order; a token whose
+ * rows cross chunks has its chunks' sums added in chunk order; then one dwte[v,c] += per token. Rows t >= T_valid are
+ * never read; rows of dwte whose token does not occur (the pad rows of the table among them) are neither read nor
+ * written. dwpe is formed as the entry it replaces forms it (already without atomics): the same bits. B * T < 2^31. */
+int gpt2mi_embed_bwd_det(const int64_t* idx, const float* dres, float* dwte, float* dwpe, int B, int T, int T_valid,
+                         int C, float p, uint64_t seed, void* workspace, void* stream);
+int gpt2mi_embed_bwd_doc_det(const int64_t* idx, const float* dres, float* dwte, float* dwpe, const int* start, int B,
+                             int T, int T_valid, int C, float p, uint64_t seed, void* workspace, void* stream);
 
 #ifdef __cplusplus
 }
