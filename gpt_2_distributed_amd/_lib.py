@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
 # additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
-ABI_MINOR = 7
+ABI_MINOR = 8
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -181,6 +181,13 @@ _SIGS = {
                                      _p, _p],
     "gpt2mi_embed_bwd_det": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p, _p],
     "gpt2mi_embed_bwd_doc_det": [_p, _p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _c_float, _c_u64, _p, _p],
+    # v24.8 Muon: every list ends (mats, items, n_items, scalars..., stream); mats / items are the device tables of
+    # muon.py muon_tables
+    "gpt2mi_muon_prepare": [_p, _p, _p, _p, _c_int, _c_float, _c_float, _c_int, _p, _p, _p],
+    "gpt2mi_muon_gram": [_p, _p, _p, _p, _c_int, _p],
+    "gpt2mi_muon_poly": [_p, _p, _p, _p, _c_int, _c_float, _c_float, _p],
+    "gpt2mi_muon_apply": [_p, _p, _p, _p, _p, _c_int, _c_float, _p],
+    "gpt2mi_muon_update": [_p, _p, _p, _p, _p, _c_int, _c_float, _c_float, _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
@@ -192,7 +199,9 @@ _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_deco
                 "gpt2mi_embed_fwd_doc": 6, "gpt2mi_embed_bwd_doc": 6,
                 **{n: 7 for n in ("gpt2mi_det_workspace_bytes", "gpt2mi_colsum_det_bf16", "gpt2mi_colsum_det_f32",
                                   "gpt2mi_layernorm_bwd_det", "gpt2mi_layernorm_bwd_det_f32", "gpt2mi_embed_bwd_det",
-                                  "gpt2mi_embed_bwd_doc_det")}}
+                                  "gpt2mi_embed_bwd_doc_det")},
+                **{n: 8 for n in ("gpt2mi_muon_prepare", "gpt2mi_muon_gram", "gpt2mi_muon_poly", "gpt2mi_muon_apply",
+                                  "gpt2mi_muon_update")}}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
              "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size,
@@ -605,6 +614,30 @@ def adamw_clipped(p, g, m, v, p_bf16, n, lr, wd, b1, b2, eps, step, grad_scale, 
 
 def norm_partials_size() -> int:
     return load().gpt2mi_norm_partials_size()
+
+
+# ---- Muon (v24.8): mats / items are the device tables of muon.py muon_tables ------------------------------------------
+def muon_prepare(grad, buf, mats, items, grad_scale, momentum, nesterov, partials, x0):
+    """buf = momentum buf + grad * grad_scale; x0 = bf16(u / (||u|| + 1e-7)) per matrix, wide form (two launches)."""
+    _call("gpt2mi_muon_prepare", _ptr(grad), _ptr(buf), _ptr(mats), _ptr(items), items.shape[0], grad_scale, momentum,
+          int(bool(nesterov)), _ptr(partials), _ptr(x0), _stream())
+
+
+def muon_gram(x, a, mats, items):
+    _call("gpt2mi_muon_gram", _ptr(x), _ptr(a), _ptr(mats), _ptr(items), items.shape[0], _stream())
+
+
+def muon_poly(a, b, mats, items, cb, cc):
+    _call("gpt2mi_muon_poly", _ptr(a), _ptr(b), _ptr(mats), _ptr(items), items.shape[0], cb, cc, _stream())
+
+
+def muon_apply(b, x, x_out, mats, items, ca):
+    _call("gpt2mi_muon_apply", _ptr(b), _ptr(x), _ptr(x_out), _ptr(mats), _ptr(items), items.shape[0], ca, _stream())
+
+
+def muon_update(p, p_bf16, o, mats, items, lr, wd):
+    _call("gpt2mi_muon_update", _ptr(p), _ptr(p_bf16), _ptr(o), _ptr(mats), _ptr(items), items.shape[0], lr, wd,
+          _stream())
 
 
 def cast_f32_bf16(x, y, n):

@@ -565,5 +565,15 @@ class GPT2(nn.Module):
         return FusedAdamW(self, lr=learning_rate, betas=betas, eps=eps, weight_decay=weight_decay,
                           max_grad_norm=max_grad_norm)
 
+    def fused_muon(self, lr: float = 0.02, momentum: float = 0.95, nesterov: bool = True, ns_steps: int = 5,
+                   weight_decay: float = 0.0, adamw_lr: float = 1e-4, adamw_betas=(0.9, 0.95), adamw_eps: float = 1e-8,
+                   adamw_weight_decay: float = 0.1, max_grad_norm: Optional[float] = None):
+        """Muon on the blocks' weight matrices (batched Newton-Schulz HIP kernels), the fused AdamW on everything
+        else: ``optim.Muon``; muon.py states the rule."""
+        from .optim import Muon
+        return Muon(self, lr=lr, momentum=momentum, nesterov=nesterov, ns_steps=ns_steps, weight_decay=weight_decay,
+                    adamw_lr=adamw_lr, adamw_betas=adamw_betas, adamw_eps=adamw_eps,
+                    adamw_weight_decay=adamw_weight_decay, max_grad_norm=max_grad_norm)
+
 
 GPT = GPT2  # nanoGPT alias used by the north star

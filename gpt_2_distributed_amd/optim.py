@@ -17,6 +17,8 @@ memory (``opt.clip_coef``; nothing is read back to the host) and gpt2mi_adamw_cl
 * ``FusedAdamW(model)``: the whole arena of a local / DDP model.
 * ``ShardedAdamW(fsdp)``: this rank's FSDP shard (flat_param); the reported grad norm is the global
   one (the reference's FSDP run reports a per-shard norm averaged over ranks, SURVEY §5 quirk iv).
+* ``Muon(model)``: Muon (muon.py states the rule) on the hidden weight matrices, as batched HIP launches over all of
+  them (csrc/muon.hip), and the fused AdamW above on the rest of the arena.
 """
 from __future__ import annotations
 
@@ -24,6 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as K
+from .muon import NS_COEFFS, muon_matrices, muon_tables
 
 
 class _FlatAdamW(torch.optim.Optimizer):
@@ -232,3 +235,123 @@ class ShardedAdamW(_FlatAdamW):
 
     def zero_grad(self, set_to_none: bool = True):
         self.fsdp.zero_grad(set_to_none=set_to_none)
+
+
+class Muon(torch.optim.Optimizer):
+    """Muon on the matrices of ``muon.muon_matrices(model)``, AdamW on every other element of the arena.
+
+    ``step()``: gpt2mi_muon_prepare (momentum, normalisation), ``ns_steps`` x (gram, poly, apply) and gpt2mi_muon_update,
+    each one launch over all the matrices, then gpt2mi_adamw over each maximal run of the arena that holds no Muon
+    matrix (moments exist for those runs only). Two param groups: [0] AdamW, [1] Muon; a schedule scales ``group["lr"]``
+    of both. ``grad_norm`` is the total gradient norm, as FusedAdamW reports it. Refused: FSDP-sharded models, fp32
+    engines (the kernels write the bf16 shadow the GEMMs read), widths that are no multiple of 64, ``max_grad_norm``."""
+    _gpt2mi_fused = True
+
+    def __init__(self, model, lr=0.02, momentum=0.95, nesterov=True, ns_steps=5, weight_decay=0.0, adamw_lr=1e-4,
+                 adamw_betas=(0.9, 0.95), adamw_eps=1e-8, adamw_weight_decay=0.1, max_grad_norm=None):
+        if max_grad_norm is not None:
+            raise ValueError("Muon: max_grad_norm is not supported (the orthogonalised update has a fixed norm; "
+                             "clipping with Muon is out of scope)")
+        if hasattr(model, "flat_param") or not hasattr(model, "layout"):
+            raise ValueError("Muon: FSDP-sharded models are not supported (a shard holds no whole matrix)")
+        eng = model.engine()
+        if eng.param_provider is not None or eng.store is not None:
+            raise ValueError("Muon: FSDP-sharded models are not supported (a shard holds no whole matrix)")
+        if model.precision == "fp32":
+            raise ValueError("Muon: precision='fp32' is not supported (the kernels compute in bf16 and write the bf16 "
+                             "shadow)")
+        if model.config.n_embd % 64:
+            raise ValueError(f"Muon: n_embd={model.config.n_embd} must be a multiple of 64")
+        self.model, self.engine, self.tail_source = model, eng, None
+        named = dict(model.named_parameters())
+        owned = muon_matrices(model)
+        names = list(dict.fromkeys(n for n, *_ in owned))
+        rest = [p for n, p in named.items() if n not in names and n != "lm_head.weight"]
+        super().__init__([dict(params=rest, lr=adamw_lr, betas=tuple(adamw_betas), eps=adamw_eps,
+                               weight_decay=adamw_weight_decay),
+                          dict(params=[named[n] for n in names], lr=lr, momentum=momentum, nesterov=bool(nesterov),
+                               ns_steps=int(ns_steps), weight_decay=weight_decay)], {})
+        dev, slots = model.arena.device, model.layout.slots
+        self.matrices = owned
+        self.tables = muon_tables([(slots[n].offset + r0 * cols, rows, cols, cols) for n, r0, rows, cols in owned], dev)
+        t = self.tables
+        self.momentum_buffer = torch.zeros(t["x_numel"], dtype=torch.float32, device=dev)
+        self.x = [torch.empty(t["x_numel"], dtype=torch.bfloat16, device=dev) for _ in range(2)]
+        self.a = [torch.empty(t["a_numel"], dtype=torch.bfloat16, device=dev) for _ in range(2)]
+        self.u_partials = torch.empty(t["p_numel"], dtype=torch.float32, device=dev)
+        # the arena outside the matrices: maximal runs (lo, hi, offset into the moments); the kernel takes 4-groups
+        spans = sorted((slots[n].offset + r0 * cols, slots[n].offset + (r0 + rows) * cols) for n, r0, rows, cols in owned)
+        self.runs, lo, at = [], 0, 0
+        for a, b in spans + [(model.arena.numel(), model.arena.numel())]:
+            if a > lo:
+                if lo % 4 or a % 4:
+                    raise ValueError(f"Muon: the arena run [{lo}, {a}) between matrices is not 4-element aligned")
+                self.runs.append((lo, a, at))
+                at += a - lo
+            lo = max(lo, b)
+        self.exp_avg = torch.zeros(at, dtype=torch.float32, device=dev)
+        self.exp_avg_sq = torch.zeros(at, dtype=torch.float32, device=dev)
+        self.partials = torch.empty(K.norm_partials_size(), dtype=torch.float32, device=dev)
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.step_count = 0
+        self.grad_scale = 1.0
+
+    def attach_tail(self, hooks):
+        """A DistributedDataParallel bucket still in flight at step(): waited for before anything reads a gradient
+        (every rank then forms the same update from the reduced gradients)."""
+        self.tail_source = hooks
+
+    def newton_schulz(self, steps):
+        """``steps`` iterations over the batch from self.x[0]; returns the buffer that holds the result."""
+        t, (a, b, c) = self.tables, NS_COEFFS
+        src = 0
+        for _ in range(steps):
+            K.muon_gram(self.x[src], self.a[0], t["mats"], t["sym"])
+            K.muon_poly(self.a[0], self.a[1], t["mats"], t["sym"], b, c)
+            K.muon_apply(self.a[1], self.x[src], self.x[src ^ 1], t["mats"], t["full"], a)
+            src ^= 1
+        return self.x[src]
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        eng = self.engine
+        if self.tail_source is not None:
+            self.tail_source.wait_tail()
+        if all(p.grad is None for p in eng.params_by_name.values()):
+            return loss  # no gradients since zero_grad(set_to_none=True): torch's optimizers skip such params
+        self.step_count += 1
+        ga, gm = self.param_groups
+        arena, t = self.model.arena, self.tables
+        K.sumsq_partials(eng.grad, arena.numel(), float(self.grad_scale), self.partials)
+        K.norm_finalize(self.partials, self.partials.numel(), self.grad_norm)
+        K.muon_prepare(eng.grad, self.momentum_buffer, t["mats"], t["tiles64"], float(self.grad_scale),
+                       float(gm["momentum"]), gm["nesterov"], self.u_partials, self.x[0])
+        o = self.newton_schulz(gm["ns_steps"])
+        K.muon_update(arena, eng.shadow, o, t["mats"], t["tiles64"], float(gm["lr"]), float(gm["weight_decay"]))
+        b1, b2 = ga["betas"]
+        for lo, hi, at in self.runs:
+            K.adamw(arena[lo:hi], eng.grad[lo:hi], self.exp_avg[at:at + hi - lo], self.exp_avg_sq[at:at + hi - lo],
+                    eng.shadow[lo:hi], hi - lo, float(ga["lr"]), float(ga["weight_decay"]), float(b1), float(b2),
+                    float(ga["eps"]), self.step_count, float(self.grad_scale), None, None)
+        eng.mark_shadow_fresh()
+        return loss
+
+    def state_dict(self):
+        return {"step": self.step_count, "momentum_buffer": self.momentum_buffer, "exp_avg": self.exp_avg,
+                "exp_avg_sq": self.exp_avg_sq, "param_groups": [dict(g, params=[]) for g in self.param_groups]}
+
+    def load_state_dict(self, sd):
+        self.step_count = int(sd["step"])
+        self.momentum_buffer.copy_(sd["momentum_buffer"])
+        self.exp_avg.copy_(sd["exp_avg"])
+        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        for g, s in zip(self.param_groups, sd["param_groups"]):
+            for k, v in s.items():
+                if k != "params":
+                    g[k] = v
+
+    zero_grad = FusedAdamW.zero_grad

@@ -102,6 +102,10 @@ def build_parser():
     # the recipe (all off by default: the reference clips at inf and keeps lr constant)
     p.add_argument("--max_grad_norm", type=float, default=0.0,
                    help="clip the global gradient norm to this value in the optimizer step (0 = off)")
+    p.add_argument("--optimizer", choices=["adamw", "muon"], default="adamw",
+                   help="muon: Muon on the blocks' weight matrices (optim.Muon), AdamW (--lr) on everything else")
+    p.add_argument("--muon_lr", type=float, default=0.02, help="muon: the learning rate of the matrices")
+    p.add_argument("--muon_momentum", type=float, default=0.95)
     p.add_argument("--lr_schedule", choices=list(KINDS), default="constant")
     p.add_argument("--warmup_steps", type=int, default=0, help="cosine: linear warmup over N optimizer steps")
     p.add_argument("--lr_decay_steps", type=int, default=0,
@@ -279,6 +283,9 @@ def main(argv=None):
     sched = schedule_from_args(args)
     scheduled = sched["kind"] != "constant"
     clip = args.max_grad_norm > 0
+    muon = args.optimizer == "muon"
+    if muon and (clip or args.training_mode == "fsdp"):
+        raise SystemExit("--optimizer muon: --max_grad_norm and --training_mode fsdp are not supported")
     ev = eval_from_args(args)
     doc = doc_mask_from_args(args)
     if ev and not args.synthetic:  # (synthetic runs write their val shard below)
@@ -330,8 +337,12 @@ def main(argv=None):
         model = FullyShardedDataParallel(base, overlap_optimizer=True, reshard_after_forward=not args.fsdp_resident)
     else:
         model = base
-    optim = model.configure_optimizers(weight_decay=0.1, learning_rate=args.lr, betas=(0.9, 0.95),
-                                       **({"max_grad_norm": args.max_grad_norm} if clip else {}))
+    if muon:  # (under ddp no bucket is deferred past the backward: every gradient is reduced when step() runs)
+        optim = base.fused_muon(lr=args.muon_lr, momentum=args.muon_momentum, adamw_lr=args.lr,
+                                adamw_betas=(0.9, 0.95), adamw_weight_decay=0.1)
+    else:
+        optim = model.configure_optimizers(weight_decay=0.1, learning_rate=args.lr, betas=(0.9, 0.95),
+                                           **({"max_grad_norm": args.max_grad_norm} if clip else {}))
     global_step, start_epoch, skip = 0, 0, 0
     # the epoch the DataLoader's persistent workers were spawned with: they keep that dataset copy, so every later
     # epoch replays its order (SURVEY §5 "epoch freeze"); a resumed run must spawn its workers with the same one
@@ -402,6 +413,8 @@ def main(argv=None):
             lr = args.lr
             if scheduled:  # a function of the steps taken, which a resume restores: no schedule state of its own
                 lr = optim.param_groups[0]["lr"] = lr_at(global_step, **sched)
+                if muon:  # the same shape for the matrices' group
+                    optim.param_groups[1]["lr"] = args.muon_lr * lr / args.lr
             optim.step()
             optim.zero_grad()
             global_step += 1

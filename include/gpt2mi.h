@@ -28,7 +28,7 @@ extern "C" {
 
 #define GPT2MI_ABI_VERSION 24
 /* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
-#define GPT2MI_ABI_MINOR 7
+#define GPT2MI_ABI_MINOR 8
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -200,6 +200,36 @@ int gpt2mi_clip_coef(const float* partials, int n, float max_norm, float* sumsq_
 int gpt2mi_adamw_clipped(float* p, const float* g, float* m, float* v, uint16_t* p_bf16, size_t n, float lr, float wd,
                          float b1, float b2, float eps, int step, float grad_scale, const float* coef_dev,
                          float* partials, float* grad_norm, void* stream);
+
+/* v24.8: Muon on the hidden weight matrices, every entry ONE launch (prepare: two) over a batch of matrices, without
+ * floating-point atomics (two runs give the same bits). The rule is gpt_2_distributed_amd/muon.py muon_reference:
+ *   buf = momentum buf + g;  u = g + momentum buf (nesterov) or buf;  X0 = u / (||u||_F + 1e-7), transposed if rows > cols;
+ *   5 x { A = X X^T;  B = b A + c A A;  X = a X + B X }, A, B and X rounded to bf16, sums in fp32;
+ *   W = W (1 - lr wd) - lr sqrt(max(1, rows / cols)) O, O = the last X, transposed back.
+ * The batch is two device tables built once (muon.py muon_tables), never a per-step host pointer array:
+ *   mats  int64 [count][8]: off (element of W[0][0] in the arenas p / p_bf16 / grad), rows, cols, ld, xoff (the matrix in
+ *         the compact buffers: buf fp32 [rows][cols], x bf16 [m][n] with m = min(rows, cols), n = max), aoff (in the
+ *         bf16 [m][m] buffers a / b), pstart, ptiles (its (rows/64)(cols/64) floats of partials);
+ *   items int32 [n_items][4]: (matrix, tile row, tile col, 0), one work item per block, a matrix's tiles consecutive:
+ *         64x64 tiles of W as stored for prepare / update; the 128x128 tiles with col >= row of [m][m] for gram / poly;
+ *         the 128x128 tiles of [m][n] for apply.
+ * rows, cols, ld and every offset are multiples of 64; the tables are read by the kernels and not checked here.
+ * Operand reads stay inside the matrix (a half last tile clamps its rows / columns, as gpt2mi_gemm_wgrad's).
+ * gpt2mi_muon_prepare: buf and x0 written, grad read times grad_scale; per matrix the sum of squares goes through
+ *   partials in an order fixed by the shape. A zero u gives X0 = 0.
+ * gpt2mi_muon_gram: a = bf16(x x^T). gpt2mi_muon_poly: b = bf16(cb a + cc a a^T), a symmetric (gram's output). Both
+ *   compute the tiles of the upper triangle and store each twice: the results are symmetric bit for bit.
+ * gpt2mi_muon_apply: x_out = bf16(ca x + b x), x_out != x (ping-pong).
+ * gpt2mi_muon_update: the fp32 master p and, unless NULL, its bf16 shadow p_bf16 at the same elements. */
+int gpt2mi_muon_prepare(const float* grad, float* buf, const int64_t* mats, const int* items, int n_items,
+                        float grad_scale, float momentum, int nesterov, float* partials, uint16_t* x0, void* stream);
+int gpt2mi_muon_gram(const uint16_t* x, uint16_t* a, const int64_t* mats, const int* items, int n_items, void* stream);
+int gpt2mi_muon_poly(const uint16_t* a, uint16_t* b, const int64_t* mats, const int* items, int n_items, float cb,
+                     float cc, void* stream);
+int gpt2mi_muon_apply(const uint16_t* b, const uint16_t* x, uint16_t* x_out, const int64_t* mats, const int* items,
+                      int n_items, float ca, void* stream);
+int gpt2mi_muon_update(float* p, uint16_t* p_bf16, const uint16_t* o, const int64_t* mats, const int* items,
+                       int n_items, float lr, float wd, void* stream);
 
 /* ---- fp32 mode: the reference model.py run WITHOUT torch.autocast (plain fp32 module; the CPU
  * trajectory goldens and the north star's "fp32 loss within 1e-4" gate). Same contracts as the bf16
