@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("GPT2MI_LIB") or os.path.join(_HERE, "libgpt2mi.so")
 # library is refused at load instead of being called with the wrong argument lists
 ABI_VERSION = 24
 # additions within that version (GPT2MI_ABI_MINOR): the bindings need at least this many
-ABI_MINOR = 8
+ABI_MINOR = 9
 
 _c_int, _c_float, _c_size, _c_u64, _p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_void_p
 
@@ -188,6 +188,15 @@ _SIGS = {
     "gpt2mi_muon_poly": [_p, _p, _p, _p, _c_int, _c_float, _c_float, _p],
     "gpt2mi_muon_apply": [_p, _p, _p, _p, _p, _c_int, _c_float, _p],
     "gpt2mi_muon_update": [_p, _p, _p, _p, _p, _c_int, _c_float, _c_float, _p],
+    # v24.9 prefill over a live cache: qkv, kcache, vcache, [kscale, vscale,] out, workspace, workspace_floats, S, B, H,
+    # head_dim, Tcap, T_src, seq, base, count (HOST arrays of S ints), stream
+    "gpt2mi_attn_chunk": [_p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    "gpt2mi_attn_chunk_fp8": [_p, _p, _p, _p, _p, _p, _p, _c_size, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _p, _p,
+                              _p, _p],
+    "gpt2mi_attn_chunk_workspace": [_c_int, _c_int, _c_int, _c_int],
+    "gpt2mi_attn_chunk_splits": [_c_int],
+    # idx, wte, wpe, x, S, T, T_valid, C, pos0 (HOST array of S ints), stream
+    "gpt2mi_embed_fwd_at": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
@@ -201,11 +210,13 @@ _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_deco
                                   "gpt2mi_layernorm_bwd_det", "gpt2mi_layernorm_bwd_det_f32", "gpt2mi_embed_bwd_det",
                                   "gpt2mi_embed_bwd_doc_det")},
                 **{n: 8 for n in ("gpt2mi_muon_prepare", "gpt2mi_muon_gram", "gpt2mi_muon_poly", "gpt2mi_muon_apply",
-                                  "gpt2mi_muon_update")}}
+                                  "gpt2mi_muon_update")},
+                **{n: 9 for n in ("gpt2mi_attn_chunk", "gpt2mi_attn_chunk_fp8", "gpt2mi_attn_chunk_workspace",
+                                  "gpt2mi_attn_chunk_splits", "gpt2mi_embed_fwd_at")}}
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
              "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size,
-             "gpt2mi_det_workspace_bytes": _c_size}
+             "gpt2mi_det_workspace_bytes": _c_size, "gpt2mi_attn_chunk_workspace": _c_size}
 
 EXPORTED = tuple(_SIGS)
 
@@ -798,7 +809,8 @@ def gemm_skinny(epilogue, M, N, K, A, lda, W, ldw, C, ldc, bias=None, resid=None
 # The entries that take a key/value cache, and their forms over an fp8 cache (v23): the same list with
 # (kscale, vscale) behind (kcache, vcache).
 _FP8_ENTRY = {"gpt2mi_kv_store": "gpt2mi_kv_store_fp8", "gpt2mi_attn_decode_ragged": "gpt2mi_attn_decode_fp8_ragged",
-              "gpt2mi_attn_extend": "gpt2mi_attn_extend_fp8", "gpt2mi_attn_decode_shared": "gpt2mi_attn_decode_shared_fp8"}
+              "gpt2mi_attn_extend": "gpt2mi_attn_extend_fp8", "gpt2mi_attn_decode_shared": "gpt2mi_attn_decode_shared_fp8",
+              "gpt2mi_attn_chunk": "gpt2mi_attn_chunk_fp8"}
 
 
 def _kv_call(name, qkv, kcache, vcache, kscale, vscale, *tail, fp8=None):
@@ -957,6 +969,35 @@ def attn_extend_fp8(qkv, kcache, vcache, kscale, vscale, out, workspace, R, B, H
     """attn_extend over an fp8 cache."""
     _kv_call("gpt2mi_attn_extend", qkv, kcache, vcache, kscale, vscale, _ptr(out), _ptr(workspace), workspace.numel(),
              R, B, H, D, Tcap, _positions(seq, R), _positions(pos, R), fp8=True)
+
+
+# ---- v24.9: prefill over a live cache (csrc/prefill_cached.hip) -----------------------------------------
+def attn_chunk_workspace(S, H, Tcap, T_src) -> int:
+    """fp32 elements of workspace that serve any attn_chunk call of these extents (0: no sequence can split)."""
+    return load().gpt2mi_attn_chunk_workspace(S, H, Tcap, T_src)
+
+
+def attn_chunk_splits(keys) -> int:
+    """The number of key ranges attn_chunk cuts a sequence of ``keys`` keys into."""
+    return load().gpt2mi_attn_chunk_splits(keys)
+
+
+def attn_chunk(qkv, kcache, vcache, out, workspace, B, H, D, Tcap, T_src, seq, base, count, kscale=None, vscale=None,
+               fp8=None):
+    """gpt2mi_attn_chunk: flash attention of the chunks qkv [S][T_src][3C] over the cache: the rows i < count[s] of
+    sequence s sit at positions base[s] + i of cache stream seq[s] and read its positions 0 .. base[s] + i, which the
+    caller has stored (kv_store at t0 = base). seq, base, count: host sequences of S ints. With kscale / vscale over an
+    fp8 cache. workspace may be None when no sequence splits."""
+    S = len(seq)
+    _kv_call("gpt2mi_attn_chunk", qkv, kcache, vcache, kscale, vscale, _ptr(out), _ptr(workspace),
+             0 if workspace is None else workspace.numel(), S, B, H, D, Tcap, T_src, _positions(seq, S),
+             _positions(base, S), _positions(count, S), fp8=fp8)
+
+
+def embed_fwd_at(idx, wte, wpe, x, S, T, C, pos0, T_valid=None):
+    """embed_fwd at p = 0 with sequence s at positions pos0[s] + t (a host sequence of S ints)."""
+    _call("gpt2mi_embed_fwd_at", _ptr(idx), _ptr(wte), _ptr(wpe), _ptr(x), S, T, T if T_valid is None else T_valid, C,
+          _positions(pos0, S), _stream())
 
 
 # ---- v22: penalties in the sampler (csrc/sample.hip, csrc/decode.hip) -----------------------------------

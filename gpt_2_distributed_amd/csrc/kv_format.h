@@ -95,6 +95,8 @@ struct KvBf16 {
   static __device__ __forceinline__ void key8(const Row& r, float* f) { unpack8(r, f); }
   static __device__ __forceinline__ float score_scale(const Row&) { return 1.f; }
   static __device__ __forceinline__ void value8(const Row& r, float* f) { unpack8(r, f); }
+  // The lane's 8 values as the bf16 operand chunk of an MFMA tile in LDS (prefill_cached.hip).
+  static __device__ __forceinline__ bf16x8 tile8(const Row& r) { return r; }
   // The same tensor seen from `n` rows further on (a layer of a [L][stream][Tcap] tensor).
   __device__ __forceinline__ KvBf16 shifted(size_t n) const { return KvBf16{rows + n * 64}; }
 };
@@ -127,6 +129,12 @@ struct KvFp8 {
   static __device__ __forceinline__ void key8(const Row& r, float* f) { kv_codes8(r.codes, f); }
   static __device__ __forceinline__ float score_scale(const Row& r) { return r.scale; }
   static __device__ __forceinline__ void value8(const Row& r, float* f) { kv_dequantize8(r, f); }
+  // code * 2^e is a bf16 value (3 mantissa bits, e >= -100): the conversion is exact
+  static __device__ __forceinline__ bf16x8 tile8(const Row& r) {
+    float f[8];
+    kv_dequantize8(r, f);
+    return bf16x8{f2bf(f[0]), f2bf(f[1]), f2bf(f[2]), f2bf(f[3]), f2bf(f[4]), f2bf(f[5]), f2bf(f[6]), f2bf(f[7])};
+  }
   __device__ __forceinline__ KvFp8 shifted(size_t n) const { return KvFp8{codes + n * 64, scales + n}; }
 };
 

@@ -877,16 +877,20 @@ class Engine:
             K.layernorm_fwd(x, self.p(pre + ".weight"), self.p(pre + ".bias"), None, out_f32, mean, rstd, M,
                             cfg.n_embd, cfg.layer_norm_eps)
 
-    def _attn_fwd(self, l, A, resid, out, B, T, act, pr, pa, seeds, doc=None):
+    def _attn_fwd(self, l, A, resid, out, B, T, act, pr, pa, seeds, doc=None, attn=None):
         """A.ln1 -> qkv GEMM -> flash attention -> proj GEMM: out = resid + drop(proj(attn)). doc: DocBounds [B, T]
-        for the document-masked kernels, None for the causal ones."""
+        for the document-masked kernels, None for the causal ones. attn: ``attn(l, A)`` in place of the flash forward,
+        from A.qkv to A.ao (a chunk over a key/value cache, DecodeSession.append); None: the launches as they were."""
         C, H = self.cfg.n_embd, self.cfg.n_head
         M = B * T
         pre = f"transformer.h.{l}."
         self._gemm(K.FWD, K.EPI_BF16, M, 3 * C, C, A.ln1, C, self.w(pre + "attn.qkv.weight", act), C, A.qkv, 3 * C,
                bias=self.p(pre + "attn.qkv.bias"))
-        with self._probe("attn_fwd"):
-            K.attn_fwd(A.qkv, A.ao, A.lse, B, T, H, C // H, pa, seeds[("attn", l)], doc=doc)
+        if attn is not None:
+            attn(l, A)
+        else:
+            with self._probe("attn_fwd"):
+                K.attn_fwd(A.qkv, A.ao, A.lse, B, T, H, C // H, pa, seeds[("attn", l)], doc=doc)
         self._gemm(K.FWD, K.EPI_RESID, M, C, C, A.ao, C, self.w(pre + "attn.proj.weight", act), C, out, C,
                bias=self.p(pre + "attn.proj.bias"), resid=resid, p_drop=pr, seed=seeds[("proj", l)])
 
@@ -900,19 +904,24 @@ class Engine:
         self._gemm(K.FWD, K.EPI_RESID, M, C, 4 * C, A.h, 4 * C, self.w(pre + "mlp.fc2.weight", act), 4 * C, out, C,
                bias=self.p(pre + "mlp.fc2.bias"), resid=resid, p_drop=pr, seed=seeds[("fc2", l)])
 
-    def _block_fwd(self, l, A, x_in, x_out, B, T, act, pr, pa, seeds, doc=None):
+    def _block_fwd(self, l, A, x_in, x_out, B, T, act, pr, pa, seeds, doc=None, attn=None):
         M = B * T
         pre = f"transformer.h.{l}."
         self._ln_fwd(x_in, pre + "ln1", A.ln1, A.m1, A.r1, M)
-        self._attn_fwd(l, A, x_in, A.xmid, B, T, act, pr, pa, seeds, doc)
+        self._attn_fwd(l, A, x_in, A.xmid, B, T, act, pr, pa, seeds, doc, attn)
         self._ln_fwd(A.xmid, pre + "ln2", A.ln2, A.m2, A.r2, M)
         self._mlp_fwd(l, A, A.xmid, x_out, M, act, pr, seeds)
 
-    def _trunk_fwd(self, ws, idx, B, T, T_valid, act, pr, pa, seeds, lnf_f32=None, doc=None, reset=False):
+    def _trunk_fwd(self, ws, idx, B, T, T_valid, act, pr, pa, seeds, lnf_f32=None, doc=None, reset=False, embed=None,
+                   attn=None):
+        """embed / attn: ``embed(x0)`` in place of the embedding launch and ``attn(l, A)`` in place of every layer's flash
+        forward (the trunk over a chunk appended to a live cache: DecodeSession.append); None: today's launches."""
         C, L = self.cfg.n_embd, self.cfg.n_layer
         x = ws.x
         self._unit("embed")
-        if reset:  # positions restart at every document: wpe[t - start[b, t]]
+        if embed is not None:
+            embed(x[0])
+        elif reset:  # positions restart at every document: wpe[t - start[b, t]]
             K.embed_fwd_doc(idx, self.p("transformer.wte.weight"), self.p("transformer.wpe.weight"), x[0], doc.start,
                             B, T, C, pr, seeds["embd"], T_valid=T_valid)
         else:
@@ -920,7 +929,7 @@ class Engine:
                         seeds["embd"], T_valid=T_valid)
         for l in range(L):
             self._unit(f"h.{l}")
-            self._block_fwd(l, ws.blocks[l], x[l], x[l + 1], B, T, act, pr, pa, seeds, doc)
+            self._block_fwd(l, ws.blocks[l], x[l], x[l + 1], B, T, act, pr, pa, seeds, doc, attn)
         self._unit("head")
         self._ln_fwd(x[L], "transformer.ln_f", ws.lnf, ws.mf, ws.rf, B * T, out_f32=lnf_f32)
 

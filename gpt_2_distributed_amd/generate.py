@@ -2,7 +2,7 @@
 --prompt_ids 50256 --max_new_tokens 64 [--temperature T --top_k K --top_p P --sampler {torch,device} --seed S --batch B
 --draft_tokens K --repetition_penalty R --presence_penalty P --frequency_penalty F --kv_dtype {bf16,fp8}
 --num_samples S --logprobs [N] --num_beams W --length_penalty A --num_return_sequences R --logit_bias T:V,T:V
---min_p M --min_new_tokens N --stop IDS [--stop IDS ...]]``.
+--min_p M --min_new_tokens N --stop IDS [--stop IDS ...] --prefix_ids IDS]``.
 
 Loads ``model.pt`` of a ``save_checkpoint`` directory (train_gpt2_distributed.py) into a GPT2 of the named size, runs
 ``GPT2.generate`` on ``--batch`` copies of the prompt and prints one JSON list of token ids per sequence (prompt
@@ -32,7 +32,11 @@ go with it; prompts x W <= 64.
 ``--logit_bias 50256:-100,198:2.5`` adds a value to a token's logit (``-inf`` bans it), ``--min_p 0.05`` drops the tokens
 less than that fraction as likely as the most likely one, ``--min_new_tokens 8`` holds ``--eos_token_id`` back for that
 many tokens and ``--stop 198,198`` (repeatable) ends a sequence at the token that completes the given tokens; the last two
-need ``--eos_token_id``. They go with either ``--sampler`` (``GPT2.generate``'s keywords), not with ``--num_beams``."""
+need ``--eos_token_id``. They go with either ``--sampler`` (``GPT2.generate``'s keywords), not with ``--num_beams``.
+
+``--prefix_ids 1,2,3`` puts the same tokens in front of every prompt (``GPT2.generate_many`` over a ``generation.SharedPrefix``: the prefix is
+computed once and each row prefills its own prompt over the prefix's cache); the printed sequences include it. It goes
+with the device sampler, not with ``--num_beams``, ``--num_samples`` or ``--draft_tokens``."""
 from __future__ import annotations
 
 import argparse
@@ -98,6 +102,9 @@ def make_parser():
     p.add_argument("--stop", type=parse_stop, action="append", default=None, metavar="IDS",
                    help="comma-separated token ids: a sequence ends at the token that completes them (needs "
                         "--eos_token_id); may be given up to 8 times, 16 tokens each")
+    p.add_argument("--prefix_ids", type=parse_stop, default=None, metavar="IDS",
+                   help="comma-separated token ids put in front of every prompt and computed once (generate_many over a "
+                        "SharedPrefix; --sampler device)")
     return p
 
 
@@ -180,6 +187,9 @@ def main(argv=None) -> int:
         pen["logprobs"] = a.logprobs
     pen.update({k: v for k, v in dict(logit_bias=a.logit_bias, min_p=a.min_p, min_new_tokens=a.min_new_tokens,
                                       stop=a.stop).items() if v})  # (only what was set: as the defaults, nothing)
+    if a.prefix_ids:
+        if a.num_beams is not None or a.num_samples > 1 or a.draft_tokens is not None:
+            raise SystemExit("--prefix_ids goes with generate_many: not with --num_beams, --num_samples or --draft_tokens")
     if a.num_beams is not None:
         # (only what the user set travels on: generate refuses the sampler's keywords beside num_beams by name)
         default = make_parser().get_default
@@ -209,12 +219,17 @@ def main(argv=None) -> int:
                 line = with_logprobs(line, res, r, len(prompts[b]), len(prompts[b]) + made, a.logprobs)
             print(json.dumps(line))
         return 0
-    if len(prompts) > 1:
+    if len(prompts) > 1 or a.prefix_ids:
         if a.sampler != "device" and a.temperature != 0:
-            raise SystemExit("several prompts are served by generate_many, which draws on the device: --sampler device")
-        outs = model.generate_many([torch.tensor(q, dtype=torch.int64, device="cuda:0") for q in prompts],
-                                   a.max_new_tokens, batch_size=a.batch, temperature=a.temperature, top_k=a.top_k,
+            raise SystemExit("several prompts (or --prefix_ids) are served by generate_many, which draws on the device: "
+                             "--sampler device")
+        served = [torch.tensor(q, dtype=torch.int64, device="cuda:0") for q in prompts]
+        if a.prefix_ids:
+            from .generation import SharedPrefix
+            served = SharedPrefix(a.prefix_ids, served)
+        outs = model.generate_many(served, a.max_new_tokens, batch_size=a.batch, temperature=a.temperature, top_k=a.top_k,
                                    top_p=a.top_p, seed=a.seed, eos_token_id=a.eos_token_id, **pen)
+        prompts = [list(a.prefix_ids or []) + q for q in prompts]
         for q, row in zip(prompts, outs):
             if a.logprobs is None:
                 print(json.dumps(row.tolist()))

@@ -802,6 +802,27 @@ class _Call(NamedTuple):
     hist: Optional[torch.Tensor]
 
 
+class SharedPrefix:
+    """``prompts`` that all open with the same ``prefix`` (a 1-D sequence of token ids), as the ``prompts`` argument of
+    ``generate_many``: every prompt is ``prefix + prompts[i]`` (a suffix may be empty), the prefix is computed once and
+    the returned sequences include it. Not a tuple or a list: nothing takes it for a list of prompts by accident."""
+
+    def __init__(self, prefix, prompts):
+        self.prefix, self.prompts = prefix, list(prompts)
+
+
+class PromptPrefix(NamedTuple):
+    """A prompt prefix run once (``DecodeSession.prefix``): its keys and values per layer as the session's cache holds
+    them, ``k`` / ``v`` ``[L][H][length][64]`` (bf16, or the fp8 codes with ``kscale`` / ``vscale`` ``[L][H][length]``),
+    and the logits row ``[Vp]`` of its last position. ``refill(row, suffix, prefix=...)`` copies it into a row."""
+    k: torch.Tensor
+    v: torch.Tensor
+    kscale: Optional[torch.Tensor]
+    vscale: Optional[torch.Tensor]
+    length: int
+    logits: torch.Tensor
+
+
 class DecodeSession:
     """The key/value cache of ``batch_size`` sequences of up to ``max_len`` tokens, and the step that extends them.
 
@@ -851,6 +872,7 @@ class DecodeSession:
         self._tok = e(B, dt=torch.int64)  # the device loop's newest tokens (DecodeSession.generate)
         self._drawn = False               # True: generate() drew _tok from the logits in place and has not stepped it
         self._refill_ws = None            # (Tp, engine.Workspace) of the last refill's one-sequence prefill
+        self._chunk_ws = None             # (Tp, fp32 workspace or None) of the last append's chunk attention
         self._plan = self._build_plan({n: getattr(self, n) for n in SCRATCH}, 0)
         self._rows = None                 # (scratch of MAX_BATCH rows, its plan): extend / speculate, on first use
         self._last = None                 # (the sampling keywords of the last call, their Sampler): _record
@@ -1054,7 +1076,7 @@ class DecodeSession:
         return self._refill_ws[1]
 
     @torch.no_grad()
-    def refill(self, row: int, prompt: torch.Tensor) -> None:
+    def refill(self, row: int, prompt: torch.Tensor, prefix: Optional[PromptPrefix] = None) -> None:
         """Replace sequence ``row`` by the 1-D ``prompt`` while the other rows keep their cache, logits and position.
 
         The prompt runs as a prefill of one sequence: its keys and values go to the row's slices of the caches
@@ -1062,20 +1084,42 @@ class DecodeSession:
         M = 1) and ``lens[row]`` becomes its length. Every shape of that prefill depends on the prompt alone, so the
         row's cache and logits are a function of (weights, prompt) only: not of the row, the batch size or what the
         other rows hold. ``generate_many``'s guarantee rests on this. A token ``generate`` drew and has not stepped is
-        stepped first (``flush``), so that afterwards every row's logits are those of its next position."""
+        stepped first (``flush``), so that afterwards every row's logits are those of its next position.
+
+        With ``prefix`` (from ``prefix()`` of this session) the row's sequence is the prefix followed by ``prompt``, the
+        suffix: the prefix's keys, values and logits are copied into the row and ``append`` runs the suffix over them,
+        so the prefix is computed once however many rows start with it. The row then holds the bits of
+        ``refill(row, prefix tokens)`` followed by ``append(row, prompt)``: a function of (weights, prefix, suffix). An
+        empty suffix leaves the prefix's logits."""
         eng, cfg = self.engine, self.cfg
         if not 0 <= int(row) < self.B:
             raise ValueError(f"row {row} not in [0, B={self.B})")
-        if prompt.dim() != 1 or not 1 <= prompt.numel() <= self.Tcap:
-            raise ValueError(f"refill takes a 1-D prompt of 1..max_len={self.Tcap} tokens (got {tuple(prompt.shape)})")
+        n0 = 0 if prefix is None else int(prefix.length)
+        if prompt.dim() != 1 or not (1 if prefix is None else 0) <= prompt.numel() <= self.Tcap - n0:
+            raise ValueError(f"refill takes a 1-D prompt of 1..max_len={self.Tcap} tokens, the prefix's {n0} included "
+                             f"(got {tuple(prompt.shape)})")
         if not prompt.is_cuda:
             raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
         self.flush()
         self._ready(True)
         self.share.leave(int(row))  # (after the flush: that step still reads the row as a member)
         self._sync_share()
+        row = int(row)
+        if prefix is not None:
+            if prefix.k.dtype != self.kcache.dtype or tuple(prefix.k.shape) != (cfg.n_layer, cfg.n_head, n0, 64):
+                raise ValueError(f"the prefix ({prefix.k.dtype} {tuple(prefix.k.shape)}) is not one of this session "
+                                 f"(kv_dtype {self.kv_dtype!r}, [L={cfg.n_layer}][H={cfg.n_head}][n][64])")
+            for dst, src in ((self.kcache, prefix.k), (self.vcache, prefix.v), (self.kscale, prefix.kscale),
+                             (self.vscale, prefix.vscale)):
+                if dst is not None:  # [L][B][H][Tcap](...): the row's positions below n0
+                    dst[:, row, :, :n0] = src
+            self.logits[row] = prefix.logits
+            self.lens[row] = n0
+            if prompt.numel():
+                self.append(row, prompt)
+            return
         eng.gemm_sched = eng.base_sched
-        row, P = int(row), prompt.numel()
+        P = prompt.numel()
         idx_p, _, _ = eng._pad(prompt.view(1, P), None)
         Tp = idx_p.size(1)
         C, Vp = cfg.n_embd, self.model.vpad
@@ -1086,6 +1130,88 @@ class DecodeSession:
         K.gemm_skinny(K.EPI_F32, 1, Vp, C, ws.lnf[P - 1], Tp * C, eng.w16("transformer.wte.weight"), C, self.logits[row],
                       Vp, workspace=self.gemm_ws)
         self.lens[row] = P
+
+    @torch.no_grad()
+    def prefix(self, tokens: torch.Tensor, row: int = 0) -> PromptPrefix:
+        """Run the 1-D ``tokens`` once, as ``refill(row, tokens)`` does, and return what that left in the row as a
+        ``PromptPrefix``: copies of its keys and values (with fp8 the codes and scales), its length and its logits. Row
+        ``row`` is the scratch: afterwards it holds the prefix like any refilled row. ``refill(r, suffix, prefix=...)``
+        then starts any row with it at the cost of a copy."""
+        self.refill(row, tokens)
+        n, row = tokens.numel(), int(row)
+        cut = lambda t: None if t is None else t[:, row, :, :n].clone()  # noqa: E731
+        return PromptPrefix(cut(self.kcache), cut(self.vcache), cut(self.kscale), cut(self.vscale), n,
+                            self.logits[row].clone())
+
+    def _chunk_workspace(self, Tp: int):
+        """The key-split workspace of append's chunk attention at padded length Tp (None: no sequence of this cache can
+        split), kept while the padded length repeats."""
+        if self._chunk_ws is None or self._chunk_ws[0] != Tp:
+            need = K.attn_chunk_workspace(1, self.cfg.n_head, self.Tcap, Tp)
+            self._chunk_ws = (Tp, torch.empty(need, dtype=F32, device=self.device) if need else None)
+        return self._chunk_ws[1]
+
+    @torch.no_grad()
+    def append(self, row: int, tokens: torch.Tensor) -> None:
+        """Append the 1-D ``tokens`` (n >= 1) to live row ``row`` at positions ``lens[row] ..`` in one pass over the
+        weights; afterwards ``logits[row]`` and ``lens[row]`` are those of the last appended token and the other rows
+        keep their bits.
+
+        The tokens run through the training trunk as one padded sequence (the prefill's GEMMs and LayerNorms, in the
+        session's one-sequence workspace) with two launches replaced: the embedding starts at position ``lens[row]``
+        (gpt2mi_embed_fwd_at), and each layer stores the chunk's keys and values into the row's cache (kv_store at
+        ``t0 = lens[row]``) and then runs the chunk attention over the cache (gpt2mi_attn_chunk: every key comes from
+        the cache, so with ``kv_dtype="fp8"`` a token's key has the quantised bits that ``step`` and ``extend`` read).
+        One sequence per call: every shape is a function of ``(lens[row], n)`` alone, so the result does not depend on
+        the batch (``refill``'s argument). The row leaves its share group, and a token ``generate`` drew and has not
+        stepped is stepped first, as in ``refill``.
+
+        ``append`` or ``extend``: ``extend`` runs every token as a decode row (the bits of n ``step`` calls, 64 rows a
+        call) and is the path for short runs; ``append`` runs the training GEMMs, whose results differ from a step's in
+        rounding. Measured at 124M widths, one sequence (tools/prefix_bench.py, profiles/decode/prefix_bench.json):
+        ``extend`` is faster up to n = 64 (``append`` takes 1.9x .. 2.6x its time at n = 16 and 64), ``append`` from
+        n = 256 on (0.63x .. 0.27x); nothing between was measured (DESIGN.md §9 "Prefill over a live cache").
+
+        ``ValueError``: a row outside [0, B), an empty row (``prefill`` / ``refill`` start one), no tokens, or
+        ``lens[row] + n > min(max_len, n_positions)``."""
+        eng, cfg = self.engine, self.cfg
+        if not 0 <= int(row) < self.B:
+            raise ValueError(f"row {row} not in [0, B={self.B})")
+        row = int(row)
+        if tokens.dim() != 1 or tokens.numel() < 1:
+            raise ValueError(f"append takes a 1-D tensor of at least one token (got {tuple(tokens.shape)})")
+        if not tokens.is_cuda:
+            raise RuntimeError("gpt_2_distributed_amd runs only on the MI355X HIP path: move the inputs to a cuda device")
+        n, limit = tokens.numel(), min(self.Tcap, cfg.n_positions)
+        if self.lens[row] == 0:
+            raise ValueError(f"append: row {row} is empty (lens[row] == 0): prefill or refill it first")
+        if self.lens[row] + int(self._drawn) + n > limit:
+            raise ValueError(f"append: lens[{row}]={self.lens[row] + int(self._drawn)} + {n} tokens exceed "
+                             f"min(max_len, n_positions)={limit}")
+        self.flush()
+        self._ready(True)
+        self.share.leave(row)
+        self._sync_share()
+        eng.gemm_sched = eng.base_sched
+        base = self.lens[row]
+        idx_p, _, _ = eng._pad(tokens.view(1, n), None)
+        Tp = idx_p.size(1)
+        C, H, Vp = cfg.n_embd, cfg.n_head, self.model.vpad
+        ws, cws = self._one_sequence_workspace(Tp), self._chunk_workspace(Tp)
+
+        def embed(x0):
+            K.embed_fwd_at(idx_p, eng.p("transformer.wte.weight"), eng.p("transformer.wpe.weight"), x0, 1, Tp, C, [base],
+                           T_valid=n)
+
+        def attn(l, A):  # the row's streams as a cache of one sequence: [H][Tcap][64]
+            kc, vc, ks, vs = (t if t is None else t[l, row] for t in (self.kcache, self.vcache, self.kscale, self.vscale))
+            K.kv_store(A.qkv, kc, vc, 1, Tp, n, base, H, 64, self.Tcap, kscale=ks, vscale=vs)
+            K.attn_chunk(A.qkv, kc, vc, A.ao, cws, 1, H, 64, self.Tcap, Tp, [0], [base], [n], kscale=ks, vscale=vs)
+
+        eng._trunk_fwd(ws, idx_p, 1, Tp, n, BF16, 0.0, 0.0, eng._seeds(0), embed=embed, attn=attn)
+        K.gemm_skinny(K.EPI_F32, 1, Vp, C, ws.lnf[n - 1], Tp * C, eng.w16("transformer.wte.weight"), C, self.logits[row],
+                      Vp, workspace=self.gemm_ws)
+        self.lens[row] = base + n
 
     @torch.no_grad()
     def flush(self) -> None:
@@ -1672,6 +1798,10 @@ def generate(model, idx, max_new_tokens: int, temperature: float = 1.0, top_k: O
     """``GPT2.generate``: see there."""
     given = dict(locals())  # (the arguments by name: what the beam path refuses)
     check_kv_dtype(kv_dtype)
+    if isinstance(idx, SharedPrefix):
+        raise ValueError("a SharedPrefix goes with generate_many, which draws tokens: " + (
+            "beam search takes a batch of whole prompts and no prefix" if num_beams is not None
+            else "generate takes a batch of whole prompts"))
     rules = (temperature, top_k, top_p, seed, eos_token_id, repetition_penalty, presence_penalty, frequency_penalty,
              min_p, min_new_tokens, stop, logit_bias)
     if num_beams is not None:
@@ -1871,19 +2001,26 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
                   allowed_token_ids=None, min_p: Optional[float] = None, min_new_tokens: int = 0, stop=None) -> list:
     """``GPT2.generate_many``: see there."""
     check_kv_dtype(kv_dtype)
+    prefix = None
+    if isinstance(prompts, SharedPrefix):
+        prefix, prompts = torch.as_tensor(prompts.prefix), prompts.prompts
+        if prefix.dim() != 1 or prefix.numel() < 1 or prefix.dtype.is_floating_point:
+            raise ValueError("prefix must be a non-empty 1-D sequence of token ids")
+        prefix = prefix.long()
+    least, shared = (1, 0) if prefix is None else (0, prefix.numel())  # (with a prefix a suffix may be empty)
     top_n = _check_logprobs(logprobs)
     if generator is not None:
         raise ValueError("generate_many draws on the device from (seed, prompt index, position): a torch.Generator is "
                          "one stream shared by the rows of a batch, so its draws would depend on the batching")
     prompts = list(prompts)
-    if any(not isinstance(p, torch.Tensor) or p.dim() != 1 or p.numel() < 1 for p in prompts):
-        raise ValueError("prompts must be non-empty 1-D token tensors")
+    if any(not isinstance(p, torch.Tensor) or p.dim() != 1 or p.numel() < least for p in prompts):
+        raise ValueError("prompts must be non-empty 1-D token tensors (in a SharedPrefix: 1-D, a suffix may be empty)")
     n = int(max_new_tokens)
     if n < 0:
         raise ValueError(f"max_new_tokens must be >= 0 (got {n})")
     if not 1 <= int(batch_size) <= MAX_BATCH:
         raise ValueError(f"batch_size {batch_size} not in [1, {MAX_BATCH}] (the decode GEMM's row limit)")
-    longest = max((p.numel() for p in prompts), default=0)
+    longest = shared + max((p.numel() for p in prompts), default=0)
     if longest + n > model.config.n_positions:
         raise ValueError(f"prompt length {longest} + max_new_tokens {n} > n_positions {model.config.n_positions}")
     if not isinstance(seed, int):
@@ -1892,16 +2029,20 @@ def generate_many(model, prompts, max_new_tokens: int, batch_size: int = 32, tem
                          frequency_penalty, min_p, min_new_tokens, stop, logit_bias, vocab_size=model.config.vocab_size,
                          allowed_token_ids=allowed_token_ids, rows=int(batch_size), device=model.arena.device,
                          per_row=False)
+    if prefix is not None:  # every prompt is prefix + prompts[i]; the prefix is computed once (serve_prompts)
+        _check_token("prefix", int(prefix.max()), model.config.vocab_size)
+        _check_token("prefix", int(prefix.min()), model.config.vocab_size)
+        prompts = [torch.cat([prefix.to(p.device), p.long()]) for p in prompts]
     if not prompts or n == 0:
         return [p.long().clone() if top_n is None else _no_logprobs(p.long().clone(), top_n) for p in prompts]
     _check_model(model)
     # (at least a chunk and two positions, so that a dummy row of one token need not start over within a chunk)
     sess = DecodeSession(model, int(batch_size), min(model.config.n_positions, max(longest + n, EOS_CHUNK + 2)),
                          kv_dtype)
-    return serve_prompts(sess, [p.long() for p in prompts], n, sampler, top_n)
+    return serve_prompts(sess, [p.long() for p in prompts], n, sampler, top_n, shared)
 
 
-def serve_prompts(sess, prompts, n: int, sampler: Sampler, logprobs: Optional[int] = None) -> list:
+def serve_prompts(sess, prompts, n: int, sampler: Sampler, logprobs: Optional[int] = None, shared: int = 0) -> list:
     """The loop of ``generate_many`` over a session (anything with DecodeSession's ``B``, ``Tcap``, ``lens``,
     ``device``, ``refill``, ``generate`` and ``flush``). Rows are slots: a slot holds prompt ``owner[row]`` (None: a
     dummy of one token whose output is dropped) and draws with ``row_id = owner[row]``. The device loop runs in chunks
@@ -1920,7 +2061,11 @@ def serve_prompts(sess, prompts, n: int, sampler: Sampler, logprobs: Optional[in
 
     With constraints in ``sampler`` every slot reads the one bias row, the generated part starts at the prompt's length,
     and with stop sequences ``seq`` holds the prompts as with penalties; a harvested prompt is cut after the token that
-    completed a stop sequence, as after eos."""
+    completed a stop sequence, as after eos.
+
+    ``shared`` > 0: every prompt starts with the same ``shared`` tokens. They are run once (``sess.prefix``, before any
+    slot is filled) and a slot is filled by ``refill(row, suffix, prefix=...)``: a copy and an ``append`` of the
+    suffix, both functions of (prefix, suffix) alone, so the guarantee holds."""
     B, dev = sess.B, sess.device
     eos_token_id, stops = sampler.eos_token_id, sampler.stop
     on = sampler.penalised or bool(stops)
@@ -1935,10 +2080,15 @@ def serve_prompts(sess, prompts, n: int, sampler: Sampler, logprobs: Optional[in
     buf = None if logprobs is None else LogprobBuffer(B, sess.Tcap, logprobs, dev)
     lp = {} if buf is None else {"logprobs": buf}
 
+    pre = sess.prefix(prompts[0][:shared].to(dev)) if shared else None
+
     def fill(row):
         owner[row] = pending.pop() if pending else None
         prompt = dummy if owner[row] is None else prompts[owner[row]].to(dev)
-        sess.refill(row, prompt)
+        if pre is None or owner[row] is None:
+            sess.refill(row, prompt)
+        else:
+            sess.refill(row, prompt[shared:], prefix=pre)
         start[row], made[row] = prompt.numel(), 0
         done[row] = 0
         if on:

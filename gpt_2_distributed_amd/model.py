@@ -546,7 +546,15 @@ class GPT2(nn.Module):
         the values are functions of the row's logits, so the guarantee covers them. ``logit_bias`` (a dict or a ``[V]``
         tensor: one row for every prompt), ``allowed_token_ids``, ``min_p``, ``min_new_tokens`` and ``stop`` as for
         ``generate``: functions of the row's own logits, position and tokens, so the guarantee holds with them; an entry
-        is cut after the token that completes a stop sequence, as after eos."""
+        is cut after the token that completes a stop sequence, as after eos.
+
+        ``prompts`` may be a ``generation.SharedPrefix(prefix, prompts)`` (``prefix`` a 1-D sequence of token ids):
+        every prompt is then ``prefix + prompts[i]`` (a suffix may be empty) and the returned sequences include the prefix. The prefix is run once (``DecodeSession.prefix``); a row starts
+        from a copy of its keys and values and only its suffix is prefilled, over the cache
+        (``DecodeSession.append``). A continuation is then a function of (weights, prefix, suffix, the sampler
+        parameters, seed, i): the guarantee holds, with every option above. The suffix runs over cached keys, so the
+        tokens may differ from those of the call on the concatenated prompts (other rounding, and
+        with ``kv_dtype="fp8"`` quantised prefix keys). Beam search is ``generate``'s, which refuses a ``SharedPrefix`` with ``ValueError``."""
         from .generation import generate_many
         return generate_many(self, prompts, max_new_tokens, batch_size, temperature, top_k, top_p, seed, eos_token_id,
                              generator, repetition_penalty, presence_penalty, frequency_penalty, kv_dtype, logprobs,

@@ -28,7 +28,7 @@ extern "C" {
 
 #define GPT2MI_ABI_VERSION 24
 /* Counts additions that move no existing signature or struct: a caller written against (24, m) runs on any (24, >= m). */
-#define GPT2MI_ABI_MINOR 8
+#define GPT2MI_ABI_MINOR 9
 
 const char* gpt2mi_last_error(void);
 int gpt2mi_abi_version(void); /* returns GPT2MI_ABI_VERSION of the built library */
@@ -835,6 +835,38 @@ int gpt2mi_embed_bwd_det(const int64_t* idx, const float* dres, float* dwte, flo
                          int C, float p, uint64_t seed, void* workspace, void* stream);
 int gpt2mi_embed_bwd_doc_det(const int64_t* idx, const float* dres, float* dwte, float* dwpe, const int* start, int B,
                              int T, int T_valid, int C, float p, uint64_t seed, void* workspace, void* stream);
+
+/* ---- v24.9: prefill over a live cache (csrc/prefill_cached.hip) -------------------------------------------------
+ * Flash attention of a chunk of new queries over keys and values that live in the key/value cache. qkv is
+ * [S][T_src][3C] bf16 (the trunk's qkv GEMM output, T_src a multiple of 64, C = 64 H); sequence s of the call is cache
+ * stream seq[s] of [B][H][Tcap][64]; its query rows i < count[s] sit at positions base[s] + i. EVERY key comes from the
+ * cache: row i attends over cache positions 0 .. base[s] + i of stream (seq[s], h), so the caller stores the chunk's
+ * own keys and values first (gpt2mi_kv_store[_fp8] with t0 = base, an earlier launch on the same stream; with an fp8
+ * cache the chunk's own keys are therefore the quantised ones, as in the step and the extend). out is [S][T_src][C]
+ * bf16, head-merged; rows i >= count[s] are written as zeros and never read from qkv. Nothing at or above position
+ * base[s] + count[s] is read; nothing in the cache is written. seq, base and count are HOST arrays of S <= 64 ints,
+ * validated before any launch (seq strictly increasing in [0, B), 1 <= count <= T_src, base >= 0,
+ * base + count <= Tcap) and passed by value. head_dim must be 64, and the other refusals of gpt2mi_attn_extend apply;
+ * 22 with a message otherwise.
+ * The keys 0 .. base + count - 1 of a sequence are cut into gpt2mi_attn_chunk_splits(base + count) contiguous ranges
+ * of whole 64-key tiles (a function of the sequence's own key count only), whose fp32 partials a second launch merges
+ * in range order; a call whose sequences all have one split launches one kernel and touches no workspace. No atomics:
+ * two runs give the same bits. workspace: gpt2mi_attn_chunk_workspace(S, H, Tcap, T_src) floats serve any call of
+ * those extents (a call needs S * H * T_src * 66 * its largest split count, or nothing with one split). */
+int gpt2mi_attn_chunk(const uint16_t* qkv, const uint16_t* kcache, const uint16_t* vcache, uint16_t* out,
+                      float* workspace, size_t workspace_floats, int S, int B, int H, int head_dim, int Tcap, int T_src,
+                      const int* seq, const int* base, const int* count, void* stream);
+int gpt2mi_attn_chunk_fp8(const uint16_t* qkv, const uint8_t* kcache, const uint8_t* vcache, const float* kscale,
+                          const float* vscale, uint16_t* out, float* workspace, size_t workspace_floats, int S, int B,
+                          int H, int head_dim, int Tcap, int T_src, const int* seq, const int* base, const int* count,
+                          void* stream);
+size_t gpt2mi_attn_chunk_workspace(int S, int H, int Tcap, int T_src);
+int gpt2mi_attn_chunk_splits(int keys);
+/* x[s,t,:] = wte[idx[s,t],:] + wpe[pos0[s] + t,:] for t < T_valid, zeros above (no table read): gpt2mi_embed_fwd
+ * without dropout, sequence s starting at position pos0[s] (HOST array of S <= 64 ints, >= 0; the caller keeps
+ * pos0[s] + T_valid within wpe). C a multiple of 4. */
+int gpt2mi_embed_fwd_at(const int64_t* idx, const float* wte, const float* wpe, float* x, int S, int T, int T_valid,
+                        int C, const int* pos0, void* stream);
 
 #ifdef __cplusplus
 }
