@@ -197,6 +197,13 @@ _SIGS = {
     "gpt2mi_attn_chunk_splits": [_c_int],
     # idx, wte, wpe, x, S, T, T_valid, C, pos0 (HOST array of S ints), stream
     "gpt2mi_embed_fwd_at": [_p, _p, _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p],
+    # policy head: logits, ld, labels, advantages, old_logprobs, ref_logprobs, clip_low, clip_high, kl_coef,
+    # entropy_coef, loss_rows, logp, ratio, kl, entropy, clipped, dlogits, ldd, M, V, ignore_index, loss, inv_count,
+    # metrics, stream
+    "gpt2mi_policy_fwd": [_p, _c_int, _p, _p, _p, _p, _c_float, _c_float, _c_float, _c_float, _p, _p, _p, _p, _p, _p,
+                          _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    "gpt2mi_policy_fwd_f32": [_p, _c_int, _p, _p, _p, _p, _c_float, _c_float, _c_float, _c_float, _p, _p, _p, _p, _p,
+                              _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
@@ -213,6 +220,8 @@ _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_deco
                                   "gpt2mi_muon_update")},
                 **{n: 9 for n in ("gpt2mi_attn_chunk", "gpt2mi_attn_chunk_fp8", "gpt2mi_attn_chunk_workspace",
                                   "gpt2mi_attn_chunk_splits", "gpt2mi_embed_fwd_at")}}
+# added to v24.9 without a new minor: an older v24.9 build (an A/B tool's) lacks them and leaves them untyped
+_UNNUMBERED = ("gpt2mi_policy_fwd", "gpt2mi_policy_fwd_f32")
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
              "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size,
@@ -249,7 +258,7 @@ def open_library(path: str, min_minor: int = ABI_MINOR) -> ctypes.CDLL:
         raise KernelError(f"{path} has C ABI v{lib.gpt2mi_abi_version()}.{minor}, the bindings expect v{ABI_VERSION}."
                           f"{min_minor} or a later minor: rebuild it")
     for name, args in _SIGS.items():
-        if _SINCE_MINOR.get(name, 0) > minor:
+        if _SINCE_MINOR.get(name, 0) > minor or (name in _UNNUMBERED and not hasattr(lib, name)):
             continue
         fn = getattr(lib, name)
         fn.argtypes = args
@@ -590,6 +599,26 @@ def attn_bwd(qkv, out, dout, lse, delta, dqkv, B, T, H, D, p_drop=0.0, seed=0, c
 def xent_fwd(logits, ld, labels, loss_rows, lse, dlogits, ldd, M, V, loss, inv_count, ignore_index=-100):
     _call("gpt2mi_xent_fwd_f32" if _f32(logits) else "gpt2mi_xent_fwd", _ptr(logits), ld, _ptr(labels), _ptr(loss_rows), _ptr(lse), _ptr(dlogits), ldd, M, V,
           ignore_index, _ptr(loss), _ptr(inv_count), _stream())
+
+
+def policy_fwd(logits, ld, labels, advantages, old_logprobs, ref_logprobs, clip_low, clip_high, kl_coef, entropy_coef,
+               loss_rows, logp, ratio, kl, entropy, clipped, dlogits, ldd, M, V, loss, inv_count, metrics,
+               ignore_index=-100):
+    """gpt2mi_policy_fwd[_f32] by the dtype of ``logits``: the policy-gradient head (csrc/policy_loss.hip). The per-row
+    inputs and outputs are fp32 [M]; old_logprobs, ref_logprobs, every per-row output, dlogits and metrics may be None."""
+    if not hasattr(load(), "gpt2mi_policy_fwd"):
+        raise KernelError("this build of libgpt2mi.so has no gpt2mi_policy_fwd: rebuild it")
+    for name, t in (("advantages", advantages), ("old_logprobs", old_logprobs), ("ref_logprobs", ref_logprobs),
+                    ("loss_rows", loss_rows), ("logp", logp), ("ratio", ratio), ("kl", kl), ("entropy", entropy),
+                    ("clipped", clipped), ("metrics", metrics)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.numel() < (4 if name == "metrics" else M)):
+            raise KernelError(f"policy_fwd: {name} must be a contiguous fp32 tensor of at least "
+                              f"{4 if name == 'metrics' else M} elements (got {t.dtype}, {tuple(t.shape)})")
+    _call("gpt2mi_policy_fwd_f32" if _f32(logits) else "gpt2mi_policy_fwd", _ptr(logits), ld, _ptr(labels),
+          _ptr(advantages), _ptr(old_logprobs), _ptr(ref_logprobs), clip_low, clip_high, kl_coef, entropy_coef,
+          _ptr(loss_rows), _ptr(logp), _ptr(ratio), _ptr(kl), _ptr(entropy), _ptr(clipped), _ptr(dlogits), ldd, M, V,
+          ignore_index, _ptr(loss), _ptr(inv_count), _ptr(metrics), _stream())
 
 
 def adamw(p, g, m, v, p_bf16, n, lr, wd, b1, b2, eps, step, grad_scale, partials, grad_norm):

@@ -381,6 +381,43 @@ class _GPT2Step(torch.autograd.Function):
         return (None, None, None, None, None) + (None,) * ctx.n_params
 
 
+@dataclass
+class PolicyCall:
+    """The per-row inputs and the coefficients of one policy-gradient forward (policy.py), and what it leaves behind:
+    the per-row outputs and the four metrics, written by the head kernel."""
+    advantages: torch.Tensor              # [B, T] fp32
+    old_logprobs: Optional[torch.Tensor]  # [B, T] fp32 or None
+    ref_logprobs: Optional[torch.Tensor]
+    clip_low: float
+    clip_high: float
+    kl_coef: float
+    entropy_coef: float
+    rows: Optional[torch.Tensor] = None     # [5, B, T] fp32: logp, ratio, kl, entropy, clipped
+    metrics: Optional[torch.Tensor] = None  # [4] fp32: the means of ratio, clipped, kl, entropy
+
+
+class _PolicyStep(torch.autograd.Function):
+    """The forward with the policy-gradient head in place of the cross entropy; the backward is _GPT2Step's."""
+
+    @staticmethod
+    def forward(ctx, engine, idx, labels, call, doc, reset, *params):
+        ctx.set_materialize_grads(False)
+        _, loss = engine._forward(idx, labels, True, doc, reset, policy=call)
+        ctx.engine = engine
+        ctx.token = engine._fwd_token
+        ctx.n_params = len(params)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        eng = ctx.engine
+        if ctx.token != eng._fwd_token:
+            raise RuntimeError("GPT2 activations were overwritten by a later forward before this backward "
+                               "(one forward/backward in flight per model)")
+        eng._backward(None, grad_loss)
+        return (None, None, None, None, None, None) + (None,) * ctx.n_params
+
+
 class _TrunkFn(torch.autograd.Function):
     """GPT2Backbone.forward(idx) (model.py:275-313): embedding -> blocks -> ln_f, fp32 output."""
 
@@ -842,6 +879,17 @@ class Engine:
         with torch.no_grad():
             return self._forward(idx, labels, False, doc, reset)
 
+    def policy_forward(self, idx: torch.Tensor, labels: torch.Tensor, call: PolicyCall,
+                       doc: Optional[DocBounds] = None, reset: bool = False) -> torch.Tensor:
+        """forward(idx, labels) with the policy-gradient head (gpt2mi_policy_fwd) in place of the cross entropy: the
+        same pad, trunk, dropout stream, saved record and lm_head GEMM, the same backward. Returns the loss; the
+        per-row outputs and the metrics are left in ``call`` ([5, B, T] and [4], fresh tensors)."""
+        reset = self._check_reset(doc, reset)
+        if self._grad_enabled():
+            return _PolicyStep.apply(self, idx, labels, call, doc, reset, *self._params)
+        with torch.no_grad():
+            return self._forward(idx, labels, False, doc, reset, policy=call)[1]
+
     # (autograd.Function.forward runs with grad mode off: whether a backward will follow is decided here)
     def backbone_forward(self, idx: torch.Tensor, doc: Optional[DocBounds] = None, reset: bool = False) -> torch.Tensor:
         reset = self._check_reset(doc, reset)
@@ -1145,7 +1193,15 @@ class Engine:
                 labels = F.pad(labels, (0, Tp - T), value=-100)
         return idx, labels, T
 
-    def _forward(self, idx, labels, need_grad, doc=None, reset=False):
+    def _pad_rows(self, t, Tp):
+        """A per-token fp32 input [B, T] of the policy head over the padded rows (0 in the padding, whose labels are
+        ignored), contiguous; None stays None."""
+        if t is None:
+            return None
+        t = t.to(F32)
+        return (F.pad(t, (0, Tp - t.shape[1])) if Tp != t.shape[1] else t).contiguous()
+
+    def _forward(self, idx, labels, need_grad, doc=None, reset=False, policy=None):
         cfg = self.cfg
         self.gemm_sched = self.base_sched  # (a backward that raised midway left its flags)
         V, Vp, C = cfg.vocab_size, self.vpad, cfg.n_embd
@@ -1167,12 +1223,27 @@ class Engine:
         loss = None
         if labels is not None:
             loss = torch.empty((), dtype=F32, device=self.device)  # fresh: callers may keep it across steps
-            K.xent_fwd(logits, Vp, labels, ws.loss_rows, ws.lse_ce, ws.dlogits if need_grad else None, Vp, M, V,
-                       loss, ws.inv_count)
+            if policy is None:
+                K.xent_fwd(logits, Vp, labels, ws.loss_rows, ws.lse_ce, ws.dlogits if need_grad else None, Vp, M, V,
+                           loss, ws.inv_count)
+            else:
+                self._policy_head(policy, logits, labels, ws, B, Tp, T, need_grad, loss)
         out = logits.view(B, Tp, Vp)
         if Tp != T:  # compact rows, so the reference's own logits.view(-1, V) (model.py:357-358) merges B and T
             out = out[:, :T].contiguous()
         return out[..., :V], loss
+
+    def _policy_head(self, call, logits, labels, ws, B, Tp, T, need_grad, loss):
+        """gpt2mi_policy_fwd over the step's logits into the step's ws.dlogits, ws.loss_rows and ws.inv_count."""
+        V, Vp, M = self.cfg.vocab_size, self.vpad, B * Tp
+        rows = torch.empty(5, B, Tp, dtype=F32, device=self.device)  # fresh: the caller keeps them
+        call.metrics = torch.empty(4, dtype=F32, device=self.device)
+        with self._probe("policy_head"):
+            K.policy_fwd(logits, Vp, labels, self._pad_rows(call.advantages, Tp), self._pad_rows(call.old_logprobs, Tp),
+                         self._pad_rows(call.ref_logprobs, Tp), call.clip_low, call.clip_high, call.kl_coef,
+                         call.entropy_coef, ws.loss_rows, rows[0], rows[1], rows[2], rows[3], rows[4],
+                         ws.dlogits if need_grad else None, Vp, M, V, loss, ws.inv_count, call.metrics)
+        call.rows = rows[:, :, :T] if Tp != T else rows
 
     # ---- evaluation: forward only, nothing kept, nothing of the training state touched --------------------
     def score(self, idx, labels, acc=None, doc=None, reset=False):

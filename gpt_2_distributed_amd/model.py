@@ -39,6 +39,8 @@ import torch.nn as nn
 from .arena import ArenaLayout, round_up
 from .packing import EOT_POSITIONS, DocBounds, check_bounds_meta
 from .packing import doc_bounds as _doc_bounds
+from .policy import METRICS as POLICY_METRICS
+from .policy import PolicyOutput
 
 
 @dataclass(frozen=True)
@@ -344,6 +346,49 @@ class GPT2(nn.Module):
         if reduction == "none":
             return rows.clone()
         return (s if reduction == "sum" else mean).reshape(()).clone()
+
+    # ---- policy-gradient fine-tuning (the reference has none) -------------------------------------------------
+    def policy_loss(self, idx: torch.Tensor, labels: torch.Tensor, advantages: torch.Tensor,
+                    old_logprobs: Optional[torch.Tensor] = None, ref_logprobs: Optional[torch.Tensor] = None,
+                    clip_low: float = 0.2, clip_high: float = 0.2, kl_coef: float = 0.0, entropy_coef: float = 0.0,
+                    doc_bounds: Optional[DocBounds] = None, reset_positions: bool = False) -> PolicyOutput:
+        """The PPO-clip / GRPO / REINFORCE loss of ``policy.policy_reference`` (the rule is stated there) on this
+        model's logits, differentiable exactly like ``forward(idx, labels)[1]``: the same forward with the fused
+        policy head (``gpt2mi_policy_fwd``) in place of the fused cross entropy, the same backward, so optimizers,
+        DDP / FSDP, ``model.deterministic`` and gradient accumulation work as they do for ``forward``.
+
+        ``labels`` [B, T] are aligned as in ``forward`` (``labels[b, t]`` is the token sampled after ``idx[b, :t+1]``;
+        -100: not counted, e.g. the prompt). ``advantages``, ``old_logprobs`` and ``ref_logprobs`` are float tensors
+        [B, T] on the model's device, read where the label counts. ``old_logprobs=None``: the ratio is exactly 1 and
+        nothing clips (on-policy REINFORCE, GRPO with one update per batch). ``ref_logprobs`` with ``kl_coef``: GRPO's
+        k3 penalty towards a reference policy. ``entropy_coef``: an entropy bonus. ``clip_low`` / ``clip_high``: the
+        ratio is clipped to [1 - clip_low, 1 + clip_high] (unequal values: DAPO's clip-higher).
+
+        The loss is the token mean over this call's counted labels, and under DDP / FSDP each rank's loss is its local
+        token mean, the convention ``forward`` has. A per-sequence or per-group normalisation is the caller's, folded
+        into ``advantages``. Returns ``PolicyOutput(loss, logprobs, ratio, kl, entropy, clipped, metrics)``: the
+        per-token fields detached fp32 [B, T], 0 where the label is ignored; ``metrics`` a dict of four device scalars
+        (``ratio``, ``clip_fraction``, ``kl``, ``entropy``: means over the counted tokens), no host synchronisation.
+        ``doc_bounds`` and ``reset_positions`` as in ``forward``. ValueError on a wrong shape, dtype, device or value."""
+        reset_positions = _checked_reset(reset_positions, doc_bounds is not None, "doc_bounds")
+        doc_bounds = _checked_bounds(doc_bounds, idx)
+        self._check_inputs(idx)
+        if labels is None or labels.shape != idx.shape or labels.dtype.is_floating_point:
+            raise ValueError(f"labels must be integer token ids of idx's shape {tuple(idx.shape)}")
+        for name, t in (("advantages", advantages), ("old_logprobs", old_logprobs), ("ref_logprobs", ref_logprobs)):
+            if t is None and name != "advantages":
+                continue
+            if not torch.is_tensor(t) or not t.dtype.is_floating_point or t.shape != idx.shape or t.device != idx.device:
+                raise ValueError(f"{name} must be a float tensor of idx's shape {tuple(idx.shape)} on {idx.device}")
+        coefs = dict(clip_low=clip_low, clip_high=clip_high, kl_coef=kl_coef, entropy_coef=entropy_coef)
+        for name, v in coefs.items():
+            if not math.isfinite(v) or (name.startswith("clip") and v < 0):
+                raise ValueError(f"{name} must be a finite number{' >= 0' if name.startswith('clip') else ''} (got {v})")
+        from .engine import PolicyCall
+        call = PolicyCall(advantages.detach(), None if old_logprobs is None else old_logprobs.detach(),
+                          None if ref_logprobs is None else ref_logprobs.detach(), **{k: float(v) for k, v in coefs.items()})
+        loss = self.engine().policy_forward(idx, labels, call, doc_bounds, reset_positions)
+        return PolicyOutput(loss, *call.rows.unbind(0), dict(zip(POLICY_METRICS, call.metrics.unbind(0))))
 
     def evaluate(self, batches, max_batches: Optional[int] = None, eot_token_id: Optional[int] = None,
                  eot: str = "end", reset_positions: bool = False) -> dict:

@@ -280,6 +280,11 @@ class DistributedDataParallel(nn.Module):
         """GPT2.score of the wrapped module (forward only: no collective)."""
         return self.module.score(*args, **kwargs)
 
+    def policy_loss(self, *args, **kwargs):
+        """GPT2.policy_loss of the wrapped module: this rank's local token mean, its backward bucketed and
+        all-reduced exactly as forward's."""
+        return self.module.policy_loss(*args, **kwargs)
+
     def evaluate(self, *args, **kwargs):
         """GPT2.evaluate of the wrapped module: the sums are all-reduced, every rank calls it with as many batches."""
         return self.module.evaluate(*args, **kwargs)
@@ -941,6 +946,11 @@ class FullyShardedDataParallel(nn.Module):
         """GPT2.score through this wrapper's unit gathers (a collective: every rank calls it), resident or resharding:
         the forward's unit hooks are the ones a training forward uses. Not between a forward and its backward."""
         return self.module.score(*args, **kwargs)
+
+    def policy_loss(self, *args, **kwargs):
+        """GPT2.policy_loss through this wrapper's unit gathers and reduce-scatters: this rank's local token mean, the
+        step otherwise forward's."""
+        return self.module.policy_loss(*args, **kwargs)
 
     def evaluate(self, *args, **kwargs):
         """GPT2.evaluate through this wrapper's unit gathers; every rank calls it with as many batches."""

@@ -868,6 +868,36 @@ int gpt2mi_attn_chunk_splits(int keys);
 int gpt2mi_embed_fwd_at(const int64_t* idx, const float* wte, const float* wpe, float* x, int S, int T, int T_valid,
                         int C, const int* pos0, void* stream);
 
+/* ---- policy-gradient head (csrc/policy_loss.hip): PPO-clip / GRPO / REINFORCE -----------------------------------
+ * Two entries added to v24.9 (GPT2MI_ABI_MINOR stays 9: a library is asked for them by name, nothing else moved).
+ * gpt2mi_xent_fwd's sibling: the same logits [M, ld] (bf16, or fp32 for _f32), labels, loss_rows [M], dlogits
+ * [M, ldd] (may be NULL: no gradient, the same per-row outputs), loss[0] and inv_count[0] = 1/N, for
+ *   loss = -(1/N) sum_rows ( min(r A, clamp(r, 1 - clip_low, 1 + clip_high) A) - kl_coef k3 + entropy_coef H )
+ * over the N rows whose label != ignore_index, with per row (y its label, p the softmax over columns < V)
+ *   logp = logit[y] - lse;   r = exp(logp - old_logprobs[row]), exactly 1 with old_logprobs = NULL;
+ *   d = ref_logprobs[row] - logp, k3 = exp(d) - d - 1 (0 with ref_logprobs = NULL; enters the loss only if
+ *   kl_coef != 0);   H = -sum_v p_v log p_v;   A = advantages[row]
+ * and dlogits_v = c (p_v - [v = y]) + entropy_coef p_v (log p_v + H), unscaled like the cross entropy's, where
+ *   c = (r A if r A <= clamp(r) A, else 0) + kl_coef (exp(d) - 1);
+ * every element is formed in fp32 and rounded once; columns [V, ldd) and ignored rows are +0. advantages,
+ * old_logprobs, ref_logprobs: fp32 [M]. Per-row outputs, fp32 [M], each may be NULL: logp, ratio, kl (k3), entropy,
+ * clipped (1 where clamp(r) != r, else 0); 0 in ignored rows. A label outside [0, V) other than ignore_index makes
+ * its row's outputs, its dlogits columns < V and the batch scalars NaN. metrics (may be NULL) receives the means over
+ * the N rows of (ratio, clipped, kl, entropy) and needs those four outputs. No atomics, fixed summation orders: two
+ * calls give the same bits. Refused with 22: a NULL logits, labels, advantages, loss_rows, loss or inv_count; M or
+ * V < 1; a row stride that is not a multiple of 8 or < V; a negative (or NaN) clip; a non-finite coefficient;
+ * metrics without the four outputs. */
+int gpt2mi_policy_fwd(const uint16_t* logits, int ld, const int64_t* labels, const float* advantages,
+                      const float* old_logprobs, const float* ref_logprobs, float clip_low, float clip_high,
+                      float kl_coef, float entropy_coef, float* loss_rows, float* logp, float* ratio, float* kl,
+                      float* entropy, float* clipped, uint16_t* dlogits, int ldd, int M, int V, int ignore_index,
+                      float* loss, float* inv_count, float* metrics, void* stream);
+int gpt2mi_policy_fwd_f32(const float* logits, int ld, const int64_t* labels, const float* advantages,
+                          const float* old_logprobs, const float* ref_logprobs, float clip_low, float clip_high,
+                          float kl_coef, float entropy_coef, float* loss_rows, float* logp, float* ratio, float* kl,
+                          float* entropy, float* clipped, float* dlogits, int ldd, int M, int V, int ignore_index,
+                          float* loss, float* inv_count, float* metrics, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
