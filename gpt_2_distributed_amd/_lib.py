@@ -204,6 +204,12 @@ _SIGS = {
                           _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
     "gpt2mi_policy_fwd_f32": [_p, _c_int, _p, _p, _p, _p, _c_float, _c_float, _c_float, _c_float, _p, _p, _p, _p, _p,
                               _p, _p, _c_int, _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    # distillation head: logits, ld, teacher, ldt, labels, temperature, ce_coef, kd_coef, reverse, loss_rows, ce, kd,
+    # dlogits, ldd, M, V, ignore_index, loss, inv_count, metrics, stream
+    "gpt2mi_distill_fwd": [_p, _c_int, _p, _c_int, _p, _c_float, _c_float, _c_float, _c_int, _p, _p, _p, _p, _c_int,
+                           _c_int, _c_int, _c_int, _p, _p, _p, _p],
+    "gpt2mi_distill_fwd_f32": [_p, _c_int, _p, _c_int, _p, _c_float, _c_float, _c_float, _c_int, _p, _p, _p, _p, _c_int,
+                               _c_int, _c_int, _c_int, _p, _p, _p, _p],
 }
 # the entries a library of minor m lacks: what came with a minor above m
 _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_decode_generate_logprobs": 1,
@@ -221,7 +227,7 @@ _SINCE_MINOR = {"gpt2mi_abi_minor": 1, "gpt2mi_sample_logprobs": 1, "gpt2mi_deco
                 **{n: 9 for n in ("gpt2mi_attn_chunk", "gpt2mi_attn_chunk_fp8", "gpt2mi_attn_chunk_workspace",
                                   "gpt2mi_attn_chunk_splits", "gpt2mi_embed_fwd_at")}}
 # added to v24.9 without a new minor: an older v24.9 build (an A/B tool's) lacks them and leaves them untyped
-_UNNUMBERED = ("gpt2mi_policy_fwd", "gpt2mi_policy_fwd_f32")
+_UNNUMBERED = ("gpt2mi_policy_fwd", "gpt2mi_policy_fwd_f32", "gpt2mi_distill_fwd", "gpt2mi_distill_fwd_f32")
 _RESTYPES = {"gpt2mi_last_error": ctypes.c_char_p, "gpt2mi_gemm_skinny_workspace": _c_size,
              "gpt2mi_attn_decode_workspace": _c_size, "gpt2mi_lm_loss_workspace": _c_size,
              "gpt2mi_beam_reorder_workspace": _c_size, "gpt2mi_gemm_wgrad_batch_scratch": _c_size,
@@ -619,6 +625,31 @@ def policy_fwd(logits, ld, labels, advantages, old_logprobs, ref_logprobs, clip_
           _ptr(advantages), _ptr(old_logprobs), _ptr(ref_logprobs), clip_low, clip_high, kl_coef, entropy_coef,
           _ptr(loss_rows), _ptr(logp), _ptr(ratio), _ptr(kl), _ptr(entropy), _ptr(clipped), _ptr(dlogits), ldd, M, V,
           ignore_index, _ptr(loss), _ptr(inv_count), _ptr(metrics), _stream())
+
+
+def distill_fwd(logits, ld, teacher, ldt, labels, temperature, ce_coef, kd_coef, kind, loss_rows, ce, kd, dlogits, ldd,
+                M, V, loss, inv_count, metrics, ignore_index=-100):
+    """gpt2mi_distill_fwd[_f32] by the dtype of ``logits``: the distillation head (csrc/distill_loss.hip) over the student
+    ``logits`` [M, ld] and the ``teacher`` logits [M, ldt] of the same dtype. kind: "forward" (KL(q || p)) or "reverse".
+    The per-row outputs are fp32 [M]; ce, kd, dlogits and metrics (fp32 [2]) may be None."""
+    if not hasattr(load(), "gpt2mi_distill_fwd"):
+        raise KernelError("this build of libgpt2mi.so has no gpt2mi_distill_fwd: rebuild it")
+    if kind not in ("forward", "reverse"):
+        raise KernelError(f"distill_fwd: kind must be 'forward' or 'reverse' (got {kind!r})")
+    if teacher.dtype != logits.dtype or logits.dtype not in (torch.bfloat16, torch.float32):
+        raise KernelError(f"distill_fwd: logits and teacher must both be bf16 or both fp32 (got {logits.dtype}, "
+                          f"{teacher.dtype})")
+    for name, t, stride in (("logits", logits, ld), ("teacher", teacher, ldt)):  # (a view of padded rows has M * V)
+        if stride % 8 or stride < V or t.numel() < M * V or t.data_ptr() % 16:
+            raise KernelError(f"distill_fwd: {name} must hold M={M} 16-byte aligned rows of a stride that is a multiple "
+                              f"of 8 and >= V={V} (stride {stride}, {t.numel()} elements)")
+    for name, t, n in (("loss_rows", loss_rows, M), ("ce", ce, M), ("kd", kd, M), ("metrics", metrics, 2)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n):
+            raise KernelError(f"distill_fwd: {name} must be a contiguous fp32 tensor of at least {n} elements "
+                              f"(got {t.dtype}, {tuple(t.shape)})")
+    _call("gpt2mi_distill_fwd_f32" if _f32(logits) else "gpt2mi_distill_fwd", _ptr(logits), ld, _ptr(teacher), ldt,
+          _ptr(labels), temperature, ce_coef, kd_coef, int(kind == "reverse"), _ptr(loss_rows), _ptr(ce), _ptr(kd),
+          _ptr(dlogits), ldd, M, V, ignore_index, _ptr(loss), _ptr(inv_count), _ptr(metrics), _stream())
 
 
 def adamw(p, g, m, v, p_bf16, n, lr, wd, b1, b2, eps, step, grad_scale, partials, grad_norm):

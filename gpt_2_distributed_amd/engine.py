@@ -418,6 +418,32 @@ class _PolicyStep(torch.autograd.Function):
         return (None, None, None, None, None, None) + (None,) * ctx.n_params
 
 
+@dataclass
+class DistillCall:
+    """The teacher's logits and the coefficients of one distillation forward (distill.py), and what it leaves behind:
+    the per-row outputs and the two metrics, written by the head kernel."""
+    teacher_logits: torch.Tensor          # [B, T, V], any float dtype
+    temperature: float
+    ce_coef: float
+    kd_coef: float
+    kind: str                             # "forward" or "reverse"
+    rows: Optional[torch.Tensor] = None     # [2, B, T] fp32: ce, kd
+    metrics: Optional[torch.Tensor] = None  # [2] fp32: the means of ce, kd
+
+
+class _DistillStep(_PolicyStep):
+    """The forward with the distillation head in place of the cross entropy; the backward is _GPT2Step's."""
+
+    @staticmethod
+    def forward(ctx, engine, idx, labels, call, doc, reset, *params):
+        ctx.set_materialize_grads(False)
+        _, loss = engine._forward(idx, labels, True, doc, reset, distill=call)
+        ctx.engine = engine
+        ctx.token = engine._fwd_token
+        ctx.n_params = len(params)
+        return loss
+
+
 class _TrunkFn(torch.autograd.Function):
     """GPT2Backbone.forward(idx) (model.py:275-313): embedding -> blocks -> ln_f, fp32 output."""
 
@@ -890,6 +916,17 @@ class Engine:
         with torch.no_grad():
             return self._forward(idx, labels, False, doc, reset, policy=call)[1]
 
+    def distill_forward(self, idx: torch.Tensor, labels: torch.Tensor, call: DistillCall,
+                        doc: Optional[DocBounds] = None, reset: bool = False) -> torch.Tensor:
+        """forward(idx, labels) with the distillation head (gpt2mi_distill_fwd) in place of the cross entropy, as
+        policy_forward: the same pad, trunk, dropout stream, saved record and lm_head GEMM, the same backward. Returns
+        the loss; the per-row outputs and the metrics are left in ``call`` ([2, B, T] and [2], fresh tensors)."""
+        reset = self._check_reset(doc, reset)
+        if self._grad_enabled():
+            return _DistillStep.apply(self, idx, labels, call, doc, reset, *self._params)
+        with torch.no_grad():
+            return self._forward(idx, labels, False, doc, reset, distill=call)[1]
+
     # (autograd.Function.forward runs with grad mode off: whether a backward will follow is decided here)
     def backbone_forward(self, idx: torch.Tensor, doc: Optional[DocBounds] = None, reset: bool = False) -> torch.Tensor:
         reset = self._check_reset(doc, reset)
@@ -1201,7 +1238,7 @@ class Engine:
         t = t.to(F32)
         return (F.pad(t, (0, Tp - t.shape[1])) if Tp != t.shape[1] else t).contiguous()
 
-    def _forward(self, idx, labels, need_grad, doc=None, reset=False, policy=None):
+    def _forward(self, idx, labels, need_grad, doc=None, reset=False, policy=None, distill=None):
         cfg = self.cfg
         self.gemm_sched = self.base_sched  # (a backward that raised midway left its flags)
         V, Vp, C = cfg.vocab_size, self.vpad, cfg.n_embd
@@ -1223,7 +1260,9 @@ class Engine:
         loss = None
         if labels is not None:
             loss = torch.empty((), dtype=F32, device=self.device)  # fresh: callers may keep it across steps
-            if policy is None:
+            if distill is not None:
+                self._distill_head(distill, logits, labels, ws, B, Tp, T, need_grad, loss)
+            elif policy is None:
                 K.xent_fwd(logits, Vp, labels, ws.loss_rows, ws.lse_ce, ws.dlogits if need_grad else None, Vp, M, V,
                            loss, ws.inv_count)
             else:
@@ -1243,6 +1282,37 @@ class Engine:
                          self._pad_rows(call.ref_logprobs, Tp), call.clip_low, call.clip_high, call.kl_coef,
                          call.entropy_coef, ws.loss_rows, rows[0], rows[1], rows[2], rows[3], rows[4],
                          ws.dlogits if need_grad else None, Vp, M, V, loss, ws.inv_count, call.metrics)
+        call.rows = rows[:, :, :T] if Tp != T else rows
+
+    def _teacher_rows(self, teacher, B, Tp, T, act):
+        """The teacher's logits [B, T, V] as the head reads them, [B * Tp rows, stride ldt]: the caller's memory itself
+        when it has the compute dtype, unit last stride, 16-byte alignment and one row stride that is a multiple of 8
+        over all B * Tp rows (what another GPT2.forward on this code base returns when T is a multiple of the tile);
+        otherwise one cast / padded copy [B, Tp, Vp], zero in the padded rows, whose labels are ignored. Columns
+        [V, ldt) are never used by the kernel and are left as they are."""
+        V, Vp = self.cfg.vocab_size, self.vpad
+        ldt = teacher.stride(1)
+        if (teacher.dtype == act and T == Tp and teacher.stride(2) == 1 and ldt % 8 == 0 and ldt >= V
+                and (B == 1 or teacher.stride(0) == T * ldt) and teacher.data_ptr() % 16 == 0
+                and (teacher.storage_offset() + B * T * ldt) * teacher.element_size()
+                <= teacher.untyped_storage().nbytes()):  # the last row's stride is the allocation's own
+            return teacher, ldt
+        rows = torch.empty(B, Tp, Vp, dtype=act, device=self.device)
+        rows[:, :T, :V].copy_(teacher)
+        if Tp != T:
+            rows[:, T:].zero_()
+        return rows, Vp
+
+    def _distill_head(self, call, logits, labels, ws, B, Tp, T, need_grad, loss):
+        """gpt2mi_distill_fwd over the step's logits into the step's ws.dlogits, ws.loss_rows and ws.inv_count."""
+        V, Vp, M = self.cfg.vocab_size, self.vpad, B * Tp
+        rows = torch.empty(2, B, Tp, dtype=F32, device=self.device)  # fresh: the caller keeps them
+        call.metrics = torch.empty(2, dtype=F32, device=self.device)
+        teacher, ldt = self._teacher_rows(call.teacher_logits, B, Tp, T, logits.dtype)
+        with self._probe("distill_head"):
+            K.distill_fwd(logits, Vp, teacher, ldt, labels, call.temperature, call.ce_coef, call.kd_coef, call.kind,
+                          ws.loss_rows, rows[0], rows[1], ws.dlogits if need_grad else None, Vp, M, V, loss,
+                          ws.inv_count, call.metrics)
         call.rows = rows[:, :, :T] if Tp != T else rows
 
     # ---- evaluation: forward only, nothing kept, nothing of the training state touched --------------------

@@ -39,6 +39,9 @@ import torch.nn as nn
 from .arena import ArenaLayout, round_up
 from .packing import EOT_POSITIONS, DocBounds, check_bounds_meta
 from .packing import doc_bounds as _doc_bounds
+from .distill import KINDS as DISTILL_KINDS
+from .distill import METRICS as DISTILL_METRICS
+from .distill import DistillOutput
 from .policy import METRICS as POLICY_METRICS
 from .policy import PolicyOutput
 
@@ -389,6 +392,48 @@ class GPT2(nn.Module):
                           None if ref_logprobs is None else ref_logprobs.detach(), **{k: float(v) for k, v in coefs.items()})
         loss = self.engine().policy_forward(idx, labels, call, doc_bounds, reset_positions)
         return PolicyOutput(loss, *call.rows.unbind(0), dict(zip(POLICY_METRICS, call.metrics.unbind(0))))
+
+    # ---- distillation from a teacher's logits (the reference has none) ----------------------------------------
+    def distill_loss(self, idx: torch.Tensor, labels: torch.Tensor, teacher_logits: torch.Tensor,
+                     temperature: float = 1.0, ce_coef: float = 0.5, kd_coef: float = 0.5, kind: str = "forward",
+                     doc_bounds: Optional[DocBounds] = None, reset_positions: bool = False) -> DistillOutput:
+        """The distillation loss of ``distill.distill_reference`` (the rule is stated there) on this model's logits,
+        ``ce_coef`` cross entropy + ``kd_coef`` temperature^2 KL to the teacher's softened distribution, differentiable
+        exactly like ``forward(idx, labels)[1]``: the same forward with the fused distillation head
+        (``gpt2mi_distill_fwd``) in place of the fused cross entropy, the same backward, so optimizers, DDP / FSDP,
+        ``model.deterministic`` and gradient accumulation work as they do for ``forward``.
+
+        ``labels`` [B, T] are aligned as in ``forward`` and always needed: -100 marks the tokens that do not count, for
+        the cross entropy and the KL alike (``ce_coef=0``: pure distillation). ``teacher_logits`` [B, T, vocab_size] is
+        a float tensor on the model's device, a constant. What another ``GPT2.forward`` on this code base returns under
+        the same autocast is read in place; anything else is cast and padded once. ``kind``: "forward" is
+        KL(teacher || student) (Hinton), "reverse" is KL(student || teacher).
+
+        The loss is the token mean over this call's counted labels (under DDP / FSDP each rank's local token mean).
+        Returns ``DistillOutput(loss, ce, kd, metrics)``: ``ce`` and ``kd`` detached fp32 [B, T], 0 where the label is
+        ignored; ``metrics`` a dict of two device scalars (``ce``, ``kd``: means over the counted tokens), no host
+        synchronisation. ``doc_bounds`` and ``reset_positions`` as in ``forward``. ValueError on a wrong shape, dtype,
+        device or value."""
+        reset_positions = _checked_reset(reset_positions, doc_bounds is not None, "doc_bounds")
+        doc_bounds = _checked_bounds(doc_bounds, idx)
+        self._check_inputs(idx)
+        if labels is None or labels.shape != idx.shape or labels.dtype.is_floating_point:
+            raise ValueError(f"labels must be integer token ids of idx's shape {tuple(idx.shape)}")
+        want = (*idx.shape, self.config.vocab_size)
+        if (not torch.is_tensor(teacher_logits) or not teacher_logits.dtype.is_floating_point
+                or tuple(teacher_logits.shape) != want or teacher_logits.device != idx.device):
+            raise ValueError(f"teacher_logits must be a float tensor of shape {want} (idx's shape and this model's "
+                             f"vocabulary) on {idx.device}")
+        if kind not in DISTILL_KINDS:
+            raise ValueError(f"kind must be one of {DISTILL_KINDS} (got {kind!r})")
+        if not (math.isfinite(temperature) and temperature > 0):
+            raise ValueError(f"temperature must be a finite number > 0 (got {temperature})")
+        if not (math.isfinite(ce_coef) and math.isfinite(kd_coef)):
+            raise ValueError(f"ce_coef and kd_coef must be finite numbers (got {ce_coef}, {kd_coef})")
+        from .engine import DistillCall
+        call = DistillCall(teacher_logits.detach(), float(temperature), float(ce_coef), float(kd_coef), kind)
+        loss = self.engine().distill_forward(idx, labels, call, doc_bounds, reset_positions)
+        return DistillOutput(loss, *call.rows.unbind(0), dict(zip(DISTILL_METRICS, call.metrics.unbind(0))))
 
     def evaluate(self, batches, max_batches: Optional[int] = None, eot_token_id: Optional[int] = None,
                  eot: str = "end", reset_positions: bool = False) -> dict:

@@ -285,6 +285,11 @@ class DistributedDataParallel(nn.Module):
         all-reduced exactly as forward's."""
         return self.module.policy_loss(*args, **kwargs)
 
+    def distill_loss(self, *args, **kwargs):
+        """GPT2.distill_loss of the wrapped module: this rank's local token mean, its backward bucketed and
+        all-reduced exactly as forward's."""
+        return self.module.distill_loss(*args, **kwargs)
+
     def evaluate(self, *args, **kwargs):
         """GPT2.evaluate of the wrapped module: the sums are all-reduced, every rank calls it with as many batches."""
         return self.module.evaluate(*args, **kwargs)
@@ -951,6 +956,11 @@ class FullyShardedDataParallel(nn.Module):
         """GPT2.policy_loss through this wrapper's unit gathers and reduce-scatters: this rank's local token mean, the
         step otherwise forward's."""
         return self.module.policy_loss(*args, **kwargs)
+
+    def distill_loss(self, *args, **kwargs):
+        """GPT2.distill_loss through this wrapper's unit gathers and reduce-scatters: this rank's local token mean, the
+        step otherwise forward's."""
+        return self.module.distill_loss(*args, **kwargs)
 
     def evaluate(self, *args, **kwargs):
         """GPT2.evaluate through this wrapper's unit gathers; every rank calls it with as many batches."""

@@ -898,6 +898,34 @@ int gpt2mi_policy_fwd_f32(const float* logits, int ld, const int64_t* labels, co
                           float* entropy, float* clipped, float* dlogits, int ldd, int M, int V, int ignore_index,
                           float* loss, float* inv_count, float* metrics, void* stream);
 
+/* ---- distillation head (csrc/distill_loss.hip): cross entropy + forward or reverse KL to teacher logits ----------
+ * Two more entries added to v24.9 without a new minor, as the policy head's. gpt2mi_xent_fwd's sibling over two
+ * logits tensors of one dtype: the student's logits [M, ld] and the teacher's [M, ldt] (bf16, or fp32 for _f32),
+ * labels, loss_rows [M], dlogits [M, ldd] (may be NULL: no gradient, the same per-row outputs), loss[0] and
+ * inv_count[0] = 1/N, for
+ *   loss = (1/N) sum_rows ( ce_coef ce + kd_coef kd )
+ * over the N rows whose label != ignore_index, with per row (y its label, softmaxes over columns < V, tau =
+ * temperature, p = softmax(s), p_tau = softmax(s / tau), q = softmax(t / tau))
+ *   ce = -log p[y];   kd = tau^2 KL(q || p_tau) with reverse = 0, tau^2 KL(p_tau || q) with reverse = 1
+ * and dlogits, unscaled like the cross entropy's,
+ *   reverse = 0:  ce_coef (p_v - [v = y]) + kd_coef tau (p_tau_v - q_v)
+ *   reverse = 1:  ce_coef (p_v - [v = y]) + kd_coef tau p_tau_v (log p_tau_v - log q_v - KL(p_tau || q));
+ * every element is formed in fp32 and rounded once; columns [V, ldd) and ignored rows are +0, and columns [V, ld) /
+ * [V, ldt) of the inputs are never used. Per-row outputs, fp32 [M], each may be NULL: ce, kd; 0 in ignored rows. A
+ * label outside [0, V) other than ignore_index makes its row's outputs, its dlogits columns < V and the batch scalars
+ * NaN. metrics (may be NULL) receives the means over the N rows of (ce, kd) and needs both outputs. No atomics, fixed
+ * summation orders: two calls give the same bits. Refused with 22: a NULL logits, teacher, labels, loss_rows, loss or
+ * inv_count; M or V < 1; a row stride that is not a multiple of 8 or < V; a temperature that is not finite and > 0; a
+ * non-finite coefficient; reverse other than 0 or 1; metrics without the two outputs. */
+int gpt2mi_distill_fwd(const uint16_t* logits, int ld, const uint16_t* teacher, int ldt, const int64_t* labels,
+                       float temperature, float ce_coef, float kd_coef, int reverse, float* loss_rows, float* ce,
+                       float* kd, uint16_t* dlogits, int ldd, int M, int V, int ignore_index, float* loss,
+                       float* inv_count, float* metrics, void* stream);
+int gpt2mi_distill_fwd_f32(const float* logits, int ld, const float* teacher, int ldt, const int64_t* labels,
+                           float temperature, float ce_coef, float kd_coef, int reverse, float* loss_rows, float* ce,
+                           float* kd, float* dlogits, int ldd, int M, int V, int ignore_index, float* loss,
+                           float* inv_count, float* metrics, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
