@@ -5,7 +5,8 @@
 // in one read of both rows and one write, a sibling of the fused cross entropy (csrc/xent_adamw.hip) and of the policy
 // head (csrc/policy_loss.hip) with the same outputs for the backward: dlogits unscaled (bf16 or fp32), loss = mean,
 // inv_count = 1/N (the alpha of the lm_head backward GEMMs). The rule in plain torch: gpt_2_distributed_amd/distill.py
-// (distill_reference). Per row, it = 1 / tau:
+// (distill_reference). What the heads share (the packed row, the workgroup reductions, the store sweep's frame, the
+// finalize kernel and the choice of kernel) is csrc/loss_head.h; here is the rule. Per row, it = 1 / tau:
 //   forward:  dlogits_v = ce_coef (p_v - [v = y]) + kd_coef tau (p_tau_v - q_v)
 //   reverse:  dlogits_v = ce_coef (p_v - [v = y]) + kd_coef tau p_tau_v (log p_tau_v - log q_v - KL(p_tau || q))
 // The row's reductions, m = max s, mt = max t (the maximum of s serves tau = 1 and tau alike):
@@ -21,13 +22,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "loss_head.h"
 
 namespace {
-
-// A logit of -inf (the padding as the reductions see it, or a masked token) is floored before it enters a difference
-// that is multiplied by that column's probability 0: 0 * (floor - floor) = 0 and 0 * (floor - x) = 0, where
-// 0 * (-inf - -inf) or 0 * -inf would put a NaN into a good row.
-constexpr float kLogFloor = -1e30f;
 
 // What a row's thread 0 reads and writes beside the logits; by value to every kernel.
 struct DistillRows {
@@ -47,23 +44,11 @@ struct DistillRowSums {
   double S1, St, Q, X;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // What the third sweep needs of a row, wave-uniform: lse = log sum e^s, lset = log sum e^(s it), lseq = log sum e^(t it),
 // and the reverse direction's KL. A bad label makes them NaN, which poisons every element of the row.
 struct DistillBcast {
   float lse, lset, lseq, kl;
 };
-
-__device__ __forceinline__ float uniform(float x) {  // a value every lane holds, into an SGPR
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
-}
-
-__device__ __forceinline__ float floored(float x) { return fmaxf(x, kLogFloor); }
 
 // The row's scalars from its reductions, by one thread; sy = the label's student logit. Stores the per-row outputs. An
 // ignored row stores zeros; a label outside [0, V) stores NaN and returns NaN (F.cross_entropy raises on such a label).
@@ -144,8 +129,8 @@ __device__ __forceinline__ void distill_accumulate(float s, float t, float ds, f
 }
 
 // --- the register-resident two-row kernel (bf16, GPT-2's vocabulary) ------------------------------------------------
-// One 1024-thread workgroup per row; the student row AND the teacher row are held packed in registers (2 x NCH chunks of
-// 8 logits per thread, 4 VGPRs a chunk: 56 VGPRs at NCH = 7) between three sweeps, each read from HBM exactly once and
+// One 1024-thread workgroup per row; the student row AND the teacher row are held packed in registers (two of
+// loss_head.h's PackedRow, 4 VGPRs a chunk of 8: 56 VGPRs at NCH = 7) between three sweeps, each read from HBM exactly once and
 // fenced so that the unpacked values of one sweep are dead before the next. One workgroup is 4 waves on each SIMD; 56
 // packed registers leave no room for a second one (64 VGPRs a wave), so the kernel asks for 4 waves per SIMD and may
 // use 128 VGPRs. Sweep 1: both maxima, one LDS exchange. Sweep 2: S1, (St,) Q and X together from the unpacked values,
@@ -156,156 +141,62 @@ template <int NCH, bool TAU1, bool REV>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(4, 4)))
 void distill_row_kernel(const bf16* __restrict__ logits, int ld, const bf16* __restrict__ teacher, int ldt,
                         bf16* __restrict__ dlogits, int ldd, DistillRows a) {
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int row = blockIdx.x, tid = threadIdx.x;
   const int V = a.V;
   const float it = TAU1 ? 1.f : a.inv_tau;
   const bf16* sp = logits + (size_t)row * ld;
-  const bf16* tp = teacher + (size_t)row * ldt;
   __shared__ float red[2][16];
   __shared__ double red64[4][16];
   __shared__ float s_bcast[4];
-  bf16x8 rs[NCH], rt[NCH];
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int c = 8 * (tid + 1024 * i);
-    rs[i] = c < ld ? *reinterpret_cast<const bf16x8*>(sp + c) : bf16x8{};
-    rt[i] = c < ldt ? *reinterpret_cast<const bf16x8*>(tp + c) : bf16x8{};
-  }
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int c = 8 * (tid + 1024 * i);
-    if (c + 8 > V) {  // the padding (and the unread tail) of both rows never wins a max and has exp(.) = 0
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (c + j >= V) rs[i][j] = rt[i][j] = (bf16)(-INFINITY);
-    }
-  }
-  auto fence = [&]() {  // both rows stay packed between the sweeps (see xent_row_kernel)
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      u32x4 x = __builtin_bit_cast(u32x4, rs[i]), z = __builtin_bit_cast(u32x4, rt[i]);
-      asm volatile("" : "+v"(x), "+v"(z));
-      rs[i] = __builtin_bit_cast(bf16x8, x);
-      rt[i] = __builtin_bit_cast(bf16x8, z);
-    }
-  };
-  float m = -INFINITY, mt = -INFINITY;
+  PackedRow<NCH> rs, rt;
+  rs.load(sp, ld, V, tid);
+  rt.load(teacher + (size_t)row * ldt, ldt, V, tid);
+  float mv[2] = {-INFINITY, -INFINITY};  // m, mt
 #pragma unroll
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      m = fmaxf(m, bf2f(rs[i][j]));
-      mt = fmaxf(mt, bf2f(rt[i][j]));
+      mv[0] = fmaxf(mv[0], rs.val(i, j));
+      mv[1] = fmaxf(mv[1], rt.val(i, j));
     }
-  fence();
-  m = wave_max(m);
-  mt = wave_max(mt);
-  if (lane == 0) {
-    red[0][w] = m;
-    red[1][w] = mt;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    float x = red[0][0], z = red[1][0];
-    for (int k = 1; k < 16; ++k) {
-      x = fmaxf(x, red[0][k]);
-      z = fmaxf(z, red[1][k]);
-    }
-    s_bcast[0] = x;
-    s_bcast[1] = z;
-  }
-  __syncthreads();
-  const float mx = uniform(s_bcast[0]), mxt = uniform(s_bcast[1]);
+  rs.fence();
+  rt.fence();
+  group_max(mv, red, s_bcast, tid);
+  const float mx = uniform(mv[0]), mxt = uniform(mv[1]);
   float S1 = 0.f, St = 0.f, Q = 0.f, X = 0.f;
 #pragma unroll
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float s = bf2f(rs[i][j]), t = bf2f(rt[i][j]);
+      const float s = rs.val(i, j), t = rt.val(i, j);
       distill_accumulate<TAU1, REV>(s, t, s - mx, t - mxt, it, S1, St, Q, X);
     }
-  fence();
-  const double wS1 = wave_sum_f64(S1), wQ = wave_sum_f64(Q), wX = wave_sum_f64(X);
-  const double wSt = TAU1 ? wS1 : wave_sum_f64(St);
-  if (lane == 0) {
-    red64[0][w] = wS1;
-    red64[1][w] = wQ;
-    red64[2][w] = wX;
-    if constexpr (!TAU1) red64[3][w] = wSt;
-  }
-  __syncthreads();  // (s_bcast[0..1] consumed before it: the row's scalars are written after it)
+  rs.fence();
+  rt.fence();
+  constexpr int NS = TAU1 ? 3 : 4;  // at tau = 1 St is S1
+  double sums[NS] = {S1, Q, X};
+  if constexpr (!TAU1) sums[3] = St;
+  group_sum_wave0(sums, red64, tid);  // (s_bcast[0..1] consumed before its barrier: the row's scalars are written after)
   const int64_t y = a.labels[row];
-  if (w == 0) {  // the 16 wave sums of each, added by wave 0's butterfly: a fixed order
-    DistillRowSums r;
-    r.m = mx;
-    r.mt = mxt;
-    r.S1 = wave_sum_f64(lane < 16 ? red64[0][lane] : 0.0);
-    r.Q = wave_sum_f64(lane < 16 ? red64[1][lane] : 0.0);
-    r.X = wave_sum_f64(lane < 16 ? red64[2][lane] : 0.0);
-    r.St = TAU1 ? r.S1 : wave_sum_f64(lane < 16 ? red64[3][lane] : 0.0);
-    if (lane == 0) {
-      const float sy = (y >= 0 && y < V) ? bf2f(sp[y]) : 0.f;
-      const DistillBcast b = distill_row_scalars<TAU1, REV>(a, row, y, sy, r);
-      s_bcast[0] = b.lse;
-      s_bcast[1] = b.lset;
-      s_bcast[2] = b.lseq;
-      s_bcast[3] = b.kl;
-    }
+  if (tid == 0) {
+    const DistillRowSums r{mx, mxt, sums[0], sums[TAU1 ? 0 : NS - 1], sums[1], sums[2]};
+    const float sy = (y >= 0 && y < V) ? bf2f(sp[y]) : 0.f;
+    const DistillBcast b = distill_row_scalars<TAU1, REV>(a, row, y, sy, r);
+    s_bcast[0] = b.lse;
+    s_bcast[1] = b.lset;
+    s_bcast[2] = b.lseq;
+    s_bcast[3] = b.kl;
   }
   __syncthreads();
   if (!dlogits) return;
-  const bool ign = (y == a.ignore_index);
   const DistillCoef k = distill_coef<TAU1, REV>(
       a, DistillBcast{uniform(s_bcast[0]), uniform(s_bcast[1]), uniform(s_bcast[2]), uniform(s_bcast[3])});
-  bf16* dp = dlogits + (size_t)row * ldd;
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int c0 = 8 * (tid + 1024 * i);
-    if (c0 >= ldd) continue;
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      o[j] = f2bf(ign ? 0.f : distill_grad<TAU1, REV>(bf2f(rs[i][j]), bf2f(rt[i][j]), k));
-    if (!ign && (uint32_t)(y - c0) < 8u)  // the label's column again, in fp32 to the end: one rounding
-      o[y - c0] = f2bf(distill_grad<TAU1, REV>(bf2f(rs[i][y - c0]), bf2f(rt[i][y - c0]), k) - a.ce_coef);
-    if (c0 + 8 > V) {  // +0 in the padding, whatever the signs (and in a NaN row)
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (c0 + j >= V) o[j] = (bf16)0.f;
-    }
-    *reinterpret_cast<bf16x8*>(dp + c0) = o;
-  }
+  store_row<NCH>(
+      dlogits + (size_t)row * ldd, ldd, V, tid, y == a.ignore_index, y, a.ce_coef,
+      [&](float s, float t) { return distill_grad<TAU1, REV>(s, t, k); }, rs, rt);
 }
 
 // --- the strided two-pass kernel (fp32 logits, or any V) ---------------------------------------------------------------
-template <typename TL>
-__device__ __forceinline__ void load8(const TL* p, float* f) {
-  if constexpr (sizeof(TL) == 2) {
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = bf2f(v[j]);
-  } else {
-    const f32x4 a = reinterpret_cast<const f32x4*>(p)[0], b = reinterpret_cast<const f32x4*>(p)[1];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f[j] = a[j];
-      f[4 + j] = b[j];
-    }
-  }
-}
-template <typename TL>
-__device__ __forceinline__ void store8(TL* p, const float* f) {
-  if constexpr (sizeof(TL) == 2) {
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = f2bf(f[j]);
-    *reinterpret_cast<bf16x8*>(p) = o;
-  } else {
-    reinterpret_cast<f32x4*>(p)[0] = f32x4{f[0], f[1], f[2], f[3]};
-    reinterpret_cast<f32x4*>(p)[1] = f32x4{f[4], f[5], f[6], f[7]};
-  }
-}
-
 // e^((from - to) it) for a maximum that moves from `from` to `to` >= from; an empty set (from = -inf) scales by 0
 // whatever `to` is, so a set of nothing but -inf logits merges cleanly too.
 __device__ __forceinline__ float rescale(float from, float to, float it) {
@@ -424,60 +315,19 @@ __global__ __launch_bounds__(256) void distill_fwd_kernel(const TL* __restrict__
   }
 }
 
-// --- the batch's scalars ------------------------------------------------------------------------------------------------
-// One workgroup; every thread adds its rows in row order, the waves and then the 16 wave sums are added in a fixed
-// order. loss = sum(loss_rows) / N, inv_count = 1 / N (N = labels != ignore_index; NaN / inf at N = 0, as the cross
-// entropy's), metrics = the means over the counted rows of (ce, kd): ignored rows hold 0 in each.
-__global__ __launch_bounds__(1024) void distill_finalize_kernel(const float* __restrict__ loss_rows,
-                                                               const int64_t* __restrict__ labels,
-                                                               const float* __restrict__ ce,
-                                                               const float* __restrict__ kd, int M, int ignore_index,
-                                                               float* __restrict__ loss, float* __restrict__ inv_count,
-                                                               float* __restrict__ metrics) {
-  constexpr int NQ = 4;
-  float q[NQ] = {0.f, 0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < M; i += 1024) {
-    q[0] += loss_rows[i];
-    q[1] += (labels[i] == ignore_index) ? 0.f : 1.f;
-    if (metrics) {
-      q[2] += ce[i];
-      q[3] += kd[i];
-    }
-  }
-  __shared__ float red[NQ][16];
-#pragma unroll
-  for (int k = 0; k < NQ; ++k) {
-    q[k] = wave_sum(q[k]);
-    if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = q[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float tot[NQ];
-    for (int k = 0; k < NQ; ++k) {
-      tot[k] = 0.f;
-      for (int w = 0; w < 16; ++w) tot[k] += red[k][w];
-    }
-    loss[0] = tot[0] / tot[1];
-    inv_count[0] = 1.f / tot[1];
-    if (metrics) {
-      metrics[0] = tot[2] / tot[1];
-      metrics[1] = tot[3] / tot[1];
-    }
-  }
-}
-
 template <typename TL, bool TAU1, bool REV>
 int distill_launch(const TL* logits, int ld, const TL* teacher, int ldt, TL* dlogits, int ldd, int M,
-                   const DistillRows& a, hipStream_t s) {
-  const int nch = (max(max(ld, ldt), dlogits ? ldd : 0) + 8 * 1024 - 1) / (8 * 1024);
-  if constexpr (sizeof(TL) == 2) {
-    if (nch == 7) {  // GPT-2's vocabulary under autocast: both rows register-resident
+                   const DistillRows& a, float* loss, float* inv_count, float* metrics, hipStream_t s) {
+  auto row = [&] {
+    if constexpr (sizeof(TL) == 2)
       distill_row_kernel<7, TAU1, REV><<<M, 1024, 0, s>>>(logits, ld, teacher, ldt, dlogits, ldd, a);
-      return gpt2mi::check_launch("distill_row");
-    }
-  }
-  distill_fwd_kernel<TL, TAU1, REV><<<M, 256, 0, s>>>(logits, ld, teacher, ldt, dlogits, ldd, a);
-  return gpt2mi::check_launch("distill_fwd");
+  };
+  auto strided = [&] {
+    distill_fwd_kernel<TL, TAU1, REV><<<M, 256, 0, s>>>(logits, ld, teacher, ldt, dlogits, ldd, a);
+  };
+  // metrics = the means over the counted rows of (ce, kd)
+  return head_launch<2>("distill", {ld, ldt, ldd, a.V, true, dlogits != nullptr, sizeof(TL) == 2}, row, strided,
+                        a.loss_rows, a.labels, M, a.ignore_index, loss, inv_count, {{a.ce, a.kd}, metrics}, s);
 }
 
 }  // namespace
@@ -490,8 +340,6 @@ static int distill_fwd_t(const TL* logits, int ld, const TL* teacher, int ldt, c
   GPT2MI_REQUIRE(M >= 1 && V >= 1, "distill_fwd: M=%d and V=%d must be >= 1", M, V);
   GPT2MI_REQUIRE(logits && teacher && labels && loss_rows && loss && inv_count,
                  "distill_fwd: logits, teacher, labels, loss_rows, loss and inv_count must not be NULL");
-  GPT2MI_REQUIRE(ld % 8 == 0 && ld >= V && ldt % 8 == 0 && ldt >= V && (dlogits == nullptr || (ldd % 8 == 0 && ldd >= V)),
-                 "distill_fwd: row strides must be multiples of 8 and >= V (ld=%d ldt=%d ldd=%d V=%d)", ld, ldt, ldd, V);
   GPT2MI_REQUIRE(isfinite(temperature) && temperature > 0.f, "distill_fwd: temperature=%g must be finite and > 0",
                  (double)temperature);
   GPT2MI_REQUIRE(isfinite(ce_coef) && isfinite(kd_coef), "distill_fwd: ce_coef=%g and kd_coef=%g must be finite",
@@ -500,17 +348,9 @@ static int distill_fwd_t(const TL* logits, int ld, const TL* teacher, int ldt, c
   GPT2MI_REQUIRE(!metrics || (ce && kd), "distill_fwd: metrics are the means of the per-row ce and kd outputs: pass both");
   hipStream_t s = (hipStream_t)stream;
   const DistillRows a{labels, temperature, 1.f / temperature, ce_coef, kd_coef, loss_rows, ce, kd, V, ignore_index};
-  const bool tau1 = temperature == 1.f;
-  int rc;
-  if (tau1)
-    rc = reverse ? distill_launch<TL, true, true>(logits, ld, teacher, ldt, dlogits, ldd, M, a, s)
-                 : distill_launch<TL, true, false>(logits, ld, teacher, ldt, dlogits, ldd, M, a, s);
-  else
-    rc = reverse ? distill_launch<TL, false, true>(logits, ld, teacher, ldt, dlogits, ldd, M, a, s)
-                 : distill_launch<TL, false, false>(logits, ld, teacher, ldt, dlogits, ldd, M, a, s);
-  if (rc) return rc;
-  distill_finalize_kernel<<<1, 1024, 0, s>>>(loss_rows, labels, ce, kd, M, ignore_index, loss, inv_count, metrics);
-  return gpt2mi::check_launch("distill_finalize");
+  auto launch = temperature == 1.f ? (reverse ? distill_launch<TL, true, true> : distill_launch<TL, true, false>)
+                                   : (reverse ? distill_launch<TL, false, true> : distill_launch<TL, false, false>);
+  return launch(logits, ld, teacher, ldt, dlogits, ldd, M, a, loss, inv_count, metrics, s);
 }
 
 GPT2MI_EXPORT int gpt2mi_distill_fwd(const uint16_t* logits, int ld, const uint16_t* teacher, int ldt,

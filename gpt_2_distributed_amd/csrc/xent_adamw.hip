@@ -4,43 +4,17 @@
 // Replaces: K13 log_softmax+nll_loss fwd/bwd (model.py:357-359), K15
 // clip_grad_norm_ (train_gpt2_distributed.py:419-421), K16 _fused_adamw_ (:356-362,424).
 #include "common.h"
+#include "loss_head.h"
 
 namespace {
 
 // --- cross entropy ------------------------------------------------------------------------------
+// (what it shares with the policy and distillation heads is in loss_head.h)
 // One 256-thread block per row of logits (bf16, row stride ld, V valid columns).
 //   pass 1: online (max, sum exp) per thread over 16-B chunks, block combine -> lse
 //   loss_row = lse - logit[label]  (0 and not counted when label == ignore_index)
 //   pass 2: dlogits = softmax - onehot (bf16, unscaled; the 1/N and upstream grad are applied as
 //           the alpha of the backward GEMMs), zero in the padded columns [V, ld_d).
-template <typename TL>
-__device__ __forceinline__ void load8(const TL* p, float* f) {
-  if constexpr (sizeof(TL) == 2) {
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = bf2f(v[j]);
-  } else {
-    const f32x4 a = reinterpret_cast<const f32x4*>(p)[0], b = reinterpret_cast<const f32x4*>(p)[1];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      f[j] = a[j];
-      f[4 + j] = b[j];
-    }
-  }
-}
-template <typename TL>
-__device__ __forceinline__ void store8(TL* p, const float* f) {
-  if constexpr (sizeof(TL) == 2) {
-    bf16x8 o;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = f2bf(f[j]);
-    *reinterpret_cast<bf16x8*>(p) = o;
-  } else {
-    reinterpret_cast<f32x4*>(p)[0] = f32x4{f[0], f[1], f[2], f[3]};
-    reinterpret_cast<f32x4*>(p)[1] = f32x4{f[4], f[5], f[6], f[7]};
-  }
-}
-
 template <typename TL>
 __global__ __launch_bounds__(256) void xent_fwd_kernel(const TL* __restrict__ logits, int ld,
                                                        const int64_t* __restrict__ labels, float* __restrict__ loss_rows,
@@ -119,7 +93,7 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const TL* __restrict__ lo
 // the whole row in registers (NCH chunks of 8 logits per thread), so the logits are read from HBM
 // ONCE: max -> sum of exp -> lse -> dlogits all from registers (the two-pass kernel above re-reads a
 // 100 KB row that no longer sits in L2 when its second pass starts: 3 passes of HBM traffic).
-// 60 VGPRs (the row packed, see fence()) = two blocks per CU, so one row's load phase overlaps another's
+// 60 VGPRs (the row packed, see PackedRow::fence) = two blocks per CU, so one row's load phase overlaps another's
 // store phase (2611 -> 2494 us at cfg 2's head; at 90 VGPRs a CU held one row at a time).
 template <int NCH>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8)))
@@ -128,59 +102,31 @@ void xent_row_kernel(const bf16* __restrict__ logits, int ld, const int64_t* __r
                                                         bf16* __restrict__ dlogits, int ldd, int V, int ignore_index) {
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const bf16* lp = logits + (size_t)row * ld;
-  __shared__ float red[16];
+  __shared__ float red[1][16];
   __shared__ float s_bcast;
-  bf16x8 raw[NCH];  // the row, packed (4 VGPRs per chunk of 8)
-#pragma unroll
-  for (int i = 0; i < NCH; ++i) {
-    const int c = 8 * (tid + 1024 * i);
-    raw[i] = c < ld ? *reinterpret_cast<const bf16x8*>(lp + c) : bf16x8{};
-    if (c + 8 > V) {  // the padding (and the unread tail) never wins the max and has exp(.) = 0
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (c + j >= V) raw[i][j] = (bf16)(-INFINITY);
-    }
-  }
-  auto val = [&](int i, int j) { return bf2f(raw[i][j]); };
-  // the row stays packed between the phases: without these fences the compiler keeps all 56 unpacked fp32 values
-  // live across the reductions (90 VGPRs = one 1024-thread block per CU, whose load and store phases never overlap)
-  auto fence = [&]() {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      u32x4 t = __builtin_bit_cast(u32x4, raw[i]);
-      asm volatile("" : "+v"(t));
-      raw[i] = __builtin_bit_cast(bf16x8, t);
-    }
-  };
-  float m = -INFINITY;
+  PackedRow<NCH> r;
+  r.load(lp, ld, V, tid);
+  float mv[1] = {-INFINITY};
 #pragma unroll
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) m = fmaxf(m, val(i, j));
-  fence();
-  m = wave_max(m);
-  if (lane == 0) red[w] = m;
-  __syncthreads();
-  if (tid == 0) {
-    float t = red[0];
-    for (int k = 1; k < 16; ++k) t = fmaxf(t, red[k]);
-    s_bcast = t;
-  }
-  __syncthreads();
-  const float mx = s_bcast;
+    for (int j = 0; j < 8; ++j) mv[0] = fmaxf(mv[0], r.val(i, j));
+  r.fence();
+  group_max(mv, red, &s_bcast, tid);
+  const float mx = mv[0];
   float sum = 0.f;
 #pragma unroll
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) sum += __expf(val(i, j) - mx);  // exp(-inf) = 0 for the padding
-  fence();
+    for (int j = 0; j < 8; ++j) sum += __expf(r.val(i, j) - mx);  // exp(-inf) = 0 for the padding
+  r.fence();
   sum = wave_sum(sum);
   __syncthreads();  // s_bcast consumed
-  if (lane == 0) red[w] = sum;
+  if (lane == 0) red[0][w] = sum;
   __syncthreads();
-  if (tid == 0) {
+  if (tid == 0) {  // the 16 wave sums one after the other (not group_sum_wave0's tree: lse keeps its bits)
     float t = 0.f;
-    for (int k = 0; k < 16; ++k) t += red[k];
+    for (int k = 0; k < 16; ++k) t += red[0][k];
     const float lse = mx + __logf(t);
     s_bcast = lse;
     lse_out[row] = lse;
@@ -193,60 +139,17 @@ void xent_row_kernel(const bf16* __restrict__ logits, int ld, const int64_t* __r
   const bool ign = (y == ignore_index);
   const float lse = (!ign && (y < 0 || y >= V)) ? __builtin_nanf("") : s_bcast;  // bad label: NaN row
   bf16* dp = dlogits + (size_t)row * ldd;
+  // not loss_head.h's store_row: the label's column is rounded twice here (softmax to bf16, then - 1), and the padding
+  // needs no pass of its own (exp(-inf) is already +0; a NaN row keeps its NaN there)
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     const int c = 8 * (tid + 1024 * i);
     if (c >= ldd) continue;
     bf16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = f2bf(ign ? 0.f : __expf(val(i, j) - lse));
+    for (int j = 0; j < 8; ++j) o[j] = f2bf(ign ? 0.f : __expf(r.val(i, j) - lse));
     if (!ign && (uint32_t)(y - c) < 8u) o[y - c] = f2bf(bf2f(o[y - c]) - 1.f);
     *reinterpret_cast<bf16x8*>(dp + c) = o;
-  }
-}
-
-// loss = sum(loss_rows)/count(valid); inv_count = 1/count (the dlogits scale for backward).
-__global__ __launch_bounds__(1024) void xent_finalize_kernel(const float* __restrict__ loss_rows,
-                                                            const int64_t* __restrict__ labels, int M, int ignore_index,
-                                                            float* __restrict__ loss, float* __restrict__ inv_count) {
-  float s = 0.f, n = 0.f;
-  // four rows' loads issued together, then added in row order (the same sums as one row per step: 33 us with one
-  // dependent load at a time over cfg 2's 65536 rows)
-  int i = threadIdx.x;
-  for (; i + 3 * 1024 < M; i += 4 * 1024) {
-    float l[4];
-    int64_t y[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      l[k] = loss_rows[i + 1024 * k];
-      y[k] = labels[i + 1024 * k];
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      s += l[k];
-      n += (y[k] == ignore_index) ? 0.f : 1.f;
-    }
-  }
-  for (; i < M; i += 1024) {
-    s += loss_rows[i];
-    n += (labels[i] == ignore_index) ? 0.f : 1.f;
-  }
-  s = wave_sum(s);
-  n = wave_sum(n);
-  __shared__ float rs[16], rn[16];
-  if ((threadIdx.x & 63) == 0) {
-    rs[threadIdx.x >> 6] = s;
-    rn[threadIdx.x >> 6] = n;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float S = 0.f, N = 0.f;
-    for (int w = 0; w < 16; ++w) {
-      S += rs[w];
-      N += rn[w];
-    }
-    loss[0] = S / N;  // NaN when every label is ignored, as F.cross_entropy
-    inv_count[0] = 1.f / N;
   }
 }
 
@@ -406,24 +309,16 @@ constexpr int kNormBlocks = 2048;
 template <typename TL>
 static int xent_fwd_t(const TL* logits, int ld, const int64_t* labels, float* loss_rows, float* lse, TL* dlogits,
                       int ldd, int M, int V, int ignore_index, float* loss, float* inv_count, void* stream) {
-  GPT2MI_REQUIRE(ld % 8 == 0 && ld >= V && (dlogits == nullptr || (ldd % 8 == 0 && ldd >= V)),
-                 "xent_fwd: row strides must be multiples of 8 and >= V (ld=%d ldd=%d V=%d)", ld, ldd, V);
   hipStream_t s = (hipStream_t)stream;
-  const int nch = (max(ld, dlogits ? ldd : 0) + 8 * 1024 - 1) / (8 * 1024);
-  if constexpr (sizeof(TL) == 2) {
-    if (nch == 7) {  // GPT-2 vocab under autocast: one register-resident pass over the bf16 logits
+  auto row = [&] {
+    if constexpr (sizeof(TL) == 2)
       xent_row_kernel<7><<<M, 1024, 0, s>>>(logits, ld, labels, loss_rows, lse, dlogits, ldd, V, ignore_index);
-      int rc = gpt2mi::check_launch("xent_row");
-      if (rc) return rc;
-      xent_finalize_kernel<<<1, 1024, 0, s>>>(loss_rows, labels, M, ignore_index, loss, inv_count);
-      return gpt2mi::check_launch("xent_finalize");
-    }
-  }
-  xent_fwd_kernel<TL><<<M, 256, 0, s>>>(logits, ld, labels, loss_rows, lse, dlogits, ldd, V, ignore_index);
-  int rc = gpt2mi::check_launch("xent_fwd");
-  if (rc) return rc;
-  xent_finalize_kernel<<<1, 1024, 0, s>>>(loss_rows, labels, M, ignore_index, loss, inv_count);
-  return gpt2mi::check_launch("xent_finalize");
+  };
+  auto strided = [&] {
+    xent_fwd_kernel<TL><<<M, 256, 0, s>>>(logits, ld, labels, loss_rows, lse, dlogits, ldd, V, ignore_index);
+  };
+  return head_launch<0>("xent", {ld, 0, ldd, V, false, dlogits != nullptr, sizeof(TL) == 2}, row, strided, loss_rows,
+                        labels, M, ignore_index, loss, inv_count, {}, s);
 }
 
 GPT2MI_EXPORT int gpt2mi_xent_fwd(const uint16_t* logits, int ld, const int64_t* labels, float* loss_rows, float* lse,

@@ -396,13 +396,14 @@ class PolicyCall:
     metrics: Optional[torch.Tensor] = None  # [4] fp32: the means of ratio, clipped, kl, entropy
 
 
-class _PolicyStep(torch.autograd.Function):
-    """The forward with the policy-gradient head in place of the cross entropy; the backward is _GPT2Step's."""
+class _HeadStep(torch.autograd.Function):
+    """The forward with another head (call: a PolicyCall or a DistillCall) in place of the cross entropy; the backward
+    is _GPT2Step's."""
 
     @staticmethod
     def forward(ctx, engine, idx, labels, call, doc, reset, *params):
         ctx.set_materialize_grads(False)
-        _, loss = engine._forward(idx, labels, True, doc, reset, policy=call)
+        _, loss = engine._forward(idx, labels, True, doc, reset, head=call)
         ctx.engine = engine
         ctx.token = engine._fwd_token
         ctx.n_params = len(params)
@@ -429,19 +430,6 @@ class DistillCall:
     kind: str                             # "forward" or "reverse"
     rows: Optional[torch.Tensor] = None     # [2, B, T] fp32: ce, kd
     metrics: Optional[torch.Tensor] = None  # [2] fp32: the means of ce, kd
-
-
-class _DistillStep(_PolicyStep):
-    """The forward with the distillation head in place of the cross entropy; the backward is _GPT2Step's."""
-
-    @staticmethod
-    def forward(ctx, engine, idx, labels, call, doc, reset, *params):
-        ctx.set_materialize_grads(False)
-        _, loss = engine._forward(idx, labels, True, doc, reset, distill=call)
-        ctx.engine = engine
-        ctx.token = engine._fwd_token
-        ctx.n_params = len(params)
-        return loss
 
 
 class _TrunkFn(torch.autograd.Function):
@@ -912,9 +900,9 @@ class Engine:
         per-row outputs and the metrics are left in ``call`` ([5, B, T] and [4], fresh tensors)."""
         reset = self._check_reset(doc, reset)
         if self._grad_enabled():
-            return _PolicyStep.apply(self, idx, labels, call, doc, reset, *self._params)
+            return _HeadStep.apply(self, idx, labels, call, doc, reset, *self._params)
         with torch.no_grad():
-            return self._forward(idx, labels, False, doc, reset, policy=call)[1]
+            return self._forward(idx, labels, False, doc, reset, head=call)[1]
 
     def distill_forward(self, idx: torch.Tensor, labels: torch.Tensor, call: DistillCall,
                         doc: Optional[DocBounds] = None, reset: bool = False) -> torch.Tensor:
@@ -923,9 +911,9 @@ class Engine:
         the loss; the per-row outputs and the metrics are left in ``call`` ([2, B, T] and [2], fresh tensors)."""
         reset = self._check_reset(doc, reset)
         if self._grad_enabled():
-            return _DistillStep.apply(self, idx, labels, call, doc, reset, *self._params)
+            return _HeadStep.apply(self, idx, labels, call, doc, reset, *self._params)
         with torch.no_grad():
-            return self._forward(idx, labels, False, doc, reset, distill=call)[1]
+            return self._forward(idx, labels, False, doc, reset, head=call)[1]
 
     # (autograd.Function.forward runs with grad mode off: whether a backward will follow is decided here)
     def backbone_forward(self, idx: torch.Tensor, doc: Optional[DocBounds] = None, reset: bool = False) -> torch.Tensor:
@@ -1238,7 +1226,7 @@ class Engine:
         t = t.to(F32)
         return (F.pad(t, (0, Tp - t.shape[1])) if Tp != t.shape[1] else t).contiguous()
 
-    def _forward(self, idx, labels, need_grad, doc=None, reset=False, policy=None, distill=None):
+    def _forward(self, idx, labels, need_grad, doc=None, reset=False, head=None):
         cfg = self.cfg
         self.gemm_sched = self.base_sched  # (a backward that raised midway left its flags)
         V, Vp, C = cfg.vocab_size, self.vpad, cfg.n_embd
@@ -1260,28 +1248,34 @@ class Engine:
         loss = None
         if labels is not None:
             loss = torch.empty((), dtype=F32, device=self.device)  # fresh: callers may keep it across steps
-            if distill is not None:
-                self._distill_head(distill, logits, labels, ws, B, Tp, T, need_grad, loss)
-            elif policy is None:
+            if head is None:
                 K.xent_fwd(logits, Vp, labels, ws.loss_rows, ws.lse_ce, ws.dlogits if need_grad else None, Vp, M, V,
                            loss, ws.inv_count)
             else:
-                self._policy_head(policy, logits, labels, ws, B, Tp, T, need_grad, loss)
+                self._run_head(head, logits, labels, ws, B, Tp, T, need_grad, loss)
         out = logits.view(B, Tp, Vp)
         if Tp != T:  # compact rows, so the reference's own logits.view(-1, V) (model.py:357-358) merges B and T
             out = out[:, :T].contiguous()
         return out[..., :V], loss
 
-    def _policy_head(self, call, logits, labels, ws, B, Tp, T, need_grad, loss):
-        """gpt2mi_policy_fwd over the step's logits into the step's ws.dlogits, ws.loss_rows and ws.inv_count."""
+    def _run_head(self, call, logits, labels, ws, B, Tp, T, need_grad, loss):
+        """gpt2mi_policy_fwd (a PolicyCall) or gpt2mi_distill_fwd (a DistillCall) over the step's logits into the step's
+        ws.dlogits, ws.loss_rows and ws.inv_count; the per-row outputs and the metrics are left in ``call``."""
         V, Vp, M = self.cfg.vocab_size, self.vpad, B * Tp
-        rows = torch.empty(5, B, Tp, dtype=F32, device=self.device)  # fresh: the caller keeps them
-        call.metrics = torch.empty(4, dtype=F32, device=self.device)
-        with self._probe("policy_head"):
-            K.policy_fwd(logits, Vp, labels, self._pad_rows(call.advantages, Tp), self._pad_rows(call.old_logprobs, Tp),
-                         self._pad_rows(call.ref_logprobs, Tp), call.clip_low, call.clip_high, call.kl_coef,
-                         call.entropy_coef, ws.loss_rows, rows[0], rows[1], rows[2], rows[3], rows[4],
-                         ws.dlogits if need_grad else None, Vp, M, V, loss, ws.inv_count, call.metrics)
+        policy = isinstance(call, PolicyCall)
+        rows = torch.empty(5 if policy else 2, B, Tp, dtype=F32, device=self.device)  # fresh: the caller keeps them
+        call.metrics = torch.empty(4 if policy else 2, dtype=F32, device=self.device)
+        out = (ws.dlogits if need_grad else None, Vp, M, V, loss, ws.inv_count, call.metrics)
+        if policy:
+            with self._probe("policy_head"):
+                K.policy_fwd(logits, Vp, labels, self._pad_rows(call.advantages, Tp),
+                             self._pad_rows(call.old_logprobs, Tp), self._pad_rows(call.ref_logprobs, Tp), call.clip_low,
+                             call.clip_high, call.kl_coef, call.entropy_coef, ws.loss_rows, *rows, *out)
+        else:
+            teacher, ldt = self._teacher_rows(call.teacher_logits, B, Tp, T, logits.dtype)
+            with self._probe("distill_head"):
+                K.distill_fwd(logits, Vp, teacher, ldt, labels, call.temperature, call.ce_coef, call.kd_coef, call.kind,
+                              ws.loss_rows, *rows, *out)
         call.rows = rows[:, :, :T] if Tp != T else rows
 
     def _teacher_rows(self, teacher, B, Tp, T, act):
@@ -1302,18 +1296,6 @@ class Engine:
         if Tp != T:
             rows[:, T:].zero_()
         return rows, Vp
-
-    def _distill_head(self, call, logits, labels, ws, B, Tp, T, need_grad, loss):
-        """gpt2mi_distill_fwd over the step's logits into the step's ws.dlogits, ws.loss_rows and ws.inv_count."""
-        V, Vp, M = self.cfg.vocab_size, self.vpad, B * Tp
-        rows = torch.empty(2, B, Tp, dtype=F32, device=self.device)  # fresh: the caller keeps them
-        call.metrics = torch.empty(2, dtype=F32, device=self.device)
-        teacher, ldt = self._teacher_rows(call.teacher_logits, B, Tp, T, logits.dtype)
-        with self._probe("distill_head"):
-            K.distill_fwd(logits, Vp, teacher, ldt, labels, call.temperature, call.ce_coef, call.kd_coef, call.kind,
-                          ws.loss_rows, rows[0], rows[1], ws.dlogits if need_grad else None, Vp, M, V, loss,
-                          ws.inv_count, call.metrics)
-        call.rows = rows[:, :, :T] if Tp != T else rows
 
     # ---- evaluation: forward only, nothing kept, nothing of the training state touched --------------------
     def score(self, idx, labels, acc=None, doc=None, reset=False):

@@ -64,8 +64,8 @@ def main():
         return attn_mode(libs, g, st)
     if os.environ.get("LIB_AB_OP") == "adamw":
         return adamw_mode(libs, g, st)
-    if os.environ.get("LIB_AB_OP") == "xent":
-        return xent_mode(libs, g, st)
+    if os.environ.get("LIB_AB_OP") in ("heads", "xent"):  # xent: the cross entropy's row of the heads alone
+        return heads_mode(libs, g, st, only="xent" if os.environ["LIB_AB_OP"] == "xent" else None)
     if os.environ.get("LIB_AB_OP") == "embed":
         return embed_mode(libs, g, st)
     outs = {}
@@ -272,40 +272,101 @@ def adamw_mode(libs, g, st):
     print("adamw " + "  ".join(f"lib{i}: {sorted(t)[2] * 1e3:8.1f} us" for i, t in times.items()), flush=True)
 
 
-def xent_mode(libs, g, st):
-    """LIB_AB_OP=xent: the register-resident cross-entropy (loss rows, lse, bf16 dlogits) at cfg 2's head
-    (65536 rows of 50257 logits, row stride 50304); outputs compared bitwise against the first library."""
-    M, V, ld = 65536, 50257, 50304
-    logits = (torch.randn(M, ld, device=dev, generator=g) * 2).to(torch.bfloat16)
-    labels = torch.randint(0, V, (M,), device=dev, generator=g)
-    labels[::97] = -100
-    res = []
-    for lib in libs:
-        res.append((torch.empty(M, device=dev), torch.empty(M, device=dev), torch.empty_like(logits),
-                    torch.empty(1, device=dev), torch.empty(1, device=dev)))
-    run = lambda lib, r: lib.gpt2mi_xent_fwd(logits.data_ptr(), ld, labels.data_ptr(), r[0].data_ptr(),  # noqa
-                                             r[1].data_ptr(), r[2].data_ptr(), ld, M, V, -100, r[3].data_ptr(),
-                                             r[4].data_ptr(), st)
-    for lib, r in zip(libs, res):
-        assert run(lib, r) == 0
-    torch.cuda.synchronize()
-    for i in range(1, len(libs)):
-        for k, name in enumerate(("loss_rows", "lse", "dlogits", "loss")):
-            if not torch.equal(res[0][k], res[i][k]):
-                print(f"MISMATCH lib{i} {name}")
-    times = {i: [] for i in range(len(libs))}
-    for _ in range(5):
-        for i, (lib, r) in enumerate(zip(libs, res)):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            for _r in range(5):
-                run(lib, r)
-            e.record()
+def heads_mode(libs, g, st, only=None):
+    """LIB_AB_OP=heads: the fused loss heads (cross entropy, policy with every option on, distillation forward at
+    tau 1 and 2 and reverse at tau 2). Every output (the per-row outputs, dlogits, loss, inv_count, the metrics) is
+    compared bit for bit against the first library at the shapes of tests/test_policy_kernels_gpu.py::SHAPES and at
+    rows of 49160 (the row kernel with a nearly empty seventh chunk and no padding), with valid labels and once more with
+    one ignored and one out-of-range label. Then each head is timed at cfg 2's head (65536 rows of 50257 logits, row
+    stride 50304) in interleaved rounds, the median round. A MISMATCH makes the process exit non-zero."""
+    from types import SimpleNamespace
+    bf = torch.bfloat16
+    P = lambda t: t.data_ptr()  # noqa: E731
+    # name: (entry, what it takes between (logits, ld) and its per-row outputs, the per-row outputs, metrics)
+    distill = lambda tau, rev: ("gpt2mi_distill_fwd", lambda c: (P(c.teacher), c.ld, P(c.labels), tau, 0.7, 0.9, rev),  # noqa
+                                ("loss_rows", "ce", "kd"), 2)
+    heads = {"xent": ("gpt2mi_xent_fwd", lambda c: (P(c.labels),), ("loss_rows", "lse"), 0),
+             "policy all": ("gpt2mi_policy_fwd", lambda c: (P(c.labels), P(c.adv), P(c.old), P(c.ref), 0.2, 0.28, 0.3, 0.05),
+                            ("loss_rows", "logp", "ratio", "kl", "entropy", "clipped"), 4),
+             "distill forward tau=1": distill(1.0, 0), "distill forward tau=2": distill(2.0, 0),
+             "distill reverse tau=2": distill(2.0, 1)}
+    if only:
+        heads = {only: heads[only]}
+
+    def case(M, V, ld, ldd, dtype, bad_labels):
+        """Seeded inputs of one shape; old and ref lie near the rows' own log-probabilities, so both sides of the clip occur."""
+        c = SimpleNamespace(M=M, V=V, ld=ld, ldd=ldd, sfx="_f32" if dtype == torch.float32 else "")
+        c.logits = (torch.randn(M, ld, device=dev, generator=g) * 2).to(dtype)
+        c.teacher = (torch.randn(M, ld, device=dev, generator=g) * 2).to(dtype)
+        c.labels = torch.randint(0, V, (M,), device=dev, generator=g)
+        c.labels[0], c.labels[1] = V - 1, 0
+        if bad_labels:
+            c.labels[M - 2], c.labels[M - 1] = -100, V
+        elif M > 64:
+            c.labels[::97] = -100
+        y = c.labels.clamp(0, V - 1)[:, None]
+        lse = torch.cat([torch.logsumexp(c.logits[i:i + 4096, :V].float(), -1) for i in range(0, M, 4096)])
+        logp = c.logits.gather(1, y)[:, 0].float() - lse
+        c.adv = torch.randn(M, device=dev, generator=g)
+        c.old = logp + torch.tensor([-0.5, -0.1, 0.0, 0.1, 0.5], device=dev).repeat(M // 5 + 1)[:M]
+        c.ref = logp + 0.3 * torch.randn(M, device=dev, generator=g)
+        return c
+
+    def state(c, rows, nm):
+        s = {n: torch.zeros(c.M, device=dev) for n in rows}
+        s.update(dlogits=torch.zeros(c.M, c.ldd, dtype=c.logits.dtype, device=dev), loss=torch.zeros(1, device=dev),
+                 inv_count=torch.zeros(1, device=dev))
+        if nm:
+            s["metrics"] = torch.zeros(nm, device=dev)
+        return s
+
+    def call(lib, c, head, s):
+        entry, inputs, rows, nm = head
+        rc = getattr(lib, entry + c.sfx)(P(c.logits), c.ld, *inputs(c), *(P(s[n]) for n in rows), P(s["dlogits"]), c.ldd,
+                                         c.M, c.V, -100, P(s["loss"]), P(s["inv_count"]),
+                                         *((P(s["metrics"]),) if nm else ()), st)
+        assert rc == 0, (entry + c.sfx, rc, lib.gpt2mi_last_error())
+
+    def compare(c, label):
+        """Every head on every library over the case; the mismatching outputs (NaNs compare by their bits)."""
+        bad = 0
+        for name, head in heads.items():
+            ss = [state(c, head[2], head[3]) for _ in libs]
+            for lib, s in zip(libs, ss):
+                call(lib, c, head, s)
             torch.cuda.synchronize()
-            times[i].append(s.elapsed_time(e) / 5)
-    gb = 2 * 2 * M * ld / 1e9
-    print("xent " + "  ".join(f"lib{i}: {sorted(t)[2] * 1e3:8.1f} us {gb / sorted(t)[2]:5.2f} TB/s"
-                              for i, t in times.items()), flush=True)
+            diff = [f"lib{i} {k}" for i in range(1, len(libs)) for k, v in ss[i].items()
+                    if not torch.equal(v.view(torch.uint8), ss[0][k].view(torch.uint8))]
+            bad += len(diff)
+            print(f"{name:22s} {label:44s} " + ("MISMATCH " + ", ".join(diff) if diff else
+                                               f"bitwise equal ({', '.join(ss[0])})"), flush=True)
+        return bad
+
+    from tests.test_policy_kernels_gpu import SHAPES
+    mismatches = 0
+    for M, V, ld, ldd, dtype in SHAPES + [(3, 49160, 49160, 49160, bf)]:
+        for bad_labels in (False, True):
+            label = f"M={M} V={V} ld={ld} ldd={ldd} {'f32' if dtype == torch.float32 else 'bf16'}" + \
+                    (" bad labels" if bad_labels else "")
+            mismatches += compare(case(M, V, ld, ldd, dtype, bad_labels), label)
+    c = case(65536, 50257, 50304, 50304, bf, False)
+    mismatches += compare(c, "M=65536 V=50257 ld=50304 bf16 (timed)")
+    for name, head in heads.items():
+        ss = [state(c, head[2], head[3]) for _ in libs]
+        times = {i: [] for i in range(len(libs))}
+        for _ in range(5):
+            for i, (lib, s) in enumerate(zip(libs, ss)):
+                b, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                b.record()
+                for _r in range(5):
+                    call(lib, c, head, s)
+                e.record()
+                torch.cuda.synchronize()
+                times[i].append(b.elapsed_time(e) / 5)
+        print(f"{name:22s} " + "  ".join(f"lib{i}: {sorted(t)[2] * 1e3:8.1f} us" for i, t in times.items()), flush=True)
+    print(f"heads A/B: {mismatches} mismatching outputs", flush=True)
+    if mismatches:
+        raise SystemExit(1)
 
 
 def decode_mode(libs, st):
